@@ -63,10 +63,13 @@ def parse():
                     help="N = 1, headline config: skip the short legs of BASELINE.json's other configurations (`other_configs`)")
     ap.add_argument('--cpu-only', action='store_true', help='only time the CPU baseline (no GPU needed)')
     ap.add_argument('--timing-steps', type=int, default=10)
-    ap.add_argument('--repeats', type=int, default=0,
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step handed its caller (trajectory, loss, policy '
+                         'gradient, updated parameters and Adam moments) as DIR/<name>.npy, float32, at most 64 MiB in all')
+    ap.add_argument('--repeats', type=int, default=1,
                     help='timed blocks of EXACTLY --steps steps each (every block bracketed by barrier + synchronize); '
-                         '`value` is the median block.  0 (default): as many as give >= 0.25 s of device time, at least 25 '
-                         'for blocks under 10 ms, at most 200')
+                         '`value` is the median block.  1 (default): the timed steps are exactly --steps.  0: as many '
+                         'blocks as give >= 0.25 s of device time, at least 25 for blocks under 10 ms, at most 200')
     ap.add_argument('--pmc', action='store_true',
                     help='N = 1: first collect the HBM-traffic and MFMA counters of this build and configuration by re-running '
                          'under rocprofv3 --pmc (one pass per counter set, a few minutes), write profiles/pmc_<config>_<precision>.json, '
@@ -205,6 +208,7 @@ class Leg:
         self.v = torch.zeros_like(self.params)
         self.loss_buf = torch.zeros(1, device=dev)
         self.n = 0
+        self.last = None        # what the latest step() handed its caller: (states, actions, rewards, policy gradient)
         self.step_dev = torch.zeros(1, dtype=torch.int64, device=dev)
         # one process: the iteration is two library calls (pmbrl_rollout_fwd, pmbrl_rollout_bwd_adam: adjoint, dW, the
         # loss on the way of the gradient reduction -- pmbrl_adam::loss_out_d --, clip + Adam); with a gradient all-reduce
@@ -217,15 +221,17 @@ class Leg:
     def step(self):
         self.n += 1
         if self.fused:
-            self.eng.forward(**self.args)
-            self.eng.backward(self.gw, adam=self.adam)
+            S, A, R = self.eng.forward(**self.args)
+            g, _, _ = self.eng.backward(self.gw, adam=self.adam)
+            self.last = (S, A, R, g)
             return
-        _, _, R = self.eng.forward(**self.args)
+        S, A, R = self.eng.forward(**self.args)
         self.eng.weighted_sum(R, self.gw, out=self.loss_buf)
         g, _, _ = self.eng.backward(self.gw)
         if self.world > 1:
             self.allreduce(g)
         self.E.clip_adam(self.params, g, self.m, self.v, self.n, 1e-4, max_norm=1.0)
+        self.last = (S, A, R, g)
 
     def restart(self):
         self.params.copy_(self.params0)
@@ -332,6 +338,35 @@ class Leg:
                          'matrix pipe / weight fetch L2->CU: %d workgroups over %d CUs' % (n_wg, N_CUS),
                  flops_per_launch=kflops[dom], avg_launch_ms=timings[dom])
         return r, kname
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(leg, out_dir):
+    """bench.py --dump-outputs: what the last timed step handed its caller, as out_dir/<name>.npy (float32) -- the
+    trajectory (states [H+1, B, D], actions [H, B, U], rewards [H, B, 1]), the loss, the flat policy gradient, and the
+    parameters and Adam moments the optimiser step left.  Call it right after Leg.timed(), before any other step.  Over
+    DUMP_MAX_BYTES in all, the trajectory keeps a fixed sample of rows (seed 0, ascending).  Returns what was written."""
+    S, A, R, g = leg.last
+    traj = dict(states=S, actions=A, rewards=R)
+    flat = dict(loss=leg.loss_buf, policy_grad=g, policy_params=leg.params, adam_exp_avg=leg.m, adam_exp_avg_sq=leg.v)
+    traj = {k: v.detach().float().cpu().numpy() for k, v in traj.items()}
+    flat = {k: v.detach().float().cpu().numpy() for k, v in flat.items()}
+    B = S.shape[1]
+    fixed = sum(v.nbytes for v in flat.values())
+    per_row = sum(v.nbytes for v in traj.values()) // B
+    rows = None
+    if fixed + per_row * B > DUMP_MAX_BYTES:
+        k = int((DUMP_MAX_BYTES - fixed) // per_row)
+        rows = np.sort(np.random.default_rng(0).choice(B, size=k, replace=False))
+        traj = {n: np.ascontiguousarray(v[:, rows]) for n, v in traj.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(traj, **flat)
+    for n, v in arrays.items():
+        np.save(os.path.join(out_dir, n + '.npy'), v)
+    return dict(dir=out_dir, arrays={n: list(v.shape) for n, v in arrays.items()},
+                bytes=int(sum(v.nbytes for v in arrays.values())), rows_sampled=None if rows is None else len(rows))
 
 
 def sclk_mhz(leg):
@@ -639,6 +674,7 @@ def main():
     primary = a.scaling if world > 1 else 'weak'
     leg = make_leg(primary, a.precision)
     dt, blocks = leg.timed(a.steps, a.warmup, dev, a.repeats)
+    dumped = dump_outputs(leg, a.dump_outputs) if a.dump_outputs and rank == 0 else None
     timings = leg.kernel_ms(a.timing_steps)
     eng, d, B, Bg, H = leg.eng, leg.d, leg.B, leg.Bg, leg.H
     prec = eng.info['precision']
@@ -703,6 +739,7 @@ def main():
         out = dict(
             metric='particle_rollouts_per_sec', value=Bg * a.steps / dt, unit='rollouts/s',
             n_gpus=world, steps=a.steps, warmup=a.warmup, ms_per_step=dt / a.steps * 1e3,
+            timed_steps=a.steps * len(blocks),
             higher_is_better=True, scaling=primary, vs_baseline=None, dtype=dtype,
             data='synthetic',
             # `value` = the MEDIAN of `timed_blocks` blocks of exactly `steps` steps each (every block bracketed by barrier +
@@ -753,6 +790,8 @@ def main():
                                  'RCCL ncclAllReduce through the C ABI on the compute stream' if rccl_ranks else
                                  'torch.distributed all_reduce (backend %s)' % a.dist_backend)
         out.update(extra)
+        if dumped is not None:
+            out['dumped_outputs'] = dumped
         if world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(d)
         print(json.dumps(out))

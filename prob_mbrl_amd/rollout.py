@@ -2,6 +2,8 @@
 by the fused HIP kernels.  Autograd sees ONE node per rollout
 (`RolloutFunction`), not thousands of aten ops: forward = pmbrl_rollout_fwd,
 backward = pmbrl_rollout_bwd (adjoint sweep + dW GEMM)."""
+import weakref
+
 import numpy as np
 import torch
 
@@ -56,7 +58,10 @@ def _scalar_of(module, name):
 
 
 class _MaskCache:
-    """bit-packed masks keyed on the identity + version of the float mask tensor"""
+    """bit-packed masks keyed on the identity + version of the float mask tensor.  Identity is the tensor object
+    itself (a weak reference), not its address: a module built after another was freed can get the freed one's id()
+    and its mask the freed mask's device block, version counter and shape -- an address-only key then hands out the
+    freed mask's bits."""
 
     def __init__(self):
         self.store = {}
@@ -64,11 +69,11 @@ class _MaskCache:
     def get(self, key, mask, B, gen=0):
         sig = (mask.data_ptr(), mask._version, tuple(mask.shape), B, gen)
         hit = self.store.get(key)
-        if hit is None or hit[0] != sig:
+        if hit is None or hit[0] != sig or hit[2]() is not mask:
             m = mask[:B]
             if m.dtype != torch.float32:
                 m = m.float()
-            hit = (sig, E.pack_mask(m.contiguous()))
+            hit = (sig, E.pack_mask(m.contiguous()), weakref.ref(mask))
             self.store[key] = hit
         return hit[1]
 
