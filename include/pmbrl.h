@@ -151,24 +151,35 @@ typedef struct pmbrl_config {
   int32_t mm_span_ranks, mm_span_rank; /* ranks a group is spread over and this rank's index among them */
 } pmbrl_config;
 
-/* Environment switches read by pmbrl_plan_create (and by nothing else in the library).  They select between code paths
- * that compute the same results -- the tests use them to hold a non-default path against the default one, the profiles to
- * time alternatives -- and are not needed for normal use: what they override is chosen from the configuration.
- *   PMBRL_FORCE_F32=1       exact-fp32 MFMA sweeps whatever pmbrl_config.precision says
- *   PMBRL_MM_PARTS=n        moment-matching groups split over n workgroups where that can be done (1: whole groups)
- *   PMBRL_LDS_TILES=0       no LDS-resident weight tiles (pmbrl_fast.h, lds_tile_s): the shape-specialised 16-row
- *                           split-precision instances count on them, so this launches the generic instances
- *   PMBRL_MM_XCH=0          split groups exchange their rows and meet at a flag barrier (the generic kernel instances)
- *                           instead of exchanging fp64 sums as data-tagged granules (tests; A/B timing)
- *   PMBRL_MM_MODE2=1        groups that span workgroups: separate moment-matching kernels between per-step launches
+/* Environment switches of a rollout plan, read by pmbrl_plan_create (and by nothing else in the library: a plan keeps
+ * what it read).  They select between code paths that compute the same results -- the tests use them to hold a
+ * non-default path against the default one, the profiles to time alternatives -- and are not needed for normal use:
+ * what they override is chosen from the configuration.
+ * Set at all (any value, 0 included):
+ *   PMBRL_MM_PERSTEP        mm_mode 3 as one launch per step instead of one launch with a device-wide barrier per step,
+ *                           and a group beyond the CU count keeps that form instead of the one-rank span form
+ *   PMBRL_MM_MODE2          groups that span workgroups: separate moment-matching kernels between per-step launches
  *                           instead of the in-sweep form (mm_mode 3)
- *   PMBRL_MM_PERSTEP=1      mm_mode 3 as one launch per step instead of one launch with a device-wide barrier per step
- *   PMBRL_MM_NO_SPAN1=1     a group beyond the CU count keeps the per-step prologue form instead of the one-rank span form
- *   PMBRL_MM_NO_WIDE=1      states wider than 6: the one-wave moment-matching routines instead of the LDS-staged
- *                           multi-wave kernels (pmbrl_mm_wide.h)
- *   PMBRL_DW_F32=1          dW GEMM on fp32 MFMA on a split-precision plan;  PMBRL_DW_SPLIT=1: the opposite
- *   PMBRL_DW_NO_WIDE=1      no LDS-staged tile kernel for layers >= PMBRL_DW_WIDE_MIN (default 128) wide
- *   PMBRL_DW_NO_LAYER13=1   no whole-layer-per-workgroup kernel for a <= 13 x 13-tile layer
+ *   PMBRL_MM_NO_BATCH       no batches of whole groups beyond the CU count: split groups keep every workgroup resident
+ *   PMBRL_DW_NO_WIDE        no LDS-staged tile kernels for the dW GEMM of layers >= 128 x 128 (the block kernel instead)
+ *   PMBRL_REG_DEBUG         the register-resident family prints its workspace offsets at every launch
+ * Off when set to 0 (on when unset or any other number):
+ *   PMBRL_LDS_TILES         LDS-resident weight tiles (pmbrl_fast.h, lds_tile_s): the shape-specialised 16-row
+ *                           split-precision instances count on them, so =0 launches the generic instances
+ *   PMBRL_MM_XCH            split groups exchange fp64 sums as data-tagged granules; =0: they exchange their rows and
+ *                           meet at a flag barrier (the generic kernel instances)
+ *   PMBRL_MM_TREE           one group in more than 8 parts through the two-level sum exchange
+ *   PMBRL_REG, PMBRL_REG_MM, PMBRL_REG_TREE, PMBRL_REG_BWD   the register-resident family (pmbrl_reg.h): at all / with
+ *                           in-sweep moment matching / with the two-level exchange / for the adjoint sweep
+ *   PMBRL_FUSE_LOSS         the loss asked for through pmbrl_adam::loss_out_d formed by the gradient reduction and
+ *                           the optimiser launch; =0: a launch of its own inside the backward call
+ *   PMBRL_ZTAB_MERGE        the noise table of split moment-matching groups formed by extra workgroups of the
+ *                           weight-pack launch; =0: a launch of its own
+ *   PMBRL_WIDE              the in-place layers of pmbrl_wide.h for 512-wide hidden layers; =0: the generic in-place
+ *                           form, on request (rows_per_wg_hint >= 64) only
+ * Values:
+ *   PMBRL_MM_PARTS=n        moment-matching groups split over n workgroups where that can be done (1: whole groups)
+ *   PMBRL_REPLAY=0|1|2      default of pmbrl_plan_set_replay (1)
  *   PMBRL_DW_PIPE=off | n0,n1,...   dW GEMM behind the adjoint sweep on a second stream: never / these step ranges
  * Read by the Python layer: PMBRL_PRECISION (default arithmetic: f32 | split | split_f16), PMBRL_LIB_PATH (the shared
  * library to load), PMBRL_TORCH_ALLREDUCE=1 (gradient all-reduce through torch.distributed instead of the C ABI). */

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -708,88 +709,104 @@ static int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, 
   return n_blocks;
 }
 
-extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan** out) {
-  if (!cfg || !out) return fail(-1, "null argument");
-  const pmbrl_config& c = *cfg;
-  if (c.B < 1 || c.D < 1 || c.U < 1 || c.H < 1) return fail(-2, "B, D, U, H must be >= 1");
-  if (c.D > 32 || c.U > 16) return fail(-2, "supported widths: D <= 32, U <= 16");
-  if (c.reward.k < 1 || c.reward.k > PMBRL_MAX_TIP) return fail(-2, "reward.k out of range");
-  pmbrl_plan* p = new pmbrl_plan();
-  memset(p, 0, sizeof(*p));
-  p->cfg = c;
-  if (p->cfg.B_global <= 0) p->cfg.B_global = c.B;
-  p->device = device;
-  p->replay = 1;
-  if (const char* e = getenv("PMBRL_REPLAY")) p->replay = std::max(0, std::min(2, atoi(e)));
-  if (c.n_pol_angle < 0 || c.n_pol_angle > PMBRL_MAX_ANGLE || c.n_dyn_angle < 0 || c.n_dyn_angle > PMBRL_MAX_ANGLE) {
-    delete p;
+// ---------------------------------------------------------------------------
+// plan creation: pmbrl_plan_create runs the stages below in order; each one fills its part of the plan from the
+// configuration, the switches and what the stages before it chose
+// ---------------------------------------------------------------------------
+static constexpr size_t PM_LDS_CAP = 160 * 1024;
+
+static bool env_set(const char* name) { return getenv(name) != nullptr; }
+static bool env_on(const char* name) {      // unset, or a number other than 0
+  const char* e = getenv(name);
+  return !(e && atoi(e) == 0);
+}
+static PlanSwitches read_switches() {
+  PlanSwitches s{};
+  s.mm_perstep = env_set("PMBRL_MM_PERSTEP");
+  s.mm_mode2 = env_set("PMBRL_MM_MODE2");
+  s.mm_no_batch = env_set("PMBRL_MM_NO_BATCH");
+  s.dw_no_wide = env_set("PMBRL_DW_NO_WIDE");
+  s.reg_debug = env_set("PMBRL_REG_DEBUG");
+  s.lds_tiles = env_on("PMBRL_LDS_TILES");
+  s.mm_xch = env_on("PMBRL_MM_XCH");
+  s.mm_tree = env_on("PMBRL_MM_TREE");
+  s.reg = env_on("PMBRL_REG");
+  s.reg_mm = env_on("PMBRL_REG_MM");
+  s.reg_tree = env_on("PMBRL_REG_TREE");
+  s.reg_bwd = env_on("PMBRL_REG_BWD");
+  s.fuse_loss = env_on("PMBRL_FUSE_LOSS");
+  s.ztab_merge = env_on("PMBRL_ZTAB_MERGE");
+  s.wide = env_on("PMBRL_WIDE");
+  if (const char* e = getenv("PMBRL_MM_PARTS")) { s.mm_parts_set = true; s.mm_parts = atoi(e); }
+  s.replay = 1;
+  if (const char* e = getenv("PMBRL_REPLAY")) s.replay = std::max(0, std::min(2, atoi(e)));
+  if (const char* e = getenv("PMBRL_DW_PIPE")) {
+    s.dw_pipe_off = !strcmp(e, "off");
+    s.dw_pipe_ranges = e[0] >= '0' && e[0] <= '9';
+    for (const char* q = e; s.dw_pipe_ranges && *q;) {
+      const int v = atoi(q);
+      if (v > 0) s.dw_pipe.push_back(v);
+      while (*q && *q != ',') ++q;
+      if (*q == ',') ++q;
+    }
+  }
+  return s;
+}
+
+// stage 1: the configuration and the two networks
+static int plan_nets(pmbrl_plan* p) {
+  const pmbrl_config& c = p->cfg;
+  if (c.n_pol_angle < 0 || c.n_pol_angle > PMBRL_MAX_ANGLE || c.n_dyn_angle < 0 || c.n_dyn_angle > PMBRL_MAX_ANGLE)
     return fail(-2, "n_pol_angle / n_dyn_angle out of range");
-  }
-  const bool angles = c.n_pol_angle > 0 || c.n_dyn_angle > 0;
-  int rc = net_plan(c.pol, p->pol, c.D + c.n_pol_angle, 2 * c.U, "policy");
-  const bool gmm = c.dyn_components > 1;
-  if (c.dyn_components < 0 || c.dyn_components > PMBRL_MAX_COMP) {
-    delete p;
+  if (c.dyn_components < 0 || c.dyn_components > PMBRL_MAX_COMP)
     return fail(-2, "dyn_components out of range (<= PMBRL_MAX_COMP)");
-  }
+  const bool gmm = c.dyn_components > 1;
+  int rc = net_plan(c.pol, p->pol, c.D + c.n_pol_angle, 2 * c.U, "policy");
   // (mixture head: n D means, n D log-stds, n logits, one log-temperature -- examples/deep_pilco_mm.py:117-121)
   if (rc == 0)
     rc = net_plan(c.dyn, p->dyn, c.D + c.U + c.n_dyn_angle, gmm ? (2 * c.D + 1) * c.dyn_components + 1 : 2 * c.D,
                   "dynamics");
-  if (rc) { delete p; return rc; }
+  return rc;
+}
 
-  // LDS leading dimension: widest activation (any layer of either net), +8 so that
-  // LD % 16 == 8 (conflict-free ds_read_b128 for the MFMA B operand)
-  int maxnt = 1;
-  for (int i = 0; i <= p->pol.nl; ++i) maxnt = std::max(maxnt, p->pol.nt[i]);
-  for (int i = 0; i <= p->dyn.nl; ++i) maxnt = std::max(maxnt, p->dyn.nt[i]);
-  p->LD = maxnt * 16 + 8;
-
-  const bool mm = (c.flags & (PMBRL_FLAG_MM_STATES | PMBRL_FLAG_MM_REWARDS)) != 0;
-  const size_t lds_cap = 160 * 1024;
-  // infer_noise_variables (utils/rollout.py:6-17, not a default anywhere) lives in the general
-  // single-wave moment-matching routines only: general kernel family, mm_mode 1 or 2
-  p->fast = !(c.flags & (PMBRL_FLAG_FORCE_GENERIC | PMBRL_FLAG_INFER_NS | PMBRL_FLAG_POL_MASKS_PER_STEP |
-                         PMBRL_FLAG_DYN_MASKS_PER_STEP)) && !angles && !gmm &&
-            pm_fast_net_ok(p->pol.dim, p->pol.nt, p->pol.nl) &&
-            pm_fast_net_ok(p->dyn.dim, p->dyn.nt, p->dyn.nl);
+// stage 2: the layout of the sweeps.  What a choice of row tiles RT (16 rows each) asks for, as functions of the
+// networks, the precision asked for and what is given
+struct StagePair { int ca, cb; };
+struct LayoutCalc {
+  const pmbrl_plan* p;
+  int maxnt;             // widest activation (any layer of either net), in 16-wide tiles
   // general family on split operands (pmbrl_gsplit.h): two fp16 pieces forward / two bf16 pieces in the adjoint;
   // an activation buffer row is then LD 16-bit elements per piece plane, LD = 16 (mod 32)
-  const bool gsplit = !p->fast && c.precision == PMBRL_PREC_SPLIT_F16 && !getenv("PMBRL_FORCE_F32");
-  const int LD_generic = gsplit ? (maxnt * 16 + 31) / 32 * 32 + 16 : p->LD;
-  // stage sizes (k-blocks) of the weight stream: every streamed layer is padded to a whole number
-  // of stage PAIRS (CA + CB k-blocks); pick, among the instantiated pairs, the one that pads least
-  struct StagePair { int ca, cb; };
-  // split-bf16 precision: offered by the fast family for workgroups of up to 32 rows
-  const bool want_split = (c.precision == PMBRL_PREC_SPLIT || c.precision == PMBRL_PREC_SPLIT_F16) && p->fast &&
-                          !getenv("PMBRL_FORCE_F32");
-  // (64-row workgroups: two fp16 piece planes fit the LDS next to everything else, three bf16 planes do not)
+  bool gsplit;
+  bool want_split;       // split-bf16 precision: offered by the fast family for workgroups of up to 32 rows
   // 64-row workgroups on split operands: two fp16 piece planes fit the LDS (three bf16 planes do not), and
   // only the shape-specialised instance keeps its inline-asm loads clear of register-allocator copies
   // (tools/check_inflight.py; the generic 64-row split instances fail that lint and are not compiled):
   // the double cart-pole shape with in-kernel moment matching (PM_SPLIT_SHAPED_RT4), fp32 otherwise
-  bool rt4_split = c.precision == PMBRL_PREC_SPLIT_F16 && mm && c.D == 6 && c.U == 1 && p->pol.nl == 3 &&
-                   p->dyn.nl == 3 && p->pol.nt[1] == 13 && p->pol.nt[2] == 13 && p->dyn.nt[1] == 13 &&
-                   p->dyn.nt[2] == 13 && !(c.flags & PMBRL_FLAG_NO_SHAPED);
-  auto prec_for = [&](int RT) {
+  bool rt4_split;
+  // LDS leading dimension of the general family: widest activation, +8 so that LD % 16 == 8 (conflict-free
+  // ds_read_b128 for the MFMA B operand)
+  int ld_generic() const { return gsplit ? (maxnt * 16 + 31) / 32 * 32 + 16 : maxnt * 16 + 8; }
+  int prec(int RT) const {
     if (!p->fast) return gsplit ? (int)PMBRL_PREC_SPLIT_F16 : 0;
-    return (want_split && (RT <= 2 || rt4_split)) ? (int)c.precision : 0;
-  };
+    return (want_split && (RT <= 2 || rt4_split)) ? (int)p->cfg.precision : 0;
+  }
   // (kdiv: 16-wide k-blocks per stage unit -- 1 on the fp32 path, 2 = one K32 block on the split path)
-  auto stream_work = [&](int m, int kdiv) {
+  long stream_work(int m, int kdiv) const {
     long w = 0;
-    const NetPlan* nets[2] = {&p->pol, &p->dyn};
-    for (const NetPlan* n : nets)
+    for (const NetPlan* n : {&p->pol, &p->dyn})
       for (int l = 1; l <= n->nl - 2; ++l) {
         const int ki = (n->nt[l] + kdiv - 1) / kdiv, ko = (n->nt[l + 1] + kdiv - 1) / kdiv;
         w += (long)n->nt[l + 1] * ((ki + m - 1) / m * m) + (long)n->nt[l] * ((ko + m - 1) / m * m);
       }
     return w;
-  };
-  auto stages_for = [&](int RT) {
+  }
+  // stage sizes (k-blocks) of the weight stream: every streamed layer is padded to a whole number
+  // of stage PAIRS (CA + CB k-blocks); pick, among the instantiated pairs, the one that pads least
+  StagePair stages(int RT) const {
     static const StagePair cand1[] = {{8, 8}, {7, 6}, {4, 4}, {2, 2}}, cand2[] = {{4, 4}, {4, 3}, {2, 2}}, cand4[] = {{2, 2}, {1, 1}};
     static const StagePair cands[] = {{4, 3}, {1, 1}};
-    const bool sp = prec_for(RT) != 0;
+    const bool sp = prec(RT) != 0;
     const StagePair* cand = sp ? cands : RT == 1 ? cand1 : (RT == 2 ? cand2 : cand4);
     const int nc = sp ? 2 : RT == 1 ? 4 : (RT == 2 ? 3 : 2);
     const int kdiv = sp ? 2 : 1;
@@ -797,208 +814,226 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
     for (int i = 1; i < nc; ++i)
       if (stream_work(cand[i].ca + cand[i].cb, kdiv) < stream_work(best.ca + best.cb, kdiv)) best = cand[i];
     return best;
-  };
+  }
   // split path: elements per row of a bf16 piece plane = padded K + 16 (conflict-free ds_read_b128)
-  auto ldb_for = [&](int RT) {
-    if (!prec_for(RT)) return 0;
-    if (!p->fast) return LD_generic;
-    const StagePair sp = stages_for(RT);
+  int ldb(int RT) const {
+    if (!prec(RT)) return 0;
+    if (!p->fast) return ld_generic();
+    const StagePair sp = stages(RT);
     const int m = sp.ca + sp.cb;
     return ((maxnt + 1) / 2 + m - 1) / m * m * 32 + 16;
-  };
-  auto ld_for = [&](int RT) {
-    if (!p->fast) return LD_generic;
-    if (prec_for(RT))   // floats per row of a buffer holding the piece planes (3 bf16 / 2 fp16 forward, 2 bf16 adjoint)
-      return ((prec_for(RT) == PMBRL_PREC_SPLIT_F16 ? 2 : 3) * ldb_for(RT) / 2 + 3) / 4 * 4;
-    const StagePair sp = stages_for(RT);
+  }
+  int ld(int RT) const {
+    if (!p->fast) return ld_generic();
+    if (prec(RT))   // floats per row of a buffer holding the piece planes (3 bf16 / 2 fp16 forward, 2 bf16 adjoint)
+      return ((prec(RT) == PMBRL_PREC_SPLIT_F16 ? 2 : 3) * ldb(RT) / 2 + 3) / 4 * 4;
+    const StagePair sp = stages(RT);
     const int m = sp.ca + sp.cb;
     return (maxnt + m - 1) / m * m * 16 + 8;   // room for the zero K padding
-  };
-  auto lds_need = [&](int RT, int mmd, int parts = 1) {
-    p->LD = ld_for(RT);
+  }
+  // LDS of a workgroup: moment matching of mmd-wide states inside the sweep (0: none), groups split over `parts`
+  // workgroups, in-place layers (general family)
+  size_t lds(int RT, int mmd, int parts = 1, bool inplace = false) const {
+    const pmbrl_config& c = p->cfg;
     if (p->fast) {
       // in-kernel moment matching: one wave per whole group of the workgroup (a group split over `parts`
       // workgroups: wave 0, and the whole group's rows in LDS)
       const int mw = parts > 1 ? 1 : (mmd && p->M <= 16 * RT) ? std::min(PF_NW, std::max(1, 16 * RT / p->M)) : PF_NW;
-      return pm_fast_lds_floats(16 * RT, p->LD, c.D, c.U, RT, p->pol.nt, p->pol.nl, p->dyn.nt,
-                                p->dyn.nl, mmd, prec_for(RT), mw, parts > 1 ? (parts > 8 ? 16 : p->M) : 0, parts > 1 ? c.H : 0) * sizeof(float);
+      return pm_fast_lds_floats(16 * RT, ld(RT), c.D, c.U, RT, p->pol.nt, p->pol.nl, p->dyn.nt, p->dyn.nl, mmd, prec(RT),
+                                mw, parts > 1 ? (parts > 8 ? 16 : p->M) : 0, parts > 1 ? c.H : 0) * sizeof(float);
     }
-    return pm_lds_floats(16 * RT, p->LD, c.D, c.U, RT, mmd, p->inplace != 0) * sizeof(float);
+    return pm_lds_floats(16 * RT, ld(RT), c.D, c.U, RT, mmd, inplace) * sizeof(float);
+  }
+};
+
+// stage 2a: moment-matching groups -- rows per group, where the moment matching runs (mm_mode) and, in the sweep,
+// the row tiles and how groups are split over workgroups
+static int plan_groups(pmbrl_plan* p, LayoutCalc& L, int cus) {
+  const pmbrl_config& c = p->cfg;
+  const PlanSwitches& sw = p->sw;
+  p->G = c.mm_groups > 0 ? c.mm_groups : 1;
+  if (c.B % p->G) return fail(-2, "B must be divisible by mm_groups");
+  p->M = c.B / p->G;
+  if (p->M < 2) return fail(-2, "moment matching needs >= 2 rows per group");
+  if (L.rt4_split && p->fast && L.lds(4, c.D) > PM_LDS_CAP) L.rt4_split = false;   // 64-row workgroups: fp32 then
+  // groups spread over ranks: the statistics cross devices between the two halves of the moment matching, so it
+  // stays outside the sweep kernels (mm_mode 2: one sweep launch per step)
+  p->span = c.mm_span_rows > 0;
+  if (p->span) {
+    if (c.mm_span_ranks < 1 || c.mm_span_rank < 0 || c.mm_span_rank >= c.mm_span_ranks)
+      return fail(-2, "mm_span_ranks / mm_span_rank out of range");
+    if (c.mm_span_offset < 0 || c.mm_span_offset + p->M > c.mm_span_rows)
+      return fail(-2, "mm_span_offset + rows per group on this rank exceeds mm_span_rows");
+    if ((long long)p->G * c.mm_span_rows > c.B_global) return fail(-2, "mm_groups x mm_span_rows exceeds B_global");
+  }
+  // in-kernel if a whole number of groups fits a workgroup's row tiles and LDS
+  p->mm_mode = 2;
+  for (int RT : {1, 2, 4}) {
+    if (p->span) break;
+    const int R = 16 * RT;
+    if (p->M <= R && L.lds(RT, c.D) <= PM_LDS_CAP) {
+      p->mm_mode = 1;
+      p->RT = RT;
+      p->rows_per_wg = (R / p->M) * p->M;
+      break;
+    }
+  }
+  // A group of 33..64 rows in ONE 64-row workgroup is throughput-bound on its CU (52 tile epilogues and
+  // 52 x 21 MFMAs per layer: 67 k cycles per step at the double cart-pole shape) while most of the chip idles.
+  // Split over two workgroups of <= 32 rows a step is 26 k cycles of GEMMs; the halves exchange their
+  // rows through HBM and meet at a group-local flag barrier (pm_group_sync), and each factors the whole
+  // group redundantly (the d x d fp64 chain is serial anyway).  Needs every workgroup resident (checked
+  // here like the device-wide barrier form).  PMBRL_MM_PARTS=1 keeps one workgroup per group.
+  const int max_wg = std::min(cus, 1024);
+  // By default where a group needs more than 16 rows: 64-row workgroups (M = 33..64) are throughput-bound on
+  // their CU, and a 32-row workgroup (M = 17..32) still takes 30 k cycles per step against 24 k for two
+  // 16-row ones with the exchange (measured on the cart-pole shapes, also with unshaped networks) -- and
+  // where a group fits no workgroup at all (more than 64 rows, or LDS): the device-wide-barrier form would
+  // take over otherwise (D = 6, 2 x 256 hidden units, 50-row groups: 8.9 ms against 4.0 ms per iteration).
+  // Groups of up to 128 rows (beyond 64 the one-wave routines walk the rows in strides).  The fewest parts
+  // that bring a part down to 16 rows while every workgroup stays resident, else to 32 rows.
+  // PMBRL_MM_PARTS=n: n parts wherever that can be done (tests); 1: whole groups.
+  const bool big = !p->span && ((p->mm_mode == 1 && p->RT >= 2) || p->mm_mode == 2 || (sw.mm_parts_set && p->mm_mode == 1));
+  auto fits = [&](int parts, int max_rows, bool resident = true) {
+    const int rpw = (p->M + parts - 1) / parts;      // the last part takes what is left of the group
+    return rpw <= max_rows && (parts - 1) * rpw < p->M && (!resident || p->G * parts <= max_wg);
   };
+  int want = 0;
+  // Round 5: 16-row parts even where they are more workgroups than CUs (the double cart-pole shape: 100 groups of 50
+  // rows = 400 parts of <= 13 rows) IF the register-resident family takes the shape (pmbrl_reg_mm.h) -- its 16-row step
+  // is a third of the latency-optimised family's 32-row step, so two launches of 200 workgroups (batches of whole groups:
+  // what the statistics exchange needs resident together is one GROUP's workgroups) beat one launch of 200 32-row ones
+  bool batched = false;
+  if (sw.mm_parts_set) want = sw.mm_parts;
+  else {
+    for (int parts = 2; parts <= 8 && !want; ++parts) if (fits(parts, 16)) want = parts;
+    if (!want && max_wg >= 64 && pm_reg_mm_shape_ok(p, L.prec(1)) && !sw.mm_no_batch)
+      for (int parts = 2; parts <= 8 && !want; ++parts)
+        if (fits(parts, 16, false) && p->G * parts <= 1024) { want = parts; batched = true; }
+    for (int parts = 2; parts <= 8 && !want; ++parts) if (fits(parts, 32)) want = parts;
+  }
+  if (p->fast && want >= 2 && want <= 8 && big && p->M <= 128 && (batched ? fits(want, 16, false) : fits(want, 32)) &&
+      (c.flags & PMBRL_FLAG_MM_STATES)) {
+    const int rpw = (p->M + want - 1) / want;
+    const int rt = rpw <= 16 ? 1 : 2;
+    if (L.lds(rt, c.D, want) <= PM_LDS_CAP) {
+      p->mm_mode = 1;
+      p->mm_parts = want;
+      p->RT = rt;
+      p->rows_per_wg = rpw;
+      if (batched) {      // balanced batches of whole groups, each batch's workgroups resident together
+        const int nb = (p->G * want + max_wg - 1) / max_wg;
+        p->mm_gpb = (p->G + nb - 1) / nb;
+        // (the register-resident family deals hardware workgroups in blocks of 8 groups -- a group's parts on one XCD --
+        //  and launches whole blocks: a batch rounded UP to blocks must still be resident together, or the parts of
+        //  the block that straddles the chip spin until other workgroups finish a whole sweep.  G = 97 in 5 parts on
+        //  256 CUs: 49 groups -> 280 workgroups; 48 -> 240)
+        const int cap = max_wg / want / 8 * 8;
+        if (cap >= 8) p->mm_gpb = std::min((p->mm_gpb + 7) / 8 * 8, cap);
+      }
+    }
+  }
+  // A group beyond 8 parts of 32 rows -- ONE group over the whole batch, the reference's default (mm_groups=None,
+  // examples/deep_pilco_mm.py:31): 16-row parts whose sums travel over two levels (pm_xch_get_tree), every workgroup
+  // resident.  Only where the instance that exchanges sums runs (compile-time state width, the cart-pole shape:
+  // PM_SPLIT_SHAPED_CASES) -- the rows + flags form of the generic instances keeps the whole group's rows in LDS.
+  // 2 500 rows: 157 parts, 13 collectors; against the device-wide-barrier form (every workgroup re-reads and
+  // re-reduces the whole group's rows every step) 3.0 -> see profiles/r04*_single_group.txt.  PMBRL_MM_TREE=0: off.
+  const bool shaped_mm1 = p->fast && L.prec(1) == PMBRL_PREC_SPLIT_F16 && c.D == 4 && c.U == 1 && hidden_tiles_3l(p) == 13 &&
+                          !(c.flags & PMBRL_FLAG_NO_SHAPED) && sw.lds_tiles && sw.mm_xch;
+  if (p->mm_mode == 2 && !p->span && !sw.mm_parts_set && shaped_mm1 && (c.flags & PMBRL_FLAG_MM_STATES) && sw.mm_tree) {
+    const int parts = (p->M + 15) / 16;
+    if (parts > 8 && (long long)p->G * parts <= max_wg && L.ld(1) == 240) {
+      const size_t tiles = (size_t)PF_NW * pm_lds_tile_floats(14, 2, 16 * ((16 * 13 - 32 * 6) / 8)) * sizeof(float);
+      if (L.lds(1, c.D, parts) + tiles + 16 <= PM_LDS_CAP) {
+        p->mm_mode = 1;
+        p->mm_parts = parts;
+        p->RT = 1;
+        p->rows_per_wg = 16;
+        int fan = 2;
+        while (fan * fan < parts) ++fan;
+        // ONE group (mm_groups=None): two collectors per XCD -- 2 fan parts of the group on every XCD, so that the
+        // members' hop to their collector stays inside that XCD's L2 (the register-resident family deals its workgroups
+        // that way: pmbrl_reg.h, pr_wg; the latency-optimised family walks the same slots in dispatch order)
+        if (p->G == 1 && parts <= 256) fan = (parts + 15) / 16;
+        p->mm_fan = fan;
+      }
+    }
+  }
+  return 0;
+}
+
+// stage 2b: row tiles of a plan whose moment matching (if any) does not run inside the sweep
+static int plain_row_tiles(pmbrl_plan* p, const LayoutCalc& L, int cus) {
+  const pmbrl_config& c = p->cfg;
+  int RT = 1;
+  if (c.rows_per_wg_hint >= 64) RT = 4;
+  else if (c.rows_per_wg_hint >= 32) RT = 2;
+  else if (c.rows_per_wg_hint == 0) {
+    // fill the chip first: >= 2 waves of workgroups over 256 CUs before growing tiles
+    if ((c.B + 15) / 16 > 1024) RT = 2;
+    if ((c.B + 31) / 32 > 1024) RT = 4;
+    // general family (wide networks, throughput-bound): 32-row workgroups halve the weight traffic
+    // per row as soon as they still give every CU two workgroups' worth of rows
+    if (!p->fast && RT == 1 && (c.B + 31) / 32 >= 512) RT = 2;
+  }
+  while (RT > 1 && L.lds(RT, 0) > PM_LDS_CAP) RT /= 2;
+  // General family on split operands: 64-row workgroups with IN-PLACE layers (one activation buffer, pmbrl_gsplit.h:
+  // gemm_layer_inplace_s) where two buffers of 64 rows do not fit the LDS.  Built to stream a 512 x 512 layer's weights
+  // once per 64 rows instead of once per 32; measured at the C5 shape (profiles/r03b_inplace_*): a hidden layer's K loop
+  // does become MFMA-bound (25 k cycles per 64 rows), but with every wave's epilogues behind one barrier they no
+  // longer overlap another wave's MFMAs (+36 k), and the stash stores of a policy layer, issued back to back, cost
+  // 26 k cycles more -- 46.7 ms per iteration against 45.3 ms for the two-buffer 32-row form.  So it is taken only
+  // on request (rows_per_wg_hint >= 64): widths <= 512, every narrow width (2U, 2D, D + U) <= 64, no mixture head,
+  // no angle features.
+  const bool angles = c.n_pol_angle > 0 || c.n_dyn_angle > 0;
+  if (L.gsplit && !angles && c.dyn_components <= 1 && L.maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
+      c.D + c.U <= PM_IP_NOFF && RT < 4) {
+    // every hidden layer 512 wide: the in-place layers of pmbrl_wide.h (compile-time shape, lean epilogue) -- taken by
+    // default as soon as 64-row workgroups still give every CU one (PMBRL_WIDE=0: the generic in-place form on
+    // request only, as before)
+    bool wide = p->sw.wide;
+    for (int i = 1; i < p->pol.nl; ++i) wide = wide && p->pol.nt[i] == 32;
+    for (int i = 1; i < p->dyn.nl; ++i) wide = wide && p->dyn.nt[i] == 32;
+    const bool want = c.rows_per_wg_hint >= 64 || (wide && c.rows_per_wg_hint == 0 && cus > 0 && (c.B + 63) / 64 >= cus);
+    if (want) {
+      p->inplace = wide ? 2 : 1;
+      if (L.lds(4, 0, 1, true) <= PM_LDS_CAP) RT = 4;
+      else p->inplace = 0;
+    }
+  }
+  return RT;
+}
+
+static int plan_layout(pmbrl_plan* p, int cus) {
+  const pmbrl_config& c = p->cfg;
+  const PlanSwitches& sw = p->sw;
+  const bool mm = (c.flags & (PMBRL_FLAG_MM_STATES | PMBRL_FLAG_MM_REWARDS)) != 0;
+  // infer_noise_variables (utils/rollout.py:6-17, not a default anywhere) lives in the general
+  // single-wave moment-matching routines only: general kernel family, mm_mode 1 or 2
+  p->fast = !(c.flags & (PMBRL_FLAG_FORCE_GENERIC | PMBRL_FLAG_INFER_NS | PMBRL_FLAG_POL_MASKS_PER_STEP |
+                         PMBRL_FLAG_DYN_MASKS_PER_STEP)) && c.n_pol_angle == 0 && c.n_dyn_angle == 0 && c.dyn_components <= 1 &&
+            pm_fast_net_ok(p->pol.dim, p->pol.nt, p->pol.nl) &&
+            pm_fast_net_ok(p->dyn.dim, p->dyn.nt, p->dyn.nl);
+  LayoutCalc L;
+  L.p = p;
+  L.maxnt = 1;
+  for (int i = 0; i <= p->pol.nl; ++i) L.maxnt = std::max(L.maxnt, p->pol.nt[i]);
+  for (int i = 0; i <= p->dyn.nl; ++i) L.maxnt = std::max(L.maxnt, p->dyn.nt[i]);
+  L.gsplit = !p->fast && c.precision == PMBRL_PREC_SPLIT_F16;
+  L.want_split = (c.precision == PMBRL_PREC_SPLIT || c.precision == PMBRL_PREC_SPLIT_F16) && p->fast;
+  L.rt4_split = c.precision == PMBRL_PREC_SPLIT_F16 && mm && c.D == 6 && c.U == 1 && hidden_tiles_3l(p) == 13 &&
+                !(c.flags & PMBRL_FLAG_NO_SHAPED);
   p->G = 1;
   p->M = c.B;
   p->mm_mode = 0;
   p->mm_parts = 1;
-  if (mm) {
-    p->G = c.mm_groups > 0 ? c.mm_groups : 1;
-    if (c.B % p->G) { delete p; return fail(-2, "B must be divisible by mm_groups"); }
-    p->M = c.B / p->G;
-    if (p->M < 2) { delete p; return fail(-2, "moment matching needs >= 2 rows per group"); }
-    if (rt4_split && p->fast && lds_need(4, c.D) > lds_cap) rt4_split = false;   // 64-row workgroups: fp32 then
-    // groups spread over ranks: the statistics cross devices between the two halves of the moment matching, so it
-    // stays outside the sweep kernels (mm_mode 2: one sweep launch per step)
-    p->span = c.mm_span_rows > 0;
-    if (p->span) {
-      if (c.mm_span_ranks < 1 || c.mm_span_rank < 0 || c.mm_span_rank >= c.mm_span_ranks) {
-        delete p; return fail(-2, "mm_span_ranks / mm_span_rank out of range");
-      }
-      if (c.mm_span_offset < 0 || c.mm_span_offset + p->M > c.mm_span_rows) {
-        delete p; return fail(-2, "mm_span_offset + rows per group on this rank exceeds mm_span_rows");
-      }
-      if ((long long)p->G * c.mm_span_rows > p->cfg.B_global) {
-        delete p; return fail(-2, "mm_groups x mm_span_rows exceeds B_global");
-      }
-    }
-    // in-kernel if a whole number of groups fits a workgroup's row tiles and LDS
-    p->mm_mode = 2;
-    for (int RT : {1, 2, 4}) {
-      if (p->span) break;
-      const int R = 16 * RT;
-      if (p->M <= R && lds_need(RT, c.D) <= lds_cap) {
-        p->mm_mode = 1;
-        p->RT = RT;
-        p->rows_per_wg = (R / p->M) * p->M;
-        break;
-      }
-    }
-    // A group of 33..64 rows in ONE 64-row workgroup is throughput-bound on its CU (52 tile epilogues and
-    // 52 x 21 MFMAs per layer: 67 k cycles per step at the double cart-pole shape) while most of the chip idles.
-    // Split over two workgroups of <= 32 rows a step is 26 k cycles of GEMMs; the halves exchange their
-    // rows through HBM and meet at a group-local flag barrier (pm_group_sync), and each factors the whole
-    // group redundantly (the d x d fp64 chain is serial anyway).  Needs every workgroup resident (checked
-    // here like the device-wide barrier form).  PMBRL_MM_PARTS=1 keeps one workgroup per group.
-    p->mm_parts = 1;
-    {
-      const char* e = getenv("PMBRL_MM_PARTS");
-      int cus = 0;
-      (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-      const int max_wg = std::min(cus, 1024);
-      // By default where a group needs more than 16 rows: 64-row workgroups (M = 33..64) are throughput-bound on
-      // their CU, and a 32-row workgroup (M = 17..32) still takes 30 k cycles per step against 24 k for two
-      // 16-row ones with the exchange (measured on the cart-pole shapes, also with unshaped networks) -- and
-      // where a group fits no workgroup at all (more than 64 rows, or LDS): the device-wide-barrier form would
-      // take over otherwise (D = 6, 2 x 256 hidden units, 50-row groups: 8.9 ms against 4.0 ms per iteration).
-      // Groups of up to 128 rows (beyond 64 the one-wave routines walk the rows in strides).  The fewest parts
-      // that bring a part down to 16 rows while every workgroup stays resident, else to 32 rows.
-      // PMBRL_MM_PARTS=n: n parts wherever that can be done (tests); 1: whole groups.
-      const bool big = !p->span && ((p->mm_mode == 1 && p->RT >= 2) || p->mm_mode == 2 || (e && p->mm_mode == 1));
-      auto fits = [&](int parts, int max_rows, bool resident = true) {
-        const int rpw = (p->M + parts - 1) / parts;      // the last part takes what is left of the group
-        return rpw <= max_rows && (parts - 1) * rpw < p->M && (!resident || p->G * parts <= max_wg);
-      };
-      int want = 0;
-      // Round 5: 16-row parts even where they are more workgroups than CUs (the double cart-pole shape: 100 groups of 50
-      // rows = 400 parts of <= 13 rows) IF the register-resident family takes the shape (pmbrl_reg_mm.h) -- its 16-row step
-      // is a third of the latency-optimised family's 32-row step, so two launches of 200 workgroups (batches of whole groups:
-      // what the statistics exchange needs resident together is one GROUP's workgroups) beat one launch of 200 32-row ones
-      bool batched = false;
-      if (e) want = atoi(e);
-      else {
-        for (int parts = 2; parts <= 8 && !want; ++parts) if (fits(parts, 16)) want = parts;
-        if (!want && max_wg >= 64 && pm_reg_mm_shape_ok(p, prec_for(1)) && !getenv("PMBRL_MM_NO_BATCH"))
-          for (int parts = 2; parts <= 8 && !want; ++parts)
-            if (fits(parts, 16, false) && p->G * parts <= 1024) { want = parts; batched = true; }
-        for (int parts = 2; parts <= 8 && !want; ++parts) if (fits(parts, 32)) want = parts;
-      }
-      p->mm_gpb = 0;
-      if (p->fast && want >= 2 && want <= 8 && big && p->M <= 128 && (batched ? fits(want, 16, false) : fits(want, 32)) &&
-          (c.flags & PMBRL_FLAG_MM_STATES)) {
-        const int rpw = (p->M + want - 1) / want;
-        const int rt = rpw <= 16 ? 1 : 2;
-        if (lds_need(rt, c.D, want) <= lds_cap) {
-          p->mm_mode = 1;
-          p->mm_parts = want;
-          p->RT = rt;
-          p->rows_per_wg = rpw;
-          if (batched) {      // balanced batches of whole groups, each batch's workgroups resident together
-            const int nb = (p->G * want + max_wg - 1) / max_wg;
-            p->mm_gpb = (p->G + nb - 1) / nb;
-            // (the register-resident family deals hardware workgroups in blocks of 8 groups -- a group's parts on one XCD --
-            //  and launches whole blocks: a batch rounded UP to blocks must still be resident together, or the parts of
-            //  the block that straddles the chip spin until other workgroups finish a whole sweep.  G = 97 in 5 parts on
-            //  256 CUs: 49 groups -> 280 workgroups; 48 -> 240)
-            if (!(getenv("PMBRL_XCH_XCD") && atoi(getenv("PMBRL_XCH_XCD")) == 0)) {
-              const int cap = max_wg / want / 8 * 8;
-              if (cap >= 8) p->mm_gpb = std::min((p->mm_gpb + 7) / 8 * 8, cap);
-            }
-          }
-        }
-      }
-      // A group beyond 8 parts of 32 rows -- ONE group over the whole batch, the reference's default (mm_groups=None,
-      // examples/deep_pilco_mm.py:31): 16-row parts whose sums travel over two levels (pm_xch_get_tree), every workgroup
-      // resident.  Only where the instance that exchanges sums runs (compile-time state width, the cart-pole shape:
-      // PM_SPLIT_SHAPED_CASES) -- the rows + flags form of the generic instances keeps the whole group's rows in LDS.
-      // 2 500 rows: 157 parts, 13 collectors; against the device-wide-barrier form (every workgroup re-reads and
-      // re-reduces the whole group's rows every step) 3.0 -> see profiles/r04*_single_group.txt.  PMBRL_MM_TREE=0: off.
-      const bool shaped_mm1 = p->fast && prec_for(1) == PMBRL_PREC_SPLIT_F16 && c.D == 4 && c.U == 1 && p->pol.nl == 3 &&
-                              p->dyn.nl == 3 && p->pol.nt[1] == 13 && p->pol.nt[2] == 13 && p->dyn.nt[1] == 13 && p->dyn.nt[2] == 13 &&
-                              !(c.flags & PMBRL_FLAG_NO_SHAPED) && !(getenv("PMBRL_LDS_TILES") && atoi(getenv("PMBRL_LDS_TILES")) == 0) &&
-                              !(getenv("PMBRL_MM_XCH") && atoi(getenv("PMBRL_MM_XCH")) == 0);
-      if (p->mm_mode == 2 && !p->span && !e && shaped_mm1 && (c.flags & PMBRL_FLAG_MM_STATES) &&
-          !(getenv("PMBRL_MM_TREE") && atoi(getenv("PMBRL_MM_TREE")) == 0)) {
-        const int parts = (p->M + 15) / 16;
-        if (parts > 8 && (long long)p->G * parts <= max_wg && ld_for(1) == 240) {
-          const size_t tiles = (size_t)PF_NW * pm_lds_tile_floats(14, 2, 16 * ((16 * 13 - 32 * 6) / 8)) * sizeof(float);
-          if (lds_need(1, c.D, parts) + tiles + 16 <= lds_cap) {
-            p->mm_mode = 1;
-            p->mm_parts = parts;
-            p->RT = 1;
-            p->rows_per_wg = 16;
-            int fan = 2;
-            while (fan * fan < parts) ++fan;
-            // ONE group (mm_groups=None): two collectors per XCD -- 2 fan parts of the group on every XCD, so that the
-            // members' hop to their collector stays inside that XCD's L2 (the register-resident family deals its workgroups
-            // that way: pmbrl_reg.h, pr_wg; the latency-optimised family walks the same slots in dispatch order)
-            if (p->G == 1 && parts <= 256) fan = (parts + 15) / 16;
-            p->mm_fan = fan;
-          }
-        }
-      }
-    }
-  }
+  if (mm)
+    if (int rc = plan_groups(p, L, cus)) return rc;
   if (p->mm_mode != 1) {
-    rt4_split = false;
-    int RT = 1;
-    if (c.rows_per_wg_hint >= 64) RT = 4;
-    else if (c.rows_per_wg_hint >= 32) RT = 2;
-    else if (c.rows_per_wg_hint == 0) {
-      // fill the chip first: >= 2 waves of workgroups over 256 CUs before growing tiles
-      if ((c.B + 15) / 16 > 1024) RT = 2;
-      if ((c.B + 31) / 32 > 1024) RT = 4;
-      // general family (wide networks, throughput-bound): 32-row workgroups halve the weight traffic
-      // per row as soon as they still give every CU two workgroups' worth of rows
-      if (!p->fast && RT == 1 && (c.B + 31) / 32 >= 512) RT = 2;
-    }
-    while (RT > 1 && lds_need(RT, 0) > lds_cap) RT /= 2;
-    // General family on split operands: 64-row workgroups with IN-PLACE layers (one activation buffer, pmbrl_gsplit.h:
-    // gemm_layer_inplace_s) where two buffers of 64 rows do not fit the LDS.  Built to stream a 512 x 512 layer's weights
-    // once per 64 rows instead of once per 32; measured at the C5 shape (profiles/r03b_inplace_*): a hidden layer's K loop
-    // does become MFMA-bound (25 k cycles per 64 rows), but with every wave's epilogues behind one barrier they no
-    // longer overlap another wave's MFMAs (+36 k), and the stash stores of a policy layer, issued back to back, cost
-    // 26 k cycles more -- 46.7 ms per iteration against 45.3 ms for the two-buffer 32-row form.  So it is taken only
-    // on request (rows_per_wg_hint >= 64): widths <= 512, every narrow width (2U, 2D, D + U) <= 64, no mixture head,
-    // no angle features.
-    if (gsplit && !angles && !gmm && maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
-        c.D + c.U <= PM_IP_NOFF && RT < 4) {
-      // every hidden layer 512 wide: the in-place layers of pmbrl_wide.h (compile-time shape, lean epilogue) -- taken by
-      // default as soon as 64-row workgroups still give every CU one (PMBRL_WIDE=0: the generic in-place form on
-      // request only, as before)
-      bool wide = true;
-      for (int i = 1; i < p->pol.nl; ++i) wide = wide && p->pol.nt[i] == 32;
-      for (int i = 1; i < p->dyn.nl; ++i) wide = wide && p->dyn.nt[i] == 32;
-      if (const char* e = getenv("PMBRL_WIDE")) wide = wide && atoi(e) != 0;
-      int cus = 0;
-      if (wide && c.rows_per_wg_hint == 0)      // (of the device the plan is for, not of the current one)
-        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-      const bool want = c.rows_per_wg_hint >= 64 || (wide && c.rows_per_wg_hint == 0 && cus > 0 && (c.B + 63) / 64 >= cus);
-      if (want) {
-        p->inplace = wide ? 2 : 1;
-        if (lds_need(4, 0) <= lds_cap) RT = 4;
-        else p->inplace = 0;
-      }
-    }
-    p->RT = RT;
-    p->rows_per_wg = 16 * RT;
+    L.rt4_split = false;
+    p->RT = plain_row_tiles(p, L, cus);
+    p->rows_per_wg = 16 * p->RT;
   } else if (c.rows_per_wg_hint > 0 && p->mm_parts <= 1) {
     // allow the caller to force fewer groups per workgroup
     const int want = std::max(p->M, (c.rows_per_wg_hint / p->M) * p->M);
@@ -1008,54 +1043,46 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
   // its per-step launches (mm_mode 3) when it has a compile-time-width instance and the partial
   // Gram tiles fit the activation buffers; otherwise separate kernels per step (mm_mode 2)
   if (p->mm_mode == 2 && !p->span && p->fast && (c.flags & PMBRL_FLAG_MM_STATES) && c.D >= 4 && c.D <= 6 &&
-      !getenv("PMBRL_MM_MODE2") && lds_need(p->RT, c.D) <= lds_cap &&
-      (size_t)2 * 16 * p->RT * ld_for(p->RT) * sizeof(float) >= (size_t)8 * 256 * sizeof(double))
+      !sw.mm_mode2 && L.lds(p->RT, c.D) <= PM_LDS_CAP &&
+      (size_t)2 * 16 * p->RT * L.ld(p->RT) * sizeof(float) >= (size_t)8 * 256 * sizeof(double))
     p->mm_mode = 3;
-  p->lds_bytes = lds_need(p->RT, (p->mm_mode == 1 || p->mm_mode == 3) ? c.D : 0, p->mm_parts);   // also fixes p->LD for the chosen RT
-  { const StagePair sp = stages_for(p->RT); p->CA = sp.ca; p->CB = sp.cb; }
-  p->prec = prec_for(p->RT);
-  p->LDB = ldb_for(p->RT);
-  if (p->lds_bytes > lds_cap) { delete p; return fail(-3, "network too wide for the fused kernel's LDS budget"); }
+  p->LD = L.ld(p->RT);
+  p->lds_bytes = L.lds(p->RT, (p->mm_mode == 1 || p->mm_mode == 3) ? c.D : 0, p->mm_parts, p->inplace != 0);
+  const StagePair sp = L.stages(p->RT);
+  p->CA = sp.ca;
+  p->CB = sp.cb;
+  p->prec = L.prec(p->RT);
+  p->LDB = L.ldb(p->RT);
+  if (p->lds_bytes > PM_LDS_CAP) return fail(-3, "network too wide for the fused kernel's LDS budget");
   p->nwg = p->mm_parts > 1 ? p->G * p->mm_parts : (c.B + p->rows_per_wg - 1) / p->rows_per_wg;
   // groups spanning workgroups, every workgroup resident at once (one per CU always fits): the
   // per-step launches become one launch whose workgroups meet at a device-wide barrier per step
-  p->mm_grid = 0;
-  if (p->mm_mode == 3 && p->RT == 1 && !getenv("PMBRL_MM_PERSTEP")) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device) == hipSuccess && p->nwg <= cus &&
-        p->nwg <= 1024)
-      p->mm_grid = 1;
-  }
+  p->mm_grid = p->mm_mode == 3 && p->RT == 1 && !sw.mm_perstep && p->nwg <= cus && p->nwg <= 1024;
   // More workgroups than CUs under ONE launch cannot meet at a barrier: the sweeps would run one launch per step with
   // the whole group's moment matching redone in the prologue of EVERY workgroup (one group of 5000 rows: 9.7 ms per
   // forward + adjoint, 10 000 rows: 23.4 ms).  The form built for groups spread over ranks does better there --
   // statistics over 16 workgroups, one factorisation, rows by all threads (pmbrl_mmx.h): 4.3 / 6.4 ms -- so such a
   // plan is the span form with ONE rank, whose exchange is the identity (profiles/r02n_span_cost.txt).
   // PMBRL_MM_PERSTEP keeps the per-step prologue form (tests).
-  int cus_now = 0;
-  (void)hipDeviceGetAttribute(&cus_now, hipDeviceAttributeMultiprocessorCount, p->device);
-  if (p->mm_mode == 3 && !p->mm_grid && !p->span && p->M >= 2048 && cus_now > 0 && p->nwg > cus_now &&
-      !(c.flags & PMBRL_FLAG_INFER_NS) && !getenv("PMBRL_MM_PERSTEP") && !getenv("PMBRL_MM_NO_SPAN1")) {
+  if (p->mm_mode == 3 && !p->mm_grid && !p->span && p->M >= 2048 && cus > 0 && p->nwg > cus &&
+      !(c.flags & PMBRL_FLAG_INFER_NS) && !sw.mm_perstep) {
     p->span = 1;
     p->cfg.mm_span_rows = p->M;
     p->cfg.mm_span_offset = p->cfg.row_offset;   // (the groups are local: only the noise row needs the shard's offset)
     p->cfg.mm_span_ranks = 1;
     p->cfg.mm_span_rank = 0;
     p->mm_mode = 2;
-    p->lds_bytes = lds_need(p->RT, 0, 1);
+    p->lds_bytes = L.lds(p->RT, 0);
   }
 
   // LDS-resident tiles of the sweeps' second streamed layer (pmbrl_fast.h, lds_tile_s): the shape-specialised 16-row
   // split-precision instances (two streamed layers of 13 or 14 tiles, stage pair = one tile) keep 8 tiles of it in the
   // LDS the workgroup has to itself anyway; the launch decides per kernel variant (pmbrl_fast_split.hip).
   // PMBRL_LDS_TILES=0: off.
-  p->wlds_off = 0;
-  p->lds_last_lanes = 0;
-  if (p->fast && p->RT == 1 && p->prec == PMBRL_PREC_SPLIT_F16 && p->CA + p->CB == 7 && p->pol.nl == 3 && p->dyn.nl == 3 &&
-      p->pol.nt[1] == p->dyn.nt[1] && p->pol.nt[2] == p->pol.nt[1] && p->dyn.nt[2] == p->pol.nt[1] &&
-      (p->pol.nt[1] == 13 || p->pol.nt[1] == 14) && !(c.flags & PMBRL_FLAG_NO_SHAPED) &&
-      !(getenv("PMBRL_LDS_TILES") && atoi(getenv("PMBRL_LDS_TILES")) == 0)) {
-    const int last_lanes = 16 * ((16 * p->pol.nt[1] - 32 * 6) / 8);
+  const int ht = hidden_tiles_3l(p);
+  if (p->fast && p->RT == 1 && p->prec == PMBRL_PREC_SPLIT_F16 && p->CA + p->CB == 7 && (ht == 13 || ht == 14) &&
+      !(c.flags & PMBRL_FLAG_NO_SHAPED) && sw.lds_tiles) {
+    const int last_lanes = 16 * ((16 * ht - 32 * 6) / 8);
     size_t base = (p->lds_bytes + 15) / 16 * 16;
     if (p->mm_parts > 1) {
       // split groups: the instances that hold the tiles exchange sums and never touch the row blocks of the rows +
@@ -1063,338 +1090,342 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
       // 100-row group in seven parts would not fit both)
       const int mw = 1;
       base = pm_fast_rows_area_off(16 * p->RT, p->LD, c.D, c.U, p->RT, p->pol.nt, p->pol.nl, p->dyn.nt, p->dyn.nl, c.D,
-                                   prec_for(p->RT), mw, p->mm_parts > 8 ? 16 : p->M, c.H) * sizeof(float);
+                                   p->prec, mw, p->mm_parts > 8 ? 16 : p->M, c.H) * sizeof(float);
       base = (base + 15) / 16 * 16;
     }
     const size_t tiles = (size_t)PF_NW * pm_lds_tile_floats(14, 2, last_lanes) * sizeof(float);
-    if (base + tiles <= lds_cap) {
+    if (base + tiles <= PM_LDS_CAP) {
       p->wlds_off = (int)(base / sizeof(float));
       p->lds_last_lanes = last_lanes;
       p->lds_bytes = std::max(p->lds_bytes, base + tiles);
     }
   }
 
-  // wide states between per-step launches: the LDS-staged multi-wave kernels (PMBRL_MM_NO_WIDE: the one-wave routines)
-  p->mm_wide = p->mm_mode == 2 && !p->span && (c.flags & PMBRL_FLAG_MM_STATES) && pm_mmw_ok(p->M, c.D, c.flags) &&
-               !getenv("PMBRL_MM_NO_WIDE");
-  HIPCHK(hipSetDevice(device));
-  // reward constants
-  {
-    RewardDev r;
-    memset(&r, 0, sizeof(r));
-    const pmbrl_reward& s = c.reward;
-    r.kind = s.kind;
-    r.expand = s.expand;
-    r.k = s.k;
-    r.n_angle = s.expand ? s.n_angle : 0;
-    if (r.n_angle > PMBRL_MAX_ANGLE) { delete p; return fail(-2, "too many angle dims"); }
-    int no = 0;
-    for (int i = 0; i < c.D; ++i) {
-      bool isang = false;
-      for (int j = 0; j < r.n_angle; ++j) isang |= (s.angle_dims[j] == i);
-      if (!isang) r.other_dims[no++] = i;
+  // wide states between per-step launches: the LDS-staged multi-wave kernels
+  p->mm_wide = p->mm_mode == 2 && !p->span && (c.flags & PMBRL_FLAG_MM_STATES) && pm_mmw_ok(p->M, c.D, c.flags);
+  return 0;
+}
+
+// stage 3: reward constants
+static int plan_reward(pmbrl_plan* p) {
+  const pmbrl_config& c = p->cfg;
+  HIPCHK(hipSetDevice(p->device));
+  RewardDev r;
+  memset(&r, 0, sizeof(r));
+  const pmbrl_reward& s = c.reward;
+  r.kind = s.kind;
+  r.expand = s.expand;
+  r.k = s.k;
+  r.n_angle = s.expand ? s.n_angle : 0;
+  if (r.n_angle > PMBRL_MAX_ANGLE) return fail(-2, "too many angle dims");
+  int no = 0;
+  for (int i = 0; i < c.D; ++i) {
+    bool isang = false;
+    for (int j = 0; j < r.n_angle; ++j) isang |= (s.angle_dims[j] == i);
+    if (!isang) r.other_dims[no++] = i;
+  }
+  for (int j = 0; j < r.n_angle; ++j) {
+    if (s.angle_dims[j] < 0 || s.angle_dims[j] >= c.D) return fail(-2, "angle dim out of range");
+    r.angle_dims[j] = s.angle_dims[j];
+  }
+  r.n_other = s.expand ? no : c.D;
+  r.De = s.expand ? no + 2 * r.n_angle : c.D;
+  if (r.De > PMBRL_MAX_DIM) return fail(-2, "expanded state too wide");
+  for (int i = 0; i < s.k; ++i) {
+    for (int j = 0; j < r.De; ++j) r.C[i * r.De + j] = s.C[i * r.De + j] / s.norm;
+    r.tt[i] = s.tip_target[i] / s.norm;
+  }
+  r.w = s.w;
+  for (int i = 0; i < s.k; ++i)
+    for (int j = 0; j < s.k; ++j) {
+      r.Q[i * s.k + j] = s.Q[i * s.k + j];
+      r.QQ[i * s.k + j] = s.Q[i * s.k + j] + s.Q[j * s.k + i];
     }
+  for (int i = 0; i < c.U; ++i)
+    for (int j = 0; j < c.U; ++j) {
+      r.R[i * c.U + j] = s.R[i * c.U + j];
+      r.RR[i * c.U + j] = s.R[i * c.U + j] + s.R[j * c.U + i];
+    }
+  for (int d = 0; d < PMBRL_MAX_DIM; ++d) r.d_copy[d] = r.d_sin[d] = r.d_cos[d] = -1;
+  if (s.expand) {
+    for (int i = 0; i < no; ++i) { r.phi_src[i] = r.other_dims[i]; r.phi_mode[i] = 0; r.d_copy[r.other_dims[i]] = i; }
     for (int j = 0; j < r.n_angle; ++j) {
-      if (s.angle_dims[j] < 0 || s.angle_dims[j] >= c.D) { delete p; return fail(-2, "angle dim out of range"); }
-      r.angle_dims[j] = s.angle_dims[j];
+      r.phi_src[no + j] = r.angle_dims[j]; r.phi_mode[no + j] = 1; r.d_sin[r.angle_dims[j]] = no + j;
+      r.phi_src[no + r.n_angle + j] = r.angle_dims[j]; r.phi_mode[no + r.n_angle + j] = 2;
+      r.d_cos[r.angle_dims[j]] = no + r.n_angle + j;
     }
-    r.n_other = s.expand ? no : c.D;
-    r.De = s.expand ? no + 2 * r.n_angle : c.D;
-    if (r.De > PMBRL_MAX_DIM) { delete p; return fail(-2, "expanded state too wide"); }
-    for (int i = 0; i < s.k; ++i) {
-      for (int j = 0; j < r.De; ++j) r.C[i * r.De + j] = s.C[i * r.De + j] / s.norm;
-      r.tt[i] = s.tip_target[i] / s.norm;
+  } else {
+    for (int i = 0; i < c.D; ++i) { r.phi_src[i] = i; r.phi_mode[i] = 0; r.d_copy[i] = i; }
+  }
+  if ((size_t)256 * (c.D | 1) * sizeof(float) > 64 * 1024)      // (rows of a block staged in LDS)
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(pm_reward_kernel_for(c.U, r.k)),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, 256 * (c.D | 1) * (int)sizeof(float)));
+  p->rew_k = r.k;
+  HIPCHK(hipMalloc(&p->rew_d, sizeof(RewardDev)));
+  HIPCHK(hipMemcpy(p->rew_d, &r, sizeof(RewardDev), hipMemcpyHostToDevice));
+  HIPCHK(hipMalloc(&p->wflag_d, sizeof(int)));
+  HIPCHK(hipMemset(p->wflag_d, 0, sizeof(int)));
+  return 0;
+}
+
+// stage 4: angle_dims feature maps (utils/angles.py:29-42: others in order, then sin, then cos)
+static int plan_angles(pmbrl_plan* p) {
+  const pmbrl_config& c = p->cfg;
+  if (c.n_pol_angle == 0 && c.n_dyn_angle == 0) return 0;
+  AngleDev a;
+  memset(&a, 0, sizeof(a));
+  auto build = [&](FeatMap& m, int width, int n_ang, const int32_t* dims, int max_dim) -> bool {
+    for (int d = 0; d < PMBRL_MAX_DIM; ++d) m.f_copy[d] = m.f_sin[d] = m.f_cos[d] = -1;
+    for (int j = 0; j < n_ang; ++j) {
+      if (dims[j] < 0 || dims[j] >= max_dim) return false;
+      for (int i = 0; i < j; ++i)
+        if (dims[i] == dims[j]) return false;
     }
-    r.w = s.w;
-    for (int i = 0; i < s.k; ++i)
-      for (int j = 0; j < s.k; ++j) {
-        r.Q[i * s.k + j] = s.Q[i * s.k + j];
-        r.QQ[i * s.k + j] = s.Q[i * s.k + j] + s.Q[j * s.k + i];
+    int no = 0;
+    for (int i = 0; i < width; ++i) {
+      bool isang = false;
+      for (int j = 0; j < n_ang; ++j) isang |= (dims[j] == i);
+      if (!isang) { m.src[no] = i; m.mode[no] = 0; m.f_copy[i] = no; ++no; }
+    }
+    for (int j = 0; j < n_ang; ++j) {
+      m.src[no + j] = dims[j]; m.mode[no + j] = 1; m.f_sin[dims[j]] = no + j;
+      m.src[no + n_ang + j] = dims[j]; m.mode[no + n_ang + j] = 2; m.f_cos[dims[j]] = no + n_ang + j;
+    }
+    m.n_feat = no + 2 * n_ang;
+    return m.n_feat <= PMBRL_MAX_DIM;
+  };
+  if (!build(a.pol, c.D, c.n_pol_angle, c.pol_angle_dims, c.D) ||
+      !build(a.dyn, c.D + c.U, c.n_dyn_angle, c.dyn_angle_dims, c.D))
+    return fail(-2, "angle dims must be distinct state dims (0 <= d < D)");
+  HIPCHK(hipMalloc(&p->ang_d, sizeof(AngleDev)));
+  HIPCHK(hipMemcpy(p->ang_d, &a, sizeof(AngleDev), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// stage 5: the policy's dW GEMM -- wave blocks of the block kernels, tile units of the wide layers, chunks
+static int plan_dw(pmbrl_plan* p) {
+  const pmbrl_config& c = p->cfg;
+  std::vector<DwBlock> blocks;
+  // split-operand form of the dW GEMM (pmbrl_dw.h, pm_dw_kernel_s): where the fp32 form is bound by the matrix
+  // core -- 32- / 64-row workgroups and the general family's wide networks; the 16-row sweeps' dW is HBM-bound
+  p->dw_split = p->prec != 0 && (p->RT >= 2 || !p->fast);
+  // wide layers of the split form go to the LDS-staged tile kernel (pmbrl_dw.h, pm_dw_wide_kernel)
+  bool wide[PM_MAXL] = {false};
+  std::vector<DwUnit> units;
+  // (layers of at least 128 x 128 on the split-precision plans: also the 200 x 200 layer of the cart-pole shapes,
+  //  whose block-kernel GEMM re-read its stash 1.5 x -- C2 0.116 -> 0.102 ms, C4 0.50 -> 0.38 ms; the exact-fp32
+  //  plans keep the fp32 block kernel for every layer)
+  p->dw_layer13 = -1;
+  if (p->prec != 0 && !p->sw.dw_no_wide)
+    for (int l = 0; l < p->pol.nl; ++l)
+      if (p->pol.nt[l + 1] * 16 >= 128 && p->pol.nt[l] * 16 >= 128) {
+        wide[l] = true;
+        if (p->dw_layer13 < 0 && p->pol.nt[l + 1] <= PM_DWL_NT && p->pol.nt[l] <= PM_DWL_NT) {
+          // a whole layer of up to 13 x 13 tiles per workgroup
+          p->dw_layer13 = l;
+          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_kernel),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
+          continue;
+        }
+        for (int m0 = 0; m0 < p->pol.nt[l + 1] * 16; m0 += PM_DWW_TM)
+          for (int n0 = 0; n0 < p->pol.nt[l] * 16; n0 += PM_DWW_TN) units.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
       }
-    for (int i = 0; i < c.U; ++i)
-      for (int j = 0; j < c.U; ++j) {
-        r.R[i * c.U + j] = s.R[i * c.U + j];
-        r.RR[i * c.U + j] = s.R[i * c.U + j] + s.R[j * c.U + i];
+  // Round 6: the wide sweeps (64-row workgroups, in-place 512-wide layers: pmbrl_wide.h) write the stashes of the 512 x 512
+  // layers PRE-SPLIT, in the layout pm_dw_wide_pre_kernel streams into LDS without touching a register (pmbrl_dw.h).
+  // Every wide layer 512 x 512 exactly (32 tiles: the stash block's tile count).  (Such a plan has dw_split: the
+  // pre-split kernels walk chunk pairs.)
+  if (!units.empty() && p->inplace == 2 && p->RT == 4) {
+    bool all = true;
+    for (const DwUnit& u : units) all = all && p->pol.nt[u.layer] == 32 && p->pol.nt[u.layer + 1] == 32 &&
+                                        p->pol.dim[u.layer] == 512 && p->pol.dim[u.layer + 1] == 512;
+    // ... and every OTHER layer narrow on one side, 512 wide on the other (first layer: <= 32 inputs; head: <= 32 outputs):
+    // pm_dw_narrow_pre_kernel -- so that EVERY 512-wide stash is pre-split and the sweeps carry one form of stash store
+    for (int l = 0; l < p->pol.nl && all; ++l) {
+      bool is = false;
+      for (const DwUnit& u : units) is = is || u.layer == l;
+      p->dw_narrow[l] = 0;
+      if (is) continue;
+      if (p->pol.nt[l + 1] == 32 && p->pol.dim[l + 1] == 512 && p->pol.nt[l] <= 2) p->dw_narrow[l] = 1;
+      else if (p->pol.nt[l] == 32 && p->pol.dim[l] == 512 && p->pol.nt[l + 1] <= 2) p->dw_narrow[l] = 2;
+      else all = false;
+    }
+    if (all) {
+      std::vector<DwUnit> pre;
+      for (int l = 0; l < p->pol.nl; ++l) {
+        if (p->dw_narrow[l]) { wide[l] = true; continue; }      // (not the block kernels': skipped by build_dw_blocks)
+        p->dw_pre_mask |= 1u << l;
+        for (int m0 = 0; m0 < 512; m0 += PM_DWP_TM)
+          for (int n0 = 0; n0 < 512; n0 += PM_DWP_TN) pre.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
       }
-    for (int d = 0; d < PMBRL_MAX_DIM; ++d) r.d_copy[d] = r.d_sin[d] = r.d_cos[d] = -1;
-    if (s.expand) {
-      for (int i = 0; i < no; ++i) { r.phi_src[i] = r.other_dims[i]; r.phi_mode[i] = 0; r.d_copy[r.other_dims[i]] = i; }
-      for (int j = 0; j < r.n_angle; ++j) {
-        r.phi_src[no + j] = r.angle_dims[j]; r.phi_mode[no + j] = 1; r.d_sin[r.angle_dims[j]] = no + j;
-        r.phi_src[no + r.n_angle + j] = r.angle_dims[j]; r.phi_mode[no + r.n_angle + j] = 2;
-        r.d_cos[r.angle_dims[j]] = no + r.n_angle + j;
-      }
+      units = pre;
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<2>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
     } else {
-      for (int i = 0; i < c.D; ++i) { r.phi_src[i] = i; r.phi_mode[i] = 0; r.d_copy[i] = i; }
-    }
-    if ((size_t)256 * (c.D | 1) * sizeof(float) > 64 * 1024)      // (rows of a block staged in LDS)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(pm_reward_kernel_for(c.U, r.k)),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, 256 * (c.D | 1) * (int)sizeof(float)));
-    p->rew_k = r.k;
-    HIPCHK(hipMalloc(&p->rew_d, sizeof(RewardDev)));
-    HIPCHK(hipMemcpy(p->rew_d, &r, sizeof(RewardDev), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&p->wflag_d, sizeof(int)));
-    HIPCHK(hipMemset(p->wflag_d, 0, sizeof(int)));
-    p->wgen = 0;
-  }
-  // angle_dims feature maps (utils/angles.py:29-42: others in order, then sin, then cos)
-  if (angles) {
-    AngleDev a;
-    memset(&a, 0, sizeof(a));
-    auto build = [&](FeatMap& m, int width, int n_ang, const int32_t* dims, int max_dim) -> bool {
-      for (int d = 0; d < PMBRL_MAX_DIM; ++d) m.f_copy[d] = m.f_sin[d] = m.f_cos[d] = -1;
-      for (int j = 0; j < n_ang; ++j) {
-        if (dims[j] < 0 || dims[j] >= max_dim) return false;
-        for (int i = 0; i < j; ++i)
-          if (dims[i] == dims[j]) return false;
-      }
-      int no = 0;
-      for (int i = 0; i < width; ++i) {
-        bool isang = false;
-        for (int j = 0; j < n_ang; ++j) isang |= (dims[j] == i);
-        if (!isang) { m.src[no] = i; m.mode[no] = 0; m.f_copy[i] = no; ++no; }
-      }
-      for (int j = 0; j < n_ang; ++j) {
-        m.src[no + j] = dims[j]; m.mode[no + j] = 1; m.f_sin[dims[j]] = no + j;
-        m.src[no + n_ang + j] = dims[j]; m.mode[no + n_ang + j] = 2; m.f_cos[dims[j]] = no + n_ang + j;
-      }
-      m.n_feat = no + 2 * n_ang;
-      return m.n_feat <= PMBRL_MAX_DIM;
-    };
-    if (!build(a.pol, c.D, c.n_pol_angle, c.pol_angle_dims, c.D) ||
-        !build(a.dyn, c.D + c.U, c.n_dyn_angle, c.dyn_angle_dims, c.D)) {
-      pmbrl_plan_destroy(p);
-      return fail(-2, "angle dims must be distinct state dims (0 <= d < D)");
-    }
-    HIPCHK(hipMalloc(&p->ang_d, sizeof(AngleDev)));
-    HIPCHK(hipMemcpy(p->ang_d, &a, sizeof(AngleDev), hipMemcpyHostToDevice));
-  }
-  {
-    std::vector<DwBlock> blocks;
-    // split-operand form of the dW GEMM (pmbrl_dw.h, pm_dw_kernel_s): where the fp32 form is bound by the matrix
-    // core -- 32- / 64-row workgroups and the general family's wide networks; the 16-row sweeps' dW is HBM-bound
-    p->dw_split = p->prec != 0 && (p->RT >= 2 || !p->fast) && !getenv("PMBRL_DW_F32");
-    if (getenv("PMBRL_DW_SPLIT") && p->prec != 0) p->dw_split = 1;
-    // wide layers of the split form go to the LDS-staged tile kernel (pmbrl_dw.h, pm_dw_wide_kernel)
-    bool wide[PM_MAXL] = {false};
-    std::vector<DwUnit> units;
-    // (layers of at least 128 x 128 on the split-precision plans: also the 200 x 200 layer of the cart-pole shapes,
-    //  whose block-kernel GEMM re-read its stash 1.5 x -- C2 0.116 -> 0.102 ms, C4 0.50 -> 0.38 ms; the exact-fp32
-    //  plans keep the fp32 block kernel for every layer)
-    const int wide_min = getenv("PMBRL_DW_WIDE_MIN") ? atoi(getenv("PMBRL_DW_WIDE_MIN")) : 128;
-    p->dw_layer13 = -1;
-    if (p->prec != 0 && !getenv("PMBRL_DW_NO_WIDE"))
-      for (int l = 0; l < p->pol.nl; ++l)
-        if (p->pol.nt[l + 1] * 16 >= wide_min && p->pol.nt[l] * 16 >= wide_min) {
-          if (p->dw_layer13 < 0 && p->pol.nt[l + 1] <= PM_DWL_NT && p->pol.nt[l] <= PM_DWL_NT && !getenv("PMBRL_DW_NO_LAYER13")) {
-            // a whole layer of up to 13 x 13 tiles per workgroup
-            wide[l] = true;
-            p->dw_layer13 = l;
-            HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
-            continue;
-          }
-          wide[l] = true;
-          for (int m0 = 0; m0 < p->pol.nt[l + 1] * 16; m0 += PM_DWW_TM)
-            for (int n0 = 0; n0 < p->pol.nt[l] * 16; n0 += PM_DWW_TN) units.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
-        }
-    // Round 6: the wide sweeps (64-row workgroups, in-place 512-wide layers: pmbrl_wide.h) write the stashes of the 512 x 512
-    // layers PRE-SPLIT, in the layout pm_dw_wide_pre_kernel streams into LDS without touching a register (pmbrl_dw.h).
-    // Every wide layer 512 x 512 exactly (32 tiles: the stash block's tile count); PMBRL_DW_PRE=0: the fp32 stash.
-    p->dw_pre_mask = 0;
-    if (!units.empty() && p->inplace == 2 && p->RT == 4 && !(getenv("PMBRL_DW_PRE") && atoi(getenv("PMBRL_DW_PRE")) == 0)) {
-      bool all = true;
-      for (const DwUnit& u : units) all = all && p->pol.nt[u.layer] == 32 && p->pol.nt[u.layer + 1] == 32 &&
-                                          p->pol.dim[u.layer] == 512 && p->pol.dim[u.layer + 1] == 512;
-      // ... and every OTHER layer narrow on one side, 512 wide on the other (first layer: <= 32 inputs; head: <= 32 outputs):
-      // pm_dw_narrow_pre_kernel -- so that EVERY 512-wide stash is pre-split and the sweeps carry one form of stash store
-      for (int l = 0; l < p->pol.nl && all; ++l) {
-        bool is = false;
-        for (const DwUnit& u : units) is = is || u.layer == l;
-        p->dw_narrow[l] = 0;
-        if (is) continue;
-        if (p->pol.nt[l + 1] == 32 && p->pol.dim[l + 1] == 512 && p->pol.nt[l] <= 2) p->dw_narrow[l] = 1;
-        else if (p->pol.nt[l] == 32 && p->pol.dim[l] == 512 && p->pol.nt[l + 1] <= 2) p->dw_narrow[l] = 2;
-        else all = false;
-      }
-      if (all) {
-        std::vector<DwUnit> pre;
-        for (int l = 0; l < p->pol.nl; ++l) {
-          if (p->dw_narrow[l]) { wide[l] = true; continue; }      // (not the block kernels': skipped by build_dw_blocks)
-          p->dw_pre_mask |= 1u << l;
-          for (int m0 = 0; m0 < 512; m0 += PM_DWP_TM)
-            for (int n0 = 0; n0 < 512; n0 += PM_DWP_TN) pre.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
-        }
-        units = pre;
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<2>),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-      } else {
-        for (int l = 0; l < PM_MAXL; ++l) p->dw_narrow[l] = 0;
-      }
-    }
-    p->n_dw_units = (int)units.size();
-    if (p->n_dw_units) {
-      HIPCHK(hipMalloc(&p->dw_units_d, units.size() * sizeof(DwUnit)));
-      HIPCHK(hipMemcpy(p->dw_units_d, units.data(), units.size() * sizeof(DwUnit), hipMemcpyHostToDevice));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWW_LDS_BYTES));
-      if (p->dw_pre_mask)
-        HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_pre_kernel),
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-    }
-    p->n_dw_blocks = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first, p->dw_split ? PM_DW_TN_S : PM_DW_TN, wide);
-    p->dw_n_chunks = c.H * p->nwg * p->RT;
-    int nsplit = std::min(256, p->dw_n_chunks);   // one 8-wave workgroup per CU
-    p->dw_chunks_per_split = (p->dw_n_chunks + nsplit - 1) / nsplit;
-    if (p->dw_split) p->dw_chunks_per_split = (p->dw_chunks_per_split + 1) & ~1;   // whole chunk pairs
-    p->dw_nsplit = (p->dw_n_chunks + p->dw_chunks_per_split - 1) / p->dw_chunks_per_split;
-    HIPCHK(hipMalloc(&p->dw_blocks_d, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock)));
-    if (!blocks.empty())
-      HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock),
-                       hipMemcpyHostToDevice));
-  }
-  {
-    // dW GEMM behind the adjoint sweep.  The sweep is latency-bound and holds nwg CUs completely (its
-    // workgroups take a CU's whole register file); with fewer workgroups than CUs the rest of the chip idles
-    // for its duration, and the dW GEMM -- 12-17 % of an iteration -- used to start when the sweep had
-    // finished.  It needs only the deltas of the steps already swept: the sweep becomes pipe_K launches
-    // over descending step ranges (the state gradient is carried through HBM, as in the per-step launch
-    // modes) and the GEMM of range k runs next to the sweep of range k+1, on a second stream, in a grid that
-    // fits the idle CUs (workgroups go round-robin to the 8 XCDs, so per XCD: CUs/8 - ceil(nwg/8) are free)
-    // with workgroups that cannot share a CU with the sweep's.  Only the last, short range is exposed.
-    // Correctness never depends on the overlap: every dependency is a stream event.
-    p->pipe_K = 1;
-    const bool no_pipe_pre = p->dw_pre_mask != 0;      // (the pre-split GEMMs run once, behind the whole sweep)
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
-    const char* e = getenv("PMBRL_DW_PIPE");
-    const int n_free = cus >= 64 && cus % 8 == 0 ? 8 * (cus / 8 - (p->nwg + 7) / 8) : 0;
-    const bool single = (p->mm_mode == 0 || p->mm_mode == 1) && p->mm_parts <= 1;   // (no second kernel next to flag barriers)
-    // Worth it where a range of the sweep is long against a launch boundary (tail of the last step, launch
-    // gap, the next launch's prologue: 15 us at 16 rows per workgroup, 40 us at 64) -- measured: the double
-    // cart-pole shape (64-row workgroups, 30 us per step) gains 7 % of an iteration, the cart-pole shapes
-    // (6 / 13 us per step) lose 1-5 %.  Proxy for the step time: rows per workgroup x weights of both nets.
-    const bool explicit_ranges = e && e[0] >= '0' && e[0] <= '9';
-    const bool long_steps = (long long)p->RT * (long long)(p->pol.n_params + p->dyn.n_params) >= 256 * 1024 && c.H >= 16;
-    if (single && !no_pipe_pre && n_free >= cus / 8 && c.H >= 2 && !(e && !strcmp(e, "off")) && (long_steps || explicit_ranges)) {
-      std::vector<int> cnt;
-      if (explicit_ranges) {     // PMBRL_DW_PIPE=n0,n1,...: steps per range, highest steps first (tests, tuning)
-        int sum = 0;
-        for (const char* q = e; *q;) {
-          const int v = atoi(q);
-          if (v > 0) { cnt.push_back(v); sum += v; }
-          while (*q && *q != ',') ++q;
-          if (*q == ',') ++q;
-        }
-        if (sum != c.H || (int)cnt.size() > PM_PIPE_MAX) cnt.clear();
-      }
-      if (cnt.empty() && long_steps) {
-        // 40 / 30 / 20 / 10 % of the horizon: the exposed tail is the GEMM of the last tenth
-        const int a3 = std::max(2, c.H / 10), a2 = a3 + std::max(2, c.H / 5), a1 = a2 + std::max(2, (3 * c.H) / 10);
-        cnt = {c.H - a1, a1 - a2, a2 - a3, a3};
-      }
-      // lower step bound of every range (the last one ends at step 0; ranges emptied by the adjustment are dropped)
-      int K = 0, lo = c.H;
-      for (size_t k = 0; k < cnt.size() && lo > 0; ++k) {
-        lo = k + 1 == cnt.size() ? 0 : std::max(0, lo - cnt[k]);
-        // split-operand GEMM: a K = 32 chunk pair must not straddle two launches
-        if (p->dw_split && ((p->nwg * p->RT) & 1) && (lo & 1)) lo -= 1;
-        if (K > 0 && lo >= p->pipe_lo[K - 1]) continue;
-        p->pipe_lo[K++] = lo;
-      }
-      if (K >= 2 && p->pipe_lo[K - 1] == 0) {
-        p->pipe_K = K;
-        p->pipe_grid = n_free;                     // workgroups (= partial rows) of a GEMM launch next to the sweep
-        p->pipe_rows = std::max(n_free, cus);      // ... of the last launch, which has the chip to itself
-        HIPCHK(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
-        for (int k = 0; k < p->pipe_K; ++k) HIPCHK(hipEventCreateWithFlags(&p->pipe_ev[k], hipEventDisableTiming));
-      }
+      for (int l = 0; l < PM_MAXL; ++l) p->dw_narrow[l] = 0;
     }
   }
+  p->n_dw_units = (int)units.size();
+  if (p->n_dw_units) {
+    HIPCHK(hipMalloc(&p->dw_units_d, units.size() * sizeof(DwUnit)));
+    HIPCHK(hipMemcpy(p->dw_units_d, units.data(), units.size() * sizeof(DwUnit), hipMemcpyHostToDevice));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWW_LDS_BYTES));
+    if (p->dw_pre_mask)
+      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_pre_kernel),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
+  }
+  p->n_dw_blocks = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first, p->dw_split ? PM_DW_TN_S : PM_DW_TN, wide);
+  p->dw_n_chunks = c.H * p->nwg * p->RT;
+  int nsplit = std::min(256, p->dw_n_chunks);   // one 8-wave workgroup per CU
+  p->dw_chunks_per_split = (p->dw_n_chunks + nsplit - 1) / nsplit;
+  if (p->dw_split) p->dw_chunks_per_split = (p->dw_chunks_per_split + 1) & ~1;   // whole chunk pairs
+  p->dw_nsplit = (p->dw_n_chunks + p->dw_chunks_per_split - 1) / p->dw_chunks_per_split;
+  HIPCHK(hipMalloc(&p->dw_blocks_d, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock)));
+  if (!blocks.empty())
+    HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
+  return 0;
+}
+
+// stage 6: dW GEMM behind the adjoint sweep.  The sweep is latency-bound and holds nwg CUs completely (its
+// workgroups take a CU's whole register file); with fewer workgroups than CUs the rest of the chip idles
+// for its duration, and the dW GEMM -- 12-17 % of an iteration -- used to start when the sweep had
+// finished.  It needs only the deltas of the steps already swept: the sweep becomes pipe_K launches
+// over descending step ranges (the state gradient is carried through HBM, as in the per-step launch
+// modes) and the GEMM of range k runs next to the sweep of range k+1, on a second stream, in a grid that
+// fits the idle CUs (workgroups go round-robin to the 8 XCDs, so per XCD: CUs/8 - ceil(nwg/8) are free)
+// with workgroups that cannot share a CU with the sweep's.  Only the last, short range is exposed.
+// Correctness never depends on the overlap: every dependency is a stream event.
+static int plan_dw_pipe(pmbrl_plan* p, int cus) {
+  const pmbrl_config& c = p->cfg;
+  const PlanSwitches& sw = p->sw;
+  p->pipe_K = 1;
+  const bool no_pipe_pre = p->dw_pre_mask != 0;      // (the pre-split GEMMs run once, behind the whole sweep)
+  const int n_free = cus >= 64 && cus % 8 == 0 ? 8 * (cus / 8 - (p->nwg + 7) / 8) : 0;
+  const bool single = (p->mm_mode == 0 || p->mm_mode == 1) && p->mm_parts <= 1;   // (no second kernel next to flag barriers)
+  // Worth it where a range of the sweep is long against a launch boundary (tail of the last step, launch
+  // gap, the next launch's prologue: 15 us at 16 rows per workgroup, 40 us at 64) -- measured: the double
+  // cart-pole shape (64-row workgroups, 30 us per step) gains 7 % of an iteration, the cart-pole shapes
+  // (6 / 13 us per step) lose 1-5 %.  Proxy for the step time: rows per workgroup x weights of both nets.
+  const bool long_steps = (long long)p->RT * (long long)(p->pol.n_params + p->dyn.n_params) >= 256 * 1024 && c.H >= 16;
+  if (!single || no_pipe_pre || n_free < cus / 8 || c.H < 2 || sw.dw_pipe_off || !(long_steps || sw.dw_pipe_ranges))
+    return 0;
+  std::vector<int> cnt;
+  if (sw.dw_pipe_ranges) {     // PMBRL_DW_PIPE=n0,n1,...: steps per range, highest steps first (tests, tuning)
+    cnt = sw.dw_pipe;
+    int sum = 0;
+    for (int v : cnt) sum += v;
+    if (sum != c.H || (int)cnt.size() > PM_PIPE_MAX) cnt.clear();
+  }
+  if (cnt.empty() && long_steps) {
+    // 40 / 30 / 20 / 10 % of the horizon: the exposed tail is the GEMM of the last tenth
+    const int a3 = std::max(2, c.H / 10), a2 = a3 + std::max(2, c.H / 5), a1 = a2 + std::max(2, (3 * c.H) / 10);
+    cnt = {c.H - a1, a1 - a2, a2 - a3, a3};
+  }
+  // lower step bound of every range (the last one ends at step 0; ranges emptied by the adjustment are dropped)
+  int K = 0, lo = c.H;
+  for (size_t k = 0; k < cnt.size() && lo > 0; ++k) {
+    lo = k + 1 == cnt.size() ? 0 : std::max(0, lo - cnt[k]);
+    // split-operand GEMM: a K = 32 chunk pair must not straddle two launches
+    if (p->dw_split && ((p->nwg * p->RT) & 1) && (lo & 1)) lo -= 1;
+    if (K > 0 && lo >= p->pipe_lo[K - 1]) continue;
+    p->pipe_lo[K++] = lo;
+  }
+  if (K >= 2 && p->pipe_lo[K - 1] == 0) {
+    p->pipe_K = K;
+    p->pipe_grid = n_free;                     // workgroups (= partial rows) of a GEMM launch next to the sweep
+    p->pipe_rows = std::max(n_free, cus);      // ... of the last launch, which has the chip to itself
+    HIPCHK(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
+    for (int k = 0; k < p->pipe_K; ++k) HIPCHK(hipEventCreateWithFlags(&p->pipe_ev[k], hipEventDisableTiming));
+  }
+  return 0;
+}
+
+// stage 7: the register-resident family, and the workspace carve-up
+static int plan_workspace(pmbrl_plan* p) {
+  const pmbrl_config& c = p->cfg;
   p->reg = pm_reg_plan_ok(p) ? 1 : 0;
   p->reg_mm = pm_reg_mm_width(p);
-  p->reg_bwd = !(getenv("PMBRL_REG_BWD") && atoi(getenv("PMBRL_REG_BWD")) == 0);      // (read once: a recorded call bakes the choice in)
-  // workspace carve-up
-  {
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-      const size_t o = off;
-      off = align_up(off + bytes, 256);
-      return o;
-    };
-    NetPlan* nets[2] = {&p->pol, &p->dyn};
-    for (NetPlan* n : nets) {
-      for (int l = 0; l < n->nl; ++l) {
-        const size_t fr = (size_t)(n->nt[l + 1] + 15) * (n->nt[l] + 15) * 256 * sizeof(float);
-        n->wf[l] = take(fr);
-        n->wb[l] = take(fr);
-        n->bias[l] = take((size_t)n->nt[l + 1] * 16 * sizeof(float));
-        if (l < n->nl - 1)
-          // u16 (generic) or 4 nibble-bytes (fast); 256 bytes of slack behind it: where the register-resident family's
-          // rows past the batch put their (zero) bytes -- lane (< 64) + 4 x tile (< 64) past the end (pmbrl_reg.h)
-          n->abits[l] = take((size_t)c.H * c.B * n->nt[l + 1] * 4 + 256);
-      }
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t o = off;
+    off = align_up(off + bytes, 256);
+    return o;
+  };
+  for (NetPlan* n : {&p->pol, &p->dyn}) {
+    for (int l = 0; l < n->nl; ++l) {
+      const size_t fr = (size_t)(n->nt[l + 1] + 15) * (n->nt[l] + 15) * 256 * sizeof(float);
+      n->wf[l] = take(fr);
+      n->wb[l] = take(fr);
+      n->bias[l] = take((size_t)n->nt[l + 1] * 16 * sizeof(float));
+      if (l < n->nl - 1)
+        // u16 (generic) or 4 nibble-bytes (fast); 256 bytes of slack behind it: where the register-resident family's
+        // rows past the batch put their (zero) bytes -- lane (< 64) + 4 x tile (< 64) past the end (pmbrl_reg.h)
+        n->abits[l] = take((size_t)c.H * c.B * n->nt[l + 1] * 4 + 256);
     }
-    const size_t Rw = 16 * p->RT;
-    for (int l = 0; l < p->pol.nl; ++l) {
-      p->off_actT[l] = take((size_t)c.H * p->nwg * p->pol.nt[l] * 16 * Rw * sizeof(float));
-      p->off_gT[l] = take((size_t)c.H * p->nwg * p->pol.nt[l + 1] * 16 * Rw * sizeof(float));
-    }
-    p->off_Tp = take((size_t)c.H * c.B * c.U * sizeof(float));
-    p->off_Td = take((size_t)c.H * c.B * c.D * sizeof(float));
-    p->off_gmm_c = take(gmm ? (size_t)c.H * c.B * (c.dyn_components + 1) * c.D * sizeof(float) : 0);
-    p->off_gmm_k = take(gmm ? (size_t)c.H * c.B * sizeof(int) : 0);
-    p->off_xt = take((size_t)c.H * c.B * c.D * sizeof(float));
-    p->off_rt = take((size_t)c.H * c.B * sizeof(float));
-    p->off_mmfac = take(p->mm_mode == 1 ? (size_t)c.H * (c.B / p->M) * pm_mm_fac_doubles(c.D) * sizeof(double)
-                        : p->mm_wide    ? (size_t)c.H * p->G * pm_mmw_fac_doubles(c.D) * sizeof(double)
-                                        : 0);
-    p->off_Jx = take((size_t)c.H * c.B * c.D * sizeof(float));
-    p->off_Ja = take((size_t)c.H * c.B * c.U * sizeof(float));
-    p->off_gxc = take((size_t)c.B * c.D * sizeof(float));
-    p->off_gxc2 = take((size_t)c.B * c.D * sizeof(float));
-    p->off_gsync = take(2 * 1024 * sizeof(unsigned));   // one flag per workgroup for the device-wide barriers (forward, backward)
-    // groups split over workgroups: the granules of their statistics exchange (pm_xch_sum; PMBRL_MM_XCH=0: rows + flags)
-    p->xch_bytes = 0;
-    if (p->mm_parts > 1 && !(getenv("PMBRL_MM_XCH") && atoi(getenv("PMBRL_MM_XCH")) == 0)) {
-      // (more than 8 parts: a second set of slots, the collectors')
-      p->xch_bytes = (size_t)(p->mm_parts > 8 ? 2 : 1) * p->nwg * PM_XCH_WG_WORDS(2) * sizeof(unsigned long long);
-      p->off_xch = take(p->xch_bytes);
-    }
-    p->off_ztab = take((p->mm_fan || p->reg_mm) ? (size_t)c.H * p->G * 2 * c.D * sizeof(double) : 0);
-    p->off_reg_linv = take(p->reg_mm ? (size_t)c.H * p->G * c.D * c.D * sizeof(double) : 0);
-    p->off_grt = take((size_t)c.H * c.B * sizeof(float));
-    {
-      // statistics exchange of groups spread over ranks: forward slots of every rank (states of one step, or the
-      // rewards of all steps), the factors the adjoint reuses
-      const size_t n_s = (size_t)p->G * pm_mmx_slot_doubles(c.D), n_r = (size_t)c.H * p->G * pm_mmx_slot_doubles(1);
-      p->off_mmx_buf = take(p->span ? (size_t)p->cfg.mm_span_ranks * std::max(n_s * PM_MMX_NB, n_r) * sizeof(double) : 0);
-      p->off_mmx_fac = take(p->span ? (size_t)c.H * p->G * pm_mm_fac_doubles(c.D) * sizeof(double) : 0);
-      p->off_mmx_rfac = take(p->span ? (size_t)c.H * p->G * pm_mm_fac_doubles(1) * sizeof(double) : 0);
-    }
-    p->off_reg_pack = take(p->reg ? pm_reg_pack_bytes() : 0);
-    for (int n = 0; n < 2; ++n)
-      for (int l = 0; l < 2; ++l) p->off_reg_ab[n][l] = take(p->reg ? (size_t)c.H * p->nwg * 1024 : 0);
-    p->off_part = take((size_t)std::max(p->dw_nsplit, p->pipe_K > 1 ? p->pipe_rows : 0) *
-                       ((p->pol.n_params + 3) / 4 * 4) * sizeof(float));
-    p->ws_bytes = off;
-    if (p->ws_bytes >= ((size_t)1 << 32)) p->reg = p->reg_mm = 0;      // (the family addresses its stashes with 32-bit workspace offsets)
   }
-  int rc2 = 0;
+  const bool gmm = c.dyn_components > 1;
+  const size_t Rw = 16 * p->RT;
+  for (int l = 0; l < p->pol.nl; ++l) {
+    p->off_actT[l] = take((size_t)c.H * p->nwg * p->pol.nt[l] * 16 * Rw * sizeof(float));
+    p->off_gT[l] = take((size_t)c.H * p->nwg * p->pol.nt[l + 1] * 16 * Rw * sizeof(float));
+  }
+  p->off_Tp = take((size_t)c.H * c.B * c.U * sizeof(float));
+  p->off_Td = take((size_t)c.H * c.B * c.D * sizeof(float));
+  p->off_gmm_c = take(gmm ? (size_t)c.H * c.B * (c.dyn_components + 1) * c.D * sizeof(float) : 0);
+  p->off_gmm_k = take(gmm ? (size_t)c.H * c.B * sizeof(int) : 0);
+  p->off_xt = take((size_t)c.H * c.B * c.D * sizeof(float));
+  p->off_rt = take((size_t)c.H * c.B * sizeof(float));
+  p->off_mmfac = take(p->mm_mode == 1 ? (size_t)c.H * (c.B / p->M) * pm_mm_fac_doubles(c.D) * sizeof(double)
+                      : p->mm_wide    ? (size_t)c.H * p->G * pm_mmw_fac_doubles(c.D) * sizeof(double)
+                                      : 0);
+  p->off_Jx = take((size_t)c.H * c.B * c.D * sizeof(float));
+  p->off_Ja = take((size_t)c.H * c.B * c.U * sizeof(float));
+  p->off_gxc = take((size_t)c.B * c.D * sizeof(float));
+  p->off_gxc2 = take((size_t)c.B * c.D * sizeof(float));
+  p->off_gsync = take(2 * 1024 * sizeof(unsigned));   // one flag per workgroup for the device-wide barriers (forward, backward)
+  // groups split over workgroups: the granules of their statistics exchange (pm_xch_sum; PMBRL_MM_XCH=0: rows + flags)
+  if (p->mm_parts > 1 && p->sw.mm_xch) {
+    // (more than 8 parts: a second set of slots, the collectors')
+    p->xch_bytes = (size_t)(p->mm_parts > 8 ? 2 : 1) * p->nwg * PM_XCH_WG_WORDS(2) * sizeof(unsigned long long);
+    p->off_xch = take(p->xch_bytes);
+  }
+  p->off_ztab = take((p->mm_fan || p->reg_mm) ? (size_t)c.H * p->G * 2 * c.D * sizeof(double) : 0);
+  p->off_reg_linv = take(p->reg_mm ? (size_t)c.H * p->G * c.D * c.D * sizeof(double) : 0);
+  p->off_grt = take((size_t)c.H * c.B * sizeof(float));
+  // statistics exchange of groups spread over ranks: forward slots of every rank (states of one step, or the
+  // rewards of all steps), the factors the adjoint reuses
+  const size_t n_s = (size_t)p->G * pm_mmx_slot_doubles(c.D), n_r = (size_t)c.H * p->G * pm_mmx_slot_doubles(1);
+  p->off_mmx_buf = take(p->span ? (size_t)c.mm_span_ranks * std::max(n_s * PM_MMX_NB, n_r) * sizeof(double) : 0);
+  p->off_mmx_fac = take(p->span ? (size_t)c.H * p->G * pm_mm_fac_doubles(c.D) * sizeof(double) : 0);
+  p->off_mmx_rfac = take(p->span ? (size_t)c.H * p->G * pm_mm_fac_doubles(1) * sizeof(double) : 0);
+  p->off_reg_pack = take(p->reg ? pm_reg_pack_bytes() : 0);
+  for (int n = 0; n < 2; ++n)
+    for (int l = 0; l < 2; ++l) p->off_reg_ab[n][l] = take(p->reg ? (size_t)c.H * p->nwg * 1024 : 0);
+  p->off_part = take((size_t)std::max(p->dw_nsplit, p->pipe_K > 1 ? p->pipe_rows : 0) *
+                     ((p->pol.n_params + 3) / 4 * 4) * sizeof(float));
+  p->ws_bytes = off;
+  if (p->ws_bytes >= ((size_t)1 << 32)) p->reg = p->reg_mm = 0;      // (the family addresses its stashes with 32-bit workspace offsets)
+  return 0;
+}
+
+// stage 8: kernel attributes, and the residency the barrier form relies on
+static int plan_attrs(pmbrl_plan* p, int cus) {
+  const pmbrl_config& c = p->cfg;
+  int rc = 0;
   if (!p->fast && p->prec) {
-    rc2 = pm_general_split_set_attr(p);
+    rc = pm_general_split_set_attr(p);
   } else if (!p->fast) {
     switch (p->RT) {
-      case 1: rc2 = set_attr<1>(p->lds_bytes); break;
-      case 2: rc2 = set_attr<2>(p->lds_bytes); break;
-      default: rc2 = set_attr<4>(p->lds_bytes); break;
+      case 1: rc = set_attr<1>(p->lds_bytes); break;
+      case 2: rc = set_attr<2>(p->lds_bytes); break;
+      default: rc = set_attr<4>(p->lds_bytes); break;
     }
   } else if (p->prec) {
-    rc2 = p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_set_attr(p) : pm_fast_split1_set_attr(p);
+    rc = p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_set_attr(p) : pm_fast_split1_set_attr(p);
   } else {
-    rc2 = pm_fast_f32_set_attr(p);
+    rc = pm_fast_f32_set_attr(p);
   }
   if (p->mm_wide) {
     const int smem = (int)pm_mmw_lds_bytes(p->M, c.D, true);
@@ -1404,37 +1435,58 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
          hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mmw_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                              smem) != hipSuccess)) {
       (void)hipGetLastError();
-      pmbrl_plan_destroy(p);
       return fail(-3, "hipFuncSetAttribute(wide moment-matching kernels) failed");
     }
   }
   if (p->mm_mode == 2 || p->mm_mode == 3) {
     const int smem = (int)(pm_mm_kernel_doubles(c.D) * sizeof(double));
-    if (smem > (int)lds_cap) { pmbrl_plan_destroy(p); return fail(-3, "moment-matching scratch exceeds the LDS"); }
-    if (smem > 64 * 1024) {
-      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mm_fwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess ||
-          hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mm_bwd_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, smem) != hipSuccess) {
-        (void)hipGetLastError();
-        pmbrl_plan_destroy(p);
-        return fail(-3, "hipFuncSetAttribute(moment-matching kernels) failed");
-      }
+    if (smem > (int)PM_LDS_CAP) return fail(-3, "moment-matching scratch exceeds the LDS");
+    if (smem > 64 * 1024 &&
+        (hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mm_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             smem) != hipSuccess ||
+         hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mm_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                             smem) != hipSuccess)) {
+      (void)hipGetLastError();
+      return fail(-3, "hipFuncSetAttribute(moment-matching kernels) failed");
     }
   }
-  if (!rc2 && p->reg) rc2 = pm_reg_set_attr(p);
-  if (rc2) { pmbrl_plan_destroy(p); return rc2; }
+  if (!rc && p->reg) rc = pm_reg_set_attr(p);
+  if (rc) return rc;
   if (p->mm_grid) {
     // the barrier-form sweep needs every workgroup resident at once: ask the runtime how many of THIS
     // kernel (registers, LDS) fit a CU instead of assuming one
     const int per_cu = p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_mmg_blocks_per_cu(p)
                        : p->prec                        ? pm_fast_split1_mmg_blocks_per_cu(p)
                                                         : pm_fast_f32_mmg_blocks_per_cu(p);
-    int cus = 0;
-    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p->device);
     if (per_cu < 1 || p->nwg > cus) p->mm_grid = 0;     // (one per CU is all that is relied upon)
   }
-  *out = p;
+  return 0;
+}
+
+extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan** out) {
+  if (!cfg || !out) return fail(-1, "null argument");
+  const pmbrl_config& c = *cfg;
+  if (c.B < 1 || c.D < 1 || c.U < 1 || c.H < 1) return fail(-2, "B, D, U, H must be >= 1");
+  if (c.D > 32 || c.U > 16) return fail(-2, "supported widths: D <= 32, U <= 16");
+  if (c.reward.k < 1 || c.reward.k > PMBRL_MAX_TIP) return fail(-2, "reward.k out of range");
+  // (every failure below frees the plan and whatever it already owns)
+  std::unique_ptr<pmbrl_plan, void (*)(pmbrl_plan*)> p(new pmbrl_plan(), pmbrl_plan_destroy);
+  p->cfg = c;
+  if (p->cfg.B_global <= 0) p->cfg.B_global = c.B;
+  p->device = device;
+  p->sw = read_switches();
+  p->replay = p->sw.replay;
+  if (int rc = plan_nets(p.get())) return rc;
+  int cus = 0;      // (of the device the plan is for, not of the current one)
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
+  if (int rc = plan_layout(p.get(), cus)) return rc;
+  if (int rc = plan_reward(p.get())) return rc;
+  if (int rc = plan_angles(p.get())) return rc;
+  if (int rc = plan_dw(p.get())) return rc;
+  if (int rc = plan_dw_pipe(p.get(), cus)) return rc;
+  if (int rc = plan_workspace(p.get())) return rc;
+  if (int rc = plan_attrs(p.get(), cus)) return rc;
+  *out = p.release();
   return 0;
 }
 
@@ -1684,7 +1736,6 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
   A.G = p->G; A.M = p->M; A.mm_mode = p->mm_mode;
   A.t0 = 0; A.t1 = c.H;
   A.rows_per_wg = p->rows_per_wg; A.nwg = p->nwg; A.Rw = 16 * p->RT; A.LD = p->LD; A.LDB = p->LDB;
-  A.stash_pre = p->dw_pre_mask;
   A.mls_pol = c.max_log_std_pol; A.mls_dyn = c.max_log_std_dyn;
   for (int l = 0; l < p->pol.nl - 1; ++l)
     if (!in->pol_mask_bits_d[l]) return fail(-1, "missing policy mask bits");
@@ -1938,8 +1989,7 @@ static int rollout_fwd_impl(pmbrl_plan* p, void* stream, void* workspace, const 
     //  the launch of its own)
     ZtabArgs Zt;
     Zt.n_blocks = 0;
-    if (p->reg && reg_fwd && (p->mm_fan || p->reg_mm) && p->mm_mode == 1 &&
-        !(getenv("PMBRL_ZTAB_MERGE") && atoi(getenv("PMBRL_ZTAB_MERGE")) == 0)) {
+    if (p->reg && reg_fwd && (p->mm_fan || p->reg_mm) && p->mm_mode == 1 && p->sw.ztab_merge) {
       Zt = pm_ztab_args(p, A);
       ztab_done = true;
     }
@@ -2274,12 +2324,11 @@ static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl
   }
   const int n = (int)p->pol.n_params;
   // the fused iteration (one process, optimiser attached): the reduction forms the gradient norm's partial sums and the
-  // go / no-go decision on the way -- pm_gradnorm_kernel's launch is not needed (PMBRL_FUSE_NORM=0: the separate launch)
-  const bool norm_fused = opt && !piped && (n + 255) / 256 <= PM_NORM_MAXB &&
-                          !(getenv("PMBRL_FUSE_NORM") && atoi(getenv("PMBRL_FUSE_NORM")) == 0);
+  // go / no-go decision on the way -- pm_gradnorm_kernel's launch is not needed
+  const bool norm_fused = opt && !piped && (n + 255) / 256 <= PM_NORM_MAXB;
   // ... and, asked for (pmbrl_adam::loss_out_d), the loss' partial sums: the optimiser launch adds them -- no loss launch
   // behind the forward call (PMBRL_FUSE_LOSS=0: pm_weighted_sum_kernel, here)
-  const bool loss_fused = norm_fused && opt->loss_out_d && !(getenv("PMBRL_FUSE_LOSS") && atoi(getenv("PMBRL_FUSE_LOSS")) == 0);
+  const bool loss_fused = norm_fused && opt->loss_out_d && p->sw.fuse_loss;
   {
     ScopedTimer tm(p, PMBRL_TIMER_DW_REDUCE, s);
     if (piped)   // every partial row was written (pm_dw_range)

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <string>
+#include <vector>
 
 #include "pmbrl.h"
 #include "pmbrl_dev.h"
@@ -29,9 +30,21 @@ struct NetPlan {
   size_t wf[PM_MAXL], wb[PM_MAXL], bias[PM_MAXL], abits[PM_MAXL];
 };
 
+// The environment switches of a rollout plan (include/pmbrl.h lists them), read once when it is created
+struct PlanSwitches {
+  bool mm_perstep, mm_mode2, mm_no_batch, dw_no_wide, reg_debug;   // set at all: on
+  bool lds_tiles, mm_xch, mm_tree, reg, reg_mm, reg_tree, reg_bwd, fuse_loss, ztab_merge, wide;   // =0: off
+  bool mm_parts_set;    // PMBRL_MM_PARTS=mm_parts
+  int mm_parts;
+  int replay;           // PMBRL_REPLAY (default 1)
+  bool dw_pipe_off, dw_pipe_ranges;   // PMBRL_DW_PIPE=off | n0,n1,... (the positive ones in dw_pipe)
+  std::vector<int> dw_pipe;
+};
+
 #define PM_PIPE_MAX 8
 struct pmbrl_plan {
   pmbrl_config cfg;
+  PlanSwitches sw;
   int device;
   int RT, rows_per_wg, nwg, LD, mm_mode, G, M, fast, CA, CB;   // CA/CB: k-blocks per weight-stream stage
   int prec, LDB;   // PMBRL_PREC_* in use; split precision: leading dimension of the bf16 piece planes
@@ -93,7 +106,6 @@ struct pmbrl_plan {
   int replay;            // 0 off, 1 the one-launch-per-step forms, 2 every form
   hipStream_t cap_stream;   // what the calls are recorded on
   struct ReplaySlot { unsigned long long key; std::vector<unsigned char> bytes; int seen, dead, aux; hipGraphExec_t exec; long long launches; } rp[2];
-  int reg_bwd;   // PMBRL_REG_BWD at plan creation (0: the family's adjoint sweep is off -- debugging aid)
   // optional per-kernel timing (hipEvents on the caller's stream)
   long long* prof_fwd;
   long long* prof_bwd;
@@ -112,7 +124,7 @@ struct ScopedTimer {
   }
 };
 
-// the instantiated (row tiles, stage pair) combinations -- keep in sync with stages_for()
+// the instantiated (row tiles, stage pair) combinations -- keep in sync with LayoutCalc::stages (pmbrl.hip)
 #define PM_FAST_CASES                                                                  \
   PM_FAST_CASE(1, 8, 8) PM_FAST_CASE(1, 7, 6) PM_FAST_CASE(1, 4, 4) PM_FAST_CASE(1, 2, 2) \
   PM_FAST_CASE(2, 4, 4) PM_FAST_CASE(2, 4, 3) PM_FAST_CASE(2, 2, 2) PM_FAST_CASE(4, 2, 2) PM_FAST_CASE(4, 1, 1)
@@ -166,6 +178,13 @@ static inline int hidden_tiles(const RolloutArgs& A) {
   for (int l = 1; l < A.pol.nl; ++l) if (A.pol.nt[l] != nt) return -1;
   for (int l = 1; l < A.dyn.nl; ++l) if (A.dyn.nt[l] != nt) return -1;
   return nt;
+}
+// ... the plan-side twin for the shape-specialised instances' networks (two hidden layers each): -1 also if a net has
+// another depth
+static inline int hidden_tiles_3l(const pmbrl_plan* p) {
+  if (p->pol.nl != 3 || p->dyn.nl != 3) return -1;
+  const int nt = p->pol.nt[1];
+  return p->pol.nt[2] == nt && p->dyn.nt[1] == nt && p->dyn.nt[2] == nt ? nt : -1;
 }
 static inline int fast_variant(int RT, const RolloutArgs& A) {
   // variant: see pmbrl_fast.h (PF_VAR_*)

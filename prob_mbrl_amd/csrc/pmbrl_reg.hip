@@ -11,14 +11,10 @@
 // the moment-matching groups, so that it can lay the groups out for this family
 bool pm_reg_shape_ok(const pmbrl_plan* p, int prec1) {
   const pmbrl_config& c = p->cfg;
-  if (const char* e = getenv("PMBRL_REG")) {
-    if (atoi(e) == 0) return false;
-  }
-  if (!p->fast || prec1 != PMBRL_PREC_SPLIT_F16 || (c.flags & PMBRL_FLAG_NO_SHAPED)) return false;
-  if (p->pol.nl != 3 || p->dyn.nl != 3) return false;
+  if (!p->sw.reg || !p->fast || prec1 != PMBRL_PREC_SPLIT_F16 || (c.flags & PMBRL_FLAG_NO_SHAPED)) return false;
+  if (hidden_tiles_3l(p) != PR_NT) return false;
   const int hid = p->pol.dim[1];
   if (p->pol.dim[2] != hid || p->dyn.dim[1] != hid || p->dyn.dim[2] != hid) return false;
-  if ((hid + 15) / 16 != PR_NT) return false;
   if (c.D + c.U > 8 || p->pol.dim[0] != c.D || p->dyn.dim[0] != c.D + c.U) return false;
   if (p->pol.dim[3] != 2 * c.U || p->dyn.dim[3] != 2 * c.D) return false;
   return true;
@@ -28,8 +24,7 @@ bool pm_reg_mm_shape_ok(const pmbrl_plan* p, int prec1) {
   const pmbrl_config& c = p->cfg;
   if (!pm_reg_shape_ok(p, prec1)) return false;
   if (!(c.flags & PMBRL_FLAG_MM_STATES) || (c.flags & PMBRL_FLAG_INFER_NS) || c.D < 4 || c.D > 6) return false;
-  if (getenv("PMBRL_MM_XCH") && atoi(getenv("PMBRL_MM_XCH")) == 0) return false;
-  if (getenv("PMBRL_REG_MM") && atoi(getenv("PMBRL_REG_MM")) == 0) return false;
+  if (!p->sw.mm_xch || !p->sw.reg_mm) return false;
   return true;
 }
 
@@ -45,7 +40,7 @@ bool pm_reg_plan_ok(const pmbrl_plan* p) {
     if (!pm_reg_mm_shape_ok(p, p->prec) || (p->mm_parts > 8) != (p->mm_fan != 0) || p->rows_per_wg > 16 || c.H >= 4096) return false;
     // (every wave of a workgroup polls four slots of a level: at most 16 members per collector, at most 16 collectors)
     if (p->mm_fan && (p->mm_fan > 16 || (p->mm_parts + p->mm_fan - 1) / p->mm_fan > 16 || c.D != 4)) return false;
-    if (getenv("PMBRL_REG_TREE") && atoi(getenv("PMBRL_REG_TREE")) == 0 && p->mm_fan) return false;
+    if (!p->sw.reg_tree && p->mm_fan) return false;
     if (p->mm_parts <= 1 && p->rows_per_wg != p->M) return false;      // (several whole groups per workgroup: not here)
   }
   return true;
@@ -131,8 +126,7 @@ static void reg_args(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const 
     R.mm.fan = p->mm_fan; R.mm.nwg = p->nwg;
     // (a group in more parts than an XCD has CUs cannot sit on one: the two-level exchange crosses the fabric)
     //  -- unless it is the ONLY group and its collectors were laid out per XCD: pmbrl.hip, mm_fan; pr_wg, mode 2)
-    const bool xcd_on = !(getenv("PMBRL_XCH_XCD") && atoi(getenv("PMBRL_XCH_XCD")) == 0);
-    R.mm.xcd = (p->mm_parts > 1 && xcd_on) ? (p->mm_fan ? (pm_reg_tree_xcd(p) ? 2 : 0) : 1) : 0;
+    R.mm.xcd = p->mm_parts > 1 ? (p->mm_fan ? (pm_reg_tree_xcd(p) ? 2 : 0) : 1) : 0;
     R.mm.tag0 = (++p->xch_gen) << 12;      // (steps < 4096; the parity of a tag is the parity of its step: the two sets alternate)
     R.mm.inv_m = 1.0 / (double)p->M;
     R.mm.inv_m1 = 1.0 / (double)(p->M - 1);
@@ -143,7 +137,7 @@ static void reg_args(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const 
 // variant of pmbrl_fast.h serves)
 bool pm_reg_can_run(const pmbrl_plan* p, const RolloutArgs& A, bool fwd) {
   if (!p->reg || (A.mm_mode != 0) != (p->reg_mm != 0)) return false;
-  if (!fwd && !p->reg_bwd) return false;
+  if (!fwd && !p->sw.reg_bwd) return false;
   const bool ext = A.grad_states || A.grad_actions || A.agn || A.zpol_ss != 0 || A.zdyn_ss != 0 ||
                    (((A.flags & PMBRL_FLAG_MM_STATES) != 0) != (p->reg_mm != 0)) || A.t0 != 0 || A.t1 != A.H || A.gx_from_carry;
   if (p->reg_mm && p->mm_parts > 1 && !A.xch) return false;
@@ -203,7 +197,7 @@ void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const fl
   ++p->reg_calls[fwd ? 0 : 1];
   RegArgs R;
   reg_args(p, ws, A, reinterpret_cast<const float*>(ws + p->off_reg_pack), pol_params, dyn_params, R);
-  if (getenv("PMBRL_REG_DEBUG"))
+  if (p->sw.reg_debug)
     fprintf(stderr, "pm_reg_launch %s: off_mmfac %zu off_reg_pack %zu gT %zu %zu %zu actT %zu %zu %zu abits %zu %zu %zu %zu ws_bytes %zu\n", fwd ? "fwd" : "bwd",
             p->off_mmfac, p->off_reg_pack, p->off_gT[0], p->off_gT[1], p->off_gT[2], p->off_actT[0], p->off_actT[1], p->off_actT[2],
             p->off_reg_ab[0][0], p->off_reg_ab[0][1], p->off_reg_ab[1][0], p->off_reg_ab[1][1], p->ws_bytes);

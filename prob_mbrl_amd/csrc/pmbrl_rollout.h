@@ -357,8 +357,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       if constexpr (IP >= 2) {
         const PwFwd w{P.bias[l], mk, P.abits[l] + (size_t)t * B * nt, P.keep[l], X,
                       A.actT[l + 1] + blk * (size_t)nt * 16 * A.Rw, L.tbl, row0, nvalid, p_ovf,
-                      (A.prof && wg == 0 && l == 1) ? A.prof + (size_t)t * 32 + 5 : nullptr,
-                      (int)((A.stash_pre >> (l + 1)) & 1u)};      // (pre-split where the next layer's dW GEMM is pm_dw_wide_pre_kernel's)
+                      (A.prof && wg == 0 && l == 1) ? A.prof + (size_t)t * 32 + 5 : nullptr};
         // (IP = 3: every 512-wide stash pre-split -- ONE form of the stash stores per kernel instance: two forms in one
         //  kernel, as two instances of the layer or as a branch around the stores, cost the forward sweep 0.5-1 ms)
         pw_hidden_fwd<IP == 3 ? 2 : 1>(P.wf[l], pm_kb32(P.nt[l]), w, wid, lane);
@@ -475,7 +474,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
                                         nullptr, LD, A.Rw, row0, nvalid, nt, lane, p_ovf};
       if constexpr (IP >= 2) {
         const PwFwd w{F.bias[l], mk, F.abits[l] + (size_t)t * B * nt, F.keep[l], X, nullptr, L.tbl, row0, nvalid, p_ovf,
-                      (A.prof && wg == 0 && l == 1) ? A.prof + (size_t)t * 32 + 15 : nullptr, 0};
+                      (A.prof && wg == 0 && l == 1) ? A.prof + (size_t)t * 32 + 15 : nullptr};
         pw_hidden_fwd<0>(F.wf[l], pm_kb32(F.nt[l]), w, wid, lane);
       } else if constexpr (IP) gemm_layer_inplace_s<RT, true>(F.wf[l], nt, pm_kb32(F.nt[l]), X, LDB, wid, lane, e);
       else if constexpr (SP) gemm_tiles_s<RT, true>(F.wf[l], nt, pm_kb32(F.nt[l]), X, LDB, wid, lane, e);
@@ -870,7 +869,7 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
                                     row0, nvalid, nt, lane};
       if constexpr (IP >= 2) {
         const PwBwd w{F.abits[l - 1] + (size_t)t * B * nt, F.keep[l - 1], X, nullptr, L.tbl, row0, nvalid,
-                      (A.prof && wg == 0 && l == 2) ? A.prof + (size_t)t * 32 + 8 : nullptr, 0};
+                      (A.prof && wg == 0 && l == 2) ? A.prof + (size_t)t * 32 + 8 : nullptr};
         pw_hidden_bwd<0>(F.wb[l], pm_kb32(F.nt[l + 1]), w, wid, lane);
       } else if constexpr (IP) gemm_layer_inplace_s<RT, false>(F.wb[l], nt, pm_kb32(F.nt[l + 1]), X, LDB, wid, lane, e);
       else if constexpr (SP) gemm_tiles_s<RT, false>(F.wb[l], nt, pm_kb32(F.nt[l + 1]), X, LDB, wid, lane, e);
@@ -1000,8 +999,7 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
       if constexpr (IP >= 2) {
         const PwBwd w{P.abits[l - 1] + (size_t)t * B * nt, P.keep[l - 1], X,
                       A.gT[l - 1] + blk * (size_t)nt * 16 * A.Rw, L.tbl, row0, nvalid,
-                      (A.prof && wg == 0 && l == 2) ? A.prof + (size_t)t * 32 + 18 : nullptr,
-                      (int)((A.stash_pre >> (l - 1)) & 1u)};
+                      (A.prof && wg == 0 && l == 2) ? A.prof + (size_t)t * 32 + 18 : nullptr};
         pw_hidden_bwd<IP == 3 ? 2 : 1>(P.wb[l], pm_kb32(P.nt[l + 1]), w, wid, lane);
       } else if constexpr (IP) gemm_layer_inplace_s<RT, false>(P.wb[l], nt, pm_kb32(P.nt[l + 1]), X, LDB, wid, lane, e);
       else if constexpr (SP) gemm_tiles_s<RT, false>(P.wb[l], nt, pm_kb32(P.nt[l + 1]), X, LDB, wid, lane, e);

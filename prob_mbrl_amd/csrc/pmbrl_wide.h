@@ -277,7 +277,6 @@ struct PwFwd {
   int row0, nvalid;
   int* ovf;
   long long* prof;        // debug: four cycle stamps of this layer (workgroup 0, thread 0) or nullptr
-  int pre;                // the stash in the pre-split form (pw_stash_pre) instead of fp32 rows
 };
 
 // lane (g, c) -> the value lane (g, n) holds, n a constant: DPP row_share (a 16-lane row is one lane group g)
@@ -409,7 +408,6 @@ struct PwBwd {
   const float* tbl;
   int row0, nvalid;
   long long* prof;
-  int pre;                // the stash in the pre-split form (pw_stash_pre)
 };
 
 // hidden layer, adjoint, in place:  g_pre = active ? (W^T g) / keep : 0   (bf16 pieces; as the forward layer)
