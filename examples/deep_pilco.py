@@ -7,6 +7,7 @@ the self-contained cart-pole of prob_mbrl_amd.envs (gym / Box2D are not part of 
 
     python examples/deep_pilco.py --ps_iters 5                 # moment matching (deep_pilco_mm)
     python examples/deep_pilco.py --no_mm --pol_batch_size 100 # particles only (deep_pilco_no_mm)
+    python examples/deep_pilco.py --learn_reward               # the dynamics model predicts the reward too
 """
 import argparse
 import copy
@@ -35,6 +36,8 @@ def parse(argv=None):
     ap.add_argument('--prioritized_replay', action='store_true')
     ap.add_argument('--mm_groups', type=int, default=None)
     ap.add_argument('--no_mm', action='store_true', help='particles only (deep_pilco_no_mm.py)')
+    ap.add_argument('--learn_reward', action='store_true',
+                    help='a learned reward head: the dynamics model predicts the reward (examples/deep_pilco_mm.py:94-99)')
     ap.add_argument('--dyn_lr', type=float, default=1e-4)
     ap.add_argument('--dyn_opt_iters', type=int, default=2000)
     ap.add_argument('--dyn_batch_size', type=int, default=100)
@@ -75,15 +78,23 @@ def main(argv=None):
         args.discount_factor = ((1.0 / args.control_H)**(2.0 / args.control_H)
                                 if args.discount_factor == 'auto' else float(args.discount_factor))
 
-    if args.dyn_components > 1:     # mixture-of-Gaussians head: (2 D + 1) n + 1 outputs
-        density, dynE = models.GaussianMixtureDensity(D, args.dyn_components), (2 * D + 1) * args.dyn_components + 1
+    # an environment without an analytic reward takes the learned path too (examples/deep_pilco_mm.py:94-99)
+    if args.learn_reward or getattr(env, 'reward_func', None) is None:
+        reward_func, args.learn_reward = None, True
     else:
-        density, dynE = models.DiagGaussianDensity(D), 2 * D
+        reward_func = env.reward_func
+    if args.dyn_components > 1:     # mixture-of-Gaussians head: (2 D + 1) n + 1 outputs
+        if args.learn_reward:
+            raise SystemExit('--learn_reward is not offered with --dyn_components > 1')
+        density, dynE = models.GaussianMixtureDensity(D, args.dyn_components), (2 * D + 1) * args.dyn_components + 1
+    else:   # (learned reward: one more mean and log-std, examples/deep_pilco_mm.py:117)
+        Dy = D + 1 if args.learn_reward else D
+        density, dynE = models.DiagGaussianDensity(Dy), 2 * Dy
     dyn = models.DynamicsModel(
         models.mlp(D + U, dynE, args.dyn_shape,
                    dropout_layers=[models.CDropout(args.dyn_drop_rate * np.ones(h)) if args.dyn_drop_rate > 0
                                    else None for h in args.dyn_shape], nonlin=torch.nn.ReLU),
-        reward_func=env.reward_func, output_density=density).float()
+        reward_func=reward_func, output_density=density).float()
     pol = models.Policy(
         models.mlp(D, 2 * U, args.pol_shape,
                    dropout_layers=[models.BDropout(args.pol_drop_rate) if args.pol_drop_rate > 0 else None
@@ -120,7 +131,7 @@ def main(argv=None):
         exp.save(results_filename)
 
         # fit the dynamics model
-        X, Y = exp.get_dynmodel_dataset(deltas=True, return_costs=False)
+        X, Y = exp.get_dynmodel_dataset(deltas=True, return_costs=args.learn_reward)
         dyn.set_dataset(X.to(dev, torch.float32), Y.to(dev, torch.float32))
         utils.train_regressor(dyn, args.dyn_opt_iters, args.dyn_batch_size, True, opt1,
                               log_likelihood=dyn.output_density.log_prob)

@@ -74,6 +74,14 @@ extern "C" {
 
 #define PMBRL_REWARD_EXP 0 /* r = exp(-w (d'Qd + u'Ru)): envs/cartpole/env.py:41-86 */
 #define PMBRL_REWARD_NEG 1 /* r = -w (d'Qd + u'Ru):      envs/rendezvous/env.py:32-45 */
+/* Learned reward: the dynamics head predicts the transition's reward next to the state change
+ * (examples/deep_pilco_mm.py:94-99,117: DiagGaussianDensity(D + 1)).  dyn.dims[n_layers] = 2 (D + 1), split as
+ * [mean_0..mean_{D-1}, mean_r | log_std_0..log_std_{D-1}, log_std_r]; my_d / Sy_d and the z_dyn_d rows are D + 1 wide
+ * (z_dyn_step_stride = B (D + 1) for a per-step draw), and r~ = my[D] + Sy[D] mean_r + z[D] exp(ls_r + log Sy[D]) with
+ * ls_r clamped as the states' log-stds (models/core.py:265-303 with the D of the tuple path).  The other fields of
+ * pmbrl_reward are ignored.  Runs on the general kernel family only (pmbrl_plan_info reports fast = 0), F32 or
+ * SPLIT_F16; not offered with the mixture head (dyn_components > 1) or with groups spread over ranks (mm_span_rows). */
+#define PMBRL_REWARD_LEARNED 2
 
 /* One MLP as built by models/core.py:15-99 (mlp): Linear -> ReLU -> dropout ...
  * -> Linear.  dims[0] = input width, dims[n_layers] = output width.
@@ -120,7 +128,7 @@ typedef struct pmbrl_config {
   float max_log_std_pol; /* models/densities.py:75: log(max_noise_std) */
   float max_log_std_dyn;
   pmbrl_mlp pol; /* dims[0] = D + n_pol_angle, dims[n] = 2U */
-  pmbrl_mlp dyn; /* dims[0] = D + U + n_dyn_angle, dims[n] = 2D */
+  pmbrl_mlp dyn; /* dims[0] = D + U + n_dyn_angle, dims[n] = 2D (2 (D + 1) with PMBRL_REWARD_LEARNED) */
   pmbrl_reward reward;
   int32_t rows_per_wg_hint; /* 0 = choose automatically */
   int32_t precision;        /* PMBRL_PREC_*: arithmetic of the hidden-width GEMMs of the sweeps */
@@ -265,14 +273,14 @@ typedef struct pmbrl_inputs {
   const float* dyn_params_d;  /* same for the dynamics MLP */
   const float* mx_d;          /* [dyn.dims[0]] (= D+U without angle dims)  models/core.py:141-145 */
   const float* iSx_d;         /* [D+U] */
-  const float* my_d;          /* [D] */
-  const float* Sy_d;          /* [D] */
+  const float* my_d;          /* [D] ([D + 1] with PMBRL_REWARD_LEARNED: the reward column last) */
+  const float* Sy_d;          /* [D] (the same) */
   const float* pol_scale_d;   /* [U]  models/core.py:201-206 */
   const float* pol_bias_d;    /* [U] */
   const uint16_t* pol_mask_bits_d[PMBRL_MAX_LAYERS]; /* per hidden layer, from pmbrl_pack_mask */
   const uint16_t* dyn_mask_bits_d[PMBRL_MAX_LAYERS];
   const float* z_pol_d;       /* [B, U]  models/densities.py:78,111-119 */
-  const float* z_dyn_d;       /* [B, D] */
+  const float* z_dyn_d;       /* [B, D] ([B, D + 1] with PMBRL_REWARD_LEARNED) */
   int64_t z_pol_step_stride;  /* elements between steps; 0 = the same frozen z at every step
                                  (resample_noise=False), B*U = a fresh [H,B,U] draw per step */
   int64_t z_dyn_step_stride;

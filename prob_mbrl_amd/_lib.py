@@ -20,7 +20,7 @@ FLAG_NO_SHAPED = 32
 FLAG_POL_MASKS_PER_STEP, FLAG_DYN_MASKS_PER_STEP = 64, 128
 FLAG_GMM_EXACT_NOISE_GRAD = 256
 MAX_COMP = 8
-REWARD_EXP, REWARD_NEG = 0, 1
+REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 INFO_COUNT = 21
 TIMER_COUNT = 8

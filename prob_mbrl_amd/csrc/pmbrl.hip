@@ -29,7 +29,7 @@ int pm_fail(int code, const std::string& msg) {
 static int fail(int code, const std::string& msg) { return pm_fail(code, msg); }
 
 extern "C" const char* pmbrl_last_error(void) { return g_err.c_str(); }
-extern "C" int pmbrl_version(void) { return 6; }
+extern "C" int pmbrl_version(void) { return 7; }
 
 // ---------------------------------------------------------------------------
 // hipGraph entry points: record the library calls queued on a stream between begin and end, replay them with one
@@ -761,11 +761,20 @@ static int plan_nets(pmbrl_plan* p) {
   if (c.dyn_components < 0 || c.dyn_components > PMBRL_MAX_COMP)
     return fail(-2, "dyn_components out of range (<= PMBRL_MAX_COMP)");
   const bool gmm = c.dyn_components > 1;
+  if (c.reward.kind != PMBRL_REWARD_EXP && c.reward.kind != PMBRL_REWARD_NEG && c.reward.kind != PMBRL_REWARD_LEARNED)
+    return fail(-2, "unknown reward kind");
+  p->learned = c.reward.kind == PMBRL_REWARD_LEARNED;
+  if (p->learned && gmm)
+    return fail(-2, "learned reward head: not offered with the mixture head (dyn_components > 1)");
+  if (p->learned && c.mm_span_rows > 0)
+    return fail(-2, "learned reward head: not offered with moment-matching groups spread over ranks (mm_span_rows > 0)");
+  if (p->learned && c.D + 1 > PMBRL_MAX_DIM) return fail(-2, "learned reward head: D + 1 exceeds PMBRL_MAX_DIM");
   int rc = net_plan(c.pol, p->pol, c.D + c.n_pol_angle, 2 * c.U, "policy");
-  // (mixture head: n D means, n D log-stds, n logits, one log-temperature -- examples/deep_pilco_mm.py:117-121)
+  // (mixture head: n D means, n D log-stds, n logits, one log-temperature -- examples/deep_pilco_mm.py:117-121;
+  //  learned reward: one more mean and log-std for the reward, examples/deep_pilco_mm.py:94-99)
   if (rc == 0)
-    rc = net_plan(c.dyn, p->dyn, c.D + c.U + c.n_dyn_angle, gmm ? (2 * c.D + 1) * c.dyn_components + 1 : 2 * c.D,
-                  "dynamics");
+    rc = net_plan(c.dyn, p->dyn, c.D + c.U + c.n_dyn_angle,
+                  gmm ? (2 * c.D + 1) * c.dyn_components + 1 : 2 * (c.D + p->learned), "dynamics");
   return rc;
 }
 
@@ -987,7 +996,7 @@ static int plain_row_tiles(pmbrl_plan* p, const LayoutCalc& L, int cus) {
   // on request (rows_per_wg_hint >= 64): widths <= 512, every narrow width (2U, 2D, D + U) <= 64, no mixture head,
   // no angle features.
   const bool angles = c.n_pol_angle > 0 || c.n_dyn_angle > 0;
-  if (L.gsplit && !angles && c.dyn_components <= 1 && L.maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
+  if (L.gsplit && !angles && c.dyn_components <= 1 && !p->learned && L.maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
       c.D + c.U <= PM_IP_NOFF && RT < 4) {
     // every hidden layer 512 wide: the in-place layers of pmbrl_wide.h (compile-time shape, lean epilogue) -- taken by
     // default as soon as 64-row workgroups still give every CU one (PMBRL_WIDE=0: the generic in-place form on
@@ -1010,9 +1019,11 @@ static int plan_layout(pmbrl_plan* p, int cus) {
   const PlanSwitches& sw = p->sw;
   const bool mm = (c.flags & (PMBRL_FLAG_MM_STATES | PMBRL_FLAG_MM_REWARDS)) != 0;
   // infer_noise_variables (utils/rollout.py:6-17, not a default anywhere) lives in the general
-  // single-wave moment-matching routines only: general kernel family, mm_mode 1 or 2
+  // single-wave moment-matching routines only: general kernel family, mm_mode 1 or 2.  So does the learned reward
+  // head (its sampling epilogue and head seed are written for that family's sweeps only)
   p->fast = !(c.flags & (PMBRL_FLAG_FORCE_GENERIC | PMBRL_FLAG_INFER_NS | PMBRL_FLAG_POL_MASKS_PER_STEP |
                          PMBRL_FLAG_DYN_MASKS_PER_STEP)) && c.n_pol_angle == 0 && c.n_dyn_angle == 0 && c.dyn_components <= 1 &&
+            !p->learned &&
             pm_fast_net_ok(p->pol.dim, p->pol.nt, p->pol.nl) &&
             pm_fast_net_ok(p->dyn.dim, p->dyn.nt, p->dyn.nl);
   LayoutCalc L;
@@ -1114,6 +1125,12 @@ static int plan_reward(pmbrl_plan* p) {
   memset(&r, 0, sizeof(r));
   const pmbrl_reward& s = c.reward;
   r.kind = s.kind;
+  if (p->learned) {      // (no constants -- the reward comes out of the dynamics head -- and rew_d stays null)
+    p->rew_k = 0;
+    HIPCHK(hipMalloc(&p->wflag_d, sizeof(int)));
+    HIPCHK(hipMemset(p->wflag_d, 0, sizeof(int)));
+    return 0;
+  }
   r.expand = s.expand;
   r.k = s.k;
   r.n_angle = s.expand ? s.n_angle : 0;
@@ -1468,7 +1485,8 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
   const pmbrl_config& c = *cfg;
   if (c.B < 1 || c.D < 1 || c.U < 1 || c.H < 1) return fail(-2, "B, D, U, H must be >= 1");
   if (c.D > 32 || c.U > 16) return fail(-2, "supported widths: D <= 32, U <= 16");
-  if (c.reward.k < 1 || c.reward.k > PMBRL_MAX_TIP) return fail(-2, "reward.k out of range");
+  if (c.reward.kind != PMBRL_REWARD_LEARNED && (c.reward.k < 1 || c.reward.k > PMBRL_MAX_TIP))
+    return fail(-2, "reward.k out of range");
   // (every failure below frees the plan and whatever it already owns)
   std::unique_ptr<pmbrl_plan, void (*)(pmbrl_plan*)> p(new pmbrl_plan(), pmbrl_plan_destroy);
   p->cfg = c;
@@ -1743,7 +1761,7 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
     if (!in->dyn_mask_bits_d[l]) return fail(-1, "missing dynamics mask bits");
   fill_net(p->pol, ws, in->pol_mask_bits_d, A.pol);
   fill_net(p->dyn, ws, in->dyn_mask_bits_d, A.dyn);
-  A.rew = p->rew_d;
+  A.rew = p->rew_d;     // (nullptr: the learned reward head, see RolloutArgs::Jx)
   A.ang = p->ang_d;
   A.x0 = in->x0_d; A.mx = in->mx_d; A.iSx = in->iSx_d; A.my = in->my_d; A.Sy = in->Sy_d;
   A.pscale = in->pol_scale_d; A.pbias = in->pol_bias_d;
@@ -2018,6 +2036,7 @@ static int rollout_fwd_impl(pmbrl_plan* p, void* stream, void* workspace, const 
   } else if (p->mm_mode != 2) {
     RolloutArgs As = A;
     if (!p->fast) { As.ext_reward = 1; As.flags &= ~PMBRL_FLAG_MM_REWARDS; }   // general family: rewards after the sweep
+    if (p->learned && mm_r) As.rewards = As.rt;     // (learned reward head: r~ before its moment matching)
     if ((p->mm_fan || p->reg_mm) && !ztab_done) {
       const ZtabArgs Z = pm_ztab_args(p, As);
       hipLaunchKernelGGL(pm_mm_ztable_kernel, dim3(Z.n_blocks), dim3(256), 0, s, Z);
@@ -2042,6 +2061,7 @@ static int rollout_fwd_impl(pmbrl_plan* p, void* stream, void* workspace, const 
     RolloutArgs Am = A, As = A;
     Am.flags &= ~PMBRL_FLAG_MM_REWARDS;   // both families: rewards are handled after the sweep
     if (!p->fast) { As.ext_reward = 1; As.flags &= ~PMBRL_FLAG_MM_REWARDS; }
+    if (p->learned && mm_r) As.rewards = As.rt;
     for (int t = 0; t < p->cfg.H; ++t) {
       As.t0 = t; As.t1 = t + 1;
       launch_fwd_rt(p, As, s);
@@ -2068,8 +2088,11 @@ static int rollout_fwd_impl(pmbrl_plan* p, void* stream, void* workspace, const 
     ScopedTimer tm(p, PMBRL_TIMER_REWARD, s);
     A.t0 = 0; A.t1 = p->cfg.H;
     const long long n = (long long)p->cfg.H * p->cfg.B;
-    hipLaunchKernelGGL(pm_reward_kernel_for(p->cfg.U, p->rew_k), dim3((unsigned)((n + 255) / 256)), dim3(256),
-                       (size_t)256 * (p->cfg.D | 1) * sizeof(float), s, A);
+    if (p->learned)     // (the sweep sampled r~ and checked it: what is left of this launch's duties)
+      hipLaunchKernelGGL(pm_reward_learned_kernel, dim3(1), dim3(64), 0, s, A);
+    else
+      hipLaunchKernelGGL(pm_reward_kernel_for(p->cfg.U, p->rew_k), dim3((unsigned)((n + 255) / 256)), dim3(256),
+                         (size_t)256 * (p->cfg.D | 1) * sizeof(float), s, A);
     if (mm_r && p->span) {
       // the rewards of all steps: one exchange for the whole horizon
       const MmxArgs X = mmx_args(p, ws, true);

@@ -138,6 +138,10 @@ struct RolloutArgs {
   double* mmfac;          // in-kernel moment matching: statistics + factor per (step, group), forward -> adjoint
   int mmfac_groups;       // groups per step in mmfac (= B / M)
   float *Jx, *Ja;         // reward Jacobian d r~/d x~ [H][B][D], d r~/d a [H][B][U] (fast kernels)
+  // Learned reward head (PMBRL_REWARD_LEARNED, general family only) -- marked by rew == nullptr; no field of its own, so
+  // that the arguments of every other kernel keep their layout: the forward sweep samples r~ from head columns D and
+  // 2D + 1 and writes it to `rewards` (the host points that at rt when the rewards are moment matched), and keeps
+  // d r~/d ls_r [H][B] in Jx for the adjoint, which seeds those two columns with dL/dr~ instead of using Jx / Ja
   int* status;          // forward: number of valid steps (atomicMin); backward: failure flag of the sweep (or nullptr)
   const int* nvalid;    // backward: the forward's status word; the sweep covers steps t < min(t1, *nvalid) (nullptr: t1)
   // backward only

@@ -1168,6 +1168,13 @@ __global__ __launch_bounds__(256) void pm_reward_all_kernel(const RolloutArgs A)
   }
 }
 
+// The reward launch of a learned reward head (PMBRL_REWARD_LEARNED): the forward sweep has sampled r~ from the dynamics
+// head, written it where the analytic launch writes its value and checked it; no Jacobians exist (the adjoint seeds the
+// head with dL/dr~).  What is left is the adjoint call's failure flag, which every forward call clears here.
+__global__ __launch_bounds__(64) void pm_reward_learned_kernel(const RolloutArgs A) {
+  if (threadIdx.x == 0 && A.status) A.status[1] = 0;
+}
+
 // moment matching of the rewards for all (t, group) at once (one wave each), and its adjoint
 // A LARGE group (mm_groups=None: one group of 2 500 rows) first brings its rows -- rewards, noise, in the adjoint the
 // upstream gradient -- into LDS, sixteen loads in flight per lane, and runs the same routine on them there: its sums walk

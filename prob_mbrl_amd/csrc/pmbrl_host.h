@@ -51,6 +51,7 @@ struct pmbrl_plan {
   size_t lds_bytes;
   NetPlan pol, dyn;
   RewardDev* rew_d;
+  int learned;         // PMBRL_REWARD_LEARNED: the dynamics head predicts the reward (general family only)
   int rew_k = PMBRL_MAX_TIP;   // tip residuals of the reward (which instance of the reward launch: pm_reward_kernel_for)
   int* wflag_d;        // weight-range flag of the fp16 packer (see RolloutArgs::wflag)
   int wgen;            // generation of the last forward call

@@ -589,9 +589,10 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
     } else
     for (int i = tid; i < R * D; i += PM_NT) {
       const int r = i / D, d = i - r * D;
+      const int Dh = A.rew ? D : D + 1;    // (learned reward head: a reward column after the means and after the log-stds)
       const float mu = Y[r * LD + d];
-      const float ls = Y[r * LD + D + d];
-      const float z = (r < nvalid) ? A.zdyn[(size_t)t * A.zdyn_ss + (size_t)(row0 + r) * D + d] : 0.f;
+      const float ls = Y[r * LD + Dh + d];
+      const float z = (r < nvalid) ? A.zdyn[(size_t)t * A.zdyn_ss + (size_t)(row0 + r) * Dh + d] : 0.f;
       const float Sy = A.Sy[d];
       const float lc = -softplusf(-ls + A.mls_dyn) + A.mls_dyn + logf(Sy);
       const float e = expf(lc);
@@ -612,6 +613,22 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       //  after the sweep -- one thread per row here was 34 k cycles of a 243 k-cycle step at D = 32)
       for (int i = tid; i < nvalid * D; i += PM_NT)
         if (!isfinite(xb[i]) || (SP && *p_ovf)) atomicMin(A.status, t);
+      if (!A.rew) {
+        // learned reward head: r~ = my_r + Sy_r mean_r + z_r exp(ls_r + log Sy_r), the states' density on column D; it is
+        // no function of x~_{t+1}: the reward launch only moment-matches it
+        const float Sy = A.Sy[D], lSy = logf(Sy), myr = A.my[D];
+        for (int r = tid; r < nvalid; r += PM_NT) {
+          const float mu = Y[r * LD + D];
+          const float ls = Y[r * LD + 2 * D + 1];
+          const float z = A.zdyn[(size_t)t * A.zdyn_ss + (size_t)(row0 + r) * (D + 1) + D];
+          const float e = expf(-softplusf(-ls + A.mls_dyn) + A.mls_dyn + lSy);
+          const float rv = mu * Sy + myr + z * e;
+          const size_t o = (size_t)t * B + row0 + r;
+          A.Jx[o] = z * e * sigmoidf(-ls + A.mls_dyn);
+          A.rewards[o] = rv;
+          if (!isfinite(rv)) atomicMin(A.status, t);
+        }
+      }
     } else
     for (int r = tid; r < R; r += PM_NT) {
       float rv = 0.f;
@@ -816,8 +833,8 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
         const int r = i / max(D, U), k = i - r * max(D, U);
         const bool v = r < nvalid;
         const size_t row = (size_t)t * B + row0 + r;
-        if (k < D && v) gxt[r * D + k] += L.gr[r] * A.Jx[row * D + k];
-        if (k < U) L.gad[r * 16 + k] = v ? L.gr[r] * A.Ja[row * U + k] : 0.f;
+        if (k < D && v && A.rew) gxt[r * D + k] += L.gr[r] * A.Jx[row * D + k];
+        if (k < U) L.gad[r * 16 + k] = (v && A.rew) ? L.gr[r] * A.Ja[row * U + k] : 0.f;   // (learned: no direct term)
       }
     } else
     for (int r = tid; r < R; r += PM_NT) {
@@ -852,8 +869,13 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
             for (int dd = 0; dd < D; ++dd) v = fmaf(gxt[r * D + dd], cp[dd], v);
           }
         } else if (r < nvalid) {
+          // (learned reward head: [gxt Sy | dL/dr~ Sy_r | gxt Td | dL/dr~ d r~/d ls_r], the reward's seed at columns D and 2D + 1)
+          const int Dh = A.rew ? D : D + 1;
+          const size_t row = (size_t)t * B + row0 + r;
           if (k < D) v = gxt[r * D + k] * A.Sy[k];
-          else if (k < 2 * D) v = gxt[r * D + k - D] * A.Td[((size_t)t * B + row0 + r) * D + k - D];
+          else if (k < Dh) v = L.gr[r] * A.Sy[D];
+          else if (k < Dh + D) v = gxt[r * D + k - Dh] * A.Td[row * D + k - Dh];
+          else if (k < 2 * Dh) v = L.gr[r] * A.Jx[row];
         }
         if constexpr (SP) pm_put_planes<R, false>(X, LDB, r, k, v);
         else X[r * LD + k] = v;

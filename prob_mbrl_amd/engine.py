@@ -288,10 +288,17 @@ class BnnStep:
         return self.loss
 
 
+# the reward spec of a learned reward head (PMBRL_REWARD_LEARNED): the dynamics head predicts the reward
+LEARNED_REWARD = dict(kind='learned')
+
+
 def make_reward_struct(spec, D, U):
     """spec: dict(kind, expand, angle_dims, C [k,De], tip_target [k], norm, w,
-    Q [k,k], R [U,U]) with numpy / float entries."""
+    Q [k,k], R [U,U]) with numpy / float entries, or LEARNED_REWARD."""
     r = _lib.Reward()
+    if spec['kind'] == 'learned':
+        r.kind = _lib.REWARD_LEARNED
+        return r
     r.kind = _lib.REWARD_EXP if spec['kind'] == 'exp' else _lib.REWARD_NEG
     r.expand = 1 if spec['expand'] else 0
     ad = [int(a) for a in spec['angle_dims']] if spec['expand'] else []
@@ -369,6 +376,9 @@ class Engine:
         for i, a in enumerate(dyn_angle_dims):
             cfg.dyn_angle_dims[i] = a
         self.n_dyn_in = D + U + len(dyn_angle_dims)
+        # learned reward head: my / Sy and the rows of z_dyn carry the reward column after the states
+        self.learned = reward_spec['kind'] == 'learned'
+        self.Dy = D + 1 if self.learned else D
         # GaussianMixtureDensity dynamics head (models/densities.py:151-259): components (0 / 1: diagonal Gaussian)
         self.n_comp = int(dyn_components) if dyn_components and int(dyn_components) > 1 else 0
         cfg.dyn_components = self.n_comp
@@ -507,7 +517,8 @@ class Engine:
         x0, pol_flat, dyn_flat, mx, iSx, my, Sy, pol_scale, pol_bias, z_pol, z_dyn = t
         assert x0.shape == (self.B, self.D), x0.shape
         assert pol_flat.numel() == self.n_pol_params and dyn_flat.numel() == self.n_dyn_params
-        assert mx.numel() == self.n_dyn_in and iSx.numel() == self.n_dyn_in and my.numel() == self.D
+        assert mx.numel() == self.n_dyn_in and iSx.numel() == self.n_dyn_in and my.numel() == self.Dy
+        assert Sy.numel() == self.Dy
         zps = zds = 0
         if z_pol.dim() == 3:
             assert z_pol.shape == (self.H, self.B, self.U)
@@ -515,10 +526,10 @@ class Engine:
         else:
             assert z_pol.shape[0] >= self.B and z_pol.shape[1] == self.U
         if z_dyn.dim() == 3:
-            assert z_dyn.shape == (self.H, self.B, self.D)
-            zds = self.B * self.D
+            assert z_dyn.shape == (self.H, self.B, self.Dy)
+            zds = self.B * self.Dy
         else:
-            assert z_dyn.shape[0] >= self.B and z_dyn.shape[1] == self.D
+            assert z_dyn.shape[0] >= self.B and z_dyn.shape[1] == self.Dy
         assert len(pol_mask_bits) == self.n_pol_layers - 1
         assert len(dyn_mask_bits) == self.n_dyn_layers - 1
         if z_mm is not None:

@@ -584,9 +584,12 @@ class Regressor(_Loadable):
 
 
 class DynamicsModel(Regressor):
-    """models/core.py:251-303.  `reward_func` must be one of prob_mbrl_amd.rewards.*
-    (an analytic reward with a `.spec(D)`); a learned reward is not offered (the reference's
-    own learned-reward branch raises)."""
+    """models/core.py:251-303.  `reward_func` is one of prob_mbrl_amd.rewards.* (an analytic reward with a
+    `.spec(D)`), or None for a learned reward: the model then has a head 2 (D + 1) wide with
+    output_density=DiagGaussianDensity(D + 1) and predicts the transition's reward in its last output column
+    (examples/deep_pilco_mm.py:94-99; trained on get_dynmodel_dataset(return_costs=True)).  The reference's own
+    learned-reward branch takes D from the concatenated-input path only (an UnboundLocalError with tuple inputs,
+    SURVEY.md 8c); here D is the width of prev_states for tuple inputs and outs.shape[-1] - 1 otherwise."""
 
     def __init__(self, model, reward_func=None, predict_done=False, **kwargs):
         super().__init__(model, **kwargs)
@@ -614,13 +617,23 @@ class DynamicsModel(Regressor):
         outs = super().forward(inputs, **kwargs)
         if not kwargs.get('return_samples', False):
             return outs
-        if not as_tuple:
-            D = outs.shape[-1]
-            prev_states, actions = inputs[..., :D], inputs[..., D:]
-        if not callable(self.reward_func):
-            raise NotImplementedError('a learned reward head is not offered (the reference raises here too)')
-        dstates = outs
-        rewards = self.reward_func(prev_states + dstates, actions)
+        if self.reward_func is None:
+            # learned reward head: [state change | reward] from one density sample
+            D = prev_states.shape[-1] if as_tuple else outs.shape[-1] - 1
+            if as_tuple and outs.shape[-1] != D + 1:
+                raise NotImplementedError('reward_func=None needs a learned reward head: widen the dynamics head to '
+                                          '2 (D + 1) outputs with DiagGaussianDensity(D + 1), or pass a reward module')
+            if not as_tuple:
+                prev_states, actions = inputs[..., :D], inputs[..., D:]
+            dstates, rewards = outs[..., :D], outs[..., D:D + 1]
+        else:
+            if not as_tuple:
+                D = outs.shape[-1]
+                prev_states, actions = inputs[..., :D], inputs[..., D:]
+            if not callable(self.reward_func):
+                raise NotImplementedError('reward_func must be callable, or None with a learned reward head')
+            dstates = outs
+            rewards = self.reward_func(prev_states + dstates, actions)
         states = dstates if deltas else prev_states + dstates
         if separate_outputs:
             return states, rewards

@@ -220,11 +220,13 @@ def loss_weights(d, B_global):
 
 
 def engine_from_problem(d, device='cuda:0', rows_per_wg_hint=0, shard=None, B_global=None,
-                        row_offset=None, force_generic=False, no_shaped=False, precision=None, mm_span=None):
+                        row_offset=None, force_generic=False, no_shaped=False, precision=None, mm_span=None,
+                        reward_spec=None):
     """Build an Engine + its device input tensors from a problem dict.
     shard=(rank, world): this rank's contiguous block of rows (whole mm groups) of ONE
     global batch described by d.  B_global/row_offset instead place the whole of d as a
-    shard of a larger global batch (weak scaling)."""
+    shard of a larger global batch (weak scaling).  reward_spec: instead of the analytic reward d describes
+    (engine.LEARNED_REWARD: a learned reward head, d's dynamics head 2 (D + 1) wide)."""
     from . import engine as E
     dev = torch.device(device)
     B, D = d['x0'].shape
@@ -248,7 +250,7 @@ def engine_from_problem(d, device='cuda:0', rows_per_wg_hint=0, shard=None, B_gl
     dyn_ps = np.asarray(d['dyn_mask0']).ndim == 3
     eng = E.Engine(Bl, D, U, H, layer_dims(d, 'pol'), list(np.asarray(d['pol_keep'])),
                    layer_dims(d, 'dyn'), list(np.asarray(d['dyn_keep'])),
-                   reward_spec_from_problem(d), mm_states=bool(d['mm_states']),
+                   reward_spec or reward_spec_from_problem(d), mm_states=bool(d['mm_states']),
                    mm_rewards=bool(d['mm_rewards']), mm_groups=Gl, device=dev, B_global=Bg,
                    row_offset=roff, rows_per_wg_hint=rows_per_wg_hint, force_generic=force_generic,
                    no_shaped=no_shaped, infer_ns=bool(d['infer_ns']) if 'infer_ns' in d else False,
