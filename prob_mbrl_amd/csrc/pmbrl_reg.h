@@ -1,5 +1,5 @@
 // Register-resident sweep kernels for the cart-pole class of shapes (round 4): three-layer policy and dynamics
-// networks with ONE hidden width of 177..208 units (13 output tiles), at most 8 network inputs (D + U <= 8), no moment
+// networks with ONE hidden width of 193..208 units (13 output tiles), at most 8 network inputs (D + U <= 8), no moment
 // matching inside the sweep, 16 rows per workgroup.  Same mathematics, same stashes and the same C ABI as the
 // latency-optimised family (pmbrl_fast.h) -- what changes is where a step's time goes:
 //
@@ -36,7 +36,7 @@
 
 #define PR_NW 4                 // waves per workgroup: one per SIMD
 #define PR_NTHR (PR_NW * 64)
-#define PR_NT 13                // output tiles of a hidden layer (hidden width 177 .. 208)
+#define PR_NT 13                // output tiles of a hidden layer (hidden width 193 .. 208: net_plan, nt = (width + 15) / 16)
 #define PR_KB 7                 // K32 blocks of a hidden width
 #define PR_SLOTS 3              // register-resident tiles per wave and hidden->hidden layer: tile 4 s + w
 #define PR_XT 12                // the tile that lives in LDS (run by wave pr_xwave(net))

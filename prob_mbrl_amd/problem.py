@@ -80,7 +80,10 @@ def _xavier(rng, out_f, in_f):
 
 
 def synthetic_problem(name='cartpole_nomm', seed=0, P=None, S=None, H=None, data_seed=None):
-    cfg = dict(CONFIGS[name])
+    """name: a key of CONFIGS, or a shape dictionary with the keys of a CONFIGS entry (tests that walk shapes no
+    benchmark configuration has).  Optional keys of a shape: z_orth, x_scale, y_scale, and mm_rewards (moment matching
+    of the rewards apart from that of the states, which 'mm' switches; default: the same as 'mm')."""
+    cfg = dict(name) if isinstance(name, dict) else dict(CONFIGS[name])
     if P is not None:
         cfg['P'] = P
     if S is not None:
@@ -135,7 +138,8 @@ def synthetic_problem(name='cartpole_nomm', seed=0, P=None, S=None, H=None, data
     d['x0'] = np.repeat(x0p, Sn, axis=0)        # utils.tile layout: row = p*S + s
     d['H'] = Hn
     d['gamma'] = np.full(Hn, 1.0 / Hn)
-    d['mm_states'] = d['mm_rewards'] = bool(cfg['mm'])
+    d['mm_states'] = bool(cfg['mm'])
+    d['mm_rewards'] = bool(cfg.get('mm_rewards', cfg['mm']))
     d['mm_groups'] = Pn if cfg['mm'] else 0
     d['maximize'] = True
     d['infer_ns'] = False

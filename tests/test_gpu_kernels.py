@@ -145,12 +145,13 @@ def test_rollout_parity(dev, name, generic):
 
 
 def _reg_fixtures():
-    """fixtures whose shape the register-resident family takes (three-layer nets of hidden width 177..208, D + U <= 8)"""
+    """fixtures whose shape the register-resident family takes (three-layer nets of hidden width 193..208, D + U <= 8:
+    tests/test_gpu_reg_envelope.py pins both ends)"""
     out = []
     for n in common.fixture_names('iter'):
         d = np.load(os.path.join(common.GOLDEN, n + '.npz'))
         if ('pol_W1' in d and int(d['pol_n_layers']) == 3 and int(d['dyn_n_layers']) == 3 and
-                176 < d['pol_W0'].shape[0] <= 208 and d['pol_W0'].shape[0] == d['dyn_W0'].shape[0]):
+                192 < d['pol_W0'].shape[0] <= 208 and d['pol_W0'].shape[0] == d['dyn_W0'].shape[0]):
             out.append(n)
     return out
 
