@@ -190,7 +190,8 @@ typedef struct pmbrl_config {
  *   PMBRL_REPLAY=0|1|2      default of pmbrl_plan_set_replay (1)
  *   PMBRL_DW_PIPE=off | n0,n1,...   dW GEMM behind the adjoint sweep on a second stream: never / these step ranges
  * Read by the Python layer: PMBRL_PRECISION (default arithmetic: f32 | split | split_f16), PMBRL_LIB_PATH (the shared
- * library to load), PMBRL_TORCH_ALLREDUCE=1 (gradient all-reduce through torch.distributed instead of the C ABI). */
+ * library to load), PMBRL_SHARDED_TAIL=0 (mc_pilco keeps the separate calls on a sharded run even where the gradient
+ * exchange could run inside pmbrl_rollout_bwd_adam), PMBRL_TORCH_ALLREDUCE=1 (gradient all-reduce through torch.distributed instead of the C ABI). */
 
 typedef struct pmbrl_plan pmbrl_plan;
 
@@ -211,7 +212,8 @@ enum {
   PMBRL_INFO_INPLACE = 18,   /* general family: 0 two activation buffers, 1 in-place layers (64-row workgroups), 2 the same on the 512-wide layers of pmbrl_wide.h */
   PMBRL_INFO_REG_FWD_CALLS = 19, /* forward sweeps of this plan the register-resident family has served so far (a graph replay counts once, when recorded) */
   PMBRL_INFO_REG_BWD_CALLS = 20, /* ... adjoint sweeps */
-  PMBRL_INFO_COUNT = 21
+  PMBRL_INFO_TAIL_CALLS = 21,    /* pmbrl_rollout_bwd_adam calls of this plan that ran with the gradient exchange inside (pmbrl_plan_set_grad_comm) */
+  PMBRL_INFO_COUNT = 22
 };
 
 const char* pmbrl_last_error(void);
@@ -372,7 +374,7 @@ int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* grads_d,
                             double eps, double max_norm, float* norm_out_d,
                             const int32_t* status_d, int32_t expect);
 
-/* ---- fused iteration tail (one process; with a gradient all-reduce in between use the separate calls) -------------
+/* ---- fused iteration tail (one process, or rows sharded over ranks: pmbrl_plan_set_grad_comm below) ----------------
  * pmbrl_plan_set_loss: dL/dr weights [H][B] (device, resident; algorithms/mc_pilco.py:134-144: +-gamma_t / B) -- every
  * pmbrl_rollout_fwd on the plan then also leaves sum_{t < valid, b} w r in *loss_out_d (the reduction of
  * pmbrl_weighted_sum_steps, queued by the forward call itself); NULL switches it off.
@@ -454,6 +456,39 @@ int pmbrl_p2p_allreduce_f64(pmbrl_p2p* p, void* stream, double* buf_d, int64_t n
 int pmbrl_plan_set_p2p(pmbrl_plan* plan, pmbrl_p2p* p);
 int pmbrl_p2p_error(pmbrl_p2p* p, int32_t* err_out);   /* host sync; 1: a wait timed out since the last call */
 void pmbrl_p2p_destroy(pmbrl_p2p* p);
+
+/* ---- the fused iteration tail on a sharded run: the collective inside pmbrl_rollout_bwd_adam ----------------------
+ * pmbrl_plan_set_grad_comm attaches the transport of the flat policy gradient to a plan: an RCCL communicator or a
+ * peer-to-peer object, at most one of the two non-NULL; both NULL detaches it.  The plan keeps the pointer and owns a
+ * small exchange buffer of its own: destroy the plan (or detach) before the transport.  Not offered for plans whose
+ * moment-matching groups are spread over ranks (mm_span_rows).
+ * With a transport attached, pmbrl_rollout_bwd_adam queues on the caller's stream, without a host synchronisation:
+ *   1. horizon agreement: every rank contributes min(status_d[0], H) as entry `rank` of a vector of `nranks` floats
+ *      (zero elsewhere), the vector is summed over the ranks, and the minimum of its entries is written to status_d[0]
+ *      where it is smaller: the adjoint sweep, the dW GEMM and the loss of every rank stop at the same step;
+ *   2. the adjoint sweep, the dW GEMM and the gradient reduction as without a transport, the reduction leaving the flat
+ *      gradient, this rank's partial loss and this rank's failure flag (status_d[1] != 0, or a peer-to-peer wait that
+ *      timed out on this rank) in one buffer of n + 2 floats;
+ *   3. ONE in-place sum of that buffer over the ranks (ncclAllReduce / the one-hop exchange: rank order, the same bits
+ *      on every rank);
+ *   4. the summed gradient into grad_pol_flat_d, the partial sums of ITS norm, and the decision: clip + Adam are taken
+ *      as pmbrl_clip_adam_guarded defines them, and also skipped when the summed failure flag is non-zero (on every
+ *      rank alike; status_d[1] is then set on every rank).  loss_out_d receives the loss summed over the ranks,
+ *      norm_out_d the norm of the summed gradient.
+ *      A peer-to-peer wait that times out INSIDE exchange 3 is not in that exchange's flag: the rank it happened on
+ *      skips the step and sets its own status_d[1] in this call, the other ranks have taken the step and learn of it in
+ *      the NEXT call's exchange (the error word of pmbrl_p2p is sticky until pmbrl_p2p_error reads it) -- one
+ *      iteration late.  The replicas differ from then on: the caller must stop, not resample.
+ * Every rank must make the call: it is a collective.  A plan with a peer-to-peer transport runs the call eagerly
+ * whatever pmbrl_plan_set_replay says (the exchange cannot be recorded); with RCCL it may be recorded, the transport is
+ * part of what two calls must have in common.  Without a transport the call is what it was, bit for bit; so is a
+ * transport of one rank.  PMBRL_INFO_TAIL_CALLS counts the calls that ran this way.
+ * Launches this adds to the one-process call: three for the horizon (vector, exchange, minimum) and three around the
+ * gradient (pack, exchange, finish).  The reduction's last stage does not yet store into the peers' slots itself, and
+ * the horizon vector is not yet written by the forward call.
+ * Returns -2 if the flat gradient (+ 2 floats) does not fit the peer-to-peer slots, -3 for groups spread over ranks:
+ * the plan is left without a transport, the separate calls still work. */
+int pmbrl_plan_set_grad_comm(pmbrl_plan* plan, pmbrl_comm* comm, pmbrl_p2p* p2p);
 
 /* Optional per-kernel timing for bench.py's roofline line: when enabled, the
  * library brackets its kernels with hipEvents on the caller's stream;

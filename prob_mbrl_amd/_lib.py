@@ -22,7 +22,8 @@ FLAG_GMM_EXACT_NOISE_GRAD = 256
 MAX_COMP = 8
 REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
-INFO_COUNT = 21
+INFO_COUNT = 22
+INFO_TAIL_CALLS = 21    # PMBRL_INFO_TAIL_CALLS
 TIMER_COUNT = 8
 TIMER_NAMES = ['pack', 'fwd', 'bwd', 'dw', 'dw_reduce', 'reward']
 
@@ -98,7 +99,7 @@ EXPORTS = [
     'pmbrl_comm_unique_id', 'pmbrl_comm_init', 'pmbrl_allreduce_sum', 'pmbrl_comm_count', 'pmbrl_comm_destroy',
     'pmbrl_plan_set_comm', 'pmbrl_plan_set_collective',
     'pmbrl_p2p_create', 'pmbrl_p2p_handle', 'pmbrl_p2p_open', 'pmbrl_p2p_allreduce_f32', 'pmbrl_p2p_allreduce_f64',
-    'pmbrl_plan_set_p2p', 'pmbrl_p2p_error', 'pmbrl_p2p_destroy',
+    'pmbrl_plan_set_p2p', 'pmbrl_p2p_error', 'pmbrl_p2p_destroy', 'pmbrl_plan_set_grad_comm',
 ]
 
 class Adam(C.Structure):
@@ -229,6 +230,8 @@ def load():
     lib.pmbrl_p2p_error.argtypes = [vp, C.POINTER(i32)]
     lib.pmbrl_p2p_destroy.restype = None
     lib.pmbrl_p2p_destroy.argtypes = [vp]
+    lib.pmbrl_plan_set_grad_comm.restype = C.c_int
+    lib.pmbrl_plan_set_grad_comm.argtypes = [vp, vp, vp]
     lib.pmbrl_plan_set_collective.restype = C.c_int
     lib.pmbrl_plan_set_collective.argtypes = [vp, COLLECTIVE_FN, vp]
     _lib = lib

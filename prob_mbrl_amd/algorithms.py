@@ -138,7 +138,10 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
         z_mm = frozen_noise['z_mm'].to(dev, torch.float32)
         z_rr = frozen_noise['z_rr'].to(dev, torch.float32)
 
+    n_resamples = [0]       # (sharded pipelined loop: compared over the ranks at the end)
+
     def resample():
+        n_resamples[0] += 1
         if frozen_noise is not None:
             return
         seed = torch.randint(2**32, [1])
@@ -177,12 +180,54 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
     # word one iteration late, from a pinned snapshot queued right behind the forward sweep.  The
     # host then never waits for a whole iteration: while it prepares iteration i+1 the device still
     # has the adjoint sweep, the dW GEMM and the Adam step of iteration i to run.
-    pipelined = (world == 1) and not callable(on_rollout) and not need_autograd
+    # Rows sharded over ranks take the same two-call loop when the gradient exchange can run INSIDE the backward call
+    # (pmbrl_plan_set_grad_comm: RCCL, or the peer-to-peer transport with PMBRL_P2P=1): the ranks agree on the horizon,
+    # sum gradient, loss and failure flag and decide the step on the device; the host reads the AGREED status one iteration
+    # late, so every rank resamples, switches arithmetic and counts optimiser steps in the same iterations.  Anything
+    # that needs the host between the sweeps (CVaR, regulariser, groups spread over ranks, hooks) keeps the separate calls.
+    # Decided per engine, the same way on every rank (tail_for): a plan that cannot take the transport -- a flat gradient
+    # beyond the peer-to-peer slots with no RCCL behind them, a refusal by the library -- keeps the separate calls.
+    # PMBRL_SHARDED_TAIL=0 keeps them everywhere (tools/bench_sharded_tail.py measured the fused call SLOWER than bench.py's
+    # separate calls with two ranks on one device; this loop's own separate calls, with their host round trips, have
+    # not been timed against it -- DESIGN_LOG.md).
+    from .distributed import sharded_tail_wanted
+    tail_eligible = (world > 1 and not callable(on_rollout) and not need_autograd and not cvar and not reg_weight > 0
+                     and mm_span is None and sharded_tail_wanted())
+    tail_of = {}            # id(engine) -> (engine, its transport or None)
+    tail_used = [None]
+
+    def tail_for(eng, n_params):
+        """The transport `eng` carries inside its backward call, or None: keep the separate calls.  Collective the first
+        time an engine is seen (the ranks meet new engines in the same iterations)."""
+        hit = tail_of.get(id(eng))
+        if hit is not None and hit[0] is eng:
+            return hit[1]
+        import torch.distributed as dist
+        from .distributed import tail_transport
+        tr = tail_transport(process_group, dev, n_params=n_params)
+        ok = 0
+        if tr is not None:
+            try:
+                eng.attach_grad_comm(tr)
+                ok = 1
+            except PmbrlError as e:
+                print('prob_mbrl_amd: rank %d keeps the separate calls of the sharded iteration (%s)' % (rank, e))
+        on_dev = dist.get_backend(process_group) == 'nccl'
+        fl = torch.tensor([ok], dtype=torch.int32, device=dev if on_dev else 'cpu')
+        dist.all_reduce(fl, op=dist.ReduceOp.MIN, group=process_group)
+        if int(fl[0]) == 0:
+            if ok:
+                eng.attach_grad_comm(None)
+            tr = None
+        tail_of[id(eng)] = (eng, tr)
+        return tr
+
+    pipelined = (world == 1 or tail_eligible) and not callable(on_rollout) and not need_autograd
     # arithmetic of the sweeps: the library default, until a rollout fails under fp16 pieces -- whose
     # range, not the rollout, may be what failed: the rest of this call then runs on the bf16 pieces
     prec = dict(name=None)
     pending = None          # (i, event, pinned status, loss, S, A, R) of the iteration in flight
-    pipe = dict(snap=[torch.empty(1, dtype=torch.int32).pin_memory() for _ in range(2)],
+    pipe = dict(snap=[torch.zeros(2, dtype=torch.int32).pin_memory() for _ in range(2)],
                 ev=[torch.cuda.Event() for _ in range(2)], step_dev=None,
                 loss=[torch.zeros(1, dtype=torch.float32, device=dev) for _ in range(2)]) if pipelined else None
 
@@ -195,8 +240,17 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
     def settle(pend):
         """Host side of a pipelined iteration, once its status word has arrived."""
         nonlocal n_opt_steps
-        j, ev, snap, loss_j, S_j, A_j, R_j = pend
+        j, ev, snap, loss_j, S_j, A_j, R_j, tail = pend
         ev.synchronize()
+        if tail is not None and int(snap[1]) != 0:
+            # the failure flag summed over the ranks with the gradient: an adjoint sweep that reported a failure of its
+            # own, or a peer-to-peer wait that had timed out before the exchange, on ANY rank -- the device skipped the
+            # step on every rank, and every rank raises here, in the same iteration.  (A wait that timed out INSIDE the
+            # gradient exchange: the rank it happened on skipped alone and raises here now -- its own status word says
+            # so, pm_tail_finish_kernel; the others raise one iteration later, from the sticky error word.)
+            raise RuntimeError('sharded iteration %d: the adjoint sweep or the gradient exchange failed on a rank (a '
+                               'barrier between workgroups or a wait for a peer timed out; PMBRL_P2P_TIMEOUT_SPINS sets '
+                               'the latter)' % j)
         n_valid = min(int(snap[0]), H)
         if n_valid < H and prec['name'] is None and E.safe_precision(pend_prec[0]) is not None:
             # (the device skipped or truncated this step on its own; no resampling: same random numbers,
@@ -248,21 +302,24 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
             #  would update the wrong numbers; the autograd form scales the gradient back)
             cache = None if (need_autograd or bundle.unit_scaled) else _adam_flat_state(opt, bundle.pol_params,
                                                                                          bundle.pol_flat)
+            tail = tail_for(bundle.engine, bundle.pol_flat.numel()) if (tail_eligible and cache is not None) else None
             if cache is None:
                 loss, states, actions, rewards = _autograd_iteration(
                     x0_, dynamics, policy, H, opt, pegasus, mm_states, mm_rewards, mm_groups, z_mm,
                     z_rr, maximize, clip_grad, cvar_eps, reg_weight, disc, on_rollout, i, rk,
                     process_group, world, value_func, replay, dist_kw)
-            elif pipelined:
+            elif pipelined and (world == 1 or tail is not None):
                 eng = bundle.engine
+                tail_used[0] = tail if tail is not None else tail_used[0]
                 if pipe['step_dev'] is None:
                     pipe['step_dev'] = torch.tensor([cache['step']], dtype=torch.int64, device=dev)
                     pipe['cache'] = cache
                 S, A, R = bundle.forward(x0_)
                 pend_prec[0] = eng.info['precision']
                 k = i & 1
-                pipe['snap'][k].copy_(eng.status[0:1], non_blocking=True)
-                pipe['ev'][k].record()
+                if tail is None:
+                    pipe['snap'][k][0:1].copy_(eng.status[0:1], non_blocking=True)
+                    pipe['ev'][k].record()
                 gw = _loss_weights(eng, gamma_full, sign, Bg, dev)
                 # (the loss: formed by the backward call's gradient reduction, written by its optimiser launch --
                 #  pmbrl_adam::loss_out_d; two buffers: the host reads iteration i's one iteration late)
@@ -273,10 +330,19 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
                 eng.backward(gw, adam=dict(params=bundle.pol_flat, exp_avg=cache['m'], exp_avg_sq=cache['v'],
                                            step=pipe['step_dev'], lr=grp['lr'], betas=grp['betas'], eps=grp['eps'],
                                            max_norm=clip_grad, expect=min_steps, loss_out=pipe['loss'][k]))
-                pending = (i, pipe['ev'][k], pipe['snap'][k], loss, S, A, R)
+                if tail is not None:
+                    # (the horizon the ranks agreed on and the summed failure flag exist only behind the backward call)
+                    pipe['snap'][k].copy_(eng.status, non_blocking=True)
+                    pipe['ev'][k].record()
+                pending = (i, pipe['ev'][k], pipe['snap'][k], loss, S, A, R, tail)
                 queued = True
             else:
                 eng = bundle.engine
+                if pipe is not None and pipe['step_dev'] is not None:
+                    # (an engine that keeps the separate calls behind one that ran the fused tail: the step count moves
+                    #  back to the host)
+                    cache['step'] = int(pipe['step_dev'].item())
+                    pipe['step_dev'] = None
                 def agreed_steps(e):
                     """Valid steps of the sweep just run -- on a sharded run the MIN over the ranks: every rank must take
                     the same branch and the same horizon, a failure anywhere truncates (or fails) the rollout
@@ -426,6 +492,25 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
         settle(pending)
     if pipe is not None and pipe['step_dev'] is not None:
         pipe['cache']['step'] = int(pipe['step_dev'].item())
+    tail = tail_used[0]
+    if tail is not None:
+        # the replicas must have walked the same iterations: a rank that resampled, switched arithmetic or stepped alone
+        # has different parameters from here on, and nothing later would notice
+        import torch.distributed as dist
+        from .distributed import P2PComm
+        mine = [n_opt_steps, n_resamples[0], 0 if prec['name'] is None else 1,
+                int(pipe['cache']['step']) if pipe.get('cache') else 0,
+                1 if (isinstance(tail, P2PComm) and tail.failed()) else 0]
+        on_dev = dist.get_backend(process_group) == 'nccl'
+        both = torch.tensor(mine + [-x for x in mine], dtype=torch.int64, device=dev if on_dev else 'cpu')
+        dist.all_reduce(both, op=dist.ReduceOp.MAX, group=process_group)
+        hi, lo = both[:len(mine)].tolist(), [-x for x in both[len(mine):].tolist()]
+        if hi[4]:
+            raise RuntimeError('peer-to-peer exchange: a rank waited for a peer that did not arrive in time '
+                               '(PMBRL_P2P_TIMEOUT_SPINS sets the wait)')
+        if hi != lo:
+            raise RuntimeError('sharded run: the ranks did not walk the same iterations (optimiser steps, resamplings, '
+                               'arithmetic switches, Adam steps: max %s, min %s)' % (hi[:4], lo[:4]))
     cache = getattr(opt, '_pmbrl_flat', None)
     if cache is not None and type(opt) is torch.optim.Adam:
         _sync_adam_state(opt, [p for p in opt.param_groups[0]['params'] if p.requires_grad], cache)

@@ -29,7 +29,7 @@ int pm_fail(int code, const std::string& msg) {
 static int fail(int code, const std::string& msg) { return pm_fail(code, msg); }
 
 extern "C" const char* pmbrl_last_error(void) { return g_err.c_str(); }
-extern "C" int pmbrl_version(void) { return 7; }
+extern "C" int pmbrl_version(void) { return 8; }
 
 // ---------------------------------------------------------------------------
 // hipGraph entry points: record the library calls queued on a stream between begin and end, replay them with one
@@ -384,6 +384,72 @@ __global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p
       pq[u] = p[j];
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// the fused iteration tail on a sharded run (pmbrl_plan_set_grad_comm): what pmbrl_rollout_bwd_adam queues around the
+// in-place sum of [flat gradient | loss partial | failure flag] over the ranks
+// ---------------------------------------------------------------------------
+// horizon agreement, 1: this rank's valid steps as entry `rank` of a vector the transport sums (both transports only sum)
+__global__ __launch_bounds__(64) void pm_tail_hvec_kernel(float* __restrict__ hvec, int world, int rank,
+                                                          const int* __restrict__ status, int H) {
+  for (int q = threadIdx.x; q < world; q += blockDim.x) hvec[q] = q == rank ? (float)min(max(status[0], 0), H) : 0.f;
+}
+// 2: the ranks' minimum, written where it is smaller than what this rank's forward sweep left (a rank whose exchange
+// timed out holds zeros for its peers: no step is valid, nothing is stepped)
+__global__ __launch_bounds__(64) void pm_tail_hmin_kernel(const float* __restrict__ hvec, int world,
+                                                          int* __restrict__ status, int H) {
+  if (threadIdx.x != 0) return;
+  int m = H;
+  for (int q = 0; q < world; ++q) m = min(m, (int)hvec[q]);
+  if (m < min(status[0], H)) status[0] = m;
+}
+// behind the gradient reduction: this rank's loss (the reduction's partial sums in workgroup order, as
+// pm_clip_adam_kernel adds them; n_loss_part = 0: already in xb[n], or not asked for) and failure flag next to the gradient
+__global__ __launch_bounds__(64) void pm_tail_pack_kernel(float* __restrict__ xb, int n, int n_loss_part, int loss_here,
+                                                          const int* __restrict__ status, const int* __restrict__ err) {
+  const int lane = threadIdx.x;
+  if (n_loss_part > 0) {
+    double ls = 0.0;
+    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    if (lane == 0) xb[n] = (float)ls;
+  } else if (!loss_here && lane == 0) {
+    xb[n] = 0.f;
+  }
+  if (lane == 0) xb[n + 1] = (status[1] != 0 || (err && *err != 0)) ? 1.f : 0.f;
+}
+// behind the exchange: the summed gradient into the caller's vector, the partial sums of ITS squares (pm_gradnorm_kernel's
+// blocks: the separate calls' norm bit for bit), the summed loss where pm_clip_adam_kernel looks for it, and the decision
+__global__ __launch_bounds__(64) void pm_tail_finish_kernel(const float* __restrict__ xb, float* __restrict__ g, long long n,
+                                                            int* __restrict__ status, int expect,
+                                                            long long* __restrict__ step, const int* __restrict__ err) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // a failure anywhere is a failure everywhere: the host reads it one iteration late.  (A wait of THIS rank that timed
+    // out in the exchange just now is not in the sum -- the flag was packed before it: this rank says so in its own
+    // status word, the others learn it from the sticky error word in the next exchange.)
+    const int bad = (xb[n + 1] != 0.f || (err && *err != 0)) ? 1 : 0;
+    if (bad) status[1] = 1;
+    const int go = (status[0] >= expect && status[1] == 0) ? 1 : 0;
+    g_adam_go = go;
+    if (go && step) step[0] += 1;
+    g_loss_part[0] = (double)xb[n];
+  }
+  double tot = 0.0;
+  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
+    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
+    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (i0 + 3 < n) {
+      t = *reinterpret_cast<const f32x4*>(xb + i0);
+      for (int r = 0; r < 4; ++r) g[i0 + r] = t[r];
+    } else {
+      for (int r = 0; r < 4; ++r)
+        if (i0 + r < n) { t[r] = xb[i0 + r]; g[i0 + r] = t[r]; }
+    }
+    tot += pm_sq4_wave(t, i0, n);
+  }
+  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
 }
 
 // all weight / bias repacking of one forward call in ONE launch (blockIdx.y = job)
@@ -1658,6 +1724,7 @@ extern "C" void pmbrl_plan_destroy(pmbrl_plan* p) {
   if (p->ang_d) (void)hipFree(p->ang_d);
   if (p->dw_blocks_d) (void)hipFree(p->dw_blocks_d);
   if (p->dw_units_d) (void)hipFree(p->dw_units_d);
+  if (p->tail_buf_d) (void)hipFree(p->tail_buf_d);
   if (p->pipe_stream) {
     (void)hipStreamDestroy(p->pipe_stream);
     for (int k = 0; k < p->pipe_K; ++k) (void)hipEventDestroy(p->pipe_ev[k]);
@@ -1691,6 +1758,7 @@ extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   info[PMBRL_INFO_INPLACE] = p->inplace;
   info[PMBRL_INFO_REG_FWD_CALLS] = p->reg_calls[0];
   info[PMBRL_INFO_REG_BWD_CALLS] = p->reg_calls[1];
+  info[PMBRL_INFO_TAIL_CALLS] = p->tail_calls;
   return 0;
 }
 
@@ -2124,6 +2192,12 @@ extern "C" int pmbrl_plan_set_loss(pmbrl_plan* p, const float* loss_weights_d, f
   return 0;
 }
 
+// the in-place fp32 sum over the ranks through the plan's gradient transport (pmbrl_plan_set_grad_comm)
+static int tail_allreduce(pmbrl_plan* p, hipStream_t s, float* buf_d, int64_t n) {
+  if (p->grad_p2p) return pmbrl_p2p_allreduce_f32(p->grad_p2p, s, buf_d, n);
+  return pmbrl_allreduce_sum(p->grad_comm, s, buf_d, n);
+}
+
 static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
                        const float* states_d, const float* actions_d,
                        const float* rewards_d, const float* grad_rewards_d,
@@ -2138,6 +2212,17 @@ static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl
   RolloutArgs A;
   int rc = fill_args(p, workspace, in, A);
   if (rc) return rc;
+  // rows sharded over ranks, optimiser attached (pmbrl_plan_set_grad_comm): the ranks agree on the horizon first -- the
+  // sweep, the dW GEMM and the loss below read the agreed status_d[0]
+  const bool tail = opt && (p->grad_comm || p->grad_p2p);
+  float* const xb = p->tail_buf_d;
+  if (tail) {
+    if (p->span && p->cfg.mm_span_ranks > 1) return fail(-3, "pmbrl_rollout_bwd_adam with a gradient transport: moment-matching groups spread over ranks are not offered");
+    float* hvec = xb + ((size_t)p->pol.n_params + 2 + 3) / 4 * 4;
+    hipLaunchKernelGGL(pm_tail_hvec_kernel, dim3(1), dim3(64), 0, s, hvec, p->tail_world, p->tail_rank, (const int*)status_d, p->cfg.H);
+    if (int rc2 = tail_allreduce(p, s, hvec, p->tail_world)) return rc2;
+    hipLaunchKernelGGL(pm_tail_hmin_kernel, dim3(1), dim3(64), 0, s, (const float*)hvec, p->tail_world, (int*)status_d, p->cfg.H);
+  }
   char* ws = static_cast<char*>(workspace);
   A.states = const_cast<float*>(states_d);
   A.actions = const_cast<float*>(actions_d);
@@ -2347,19 +2432,22 @@ static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl
   }
   const int n = (int)p->pol.n_params;
   // the fused iteration (one process, optimiser attached): the reduction forms the gradient norm's partial sums and the
-  // go / no-go decision on the way -- pm_gradnorm_kernel's launch is not needed
-  const bool norm_fused = opt && !piped && (n + 255) / 256 <= PM_NORM_MAXB;
+  // go / no-go decision on the way -- pm_gradnorm_kernel's launch is not needed.  (Rows sharded over ranks: the norm is
+  // that of the SUMMED gradient -- pm_tail_finish_kernel, behind the exchange.)
+  const bool part_ok = opt && !piped && (n + 255) / 256 <= PM_NORM_MAXB;
+  const bool norm_fused = part_ok && !tail;
   // ... and, asked for (pmbrl_adam::loss_out_d), the loss' partial sums: the optimiser launch adds them -- no loss launch
   // behind the forward call (PMBRL_FUSE_LOSS=0: pm_weighted_sum_kernel, here)
-  const bool loss_fused = norm_fused && opt->loss_out_d && p->sw.fuse_loss;
+  const bool loss_fused = part_ok && opt->loss_out_d && p->sw.fuse_loss;
+  float* const red_out = tail ? xb : grad_pol_flat_d;
   {
     ScopedTimer tm(p, PMBRL_TIMER_DW_REDUCE, s);
     if (piped)   // every partial row was written (pm_dw_range)
       hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, W.part, p->pipe_rows, n,
-                         W.part_stride, grad_pol_flat_d, (const int*)nullptr, 0, 1);
+                         W.part_stride, red_out, (const int*)nullptr, 0, 1);
     else
       hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, W.part, p->dw_nsplit, n,
-                         W.part_stride, grad_pol_flat_d, (const int*)status_d, W.chunks_per_step, W.chunks_per_split,
+                         W.part_stride, red_out, (const int*)status_d, W.chunks_per_step, W.chunks_per_split,
                          norm_fused ? 1 : 0, (const int*)status_d, opt ? (opt->expect_steps > 0 ? opt->expect_steps : p->cfg.H) : 0,
                          opt ? reinterpret_cast<long long*>(opt->step_d) : (long long*)nullptr,
                          loss_fused ? rewards_d : (const float*)nullptr, grad_rewards_d, (long long)p->cfg.H * p->cfg.B,
@@ -2369,17 +2457,31 @@ static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl
   if (opt && opt->loss_out_d && !loss_fused) {
     const long long nn = (long long)p->cfg.H * p->cfg.B;
     const int nbl = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (nn + 2047) / 2048));
-    hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nbl), dim3(256), 0, s, rewards_d, grad_rewards_d, nn, opt->loss_out_d,
-                       (const int*)status_d, (long long)p->cfg.B);
+    hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nbl), dim3(256), 0, s, rewards_d, grad_rewards_d, nn,
+                       tail ? xb + n : opt->loss_out_d, (const int*)status_d, (long long)p->cfg.B);
   }
   HIPCHK(hipGetLastError());
+  const int expect = opt ? (opt->expect_steps > 0 ? opt->expect_steps : p->cfg.H) : 0;
+  if (tail) {
+    // [gradient | loss partial | failure flag] summed over the ranks in place, then the summed gradient's norm and the
+    // decision every rank takes alike; the optimiser launch is the one-process one
+    hipLaunchKernelGGL(pm_tail_pack_kernel, dim3(1), dim3(64), 0, s, xb, n, loss_fused ? (n + 255) / 256 : 0,
+                       opt->loss_out_d && !loss_fused ? 1 : 0, (const int*)status_d, (const int*)p->tail_err_d);
+    if (int rc2 = tail_allreduce(p, s, xb, (int64_t)n + 2)) return rc2;
+    hipLaunchKernelGGL(pm_tail_finish_kernel, dim3(pm_norm_blocks(n)), dim3(64), 0, s, (const float*)xb, grad_pol_flat_d,
+                       (long long)n, (int*)status_d, expect, reinterpret_cast<long long*>(opt->step_d), (const int*)p->tail_err_d);
+    HIPCHK(hipGetLastError());
+    return clip_adam_guarded_impl(stream, opt->params_d, grad_pol_flat_d, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d,
+                                  opt->lr, opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, status_d, expect,
+                                  true, opt->loss_out_d, opt->loss_out_d ? 1 : 0);
+  }
   // the optimiser step behind it, decided on the device (a form with the reduction, the norm and the update in ONE launch
   // around a device-wide barrier was measured at the C2 shape: 25.6 us against 13.7 + 4.7 + 7.1 us for the three launches
   // -- the barrier's L2 round trips cost what two launches do; not kept)
   if (opt)
     return clip_adam_guarded_impl(stream, opt->params_d, grad_pol_flat_d, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d,
                                   opt->lr, opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, status_d,
-                                  opt->expect_steps > 0 ? opt->expect_steps : p->cfg.H, norm_fused,
+                                  expect, norm_fused,
                                   loss_fused ? opt->loss_out_d : nullptr, loss_fused ? (n + 255) / 256 : 0);
   return 0;
 }
@@ -2392,6 +2494,15 @@ static int rollout_bwd_replay(pmbrl_plan* p, void* stream, void* workspace, cons
                               float* action_grad_norms_d, int32_t* status_d, const pmbrl_adam* opt) {
   if (!p || !in) return fail(-1, "null argument");
   HIPCHK(hipSetDevice(p->device));
+  const bool tail = opt && (p->grad_comm || p->grad_p2p);
+  if (tail) ++p->tail_calls;
+  if (tail && p->grad_p2p) {
+    // the peer-to-peer exchange cannot be recorded (its generation is a kernel argument): eagerly, whatever
+    // pmbrl_plan_set_replay says
+    if (p->rp[1].exec || p->rp[1].seen) replay_drop(p, 1);
+    return rollout_bwd(p, stream, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d, grad_states_d,
+                       grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d, status_d, opt);
+  }
   ReplayKey K;
   K.val(stream); K.val(workspace); K.add(in, sizeof(*in));
   K.val(states_d); K.val(actions_d); K.val(rewards_d); K.val(grad_rewards_d); K.val(grad_states_d); K.val(grad_actions_d);
@@ -2402,6 +2513,9 @@ static int rollout_bwd_replay(pmbrl_plan* p, void* stream, void* workspace, cons
     K.val(opt->params_d); K.val(opt->exp_avg_d); K.val(opt->exp_avg_sq_d); K.val(opt->step_d);
     K.val(opt->lr); K.val(opt->beta1); K.val(opt->beta2); K.val(opt->eps); K.val(opt->max_norm);
     K.val(opt->norm_out_d); K.val(opt->expect_steps);
+  }
+  if (tail) {     // the transport, its buffer and the loss output: every pointer of a call with the exchange inside
+    K.val(p->grad_comm); K.val(p->tail_buf_d); K.val(opt->loss_out_d);
   }
   // what the forward call left behind decides which conversions the adjoint call queues (weights repacked for the other
   // family, activity words unpacked): a recording is only good for the state it was recorded in
@@ -2961,6 +3075,45 @@ extern "C" int pmbrl_plan_set_collective(pmbrl_plan* plan, pmbrl_collective_fn f
   if (!plan) return fail(-1, "null argument");
   plan->coll = fn;
   plan->coll_ctx = ctx;
+  return 0;
+}
+
+extern "C" int pmbrl_plan_set_grad_comm(pmbrl_plan* plan, pmbrl_comm* comm, pmbrl_p2p* p2p) {
+  if (!plan) return fail(-1, "null argument");
+  if (comm && p2p) return fail(-1, "pmbrl_plan_set_grad_comm: at most one of the two transports");
+  HIPCHK(hipSetDevice(plan->device));
+  // whatever follows, the plan first lets go of the transport it had (a refusal leaves it without one)
+  for (int k = 0; k < 2; ++k) replay_drop(plan, k);     // (a recording holds the transport it was made with)
+  if (plan->tail_buf_d) {
+    HIPCHK(hipDeviceSynchronize());                       // (calls still queued may read it)
+    HIPCHK(hipFree(plan->tail_buf_d));
+    plan->tail_buf_d = nullptr;
+  }
+  plan->grad_comm = nullptr;
+  plan->grad_p2p = nullptr;
+  plan->tail_err_d = nullptr;
+  // (a plan of LOCAL groups that runs the span form with one rank -- plan_layout: groups beyond the CU count -- is fine)
+  if ((comm || p2p) && plan->span && plan->cfg.mm_span_ranks > 1)
+    return fail(-3, "pmbrl_plan_set_grad_comm: not offered with moment-matching groups spread over ranks (mm_span_rows)");
+  int rank = 0, world = 1;
+  int* err_d = nullptr;
+  const size_t n = plan->pol.n_params;
+  if (comm) { rank = comm->rank; world = comm->nranks; }
+  if (p2p) {
+    size_t cap = 0;
+    pm_p2p_describe(p2p, &rank, &world, &cap, &err_d);
+    if ((n + 2) * sizeof(float) > cap)
+      return fail(-2, "pmbrl_plan_set_grad_comm: the flat gradient is larger than the peer-to-peer slots (max_bytes of pmbrl_p2p_create)");
+  }
+  if (!comm && !p2p) return 0;
+  const size_t nx = (n + 2 + 3) / 4 * 4 + (size_t)world;
+  HIPCHK(hipMalloc(&plan->tail_buf_d, nx * sizeof(float)));
+  HIPCHK(hipMemset(plan->tail_buf_d, 0, nx * sizeof(float)));
+  plan->grad_comm = comm;
+  plan->grad_p2p = p2p;
+  plan->tail_rank = rank;
+  plan->tail_world = world;
+  plan->tail_err_d = err_d;
   return 0;
 }
 

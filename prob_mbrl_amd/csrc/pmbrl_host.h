@@ -107,6 +107,13 @@ struct pmbrl_plan {
   int replay;            // 0 off, 1 the one-launch-per-step forms, 2 every form
   hipStream_t cap_stream;   // what the calls are recorded on
   struct ReplaySlot { unsigned long long key; std::vector<unsigned char> bytes; int seen, dead, aux; hipGraphExec_t exec; long long launches; } rp[2];
+  // gradient transport of the fused iteration tail on a sharded run (pmbrl_plan_set_grad_comm): at most one of the two
+  pmbrl_comm* grad_comm;
+  pmbrl_p2p* grad_p2p;
+  int tail_rank, tail_world;
+  float* tail_buf_d;       // [n + 2 rounded up to 4 | tail_world]: gradient, loss partial, failure flag | horizon vector
+  int* tail_err_d;         // the peer-to-peer object's error word (nullptr: RCCL)
+  mutable int tail_calls;  // pmbrl_rollout_bwd_adam calls that ran with the exchange inside (pmbrl_plan_info)
   // optional per-kernel timing (hipEvents on the caller's stream)
   long long* prof_fwd;
   long long* prof_bwd;
@@ -196,6 +203,8 @@ static inline int fast_variant(int RT, const RolloutArgs& A) {
   return mmg ? PF_VAR_MMG : mm ? PF_VAR_MM : (ext ? PF_VAR_EXT : PF_VAR_LEAN);
 }
 
+// peer-to-peer transport (pmbrl_p2p.hip): what the fused iteration tail needs to know of one
+void pm_p2p_describe(const pmbrl_p2p* p, int* rank, int* nranks, size_t* cap_bytes, int** err_d);
 // register-resident family (pmbrl_reg.hip)
 bool pm_reg_plan_ok(const pmbrl_plan* p);
 bool pm_reg_shape_ok(const pmbrl_plan* p, int prec1);

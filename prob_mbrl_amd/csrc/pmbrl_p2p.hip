@@ -186,6 +186,10 @@ extern "C" int pmbrl_plan_set_p2p(pmbrl_plan* plan, pmbrl_p2p* p) {
   return pmbrl_plan_set_collective(plan, pm_coll_p2p, p);
 }
 
+void pm_p2p_describe(const pmbrl_p2p* p, int* rank, int* nranks, size_t* cap_bytes, int** err_d) {
+  *rank = p->rank; *nranks = p->nranks; *cap_bytes = p->cap; *err_d = p->err_d;
+}
+
 // host sync: 1 if a wait timed out since the last call (a peer never arrived), 0 otherwise
 extern "C" int pmbrl_p2p_error(pmbrl_p2p* p, int32_t* err_out) {
   if (!p || !err_out) return pm_fail(-1, "null argument");

@@ -117,12 +117,25 @@ class P2PComm:
         self.device = dev
         self.max_bytes = int(max_bytes)
         self.p2p = C.c_void_p()
-        _lib.check(self.lib.pmbrl_p2p_create(self.rank, self.world, dev.index or 0, int(max_bytes), C.byref(self.p2p)),
-                   'pmbrl_p2p_create')
-        hb = C.create_string_buffer(64)
-        _lib.check(self.lib.pmbrl_p2p_handle(self.p2p, hb), 'pmbrl_p2p_handle')
+        # (a rank that cannot create its object still ENTERS the gather below, with the reason: raising before it would
+        #  leave the other ranks waiting there -- every rank raises together instead)
+        mine = None
+        try:
+            _lib.check(self.lib.pmbrl_p2p_create(self.rank, self.world, dev.index or 0, int(max_bytes), C.byref(self.p2p)),
+                       'pmbrl_p2p_create')
+            hb = C.create_string_buffer(64)
+            _lib.check(self.lib.pmbrl_p2p_handle(self.p2p, hb), 'pmbrl_p2p_handle')
+            mine = bytes(hb.raw)
+        except Exception as e:      # noqa: BLE001
+            mine = 'error on rank %d: %s' % (self.rank, e)
         handles = [None] * self.world
-        dist.all_gather_object(handles, bytes(hb.raw), group=group)
+        dist.all_gather_object(handles, mine, group=group)
+        bad = [h for h in handles if not isinstance(h, bytes)]
+        if bad:
+            # (a PmbrlError like the failed call's own, not a RuntimeError: mc_pilco takes those for failed rollouts.
+            #  pmbrl_p2p_open below is not covered: a rank whose open fails raises alone, the others wait in the barrier)
+            self.close()
+            raise _lib.PmbrlError('peer-to-peer transport unavailable (%s)' % '; '.join(bad))
         for q, h in enumerate(handles):
             if q != self.rank:
                 _lib.check(self.lib.pmbrl_p2p_open(self.p2p, q, C.c_char_p(h)), 'pmbrl_p2p_open')
@@ -191,8 +204,40 @@ def get_p2p(group=None, device=None, max_bytes=4 << 20):
     statistics of groups spread over ranks); all ranks must sit on one node."""
     key = (id(group), str(device))
     if key not in _P2PS:
-        _P2PS[key] = P2PComm(group, device, max_bytes=max_bytes)
+        try:
+            _P2PS[key] = P2PComm(group, device, max_bytes=max_bytes)
+        except _lib.PmbrlError as e:
+            _P2PS[key] = e          # (not tried again at every call: the creation is a collective)
+    if isinstance(_P2PS[key], Exception):
+        raise _P2PS[key]
     return _P2PS[key]
+
+
+def sharded_tail_wanted():
+    """PMBRL_SHARDED_TAIL=0: mc_pilco keeps the separate calls on a sharded run even where the gradient exchange could
+    run inside the backward call (default: on)."""
+    return _env_int('PMBRL_SHARDED_TAIL', 1) != 0
+
+
+def tail_transport(group=None, device=None, n_params=None):
+    """The transport the fused iteration tail of a sharded run can carry inside pmbrl_rollout_bwd_adam
+    (Engine.attach_grad_comm) for this process group: the P2PComm with PMBRL_P2P=1 (the ranks of one node; gloo is then
+    enough for bootstrap), the GradComm on an nccl group, None otherwise (gloo without the peer-to-peer transport, RCCL
+    unavailable, a flat gradient of n_params floats beyond the peer-to-peer slots with no RCCL behind them) -- the
+    caller then keeps the separate calls.  Collective on first use; every rank gets the same answer."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return None
+    if p2p_wanted():
+        p2p = None
+        try:
+            p2p = get_p2p(group, device)      # (raises on every rank or on none: P2PComm.__init__)
+        except _lib.PmbrlError as e:
+            if dist.get_rank(group) == 0:
+                print('prob_mbrl_amd: %s; the sharded iteration keeps the separate calls' % e)
+        if p2p is not None and (n_params is None or 4 * (int(n_params) + 2) <= p2p.max_bytes):
+            return p2p
+    return get_comm(group, device)
 
 
 def _env_int(name, default=0):
@@ -223,7 +268,7 @@ def p2p_check(group=None, device=None):
     p2p = _P2PS.get(key)
     # (a rank without the cached object still ENTERS the collective below: p2p_wanted() is the same on every rank, the
     #  cache lookup need not be -- a rank that returned here would leave the others waiting in the all-reduce)
-    bad = 1 if (p2p is not None and p2p.failed()) else 0
+    bad = 1 if (p2p is not None and not isinstance(p2p, Exception) and p2p.failed()) else 0
     if dist.get_backend(group) == 'nccl':
         fl = torch.tensor([bad], dtype=torch.int32, device=device)
         dist.all_reduce(fl, op=dist.ReduceOp.MAX, group=group)

@@ -388,6 +388,7 @@ class Engine:
         if self.mm_span:
             cfg.mm_span_rows, cfg.mm_span_offset, cfg.mm_span_ranks, cfg.mm_span_rank = self.mm_span
         self._coll = None
+        self._grad_comm = None
         self.cfg = cfg
         self.B, self.D, self.U, self.H = B, D, U, H
         self.n_pol_layers = len(pol_dims) - 1
@@ -486,6 +487,32 @@ class Engine:
         fn = _lib.COLLECTIVE_FN(allreduce)
         _lib.check(self.lib.pmbrl_plan_set_collective(self.plan, fn, None), 'pmbrl_plan_set_collective')
         self._coll = (group, fn)      # keeps the callback alive as long as the plan may call it
+
+    def attach_grad_comm(self, transport):
+        """The gradient transport of the fused iteration tail on a sharded run (pmbrl_plan_set_grad_comm): a
+        distributed.GradComm (RCCL) or distributed.P2PComm (one-hop peer-to-peer exchange); None detaches it.  With one
+        attached, backward(adam=...) is a collective every rank must call: the ranks agree on the horizon, the flat
+        gradient, the loss and the failure flag are summed over them inside the call, and clip + Adam run on the sum --
+        nothing returns to the host in between.  tail_calls() counts the calls that ran this way."""
+        if transport is self._grad_comm:
+            return
+        from .distributed import GradComm, P2PComm
+        comm = p2p = None
+        if isinstance(transport, P2PComm):
+            p2p = transport.p2p
+        elif isinstance(transport, GradComm):
+            comm = transport.comm
+        elif transport is not None:
+            raise TypeError('attach_grad_comm: a distributed.GradComm, a distributed.P2PComm or None')
+        self._grad_comm = None           # (a refused transport leaves the plan without one: pmbrl.h)
+        _lib.check(self.lib.pmbrl_plan_set_grad_comm(self.plan, comm, p2p), 'pmbrl_plan_set_grad_comm')
+        self._grad_comm = transport      # keeps the transport alive as long as the plan may use it
+
+    def tail_calls(self):
+        """backward(adam=...) calls of this plan that ran with the gradient exchange inside (attach_grad_comm)."""
+        info = (C.c_int32 * _lib.INFO_COUNT)()
+        _lib.check(self.lib.pmbrl_plan_info(self.plan, info), 'plan_info')
+        return int(info[_lib.INFO_TAIL_CALLS])
 
     def any_rank(self, flag):
         """True on every rank if `flag` is set on any rank of the group attached with attach_collective (collective:
