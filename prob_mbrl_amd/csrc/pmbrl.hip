@@ -210,10 +210,6 @@ static inline pm_reward_kernel_t pm_reward_kernel_for(int U, int k) {
                 : (U <= 8 ? pm_reward_all_kernel<8, PMBRL_MAX_TIP> : pm_reward_all_kernel<16, PMBRL_MAX_TIP>);
 }
 static inline int pm_norm_blocks(long long n) { return (int)std::max<long long>(1, std::min<long long>(PM_NORM_MAXB, (n + 255) / 256)); }
-static int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
-                                  int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
-                                  double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                                  float* loss_out_d = nullptr, int n_loss_part = 0);
 #define PM_RED_MAXB 128
 __device__ double g_red_part[2][PM_RED_MAXB];
 __device__ unsigned g_red_count;
@@ -384,6 +380,32 @@ __global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p
       pq[u] = p[j];
     }
   }
+}
+
+static void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
+                                long long n_per_step) {
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 2047) / 2048));
+  hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, s, a, w, n, out, nvalid, n_per_step);
+}
+
+// norm_done: the partial sums of squares and the go / no-go decision are already on the device (the fused iteration's
+// gradient reduction formed them: pm_dw_reduce, norm_on)
+static int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
+                                  int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
+                                  double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
+                                  float* loss_out_d = nullptr, int n_loss_part = 0) {
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
+  const int np = pm_norm_blocks(n);
+  if (!norm_done)
+    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
+                       (long long)n, (const int*)status_d, (int)expect, reinterpret_cast<long long*>(step_d), 1);
+  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
+                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, (float)lr, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, 1.f, 1.f,
+                     (float)max_norm, norm_out_d, reinterpret_cast<const long long*>(step_d), 1, log(beta1), log(beta2), lr,
+                     loss_out_d, n_loss_part);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 // ---------------------------------------------------------------------------
@@ -1368,6 +1390,23 @@ static int plan_dw(pmbrl_plan* p) {
   HIPCHK(hipMalloc(&p->dw_blocks_d, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock)));
   if (!blocks.empty())
     HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
+  // what the GEMM's argument record holds of the plan: a call copies it and adds its workspace pointers (dw_call_args)
+  DwArgs& W = p->dw_args;
+  memset(&W, 0, sizeof(W));
+  W.nl = p->pol.nl;
+  W.nsplit = p->dw_nsplit;
+  W.n_chunks = p->dw_n_chunks;
+  W.chunks_per_split = p->dw_chunks_per_split;
+  W.RT = p->RT;
+  W.Rw = 16 * p->RT;
+  W.n_params = (int)p->pol.n_params;
+  W.part_stride = (W.n_params + 3) / 4 * 4;
+  for (int i = 0; i <= p->pol.nl; ++i) { W.dim[i] = p->pol.dim[i]; W.nt[i] = p->pol.nt[i]; }
+  for (int l = 0; l < p->pol.nl; ++l) { W.w_off[l] = (int)p->pol.w_off[l]; W.b_off[l] = (int)p->pol.b_off[l]; }
+  W.blocks = p->dw_blocks_d;
+  for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first[w];
+  W.chunks_per_step = p->nwg * p->RT;
+  W.split_prec = p->dw_split;
   return 0;
 }
 
@@ -1386,7 +1425,7 @@ static int plan_dw_pipe(pmbrl_plan* p, int cus) {
   p->pipe_K = 1;
   const bool no_pipe_pre = p->dw_pre_mask != 0;      // (the pre-split GEMMs run once, behind the whole sweep)
   const int n_free = cus >= 64 && cus % 8 == 0 ? 8 * (cus / 8 - (p->nwg + 7) / 8) : 0;
-  const bool single = (p->mm_mode == 0 || p->mm_mode == 1) && p->mm_parts <= 1;   // (no second kernel next to flag barriers)
+  const bool single = sweep_form(p) == SweepForm::Whole && p->mm_parts <= 1;   // (no second kernel next to flag barriers)
   // Worth it where a range of the sweep is long against a launch boundary (tail of the last step, launch
   // gap, the next launch's prologue: 15 us at 16 rows per workgroup, 40 us at 64) -- measured: the double
   // cart-pole shape (64-row workgroups, 30 us per step) gains 7 % of an iteration, the cart-pole shapes
@@ -1578,7 +1617,8 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
 // replay of repeated calls (include/pmbrl.h: pmbrl_plan_set_replay)
 // ---------------------------------------------------------------------------
 static bool per_step_launches(const pmbrl_plan* p) {
-  return (p->mm_mode == 2 || (p->mm_mode == 3 && !p->mm_grid)) && p->cfg.H >= 4;
+  const SweepForm f = sweep_form(p);
+  return (f == SweepForm::StepExternal || f == SweepForm::StepInSweep) && p->cfg.H >= 4;
 }
 static bool replay_wanted(const pmbrl_plan* p) {
   if (p->replay == 0 || p->span || p->coll) return false;
@@ -1987,9 +2027,14 @@ static void launch_bwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t
 
 // groups spread over ranks (pmbrl_mmx.h): the in-place fp64 sum of the statistics buffer over the ranks
 static int mmx_exchange(pmbrl_plan* p, hipStream_t s, double* buf, size_t n) {
-  if (p->cfg.mm_span_ranks == 1 && !p->coll) return 0;   // one rank: the sum over the ranks is the identity
-  if (!p->coll) return fail(-3, "moment-matching groups spread over ranks: attach a collective first (pmbrl_plan_set_comm / pmbrl_plan_set_collective)");
+  if (!p->coll) return 0;   // one rank (check_collective): the sum over the ranks is the identity
   if (int rc = p->coll(p->coll_ctx, (void*)s, buf, (int64_t)n)) return fail(-4, "statistics all-reduce failed (" + std::to_string(rc) + ")");
+  return 0;
+}
+// ... which more than one rank cannot do without a collective: refused by both calls before they queue anything
+static int check_collective(const pmbrl_plan* p) {
+  if (p->span && p->cfg.mm_span_ranks != 1 && !p->coll)
+    return fail(-3, "moment-matching groups spread over ranks: attach a collective first (pmbrl_plan_set_comm / pmbrl_plan_set_collective)");
   return 0;
 }
 // dynamic LDS of pm_mmx_apply_kernel: room for the slots of every (rank, workgroup) if that fits (pmbrl_mmx.h)
@@ -1997,16 +2042,81 @@ static size_t mmx_apply_lds(int d, const MmxArgs& X, size_t other) {
   const size_t want = pm_mmx_apply_lds_doubles(d, X.nranks * X.nb) * sizeof(double);
   return want <= PM_MMX_LDS_MAX ? std::max(want, other) : other;
 }
-static MmxArgs mmx_args(const pmbrl_plan* p, char* ws, bool rewards) {
+// one exchange's launch shape: the states of step t (width D, G groups, the sums of a group over X.nb workgroups) or the
+// rewards of all steps at once (width 1, H x G items of one workgroup with fewer waves each)
+struct MmxShape {
   MmxArgs X;
+  int d, items, nw, nws;   // waves of the apply / of the statistics workgroups
+  size_t scr;
+};
+static MmxShape mmx_shape(const pmbrl_plan* p, char* ws, bool rewards, int t) {
+  MmxShape S;
+  MmxArgs& X = S.X;
   X.nranks = p->cfg.mm_span_ranks;
   X.rank = p->cfg.mm_span_rank;
   X.span_rows = p->cfg.mm_span_rows;
   X.span_off = p->cfg.mm_span_offset;
   X.buf = reinterpret_cast<double*>(ws + p->off_mmx_buf);
   X.fac = reinterpret_cast<double*>(ws + (rewards ? p->off_mmx_rfac : p->off_mmx_fac));
-  X.nb = rewards ? 1 : pm_mmx_blocks(p->M);   // (rewards: H x G workgroups already)
-  return X;
+  X.nb = rewards ? 1 : pm_mmx_blocks(p->M);
+  if (!rewards) X.fac += (size_t)t * p->G * pm_mm_fac_doubles(p->cfg.D);
+  S.d = rewards ? 1 : p->cfg.D;
+  S.items = rewards ? p->cfg.H * p->G : p->G;
+  S.nw = rewards ? std::min(4, pm_mmx_waves(p->M, 1)) : pm_mmx_waves(p->M, p->cfg.D);
+  S.nws = rewards ? S.nw : pm_mmx_waves((p->M + X.nb - 1) / X.nb, p->cfg.D);
+  S.scr = pm_mmx_lds_doubles(S.d, S.nw) * sizeof(double);
+  return S;
+}
+// forward: own statistics -> sum over the ranks -> factor + own rows.  (Here and in mmx_bwd the branches name the kernel
+// instances in the order the device code object has always laid them out: states first forward, rewards first adjoint)
+static int mmx_fwd(pmbrl_plan* p, char* ws, const RolloutArgs& A, bool rewards, int t, hipStream_t s) {
+  const MmxShape S = mmx_shape(p, ws, rewards, t);
+  const dim3 gs(S.items * S.X.nb, S.X.nranks), bs(64 * S.nws), ga(S.items), ba(64 * S.nw);
+  const size_t n = (size_t)S.X.nranks * S.X.nb * S.items * pm_mmx_slot_doubles(S.d), lds = mmx_apply_lds(S.d, S.X, S.scr);
+  if (!rewards) {
+    hipLaunchKernelGGL(pm_mmx_stats_kernel<0>, gs, bs, S.scr, s, A, S.X, t);
+    if (int rc = mmx_exchange(p, s, S.X.buf, n)) return rc;
+    hipLaunchKernelGGL(pm_mmx_apply_kernel<0>, ga, ba, lds, s, A, S.X, t);
+  } else {
+    hipLaunchKernelGGL(pm_mmx_stats_kernel<1>, gs, bs, S.scr, s, A, S.X, t);
+    if (int rc = mmx_exchange(p, s, S.X.buf, n)) return rc;
+    hipLaunchKernelGGL(pm_mmx_apply_kernel<1>, ga, ba, lds, s, A, S.X, t);
+  }
+  return 0;
+}
+// adjoint: own sums -> sum over the ranks -> own rows (grt: where the rewards' adjoint leaves dL/dr~)
+static int mmx_bwd(pmbrl_plan* p, char* ws, const RolloutArgs& A, bool rewards, int t, float* grt, hipStream_t s) {
+  const MmxShape S = mmx_shape(p, ws, rewards, t);
+  const dim3 gs(S.items * S.X.nb), bs(64 * S.nws), ga(S.items), ba(64 * S.nw);
+  const size_t n = (size_t)S.X.nb * S.items * pm_mmx_bwd_doubles(S.d);
+  if (rewards) {
+    hipLaunchKernelGGL(pm_mmx_bwd_sums_kernel<1>, gs, bs, S.scr, s, A, S.X, t);
+    if (int rc = mmx_exchange(p, s, S.X.buf, n)) return rc;
+    hipLaunchKernelGGL(pm_mmx_bwd_apply_kernel<1>, ga, ba, S.scr, s, A, S.X, t, grt);
+  } else {
+    hipLaunchKernelGGL(pm_mmx_bwd_sums_kernel<0>, gs, bs, S.scr, s, A, S.X, t);
+    if (int rc = mmx_exchange(p, s, S.X.buf, n)) return rc;
+    hipLaunchKernelGGL(pm_mmx_bwd_apply_kernel<0>, ga, ba, S.scr, s, A, S.X, t, grt);
+  }
+  return 0;
+}
+
+// groups split over workgroups (mm_parts > 1), before a whole-horizon sweep: the group-local barrier flags and the tags of
+// the exchange granules.  The latency-optimised family counts both from zero in every launch.  The register-resident
+// family (reg_now) touches no flags and tags its granules with a launch generation instead -- once zeroed, never again:
+// four 5 us fill kernels less per iteration.
+// (A RECORDED launch is replayed with the generation it was recorded with: two replays of a forward call with no
+//  adjoint call between them would meet their own tags of the replay before -- stale sums accepted.  A recording
+//  therefore carries the fill; what it leaves behind is its generation's tags, which no later launch takes for its own)
+static int xch_prepare(pmbrl_plan* p, const RolloutArgs& A, bool reg_now, hipStream_t s) {
+  if (p->mm_parts <= 1) return 0;
+  if (!reg_now) HIPCHK(hipMemsetAsync(A.gsync, 0, 1024 * sizeof(unsigned), s));
+  const bool rec = pm_stream_recording(s);
+  if (A.xch && (!reg_now || !p->xch_zeroed || rec)) {
+    HIPCHK(hipMemsetAsync(A.xch, 0, p->xch_bytes, s));
+    p->xch_zeroed = (reg_now && !rec) ? 1 : 0;
+  }
+  return 0;
 }
 
 // the sweep families' fragment-packed weights of this call's parameters (pm_pack_all); status_d: the forward
@@ -2022,167 +2132,183 @@ static void launch_pack_all(pmbrl_plan* p, char* ws, const pmbrl_inputs* in, hip
   hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
 }
 
-static int rollout_fwd_impl(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
-                            float* states_d, float* actions_d, float* rewards_d, int32_t* status_d);
+// the arguments of one pmbrl_rollout_fwd call: filled once by the entry point (which also derives the replay key from them)
+struct FwdCall {
+  hipStream_t stream;
+  void* workspace;
+  const pmbrl_inputs* in;
+  float *states, *actions, *rewards;
+  int32_t* status;
+};
+
+// every refusal that depends on the plan and the arguments alone: nothing has been queued when one is returned
+static int check_fwd(const pmbrl_plan* p, const FwdCall& C) {
+  if (!p || !C.workspace || !C.in || !C.states || !C.actions || !C.rewards || !C.status) return fail(-1, "null argument");
+  if (!C.in->pol_params_d || !C.in->dyn_params_d) return fail(-1, "null parameter pointer");
+  return check_collective(p);
+}
+
+// stage 1: the weights of this call's parameters in the form the sweep's family reads.  *ztab_done: the noise table of split
+// moment-matching groups rode along
+static int fwd_pack(pmbrl_plan* p, const FwdCall& C, const RolloutArgs& A, bool reg_fwd, bool* ztab_done) {
+  hipStream_t s = C.stream;
+  char* ws = static_cast<char*>(C.workspace);
+  ScopedTimer tm(p, PMBRL_TIMER_PACK, s);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(s, &cap);
+  // (the flag only ever grows: start over before the counter wraps -- and in every recorded call, whose replays all
+  //  carry the generation number of the recording)
+  if (p->wgen >= 0x7ffffff0 || cap == hipStreamCaptureStatusActive) {
+    HIPCHK(hipMemsetAsync(p->wflag_d, 0, sizeof(int), s));
+    if (p->wgen >= 0x7ffffff0) p->wgen = 0;
+  }
+  ++p->wgen;
+  // the register-resident family serves this call (pmbrl_reg.h): only ITS weights are packed now -- the
+  // latency-optimised family's are packed by the adjoint call if it turns out to need them (optional outputs)
+  if (!reg_fwd) launch_pack_all(p, ws, C.in, s, C.status);
+  p->old_pack_stale = reg_fwd ? 1 : 0;
+  p->abits_packed = reg_fwd ? 1 : 0;
+  // (the noise table of split moment-matching groups rides in the same launch: extra workgroups, PMBRL_ZTAB_MERGE=0 for
+  //  the launch of its own)
+  ZtabArgs Zt;
+  Zt.n_blocks = 0;
+  if (p->reg && reg_fwd && (p->mm_fan || p->reg_mm) && p->mm_mode == 1 && p->sw.ztab_merge) {
+    Zt = pm_ztab_args(p, A);
+    *ztab_done = true;
+  }
+  if (p->reg)
+    pm_reg_pack_launch(p, ws, C.in->pol_params_d, C.in->dyn_params_d, p->wflag_d, p->wgen, s, reg_fwd ? C.status : nullptr, &Zt);
+  return 0;
+}
+
+// stage 2, SweepForm::Barrier: one launch; the workgroups meet after every step and moment-match the sampled states (x_H included)
+static int fwd_sweep_barrier(pmbrl_plan* p, const FwdCall& C, RolloutArgs A) {
+  HIPCHK(hipMemsetAsync(A.gsync, 0, 1024 * sizeof(unsigned), C.stream));
+  A.t0 = 0; A.t1 = p->cfg.H;
+  launch_fwd_rt(p, A, C.stream);
+  return 0;
+}
+
+// SweepForm::StepInSweep: one launch per step; step t's launch first moment-matches the states sampled by step t-1
+static int fwd_sweep_steps(pmbrl_plan* p, const FwdCall& C, RolloutArgs A) {
+  for (int t = 0; t < p->cfg.H; ++t) {
+    A.t0 = t; A.t1 = t + 1;
+    launch_fwd_rt(p, A, C.stream);
+  }
+  A.flags &= ~PMBRL_FLAG_MM_REWARDS;
+  hipLaunchKernelGGL(pm_mm_fwd_kernel, dim3(p->G), dim3(PM_MM_NW * 64),
+                     pm_mm_kernel_doubles(p->cfg.D) * sizeof(double), C.stream, A, p->cfg.H - 1);   // x_H
+  return 0;
+}
+
+// the sweep's own arguments where the rewards are formed behind it
+static RolloutArgs fwd_sweep_args(const pmbrl_plan* p, const RolloutArgs& A) {
+  RolloutArgs As = A;
+  if (!p->fast) { As.ext_reward = 1; As.flags &= ~PMBRL_FLAG_MM_REWARDS; }   // general family: rewards after the sweep
+  if (p->learned && (p->cfg.flags & PMBRL_FLAG_MM_REWARDS)) As.rewards = As.rt;     // (learned reward head: r~ before its moment matching)
+  return As;
+}
+
+// SweepForm::Whole: the whole horizon in one launch of the register-resident or the latency-optimised / general family
+static int fwd_sweep_whole(pmbrl_plan* p, const FwdCall& C, const RolloutArgs& A, bool ztab_done) {
+  hipStream_t s = C.stream;
+  const RolloutArgs As = fwd_sweep_args(p, A);
+  if ((p->mm_fan || p->reg_mm) && !ztab_done) {
+    const ZtabArgs Z = pm_ztab_args(p, As);
+    hipLaunchKernelGGL(pm_mm_ztable_kernel, dim3(Z.n_blocks), dim3(256), 0, s, Z);
+  }
+  const bool reg_now = pm_reg_can_run(p, As, true);
+  if (int rc = xch_prepare(p, As, reg_now, s)) return rc;
+  if (reg_now) pm_reg_launch(p, static_cast<char*>(C.workspace), As, C.in->pol_params_d, C.in->dyn_params_d, s, true);
+  else launch_fwd_rt(p, As, s);
+  return 0;
+}
+
+// SweepForm::StepExternal: one launch per step, the moment matching of its states in kernels of their own behind it
+static int fwd_sweep_external(pmbrl_plan* p, const FwdCall& C, const RolloutArgs& A) {
+  hipStream_t s = C.stream;
+  char* ws = static_cast<char*>(C.workspace);
+  const size_t smem = pm_mm_kernel_doubles(p->cfg.D) * sizeof(double);
+  RolloutArgs Am = A, As = fwd_sweep_args(p, A);
+  Am.flags &= ~PMBRL_FLAG_MM_REWARDS;   // both families: rewards are handled after the sweep
+  for (int t = 0; t < p->cfg.H; ++t) {
+    As.t0 = t; As.t1 = t + 1;
+    launch_fwd_rt(p, As, s);
+    if (p->mm_wide) {
+      hipLaunchKernelGGL(pm_mmw_fwd_kernel, dim3(p->G), dim3(PM_MMW_NT), pm_mmw_lds_bytes(p->M, p->cfg.D, false), s, Am, t,
+                         reinterpret_cast<double*>(ws + p->off_mmfac));
+    } else if (!p->span) {
+      hipLaunchKernelGGL(pm_mm_fwd_kernel, dim3(p->G), dim3(PM_MM_NW * 64), smem, s, Am, t);
+    } else if (p->cfg.flags & PMBRL_FLAG_MM_STATES) {
+      if (int rc = mmx_fwd(p, ws, Am, false, t, s)) return rc;
+    }
+  }
+  return 0;
+}
+
+// stage 3: rewards (+ Jacobians) of all row-steps in one parallel pass, then their moment matching
+static int fwd_rewards(pmbrl_plan* p, const FwdCall& C, const RolloutArgs& A) {
+  hipStream_t s = C.stream;
+  const long long n = (long long)p->cfg.H * p->cfg.B;
+  if (p->learned)     // (the sweep sampled r~ and checked it: what is left of this launch's duties)
+    hipLaunchKernelGGL(pm_reward_learned_kernel, dim3(1), dim3(64), 0, s, A);
+  else
+    hipLaunchKernelGGL(pm_reward_kernel_for(p->cfg.U, p->rew_k), dim3((unsigned)((n + 255) / 256)), dim3(256),
+                       (size_t)256 * (p->cfg.D | 1) * sizeof(float), s, A);
+  if (!(p->cfg.flags & PMBRL_FLAG_MM_REWARDS)) return 0;
+  if (p->span) return mmx_fwd(p, static_cast<char*>(C.workspace), A, true, 0, s);   // one exchange for the whole horizon
+  hipLaunchKernelGGL(pm_mm_rewards_fwd_kernel, dim3(p->cfg.H * p->G), dim3(64), pm_mmr_lds_bytes(p->M, 2), s, A);
+  return 0;
+}
+
+static int rollout_fwd_impl(pmbrl_plan* p, const FwdCall& C) {
+  hipStream_t s = C.stream;
+  RolloutArgs A;
+  if (int rc = fill_args(p, C.workspace, C.in, A)) return rc;
+  A.states = C.states; A.actions = C.actions; A.rewards = C.rewards; A.status = C.status;
+  A.prof = p->prof_fwd;
+  const bool reg_fwd = pm_reg_can_run(p, A, true);
+  bool ztab_done = false;
+  if (int rc = fwd_pack(p, C, A, reg_fwd, &ztab_done)) return rc;
+  A.wflag = p->prec == PMBRL_PREC_SPLIT_F16 ? p->wflag_d : nullptr;
+  A.wgen = p->wgen;
+  {
+    ScopedTimer tm(p, PMBRL_TIMER_FWD, s);
+    int rc = 0;
+    switch (sweep_form(p)) {
+      case SweepForm::Barrier: rc = fwd_sweep_barrier(p, C, A); break;
+      case SweepForm::StepInSweep: rc = fwd_sweep_steps(p, C, A); break;
+      case SweepForm::Whole: rc = fwd_sweep_whole(p, C, A, ztab_done); break;
+      case SweepForm::StepExternal: rc = fwd_sweep_external(p, C, A); break;
+    }
+    if (rc) return rc;
+  }
+  {
+    ScopedTimer tm(p, PMBRL_TIMER_REWARD, s);
+    if (int rc = fwd_rewards(p, C, A)) return rc;
+    // the loss (pmbrl_plan_set_loss).  (Folding this sum into the reward launch -- per-block partials, last block finishes --
+    // was measured: the reward launch grew by what the separate reduction costs, 391 arrivals on one counter; not kept)
+    if (p->loss_w)
+      launch_weighted_sum(s, C.rewards, p->loss_w, (long long)p->cfg.H * p->cfg.B, p->loss_out, C.status, p->cfg.B);
+  }
+  HIPCHK(hipGetLastError());
+  return 0;
+}
 
 extern "C" int pmbrl_rollout_fwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
                                  float* states_d, float* actions_d, float* rewards_d,
                                  int32_t* status_d) {
-  if (!p || !workspace || !in || !states_d || !actions_d || !rewards_d || !status_d)
-    return fail(-1, "null argument");
-  if (!in->pol_params_d || !in->dyn_params_d) return fail(-1, "null parameter pointer");
+  const FwdCall C{(hipStream_t)stream, workspace, in, states_d, actions_d, rewards_d, status_d};
+  if (int rc = check_fwd(p, C)) return rc;
   HIPCHK(hipSetDevice(p->device));
   ReplayKey K;
-  K.val(stream); K.val(workspace); K.add(in, sizeof(*in));
-  K.val(states_d); K.val(actions_d); K.val(rewards_d); K.val(status_d); K.val(p->loss_w); K.val(p->loss_out);
-  return replay_call(p, 0, K, (hipStream_t)stream, [&](hipStream_t on) {
-    return rollout_fwd_impl(p, on, workspace, in, states_d, actions_d, rewards_d, status_d);
+  K.val(C.stream); K.val(C.workspace); K.add(C.in, sizeof(*C.in));
+  K.val(C.states); K.val(C.actions); K.val(C.rewards); K.val(C.status); K.val(p->loss_w); K.val(p->loss_out);
+  return replay_call(p, 0, K, C.stream, [&](hipStream_t on) {
+    FwdCall Con = C;
+    Con.stream = on;
+    return rollout_fwd_impl(p, Con);
   });
-}
-
-static int rollout_fwd_impl(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
-                            float* states_d, float* actions_d, float* rewards_d, int32_t* status_d) {
-  hipStream_t s = (hipStream_t)stream;
-  RolloutArgs A;
-  int rc = fill_args(p, workspace, in, A);
-  if (rc) return rc;
-  A.states = states_d; A.actions = actions_d; A.rewards = rewards_d; A.status = status_d;
-  A.prof = p->prof_fwd;
-  char* ws = static_cast<char*>(workspace);
-  // the register-resident family serves this call (pmbrl_reg.h): only ITS weights are packed now -- the
-  // latency-optimised family's are packed by the adjoint call if it turns out to need them (optional outputs)
-  const bool reg_fwd = pm_reg_can_run(p, A, true);
-  bool ztab_done = false;
-  {
-    ScopedTimer tm(p, PMBRL_TIMER_PACK, s);
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(s, &cap);
-    // (the flag only ever grows: start over before the counter wraps -- and in every recorded call, whose replays all
-    //  carry the generation number of the recording)
-    if (p->wgen >= 0x7ffffff0 || cap == hipStreamCaptureStatusActive) {
-      HIPCHK(hipMemsetAsync(p->wflag_d, 0, sizeof(int), s));
-      if (p->wgen >= 0x7ffffff0) p->wgen = 0;
-    }
-    ++p->wgen;
-    if (!reg_fwd) {
-      launch_pack_all(p, ws, in, s, status_d);
-      p->old_pack_stale = 0;
-    } else {
-      p->old_pack_stale = 1;
-    }
-    p->abits_packed = reg_fwd ? 1 : 0;
-    // (the noise table of split moment-matching groups rides in the same launch: extra workgroups, PMBRL_ZTAB_MERGE=0 for
-    //  the launch of its own)
-    ZtabArgs Zt;
-    Zt.n_blocks = 0;
-    if (p->reg && reg_fwd && (p->mm_fan || p->reg_mm) && p->mm_mode == 1 && p->sw.ztab_merge) {
-      Zt = pm_ztab_args(p, A);
-      ztab_done = true;
-    }
-    if (p->reg) pm_reg_pack_launch(p, ws, in->pol_params_d, in->dyn_params_d, p->wflag_d, p->wgen, s, reg_fwd ? status_d : nullptr, &Zt);
-  }
-  A.wflag = p->prec == PMBRL_PREC_SPLIT_F16 ? p->wflag_d : nullptr;
-  A.wgen = p->wgen;
-  const bool mm_r = (p->cfg.flags & PMBRL_FLAG_MM_REWARDS) != 0;
-  {
-  ScopedTimer tm(p, PMBRL_TIMER_FWD, s);
-  if (p->mm_mode == 3 && p->mm_grid) {
-    // one launch; the workgroups meet after every step and moment-match the sampled states (x_H included)
-    HIPCHK(hipMemsetAsync(A.gsync, 0, 1024 * sizeof(unsigned), s));
-    A.t0 = 0; A.t1 = p->cfg.H;
-    launch_fwd_rt(p, A, s);
-  } else if (p->mm_mode == 3) {
-    // one launch per step; step t's launch first moment-matches the states sampled by step t-1
-    for (int t = 0; t < p->cfg.H; ++t) {
-      A.t0 = t; A.t1 = t + 1;
-      launch_fwd_rt(p, A, s);
-    }
-    RolloutArgs Am = A;
-    Am.flags &= ~PMBRL_FLAG_MM_REWARDS;
-    hipLaunchKernelGGL(pm_mm_fwd_kernel, dim3(p->G), dim3(PM_MM_NW * 64),
-                       pm_mm_kernel_doubles(p->cfg.D) * sizeof(double), s, Am, p->cfg.H - 1);   // x_H
-  } else if (p->mm_mode != 2) {
-    RolloutArgs As = A;
-    if (!p->fast) { As.ext_reward = 1; As.flags &= ~PMBRL_FLAG_MM_REWARDS; }   // general family: rewards after the sweep
-    if (p->learned && mm_r) As.rewards = As.rt;     // (learned reward head: r~ before its moment matching)
-    if ((p->mm_fan || p->reg_mm) && !ztab_done) {
-      const ZtabArgs Z = pm_ztab_args(p, As);
-      hipLaunchKernelGGL(pm_mm_ztable_kernel, dim3(Z.n_blocks), dim3(256), 0, s, Z);
-    }
-    // (the granules' tags: zeroed per launch for the latency-optimised family, whose tags count the steps from 1; the
-    //  register-resident family's carry a launch generation instead -- once zeroed, never again: two 5 us fill kernels less;
-    //  nor does that family touch the group-local barrier flags: two more)
-    const bool reg_now = pm_reg_can_run(p, As, true);
-    if (p->mm_parts > 1 && !reg_now) HIPCHK(hipMemsetAsync(As.gsync, 0, 1024 * sizeof(unsigned), s));   // group-local barriers
-    // (a RECORDED launch is replayed with the generation it was recorded with: two replays of a forward call with no
-    //  adjoint call between them would meet their own tags of the replay before -- stale sums accepted.  A recording
-    //  therefore carries the fill; what it leaves behind is its generation's tags, which no later launch takes for its own)
-    const bool xch_rec = pm_stream_recording(s);
-    if (p->mm_parts > 1 && As.xch && (!reg_now || !p->xch_zeroed || xch_rec)) {
-      HIPCHK(hipMemsetAsync(As.xch, 0, p->xch_bytes, s));
-      p->xch_zeroed = (reg_now && !xch_rec) ? 1 : 0;
-    }
-    if (reg_now) pm_reg_launch(p, ws, As, in->pol_params_d, in->dyn_params_d, s, true);
-    else launch_fwd_rt(p, As, s);
-  } else {
-    const size_t smem = pm_mm_kernel_doubles(p->cfg.D) * sizeof(double);
-    RolloutArgs Am = A, As = A;
-    Am.flags &= ~PMBRL_FLAG_MM_REWARDS;   // both families: rewards are handled after the sweep
-    if (!p->fast) { As.ext_reward = 1; As.flags &= ~PMBRL_FLAG_MM_REWARDS; }
-    if (p->learned && mm_r) As.rewards = As.rt;
-    for (int t = 0; t < p->cfg.H; ++t) {
-      As.t0 = t; As.t1 = t + 1;
-      launch_fwd_rt(p, As, s);
-      if (p->mm_wide) {
-        hipLaunchKernelGGL(pm_mmw_fwd_kernel, dim3(p->G), dim3(PM_MMW_NT), pm_mmw_lds_bytes(p->M, p->cfg.D, false), s, Am, t,
-                           reinterpret_cast<double*>(ws + p->off_mmfac));
-      } else if (!p->span) {
-        hipLaunchKernelGGL(pm_mm_fwd_kernel, dim3(p->G), dim3(PM_MM_NW * 64), smem, s, Am, t);
-      } else if (p->cfg.flags & PMBRL_FLAG_MM_STATES) {
-        // groups spread over ranks: own statistics -> sum over the ranks -> factor + own rows
-        MmxArgs X = mmx_args(p, ws, false);
-        X.fac += (size_t)t * p->G * pm_mm_fac_doubles(p->cfg.D);
-        const int nw = pm_mmx_waves(p->M, p->cfg.D), nws = pm_mmx_waves((p->M + X.nb - 1) / X.nb, p->cfg.D);
-        const size_t scr = pm_mmx_lds_doubles(p->cfg.D, nw) * sizeof(double);
-        hipLaunchKernelGGL(pm_mmx_stats_kernel<0>, dim3(p->G * X.nb, X.nranks), dim3(64 * nws), scr, s, Am, X, t);
-        if (int rc = mmx_exchange(p, s, X.buf, (size_t)X.nranks * X.nb * p->G * pm_mmx_slot_doubles(p->cfg.D))) return rc;
-        hipLaunchKernelGGL(pm_mmx_apply_kernel<0>, dim3(p->G), dim3(64 * nw), mmx_apply_lds(p->cfg.D, X, scr), s, Am, X, t);
-      }
-    }
-  }
-  }
-  {
-    // rewards (+ Jacobians) of all row-steps in one parallel pass, then their moment matching
-    ScopedTimer tm(p, PMBRL_TIMER_REWARD, s);
-    A.t0 = 0; A.t1 = p->cfg.H;
-    const long long n = (long long)p->cfg.H * p->cfg.B;
-    if (p->learned)     // (the sweep sampled r~ and checked it: what is left of this launch's duties)
-      hipLaunchKernelGGL(pm_reward_learned_kernel, dim3(1), dim3(64), 0, s, A);
-    else
-      hipLaunchKernelGGL(pm_reward_kernel_for(p->cfg.U, p->rew_k), dim3((unsigned)((n + 255) / 256)), dim3(256),
-                         (size_t)256 * (p->cfg.D | 1) * sizeof(float), s, A);
-    if (mm_r && p->span) {
-      // the rewards of all steps: one exchange for the whole horizon
-      const MmxArgs X = mmx_args(p, ws, true);
-      const int nw = std::min(4, pm_mmx_waves(p->M, 1));   // (H x G workgroups: fewer waves each)
-      const size_t scr = pm_mmx_lds_doubles(1, nw) * sizeof(double);
-      const int n_items = p->cfg.H * p->G;
-      hipLaunchKernelGGL(pm_mmx_stats_kernel<1>, dim3(n_items, X.nranks), dim3(64 * nw), scr, s, A, X, 0);
-      if (int rc = mmx_exchange(p, s, X.buf, (size_t)X.nranks * n_items * pm_mmx_slot_doubles(1))) return rc;
-      hipLaunchKernelGGL(pm_mmx_apply_kernel<1>, dim3(n_items), dim3(64 * nw), mmx_apply_lds(1, X, scr), s, A, X, 0);
-    } else if (mm_r)
-      hipLaunchKernelGGL(pm_mm_rewards_fwd_kernel, dim3(p->cfg.H * p->G), dim3(64), pm_mmr_lds_bytes(p->M, 2), s, A);
-    if (p->loss_w) {
-      // (folding this sum into the reward launch -- per-block partials, last block finishes -- was measured: the
-      //  reward launch grew by what the separate reduction costs, 391 arrivals on one counter; not kept)
-      const long long nn = (long long)p->cfg.H * p->cfg.B;
-      const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (nn + 2047) / 2048));
-      hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, s, (const float*)rewards_d, p->loss_w, nn,
-                         p->loss_out, (const int*)status_d, (long long)p->cfg.B);
-    }
-  }
-  HIPCHK(hipGetLastError());
-  return 0;
 }
 
 extern "C" int pmbrl_plan_set_loss(pmbrl_plan* p, const float* loss_weights_d, float* loss_out_d) {
@@ -2198,239 +2324,263 @@ static int tail_allreduce(pmbrl_plan* p, hipStream_t s, float* buf_d, int64_t n)
   return pmbrl_allreduce_sum(p->grad_comm, s, buf_d, n);
 }
 
-static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
-                       const float* states_d, const float* actions_d,
-                       const float* rewards_d, const float* grad_rewards_d,
-                       const float* grad_states_d, const float* grad_actions_d,
-                       float* grad_pol_flat_d, float* grad_x0_d,
-                       float* action_grad_norms_d, int32_t* status_d, const pmbrl_adam* opt) {
-  if (!p || !workspace || !in || !states_d || !actions_d || !rewards_d || !grad_rewards_d ||
-      !grad_pol_flat_d)
-    return fail(-1, "null argument");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipSetDevice(p->device));
-  RolloutArgs A;
-  int rc = fill_args(p, workspace, in, A);
-  if (rc) return rc;
-  // rows sharded over ranks, optimiser attached (pmbrl_plan_set_grad_comm): the ranks agree on the horizon first -- the
-  // sweep, the dW GEMM and the loss below read the agreed status_d[0]
-  const bool tail = opt && (p->grad_comm || p->grad_p2p);
-  float* const xb = p->tail_buf_d;
-  if (tail) {
-    if (p->span && p->cfg.mm_span_ranks > 1) return fail(-3, "pmbrl_rollout_bwd_adam with a gradient transport: moment-matching groups spread over ranks are not offered");
-    float* hvec = xb + ((size_t)p->pol.n_params + 2 + 3) / 4 * 4;
-    hipLaunchKernelGGL(pm_tail_hvec_kernel, dim3(1), dim3(64), 0, s, hvec, p->tail_world, p->tail_rank, (const int*)status_d, p->cfg.H);
-    if (int rc2 = tail_allreduce(p, s, hvec, p->tail_world)) return rc2;
-    hipLaunchKernelGGL(pm_tail_hmin_kernel, dim3(1), dim3(64), 0, s, (const float*)hvec, p->tail_world, (int*)status_d, p->cfg.H);
-  }
-  char* ws = static_cast<char*>(workspace);
-  A.states = const_cast<float*>(states_d);
-  A.actions = const_cast<float*>(actions_d);
-  A.rewards = const_cast<float*>(rewards_d);
-  A.grad_rewards = grad_rewards_d;
-  A.grad_states = grad_states_d;
-  A.grad_actions = grad_actions_d;
-  A.grad_x0 = grad_x0_d;
-  A.agn = action_grad_norms_d;
+// the arguments of one pmbrl_rollout_bwd(_adam) call: filled once by the entry point (opt: nullptr without the optimiser)
+struct BwdCall {
+  hipStream_t stream;
+  void* workspace;
+  const pmbrl_inputs* in;
+  const float *states, *actions, *rewards;
+  const float *grad_rewards, *grad_states, *grad_actions;
+  float *grad_pol_flat, *grad_x0, *action_grad_norms;
+  int32_t* status;
+  const pmbrl_adam* opt;
+};
+// rows sharded over ranks, optimiser attached (pmbrl_plan_set_grad_comm): the exchange runs inside the call
+static bool bwd_tail(const pmbrl_plan* p, const BwdCall& C) { return C.opt && (p->grad_comm || p->grad_p2p); }
+static int expect_steps(const pmbrl_plan* p, const pmbrl_adam* opt) {
+  return opt ? (opt->expect_steps > 0 ? opt->expect_steps : p->cfg.H) : 0;
+}
+
+// every refusal that depends on the plan and the arguments alone (reg_bwd: the register-resident family serves the sweep):
+// nothing has been queued when one is returned
+static int check_bwd(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
+  if (bwd_tail(p, C) && p->span && p->cfg.mm_span_ranks > 1)
+    return fail(-3, "pmbrl_rollout_bwd_adam with a gradient transport: moment-matching groups spread over ranks are not offered");
+  if (p->reg && p->old_pack_stale && !reg_bwd && (!C.in->pol_params_d || !C.in->dyn_params_d)) return fail(-1, "null parameter pointer");
+  if (int rc = check_collective(p)) return rc;
+  const SweepForm form = sweep_form(p);
+  if (C.grad_states && (form == SweepForm::Barrier || form == SweepForm::StepInSweep))
+    return fail(-3, "grad_states with moment-matching groups spanning workgroups: not offered");
+  if (C.grad_states && form == SweepForm::StepExternal) return fail(-3, "grad_states with external moment matching: not offered");
+  return 0;
+}
+
+// the sweep arguments of this call
+static int bwd_args(const pmbrl_plan* p, const BwdCall& C, RolloutArgs& A) {
+  if (int rc = fill_args(p, C.workspace, C.in, A)) return rc;
+  A.states = const_cast<float*>(C.states);
+  A.actions = const_cast<float*>(C.actions);
+  A.rewards = const_cast<float*>(C.rewards);
+  A.grad_rewards = C.grad_rewards;
+  A.grad_states = C.grad_states;
+  A.grad_actions = C.grad_actions;
+  A.grad_x0 = C.grad_x0;
+  A.agn = C.action_grad_norms;
   A.prof = p->prof_bwd;
-  // status_d[0]: valid steps of the forward sweep (the adjoint covers only those); status_d[1]: set by
+  // status[0]: valid steps of the forward sweep (the adjoint covers only those); status[1]: set by
   // the sweep if its device-wide barrier timed out
-  A.nvalid = status_d;
-  A.status = status_d ? status_d + 1 : nullptr;
   // (cleared by the FORWARD call's reward launch -- pm_reward_all_kernel -- since round 5: as a memset of its own here it
   //  was a 5 us fill kernel in every iteration, 1 % of the cart-pole shape's)
-  // this call goes to the latency-optimised family after a forward call that packed the register-resident family's
-  // weights only: pack the others now (same parameters: the caller hands the same inputs to both calls)
-  const bool reg_bwd = pm_reg_can_run(p, A, false);
-  if (p->reg && p->old_pack_stale && !reg_bwd) {
-    if (!in->pol_params_d || !in->dyn_params_d) return fail(-1, "null parameter pointer");
-    launch_pack_all(p, ws, in, s, nullptr);
-  }
-  // ... and its activity bits are in that family's form.  (Neither note is cleared here: a recorded adjoint call --
-  // pmbrl_plan_set_replay -- must contain both conversions whenever the forward call before it was of that kind.)
-  if (p->reg && p->abits_packed && !reg_bwd) pm_reg_unpack_abits(p, ws, s);
-  float* grt = reinterpret_cast<float*>(ws + p->off_grt);
-  const bool mm_r = (p->cfg.flags & PMBRL_FLAG_MM_REWARDS) != 0;
-  if (!p->fast) { A.ext_reward = 1; }
-  if (mm_r && p->span) {
-    const MmxArgs X = mmx_args(p, ws, true);
-    const int nw = std::min(4, pm_mmx_waves(p->M, 1));
-    const size_t scr = pm_mmx_lds_doubles(1, nw) * sizeof(double);
-    const int n_items = p->cfg.H * p->G;
-    hipLaunchKernelGGL(pm_mmx_bwd_sums_kernel<1>, dim3(n_items), dim3(64 * nw), scr, s, A, X, 0);
-    if (int rc = mmx_exchange(p, s, X.buf, (size_t)n_items * pm_mmx_bwd_doubles(1))) return rc;
-    hipLaunchKernelGGL(pm_mmx_bwd_apply_kernel<1>, dim3(n_items), dim3(64 * nw), scr, s, A, X, 0, grt);
-    A.grad_rewards = grt;
-  } else if (mm_r) {
-    // adjoint of the reward moment matching for all (t, group) up front
-    hipLaunchKernelGGL(pm_mm_rewards_bwd_kernel, dim3(p->cfg.H * p->G), dim3(64), pm_mmr_lds_bytes(p->M, 3), s, A, grt);
+  A.nvalid = C.status;
+  A.status = C.status ? C.status + 1 : nullptr;
+  if (!p->fast) A.ext_reward = 1;
+  return 0;
+}
+
+// stage 1 (sharded tail): the ranks agree on the horizon first -- the sweep, the dW GEMM and the loss read the agreed status[0]
+static int bwd_agree_horizon(pmbrl_plan* p, const BwdCall& C) {
+  hipStream_t s = C.stream;
+  float* hvec = p->tail_buf_d + ((size_t)p->pol.n_params + 2 + 3) / 4 * 4;
+  hipLaunchKernelGGL(pm_tail_hvec_kernel, dim3(1), dim3(64), 0, s, hvec, p->tail_world, p->tail_rank, (const int*)C.status, p->cfg.H);
+  if (int rc = tail_allreduce(p, s, hvec, p->tail_world)) return rc;
+  hipLaunchKernelGGL(pm_tail_hmin_kernel, dim3(1), dim3(64), 0, s, (const float*)hvec, p->tail_world, (int*)C.status, p->cfg.H);
+  return 0;
+}
+
+// stage 2: this call goes to the latency-optimised family after a forward call that served the register-resident one -- pack
+// the other family's weights now (same parameters: the caller hands the same inputs to both calls) and unpack the activity
+// bits from that family's form.  (Neither note is cleared here: a recorded adjoint call -- pmbrl_plan_set_replay -- must
+// contain both conversions whenever the forward call before it was of that kind.)
+static void bwd_convert_family(pmbrl_plan* p, const BwdCall& C) {
+  char* ws = static_cast<char*>(C.workspace);
+  if (p->old_pack_stale) launch_pack_all(p, ws, C.in, C.stream, nullptr);
+  if (p->abits_packed) pm_reg_unpack_abits(p, ws, C.stream);
+}
+
+// stage 3: adjoint of the reward moment matching for all (t, group) up front; the sweep then reads dL/dr~ from the workspace
+static int bwd_reward_adjoint(pmbrl_plan* p, const BwdCall& C, RolloutArgs& A, float* grt) {
+  if (p->cfg.flags & PMBRL_FLAG_MM_REWARDS) {
+    if (p->span) {
+      if (int rc = mmx_bwd(p, static_cast<char*>(C.workspace), A, true, 0, grt, C.stream)) return rc;
+    } else {
+      hipLaunchKernelGGL(pm_mm_rewards_bwd_kernel, dim3(p->cfg.H * p->G), dim3(64), pm_mmr_lds_bytes(p->M, 3), C.stream, A, grt);
+    }
     A.grad_rewards = grt;
   }
   if (!p->fast) A.flags &= ~PMBRL_FLAG_MM_REWARDS;   // (general sweeps: the reward side is done, see ext_reward)
-  // dW GEMM over the stashes + deterministic reduction
-  DwArgs W;
-  memset(&W, 0, sizeof(W));
-  W.nl = p->pol.nl;
-  W.nsplit = p->dw_nsplit;
-  W.n_chunks = p->dw_n_chunks;
-  W.chunks_per_split = p->dw_chunks_per_split;
-  W.RT = p->RT;
-  W.Rw = 16 * p->RT;
-  W.n_params = (int)p->pol.n_params;
-  W.part_stride = (W.n_params + 3) / 4 * 4;
-  for (int i = 0; i <= p->pol.nl; ++i) {
-    W.dim[i] = p->pol.dim[i];
-    W.nt[i] = p->pol.nt[i];
+  return 0;
+}
+
+// the dW GEMM's arguments: the plan's part (plan_dw) + this call's stashes, partial rows and status word
+static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A) {
+  DwArgs W = p->dw_args;
+  for (int l = 0; l < p->pol.nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
+  W.part = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_part);
+  W.nvalid = C.status;
+  return W;
+}
+// ... of launch k of the pipelined form: the chunks of step range k, dealt to the partial rows of a grid next to the sweep
+// (the last launch has the chip to itself)
+static DwArgs dw_range_args(const pmbrl_plan* p, const DwArgs& W, int k) {
+  DwArgs Wk = W;
+  const int cps = W.chunks_per_step;
+  Wk.pipe = 1;
+  Wk.pipe_k = k;
+  Wk.nsplit = k + 1 == p->pipe_K ? p->pipe_rows : p->pipe_grid;
+  Wk.rows_before = p->pipe_grid;
+  Wk.c_begin = p->pipe_lo[k] * cps;
+  Wk.c_end = (k ? p->pipe_lo[k - 1] : p->cfg.H) * cps;
+  Wk.chunks_per_split = (Wk.c_end - Wk.c_begin + Wk.nsplit - 1) / Wk.nsplit;
+  if (p->dw_split) Wk.chunks_per_split = (Wk.chunks_per_split + 1) & ~1;
+  return Wk;
+}
+// The dW GEMM over the chunks W describes, one partial row per workgroup: the only place that chooses its kernels.
+// (The pipelined ranges never meet a plan without block-kernel layers or with pre-split stashes: such a plan has
+//  dw_pre_mask -- the first layer's input is at most 40 wide, so only pm_dw_narrow_pre_kernel takes it from the block
+//  kernel -- and plan_dw_pipe leaves the pipeline off for it.)
+static void launch_dw_gemms(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
+  const dim3 rows(W.nsplit), units((W.nsplit + 7) / 8 * 8 * p->n_dw_units);
+  if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
+  else if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, rows, dim3(PM_DW_NT), 0, s, W);
+  else hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W);
+  if (p->dw_pre_mask)
+    for (int l = 0; l < p->pol.nl; ++l) {
+      if (!p->dw_narrow[l]) continue;
+      const int g_wide = p->dw_narrow[l] == 1 ? 1 : 0, nt_n = g_wide ? p->pol.nt[l] : p->pol.nt[l + 1];
+      if (nt_n <= 1) hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<1>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
+      else hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<2>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
+    }
+  if (p->n_dw_units && p->dw_pre_mask)
+    hipLaunchKernelGGL(pm_dw_wide_pre_kernel, units, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
+  else if (p->n_dw_units)
+    hipLaunchKernelGGL(pm_dw_wide_kernel, units, dim3(PM_DW_NT), PM_DWW_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
+  if (p->dw_layer13 >= 0)
+    hipLaunchKernelGGL(pm_dw_layer_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
+}
+
+// stage 4, the groups spanning workgroups (mm_mode 3): dL/dx travels between the steps through two carry buffers.
+// SweepForm::Barrier: one launch, the workgroups meet at a device-wide barrier per step
+static int bwd_sweep_barrier(pmbrl_plan* p, const BwdCall& C, RolloutArgs A) {
+  hipStream_t s = C.stream;
+  HIPCHK(hipMemsetAsync(A.gx_carry, 0, (size_t)p->cfg.B * p->cfg.D * sizeof(float), s));
+  A.gx_from_carry = 1;
+  A.gsync += 1024;
+  HIPCHK(hipMemsetAsync(A.gsync, 0, 1024 * sizeof(unsigned), s));
+  A.gx_carry_out = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_gxc2);
+  A.t0 = 0; A.t1 = p->cfg.H;
+  launch_bwd_rt(p, A, s);
+  return 0;
+}
+// SweepForm::StepInSweep: one launch per step
+static int bwd_sweep_steps(pmbrl_plan* p, const BwdCall& C, RolloutArgs A) {
+  hipStream_t s = C.stream;
+  float* cbuf[2] = {A.gx_carry, reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_gxc2)};
+  HIPCHK(hipMemsetAsync(cbuf[0], 0, (size_t)p->cfg.B * p->cfg.D * sizeof(float), s));
+  A.gx_from_carry = 1;
+  for (int t = p->cfg.H - 1, k = 0; t >= 0; --t, k ^= 1) {
+    A.gx_carry = cbuf[k];           // dL/dx_{t+1}, all rows (read by every workgroup of the group)
+    A.gx_carry_out = cbuf[k ^ 1];   // dL/dx_t of this workgroup's rows
+    A.t0 = t; A.t1 = t + 1;
+    launch_bwd_rt(p, A, s);
   }
-  for (int l = 0; l < p->pol.nl; ++l) {
-    W.w_off[l] = (int)p->pol.w_off[l];
-    W.b_off[l] = (int)p->pol.b_off[l];
-    W.actT[l] = A.actT[l];
-    W.gT[l] = A.gT[l];
+  return 0;
+}
+// SweepForm::Whole as K launches over the descending step ranges [lo[k], lo[k-1]) (lo[-1] = H; one range: [0, H)).  More
+// than one (the plan's pipe_lo): the dW GEMM of range k goes out on the second stream behind the sweep of that range, next
+// to the sweep of range k+1; the last range's GEMM is bwd_dw's
+static int bwd_sweep_whole(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, const DwArgs& W, bool reg_bwd, int K, const int* lo) {
+  hipStream_t s = C.stream;
+  char* ws = static_cast<char*>(C.workspace);
+  if (p->mm_parts > 1) {
+    // groups split over workgroups: their own flags, and two buffers for the rows of dL/dx they exchange
+    A.gsync += 1024;
+    A.gx_carry_out = reinterpret_cast<float*>(ws + p->off_gxc2);
+    if (int rc = xch_prepare(p, A, reg_bwd, s)) return rc;
   }
-  W.blocks = p->dw_blocks_d;
-  for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first[w];
-  W.part = reinterpret_cast<float*>(ws + p->off_part);
-  W.nvalid = status_d;
-  W.chunks_per_step = p->nwg * p->RT;
-  W.split_prec = p->dw_split;
-  const bool pipe = p->pipe_K > 1 && !p->prof_bwd;
-  auto launch_dw = [&](int k, hipStream_t st) {
-    DwArgs Wk = W;
-    const int cps = W.chunks_per_step;
-    Wk.pipe = 1;
-    Wk.pipe_k = k;
-    const bool last = k + 1 == p->pipe_K;
-    Wk.nsplit = last ? p->pipe_rows : p->pipe_grid;
-    Wk.rows_before = p->pipe_grid;
-    Wk.c_begin = p->pipe_lo[k] * cps;
-    Wk.c_end = (k ? p->pipe_lo[k - 1] : p->cfg.H) * cps;
-    Wk.chunks_per_split = (Wk.c_end - Wk.c_begin + Wk.nsplit - 1) / Wk.nsplit;
-    if (p->dw_split) Wk.chunks_per_split = (Wk.chunks_per_split + 1) & ~1;
-    if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, dim3(Wk.nsplit), dim3(PM_DW_NT), 0, st, Wk);
-    else hipLaunchKernelGGL(pm_dw_kernel, dim3(Wk.nsplit), dim3(PM_DW_NT), 0, st, Wk);
-    if (p->n_dw_units && p->dw_pre_mask)
-      hipLaunchKernelGGL(pm_dw_wide_pre_kernel, dim3((Wk.nsplit + 7) / 8 * 8 * p->n_dw_units), dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, st, Wk,
-                         p->dw_units_d, p->n_dw_units);
-    else if (p->n_dw_units)
-      hipLaunchKernelGGL(pm_dw_wide_kernel, dim3((Wk.nsplit + 7) / 8 * 8 * p->n_dw_units), dim3(PM_DW_NT), PM_DWW_LDS_BYTES, st, Wk,
-                         p->dw_units_d, p->n_dw_units);
-    if (p->dw_layer13 >= 0)
-      hipLaunchKernelGGL(pm_dw_layer_kernel, dim3(Wk.nsplit), dim3(PM_DW_NT), PM_DWL_LDS_BYTES, st, Wk, p->dw_layer13);
-  };
-  if (p->mm_mode == 3) {
-    ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
-    if (grad_states_d) return fail(-3, "grad_states with moment-matching groups spanning workgroups: not offered");
-    float* cbuf[2] = {A.gx_carry, reinterpret_cast<float*>(ws + p->off_gxc2)};
-    HIPCHK(hipMemsetAsync(cbuf[0], 0, (size_t)p->cfg.B * p->cfg.D * sizeof(float), s));
-    A.gx_from_carry = 1;
-    int k = 0;
-    if (p->mm_grid) {
-      A.gsync += 1024;
-      HIPCHK(hipMemsetAsync(A.gsync, 0, 1024 * sizeof(unsigned), s));
-      A.gx_carry_out = cbuf[1];
-      A.t0 = 0; A.t1 = p->cfg.H;
-      launch_bwd_rt(p, A, s);
-    } else
-    for (int t = p->cfg.H - 1; t >= 0; --t, k ^= 1) {
-      A.gx_carry = cbuf[k];           // dL/dx_{t+1}, all rows (read by every workgroup of the group)
-      A.gx_carry_out = cbuf[k ^ 1];   // dL/dx_t of this workgroup's rows
-      A.t0 = t; A.t1 = t + 1;
-      launch_bwd_rt(p, A, s);
-    }
-    A.gx_carry = cbuf[0];
-    A.gx_carry_out = nullptr;
-  } else if (p->mm_mode != 2 && pipe) {
-    // range k of the sweep on s; the dW GEMM of range k on the second stream behind it (the last one below, on s)
-    ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
-    for (int k = 0; k < p->pipe_K; ++k) {
-      A.t0 = p->pipe_lo[k];
-      A.t1 = k ? p->pipe_lo[k - 1] : p->cfg.H;
-      A.gx_from_carry = k > 0;
-      if (reg_bwd) pm_reg_launch(p, ws, A, in->pol_params_d, in->dyn_params_d, s, false);
-      else launch_bwd_rt(p, A, s);
-      if (k + 1 < p->pipe_K) {
-        HIPCHK(hipEventRecord(p->pipe_ev[k], s));
-        HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[k], 0));
-        launch_dw(k, p->pipe_stream);
-      }
-    }
-    A.t0 = 0; A.t1 = p->cfg.H;
-  } else if (p->mm_mode != 2) {
-    ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
-    A.gx_from_carry = 0;
-    if (p->mm_parts > 1) {
-      // groups split over workgroups: their own flags, and two buffers for the rows of dL/dx they exchange
-      A.gsync += 1024;
-      if (!reg_bwd) HIPCHK(hipMemsetAsync(A.gsync, 0, 1024 * sizeof(unsigned), s));
-      const bool xch_rec = pm_stream_recording(s);      // (see the forward call)
-      if (A.xch && (!reg_bwd || !p->xch_zeroed || xch_rec)) {
-        HIPCHK(hipMemsetAsync(A.xch, 0, p->xch_bytes, s));
-        p->xch_zeroed = (reg_bwd && !xch_rec) ? 1 : 0;
-      }
-      A.gx_carry_out = reinterpret_cast<float*>(ws + p->off_gxc2);
-    }
-    if (reg_bwd) pm_reg_launch(p, ws, A, in->pol_params_d, in->dyn_params_d, s, false);
+  for (int k = 0; k < K; ++k) {
+    A.t0 = lo[k];
+    A.t1 = k ? lo[k - 1] : p->cfg.H;
+    A.gx_from_carry = k > 0;
+    if (reg_bwd) pm_reg_launch(p, ws, A, C.in->pol_params_d, C.in->dyn_params_d, s, false);
     else launch_bwd_rt(p, A, s);
-    A.gx_carry_out = nullptr;
-  } else {
-    ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
-    if (grad_states_d) return fail(-3, "grad_states with external moment matching: not offered");
-    const size_t smem = pm_mm_kernel_doubles(p->cfg.D) * sizeof(double);
-    HIPCHK(hipMemsetAsync(A.gx_carry, 0, (size_t)p->cfg.B * p->cfg.D * sizeof(float), s));
-    RolloutArgs Am = A;
-    Am.flags &= ~PMBRL_FLAG_MM_REWARDS;   // rewards already handled above
-    A.gx_from_carry = 1;
-    for (int t = p->cfg.H - 1; t >= 0; --t) {
-      if (p->mm_wide) {
-        hipLaunchKernelGGL(pm_mmw_bwd_kernel, dim3(p->G), dim3(PM_MMW_NT), pm_mmw_lds_bytes(p->M, p->cfg.D, true), s, Am, t,
-                           reinterpret_cast<const double*>(ws + p->off_mmfac));
-      } else if (!p->span) {
-        hipLaunchKernelGGL(pm_mm_bwd_kernel, dim3(p->G), dim3(PM_MM_NW * 64), smem, s, Am, t, grt);
-      } else if (p->cfg.flags & PMBRL_FLAG_MM_STATES) {
-        MmxArgs X = mmx_args(p, ws, false);
-        X.fac += (size_t)t * p->G * pm_mm_fac_doubles(p->cfg.D);
-        const int nw = pm_mmx_waves(p->M, p->cfg.D), nws = pm_mmx_waves((p->M + X.nb - 1) / X.nb, p->cfg.D);
-        const size_t scr = pm_mmx_lds_doubles(p->cfg.D, nw) * sizeof(double);
-        hipLaunchKernelGGL(pm_mmx_bwd_sums_kernel<0>, dim3(p->G * X.nb), dim3(64 * nws), scr, s, Am, X, t);
-        if (int rc = mmx_exchange(p, s, X.buf, (size_t)X.nb * p->G * pm_mmx_bwd_doubles(p->cfg.D))) return rc;
-        hipLaunchKernelGGL(pm_mmx_bwd_apply_kernel<0>, dim3(p->G), dim3(64 * nw), scr, s, Am, X, t, (float*)nullptr);
-      }
-      A.t0 = t; A.t1 = t + 1;
-      launch_bwd_rt(p, A, s);
+    if (k + 1 < K) {
+      HIPCHK(hipEventRecord(p->pipe_ev[k], s));
+      HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[k], 0));
+      launch_dw_gemms(p, dw_range_args(p, W, k), p->pipe_stream);
     }
   }
-  const bool piped = pipe && p->mm_mode != 2 && p->mm_mode != 3;
+  return 0;
+}
+// SweepForm::StepExternal: one launch per step behind the adjoint of that step's moment matching
+static int bwd_sweep_external(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, float* grt) {
+  hipStream_t s = C.stream;
+  char* ws = static_cast<char*>(C.workspace);
+  const size_t smem = pm_mm_kernel_doubles(p->cfg.D) * sizeof(double);
+  HIPCHK(hipMemsetAsync(A.gx_carry, 0, (size_t)p->cfg.B * p->cfg.D * sizeof(float), s));
+  RolloutArgs Am = A;
+  Am.flags &= ~PMBRL_FLAG_MM_REWARDS;   // rewards already handled (bwd_reward_adjoint)
+  A.gx_from_carry = 1;
+  for (int t = p->cfg.H - 1; t >= 0; --t) {
+    if (p->mm_wide) {
+      hipLaunchKernelGGL(pm_mmw_bwd_kernel, dim3(p->G), dim3(PM_MMW_NT), pm_mmw_lds_bytes(p->M, p->cfg.D, true), s, Am, t,
+                         reinterpret_cast<const double*>(ws + p->off_mmfac));
+    } else if (!p->span) {
+      hipLaunchKernelGGL(pm_mm_bwd_kernel, dim3(p->G), dim3(PM_MM_NW * 64), smem, s, Am, t, grt);
+    } else if (p->cfg.flags & PMBRL_FLAG_MM_STATES) {
+      if (int rc = mmx_bwd(p, ws, Am, false, t, nullptr, s)) return rc;
+    }
+    A.t0 = t; A.t1 = t + 1;
+    launch_bwd_rt(p, A, s);
+  }
+  return 0;
+}
+
+// stage 5: the dW GEMM over the stashes (piped: what is left of it, the last range)
+static int bwd_dw(pmbrl_plan* p, const BwdCall& C, const DwArgs& W, bool piped) {
+  ScopedTimer tm(p, PMBRL_TIMER_DW, C.stream);
+  if (!piped) {
+    launch_dw_gemms(p, W, C.stream);
+    return 0;
+  }
+  // the rows of the last range are added to what the second stream left: join it first
+  HIPCHK(hipEventRecord(p->pipe_ev[p->pipe_K - 1], p->pipe_stream));
+  HIPCHK(hipStreamWaitEvent(C.stream, p->pipe_ev[p->pipe_K - 1], 0));
+  launch_dw_gemms(p, dw_range_args(p, W, p->pipe_K - 1), C.stream);
+  return 0;
+}
+
+static int rollout_bwd(pmbrl_plan* p, const BwdCall& C) {
+  hipStream_t s = C.stream;
+  RolloutArgs A;
+  if (int rc = bwd_args(p, C, A)) return rc;
+  const bool reg_bwd = pm_reg_can_run(p, A, false);
+  if (int rc = check_bwd(p, C, reg_bwd)) return rc;
+  const pmbrl_adam* opt = C.opt;
+  const bool tail = bwd_tail(p, C);
+  float* const xb = p->tail_buf_d;
+  if (tail)
+    if (int rc = bwd_agree_horizon(p, C)) return rc;
+  if (p->reg && !reg_bwd) bwd_convert_family(p, C);
+  float* grt = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_grt);
+  if (int rc = bwd_reward_adjoint(p, C, A, grt)) return rc;
+  const DwArgs W = dw_call_args(p, C, A);
+  const SweepForm form = sweep_form(p);
+  const bool piped = form == SweepForm::Whole && p->pipe_K > 1 && !p->prof_bwd;
   {
-    ScopedTimer tm(p, PMBRL_TIMER_DW, s);
-    if (piped) {
-      // the rows of the last range are added to what the second stream left: join it first
-      HIPCHK(hipEventRecord(p->pipe_ev[p->pipe_K - 1], p->pipe_stream));
-      HIPCHK(hipStreamWaitEvent(s, p->pipe_ev[p->pipe_K - 1], 0));
-      launch_dw(p->pipe_K - 1, s);
+    ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
+    static const int whole[1] = {0};
+    int rc = 0;
+    switch (form) {
+      case SweepForm::Barrier: rc = bwd_sweep_barrier(p, C, A); break;
+      case SweepForm::StepInSweep: rc = bwd_sweep_steps(p, C, A); break;
+      case SweepForm::Whole: rc = bwd_sweep_whole(p, C, A, W, reg_bwd, piped ? p->pipe_K : 1, piped ? p->pipe_lo : whole); break;
+      case SweepForm::StepExternal: rc = bwd_sweep_external(p, C, A, grt); break;
     }
-    else {
-      if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
-      else if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, dim3(p->dw_nsplit), dim3(PM_DW_NT), 0, s, W);
-      else hipLaunchKernelGGL(pm_dw_kernel, dim3(p->dw_nsplit), dim3(PM_DW_NT), 0, s, W);
-      if (p->dw_pre_mask)
-        for (int l = 0; l < p->pol.nl; ++l) {
-          if (!p->dw_narrow[l]) continue;
-          const int g_wide = p->dw_narrow[l] == 1 ? 1 : 0, nt_n = g_wide ? p->pol.nt[l] : p->pol.nt[l + 1];
-          if (nt_n <= 1) hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<1>, dim3(p->dw_nsplit), dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
-          else hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<2>, dim3(p->dw_nsplit), dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
-        }
-      if (p->n_dw_units && p->dw_pre_mask)
-        hipLaunchKernelGGL(pm_dw_wide_pre_kernel, dim3((p->dw_nsplit + 7) / 8 * 8 * p->n_dw_units), dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W,
-                           p->dw_units_d, p->n_dw_units);
-      else if (p->n_dw_units)
-        hipLaunchKernelGGL(pm_dw_wide_kernel, dim3((p->dw_nsplit + 7) / 8 * 8 * p->n_dw_units), dim3(PM_DW_NT), PM_DWW_LDS_BYTES, s, W,
-                           p->dw_units_d, p->n_dw_units);
-      if (p->dw_layer13 >= 0)
-        hipLaunchKernelGGL(pm_dw_layer_kernel, dim3(p->dw_nsplit), dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
-    }
+    if (rc) return rc;
   }
+  if (int rc = bwd_dw(p, C, W, piped)) return rc;
   const int n = (int)p->pol.n_params;
+  const int expect = expect_steps(p, opt);
   // the fused iteration (one process, optimiser attached): the reduction forms the gradient norm's partial sums and the
   // go / no-go decision on the way -- pm_gradnorm_kernel's launch is not needed.  (Rows sharded over ranks: the norm is
   // that of the SUMMED gradient -- pm_tail_finish_kernel, behind the exchange.)
@@ -2439,7 +2589,8 @@ static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl
   // ... and, asked for (pmbrl_adam::loss_out_d), the loss' partial sums: the optimiser launch adds them -- no loss launch
   // behind the forward call (PMBRL_FUSE_LOSS=0: pm_weighted_sum_kernel, here)
   const bool loss_fused = part_ok && opt->loss_out_d && p->sw.fuse_loss;
-  float* const red_out = tail ? xb : grad_pol_flat_d;
+  const int n_loss_part = loss_fused ? (n + 255) / 256 : 0;
+  float* const red_out = tail ? xb : C.grad_pol_flat;
   {
     ScopedTimer tm(p, PMBRL_TIMER_DW_REDUCE, s);
     if (piped)   // every partial row was written (pm_dw_range)
@@ -2447,66 +2598,45 @@ static int rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, const pmbrl
                          W.part_stride, red_out, (const int*)nullptr, 0, 1);
     else
       hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, W.part, p->dw_nsplit, n,
-                         W.part_stride, red_out, (const int*)status_d, W.chunks_per_step, W.chunks_per_split,
-                         norm_fused ? 1 : 0, (const int*)status_d, opt ? (opt->expect_steps > 0 ? opt->expect_steps : p->cfg.H) : 0,
+                         W.part_stride, red_out, (const int*)C.status, W.chunks_per_step, W.chunks_per_split,
+                         norm_fused ? 1 : 0, (const int*)C.status, expect,
                          opt ? reinterpret_cast<long long*>(opt->step_d) : (long long*)nullptr,
-                         loss_fused ? rewards_d : (const float*)nullptr, grad_rewards_d, (long long)p->cfg.H * p->cfg.B,
+                         loss_fused ? C.rewards : (const float*)nullptr, C.grad_rewards, (long long)p->cfg.H * p->cfg.B,
                          (long long)p->cfg.B);
   }
   // the loss asked for with the optimiser step, where the reduction does not form it on the way: a launch of its own
-  if (opt && opt->loss_out_d && !loss_fused) {
-    const long long nn = (long long)p->cfg.H * p->cfg.B;
-    const int nbl = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (nn + 2047) / 2048));
-    hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nbl), dim3(256), 0, s, rewards_d, grad_rewards_d, nn,
-                       tail ? xb + n : opt->loss_out_d, (const int*)status_d, (long long)p->cfg.B);
-  }
+  if (opt && opt->loss_out_d && !loss_fused)
+    launch_weighted_sum(s, C.rewards, C.grad_rewards, (long long)p->cfg.H * p->cfg.B, tail ? xb + n : opt->loss_out_d, C.status,
+                        p->cfg.B);
   HIPCHK(hipGetLastError());
-  const int expect = opt ? (opt->expect_steps > 0 ? opt->expect_steps : p->cfg.H) : 0;
+  if (!opt) return 0;
   if (tail) {
     // [gradient | loss partial | failure flag] summed over the ranks in place, then the summed gradient's norm and the
     // decision every rank takes alike; the optimiser launch is the one-process one
-    hipLaunchKernelGGL(pm_tail_pack_kernel, dim3(1), dim3(64), 0, s, xb, n, loss_fused ? (n + 255) / 256 : 0,
-                       opt->loss_out_d && !loss_fused ? 1 : 0, (const int*)status_d, (const int*)p->tail_err_d);
-    if (int rc2 = tail_allreduce(p, s, xb, (int64_t)n + 2)) return rc2;
-    hipLaunchKernelGGL(pm_tail_finish_kernel, dim3(pm_norm_blocks(n)), dim3(64), 0, s, (const float*)xb, grad_pol_flat_d,
-                       (long long)n, (int*)status_d, expect, reinterpret_cast<long long*>(opt->step_d), (const int*)p->tail_err_d);
+    hipLaunchKernelGGL(pm_tail_pack_kernel, dim3(1), dim3(64), 0, s, xb, n, n_loss_part,
+                       opt->loss_out_d && !loss_fused ? 1 : 0, (const int*)C.status, (const int*)p->tail_err_d);
+    if (int rc = tail_allreduce(p, s, xb, (int64_t)n + 2)) return rc;
+    hipLaunchKernelGGL(pm_tail_finish_kernel, dim3(pm_norm_blocks(n)), dim3(64), 0, s, (const float*)xb, C.grad_pol_flat,
+                       (long long)n, (int*)C.status, expect, reinterpret_cast<long long*>(opt->step_d), (const int*)p->tail_err_d);
     HIPCHK(hipGetLastError());
-    return clip_adam_guarded_impl(stream, opt->params_d, grad_pol_flat_d, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d,
-                                  opt->lr, opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, status_d, expect,
-                                  true, opt->loss_out_d, opt->loss_out_d ? 1 : 0);
   }
   // the optimiser step behind it, decided on the device (a form with the reduction, the norm and the update in ONE launch
   // around a device-wide barrier was measured at the C2 shape: 25.6 us against 13.7 + 4.7 + 7.1 us for the three launches
-  // -- the barrier's L2 round trips cost what two launches do; not kept)
-  if (opt)
-    return clip_adam_guarded_impl(stream, opt->params_d, grad_pol_flat_d, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d,
-                                  opt->lr, opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, status_d,
-                                  expect, norm_fused,
-                                  loss_fused ? opt->loss_out_d : nullptr, loss_fused ? (n + 255) / 256 : 0);
-  return 0;
+  // -- the barrier's L2 round trips cost what two launches do; not kept).  Behind the exchange the norm is done and the
+  // loss is one summed partial; otherwise both are as the reduction left them
+  return clip_adam_guarded_impl(s, opt->params_d, C.grad_pol_flat, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d, opt->lr,
+                                opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, C.status, expect,
+                                tail || norm_fused, tail || loss_fused ? opt->loss_out_d : nullptr,
+                                tail ? (opt->loss_out_d ? 1 : 0) : n_loss_part);
 }
 
-static int rollout_bwd_replay(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
-                              const float* states_d, const float* actions_d,
-                              const float* rewards_d, const float* grad_rewards_d,
-                              const float* grad_states_d, const float* grad_actions_d,
-                              float* grad_pol_flat_d, float* grad_x0_d,
-                              float* action_grad_norms_d, int32_t* status_d, const pmbrl_adam* opt) {
-  if (!p || !in) return fail(-1, "null argument");
-  HIPCHK(hipSetDevice(p->device));
-  const bool tail = opt && (p->grad_comm || p->grad_p2p);
-  if (tail) ++p->tail_calls;
-  if (tail && p->grad_p2p) {
-    // the peer-to-peer exchange cannot be recorded (its generation is a kernel argument): eagerly, whatever
-    // pmbrl_plan_set_replay says
-    if (p->rp[1].exec || p->rp[1].seen) replay_drop(p, 1);
-    return rollout_bwd(p, stream, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d, grad_states_d,
-                       grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d, status_d, opt);
-  }
+// what makes two adjoint calls "the same" (pmbrl_plan_set_replay)
+static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C) {
+  const pmbrl_adam* opt = C.opt;
   ReplayKey K;
-  K.val(stream); K.val(workspace); K.add(in, sizeof(*in));
-  K.val(states_d); K.val(actions_d); K.val(rewards_d); K.val(grad_rewards_d); K.val(grad_states_d); K.val(grad_actions_d);
-  K.val(grad_pol_flat_d); K.val(grad_x0_d); K.val(action_grad_norms_d); K.val(status_d);
+  K.val(C.stream); K.val(C.workspace); K.add(C.in, sizeof(*C.in));
+  K.val(C.states); K.val(C.actions); K.val(C.rewards); K.val(C.grad_rewards); K.val(C.grad_states); K.val(C.grad_actions);
+  K.val(C.grad_pol_flat); K.val(C.grad_x0); K.val(C.action_grad_norms); K.val(C.status);
   const int has_opt = opt ? 1 : 0;
   K.val(has_opt);
   if (opt) {      // field by field: the struct's padding bytes are not arguments (a caller's stack copy need not repeat them)
@@ -2514,15 +2644,31 @@ static int rollout_bwd_replay(pmbrl_plan* p, void* stream, void* workspace, cons
     K.val(opt->lr); K.val(opt->beta1); K.val(opt->beta2); K.val(opt->eps); K.val(opt->max_norm);
     K.val(opt->norm_out_d); K.val(opt->expect_steps);
   }
-  if (tail) {     // the transport, its buffer and the loss output: every pointer of a call with the exchange inside
+  if (bwd_tail(p, C)) {     // the transport, its buffer and the loss output: every pointer of a call with the exchange inside
     K.val(p->grad_comm); K.val(p->tail_buf_d); K.val(opt->loss_out_d);
   }
   // what the forward call left behind decides which conversions the adjoint call queues (weights repacked for the other
   // family, activity words unpacked): a recording is only good for the state it was recorded in
   K.val(p->old_pack_stale); K.val(p->abits_packed);
-  return replay_call(p, 1, K, (hipStream_t)stream, [&](hipStream_t on) {
-    return rollout_bwd(p, on, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d, grad_states_d,
-                       grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d, status_d, opt);
+  return K;
+}
+
+static int rollout_bwd_replay(pmbrl_plan* p, const BwdCall& C) {
+  if (!p || !C.workspace || !C.in || !C.states || !C.actions || !C.rewards || !C.grad_rewards || !C.grad_pol_flat)
+    return fail(-1, "null argument");
+  HIPCHK(hipSetDevice(p->device));
+  const bool tail = bwd_tail(p, C);
+  if (tail) ++p->tail_calls;
+  if (tail && p->grad_p2p) {
+    // the peer-to-peer exchange cannot be recorded (its generation is a kernel argument): eagerly, whatever
+    // pmbrl_plan_set_replay says
+    if (p->rp[1].exec || p->rp[1].seen) replay_drop(p, 1);
+    return rollout_bwd(p, C);
+  }
+  return replay_call(p, 1, bwd_key(p, C), C.stream, [&](hipStream_t on) {
+    BwdCall Con = C;
+    Con.stream = on;
+    return rollout_bwd(p, Con);
   });
 }
 
@@ -2532,8 +2678,9 @@ extern "C" int pmbrl_rollout_bwd(pmbrl_plan* p, void* stream, void* workspace, c
                                  const float* grad_states_d, const float* grad_actions_d,
                                  float* grad_pol_flat_d, float* grad_x0_d,
                                  float* action_grad_norms_d, int32_t* status_d) {
-  return rollout_bwd_replay(p, stream, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d, grad_states_d,
-                            grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d, status_d, nullptr);
+  return rollout_bwd_replay(p, BwdCall{(hipStream_t)stream, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d,
+                                       grad_states_d, grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d,
+                                       status_d, nullptr});
 }
 
 extern "C" int pmbrl_rollout_bwd_adam(pmbrl_plan* p, void* stream, void* workspace, const pmbrl_inputs* in,
@@ -2544,8 +2691,9 @@ extern "C" int pmbrl_rollout_bwd_adam(pmbrl_plan* p, void* stream, void* workspa
                                       float* action_grad_norms_d, int32_t* status_d, const pmbrl_adam* opt) {
   if (!opt || !status_d || !opt->params_d || !opt->exp_avg_d || !opt->exp_avg_sq_d || !opt->step_d)
     return fail(-1, "null argument");
-  return rollout_bwd_replay(p, stream, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d, grad_states_d,
-                            grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d, status_d, opt);
+  return rollout_bwd_replay(p, BwdCall{(hipStream_t)stream, workspace, in, states_d, actions_d, rewards_d, grad_rewards_d,
+                                       grad_states_d, grad_actions_d, grad_pol_flat_d, grad_x0_d, action_grad_norms_d,
+                                       status_d, opt});
 }
 
 // ---------------------------------------------------------------------------
@@ -3120,9 +3268,7 @@ extern "C" int pmbrl_plan_set_grad_comm(pmbrl_plan* plan, pmbrl_comm* comm, pmbr
 extern "C" int pmbrl_weighted_sum(void* stream, const float* a_d, const float* w_d, int64_t n,
                                   float* out_d) {
   if (!a_d || !w_d || !out_d || n < 0) return fail(-1, "bad argument");
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 2047) / 2048));
-  hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a_d, w_d,
-                     (long long)n, out_d, (const int*)nullptr, 0ll);
+  launch_weighted_sum((hipStream_t)stream, a_d, w_d, n, out_d, nullptr, 0);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3130,10 +3276,7 @@ extern "C" int pmbrl_weighted_sum(void* stream, const float* a_d, const float* w
 extern "C" int pmbrl_weighted_sum_steps(void* stream, const float* a_d, const float* w_d, int64_t n_per_step,
                                         int32_t n_steps, const int32_t* status_d, float* out_d) {
   if (!a_d || !w_d || !out_d || n_per_step < 0 || n_steps < 0) return fail(-1, "bad argument");
-  const long long n = (long long)n_per_step * n_steps;
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 2047) / 2048));
-  hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, a_d, w_d, n, out_d,
-                     (const int*)status_d, (long long)n_per_step);
+  launch_weighted_sum((hipStream_t)stream, a_d, w_d, (long long)n_per_step * n_steps, out_d, status_d, n_per_step);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -3170,26 +3313,6 @@ extern "C" int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* gra
   return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, lr, beta1, beta2, eps, max_norm,
                                 norm_out_d, status_d, expect, false);
 }
-// norm_done: the partial sums of squares and the go / no-go decision are already on the device (the fused iteration's
-// gradient reduction formed them: pm_dw_reduce, norm_on)
-static int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
-                                  int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
-                                  double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                                  float* loss_out_d, int n_loss_part) {
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
-  const int np = pm_norm_blocks(n);
-  if (!norm_done)
-    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
-                       (long long)n, (const int*)status_d, (int)expect, reinterpret_cast<long long*>(step_d), 1);
-  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
-                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, (float)lr, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, 1.f, 1.f,
-                     (float)max_norm, norm_out_d, reinterpret_cast<const long long*>(step_d), 1, log(beta1), log(beta2), lr,
-                     loss_out_d, n_loss_part);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
 // ---------------------------------------------------------------------------
 // test hook: y = x W^T + b through gemm_tiles / gemm_narrow
 // ---------------------------------------------------------------------------

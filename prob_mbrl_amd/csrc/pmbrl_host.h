@@ -1,7 +1,8 @@
 // Host-side declarations shared by the translation units of libpmbrl_hip.so.  The library is built from
 // several .hip files so that the kernel families compile in parallel: pmbrl.hip (C ABI, plan, small kernels,
-// general kernel family), pmbrl_fast_f32.hip (latency-optimised sweeps, exact fp32 MFMA) and
-// pmbrl_fast_split.hip (the same on split bf16 / fp16 operands; compiled once per precision).
+// general kernel family), pmbrl_general_split.hip (the general family on split operands), pmbrl_fast_f32.hip
+// (latency-optimised sweeps, exact fp32 MFMA), pmbrl_fast_split.hip (the same on split bf16 / fp16 operands; compiled
+// once per precision), pmbrl_reg.hip (register-resident family) and pmbrl_p2p.hip (peer-to-peer transport): seven objects.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,7 @@ struct pmbrl_plan {
   unsigned dw_pre_mask;   // layers whose dW GEMM reads pre-split stashes (pm_dw_wide_pre_kernel; the wide sweeps write them)
   int dw_layer13;       // >= 0: this layer (at most 13 x 13 tiles) runs whole in one workgroup per row-step range (pm_dw_layer_kernel)
   int n_dw_blocks, dw_nsplit, dw_chunks_per_split, dw_n_chunks;
+  DwArgs dw_args;       // what the dW GEMM's argument record holds of the plan (plan_dw); a call adds its workspace pointers and nvalid
   // dW GEMM behind the adjoint sweep (pmbrl_rollout_bwd): the sweep as pipe_K launches over descending step
   // ranges [pipe_lo[k], pipe_lo[k-1]); the GEMM of range k runs on pipe_stream, on the CUs the sweep leaves
   // idle, while the sweep is in range k+1.  pipe_K <= 1: off.
@@ -121,6 +123,18 @@ struct pmbrl_plan {
   hipEvent_t ev[PMBRL_TIMER_COUNT][2];
   bool ev_set[PMBRL_TIMER_COUNT];
 };
+
+// How a plan's sweeps go out: what the two rollout calls, the replay default and the dW pipeline branch on
+enum class SweepForm {
+  Barrier,        // one launch; groups spanning workgroups meet at a device-wide barrier per step (mm_mode 3, mm_grid)
+  StepInSweep,    // one launch per step, each moment-matching the states of the step before in its prologue (mm_mode 3)
+  Whole,          // the whole horizon in one launch, moment matching (if any) inside it (mm_mode 0 / 1)
+  StepExternal    // one launch per step with the moment-matching kernels between them (mm_mode 2)
+};
+static inline SweepForm sweep_form(const pmbrl_plan* p) {
+  if (p->mm_mode == 3) return p->mm_grid ? SweepForm::Barrier : SweepForm::StepInSweep;
+  return p->mm_mode == 2 ? SweepForm::StepExternal : SweepForm::Whole;
+}
 
 struct ScopedTimer {
   pmbrl_plan* p; int slot; hipStream_t s;
