@@ -48,6 +48,18 @@ def max_over_ranks(x, device, group=None):
     return float(t.item())
 
 
+def ints_over_ranks(values, op, group=None, device=None):
+    """The list of integers `values` reduced element by element over the ranks of `group`, `op` 'min' or 'max', as a
+    list on every rank: an int64 tensor on `device` for an nccl group, on the host otherwise (gloo).  A host sync.
+    `values` itself at world size 1 or without an initialised process group."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
+        return values
+    t = torch.tensor(values, dtype=torch.int64, device=device if dist.get_backend(group) == 'nccl' else 'cpu')
+    dist.all_reduce(t, op=dict(min=dist.ReduceOp.MIN, max=dist.ReduceOp.MAX)[op], group=group)
+    return t.tolist()
+
+
 class GradComm:
     """RCCL communicator behind the C ABI (pmbrl_comm_*): the gradient all-reduce is issued on the
     compute stream right behind the adjoint sweep's dW reduction -- one library call, no second
@@ -269,13 +281,7 @@ def p2p_check(group=None, device=None):
     # (a rank without the cached object still ENTERS the collective below: p2p_wanted() is the same on every rank, the
     #  cache lookup need not be -- a rank that returned here would leave the others waiting in the all-reduce)
     bad = 1 if (p2p is not None and not isinstance(p2p, Exception) and p2p.failed()) else 0
-    if dist.get_backend(group) == 'nccl':
-        fl = torch.tensor([bad], dtype=torch.int32, device=device)
-        dist.all_reduce(fl, op=dist.ReduceOp.MAX, group=group)
-    else:
-        fl = torch.tensor([bad], dtype=torch.int32)
-        dist.all_reduce(fl, op=dist.ReduceOp.MAX, group=group)
-    if int(fl[0]):
+    if ints_over_ranks([bad], 'max', group, device)[0]:
         raise RuntimeError('peer-to-peer exchange: a rank waited for a peer that did not arrive in time (the exchange '
                            'was not completed; PMBRL_P2P_TIMEOUT_SPINS sets the wait)')
 

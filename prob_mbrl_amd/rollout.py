@@ -314,13 +314,10 @@ class Bundle:
         return out
 
     def forward(self, x0, out=None):
-        if self.pol_unit or self.dyn_unit:
-            return self.engine.forward(x0, self.scale_unit_rows(self.pol_flat, self.pol_unit),
-                                       self.scale_unit_rows(self.dyn_flat, self.dyn_unit), self.mx, self.iSx, self.my,
-                                       self.Sy, self.scale, self.bias, self.pol_bits, self.dyn_bits,
-                                       self.z_pol, self.z_dyn, self.z_mm, self.z_rr, out=out, z_pi=self.z_pi,
-                                       u_cat=self.u_cat)
-        return self.engine.forward(x0, self.pol_flat, self.dyn_flat, self.mx, self.iSx, self.my,
+        # (per-unit rates: the kernels see scaled copies of the two flat parameter vectors)
+        pol_flat = self.scale_unit_rows(self.pol_flat, self.pol_unit)
+        dyn_flat = self.scale_unit_rows(self.dyn_flat, self.dyn_unit)
+        return self.engine.forward(x0, pol_flat, dyn_flat, self.mx, self.iSx, self.my,
                                    self.Sy, self.scale, self.bias, self.pol_bits, self.dyn_bits,
                                    self.z_pol, self.z_dyn, self.z_mm, self.z_rr, out=out, z_pi=self.z_pi,
                                    u_cat=self.u_cat)
@@ -402,21 +399,12 @@ def rollout(states, dynamics, policy, steps, resample_model=False, resample_poli
     def _agree(n_local, failed_local):
         if agree_group is None:
             return n_local, failed_local
-        import torch.distributed as dist
-        if dist.get_world_size(agree_group) == 1:
-            return n_local, failed_local
-        v = torch.tensor([n_local, -int(failed_local)], dtype=torch.int32, device=bundle.device)
-        if dist.get_backend(agree_group) == 'nccl':
-            dist.all_reduce(v, op=dist.ReduceOp.MIN, group=agree_group)
-        else:
-            host = v.cpu()
-            dist.all_reduce(host, op=dist.ReduceOp.MIN, group=agree_group)
-            v = host
-        n_all, failed_all = int(v[0]), int(v[1]) < 0
+        from .distributed import ints_over_ranks
+        n_all, failed_all = ints_over_ranks([n_local, -int(failed_local)], 'min', agree_group, bundle.device)
         if n_all < n_local:
             # what the adjoint sweep, the dW GEMM and the loss of THIS rank read: stop where the slowest rank stopped
-            bundle.engine.status[0:1].copy_(torch.tensor([n_all], dtype=torch.int32))
-        return n_all, failed_all
+            bundle.engine.status[0:1].fill_(n_all)
+        return n_all, failed_all < 0
 
     while True:
         bundle = Bundle(dynamics, policy, B, int(steps), resample_state_noise, resample_action_noise,

@@ -80,3 +80,41 @@ def test_shard_bounds_cover_whole_groups():
             seen.append((lo, hi))
         assert seen[0][0] == 0 and seen[-1][1] == B
         assert all(a[1] == b[0] for a, b in zip(seen[:-1], seen[1:]))
+
+
+def _ints_worker(rank, world, port, out):
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    try:
+        from prob_mbrl_amd import distributed as D
+        mine = [rank + 3, -rank]
+        out.put((rank, D.ints_over_ranks(mine, 'min', dist.group.WORLD, torch.device('cpu')),
+                 D.ints_over_ranks(mine, 'max', dist.group.WORLD, torch.device('cpu'))))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_ints_over_ranks_min_and_max_on_two_gloo_ranks():
+    """[rank + 3, -rank] over ranks 0 and 1: the element-wise minimum is [3, -1], the maximum [4, 0], as lists of
+    Python integers on both ranks; without a process group the helper hands its input back."""
+    from prob_mbrl_amd import distributed as D
+    vals = [5, -7]
+    assert not dist.is_initialized()
+    assert D.ints_over_ranks(vals, 'min', None, torch.device('cpu')) is vals
+    assert D.ints_over_ranks(vals, 'max', None, torch.device('cpu')) is vals
+    world = 2
+    ctx = mp.get_context('spawn')
+    out = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_ints_worker, args=(r, world, port, out)) for r in range(world)]
+    for p in procs:
+        p.start()
+    got = sorted(out.get(timeout=120) for _ in range(world))
+    for p in procs:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert [g[0] for g in got] == [0, 1]
+    for _, lo, hi in got:
+        assert lo == [3, -1] and hi == [4, 0]
+        assert all(type(x) is int for x in lo + hi)

@@ -1,5 +1,5 @@
-import time, sys, numpy as np, torch
-sys.path.insert(0, '/root/repo')
+import os, time, sys, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from functools import partial
 import prob_mbrl_amd as pm
 dev = 'cuda:0'
