@@ -4,4 +4,6 @@ from prob_mbrl_amd.models import *  # noqa: F401,F403
 from prob_mbrl_amd.models import (BDropout, BSequential, CDropout, DiagGaussianDensity, DynamicsModel,  # noqa: F401
                                   GaussianMixtureDensity, Policy, Regressor, StochasticModule, mlp)
 
-from . import core, densities, modules  # noqa: E402,F401
+from prob_mbrl_amd.activations import Swish  # noqa: E402,F401
+
+from . import activations, core, densities, modules  # noqa: E402,F401

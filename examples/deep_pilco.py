@@ -38,6 +38,8 @@ def parse(argv=None):
     ap.add_argument('--no_mm', action='store_true', help='particles only (deep_pilco_no_mm.py)')
     ap.add_argument('--learn_reward', action='store_true',
                     help='a learned reward head: the dynamics model predicts the reward (examples/deep_pilco_mm.py:94-99)')
+    ap.add_argument('--nonlin', type=str, default='relu', choices=['relu', 'tanh', 'silu'],
+                    help='activation of the hidden layers of the dynamics model and the policy')
     ap.add_argument('--dyn_lr', type=float, default=1e-4)
     ap.add_argument('--dyn_opt_iters', type=int, default=2000)
     ap.add_argument('--dyn_batch_size', type=int, default=100)
@@ -90,15 +92,18 @@ def main(argv=None):
     else:   # (learned reward: one more mean and log-std, examples/deep_pilco_mm.py:117)
         Dy = D + 1 if args.learn_reward else D
         density, dynE = models.DiagGaussianDensity(Dy), 2 * Dy
+    # --nonlin: one activation for the hidden layers of both networks (relu | tanh | silu)
+    from prob_mbrl_amd.activations import module_of
+    nonlin = module_of(args.nonlin)
     dyn = models.DynamicsModel(
         models.mlp(D + U, dynE, args.dyn_shape,
                    dropout_layers=[models.CDropout(args.dyn_drop_rate * np.ones(h)) if args.dyn_drop_rate > 0
-                                   else None for h in args.dyn_shape], nonlin=torch.nn.ReLU),
+                                   else None for h in args.dyn_shape], nonlin=nonlin),
         reward_func=reward_func, output_density=density).float()
     pol = models.Policy(
         models.mlp(D, 2 * U, args.pol_shape,
                    dropout_layers=[models.BDropout(args.pol_drop_rate) if args.pol_drop_rate > 0 else None
-                                   for h in args.pol_shape], nonlin=torch.nn.ReLU,
+                                   for h in args.pol_shape], nonlin=nonlin,
                    output_nonlin=partial(models.DiagGaussianDensity, U)), maxU, minU).float()
     exp = utils.ExperienceDataset()
     if args.load_from is not None:

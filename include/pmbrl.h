@@ -83,7 +83,18 @@ extern "C" {
  * SPLIT_F16; not offered with the mixture head (dyn_components > 1) or with groups spread over ranks (mm_span_rows). */
 #define PMBRL_REWARD_LEARNED 2
 
-/* One MLP as built by models/core.py:15-99 (mlp): Linear -> ReLU -> dropout ...
+/* Activation of a network's hidden layers (models/core.py:15-99, nonlin=): ONE for all hidden layers of a network,
+ * chosen per network -- pmbrl_config::pol_act / dyn_act, pmbrl_mlp_call::act, pmbrl_bnn_config::act, each the LAST field
+ * of its struct (pmbrl_mlp keeps its layout); 0 = ReLU, so a zero-initialised struct means what it did.  TANH = torch.nn.Tanh, SILU = torch.nn.SiLU = models/activations.py:4-6 (Swish, x sigmoid(x)).
+ * A rollout plan with a network that is not ReLU runs on the general kernel family (pmbrl_plan_info: fast = 0,
+ * PMBRL_INFO_REG = 0, PMBRL_INFO_INPLACE = 0), F32 or SPLIT_F16; its forward sweep leaves act'(pre-activation) x mask /
+ * keep per hidden unit and row-step for the adjoint (4 bytes each, in place of the 1-bit activity flags of ReLU).
+ * Any other value: plan creation (pmbrl_plan_create, pmbrl_bnn_plan_create) and the stand-alone calls return -2. */
+#define PMBRL_ACT_RELU 0
+#define PMBRL_ACT_TANH 1
+#define PMBRL_ACT_SILU 2
+
+/* One MLP as built by models/core.py:15-99 (mlp): Linear -> activation -> dropout ...
  * -> Linear.  dims[0] = input width, dims[n_layers] = output width.
  * keep[i] is the keep-probability the masked activation of hidden layer i is
  * DIVIDED by (BDropout, models/modules.py:61) or 1.0 (eval-mode CDropout,
@@ -157,6 +168,7 @@ typedef struct pmbrl_config {
    * per step.  Not offered together with grad_states. */
   int32_t mm_span_rows, mm_span_offset;
   int32_t mm_span_ranks, mm_span_rank; /* ranks a group is spread over and this rank's index among them */
+  int32_t pol_act, dyn_act;            /* PMBRL_ACT_*: the hidden layers' activation of the policy / the dynamics model */
 } pmbrl_config;
 
 /* Environment switches of a rollout plan, read by pmbrl_plan_create (and by nothing else in the library: a plan keeps
@@ -533,7 +545,7 @@ int pmbrl_plan_set_prof(pmbrl_plan* plan, long long* fwd_d, long long* bwd_d);
  * (models/core.py:169-187, 265-303) compute outside a rollout (apply_controller, model
  * evaluation):
  *   xin = (x - in_shift) * in_iscale                      (both NULL: xin = x)
- *   h   = relu(xin W0^T + b0) * mask0 / keep0 ; ...       (mask NULL: no dropout on that layer)
+ *   h   = act(xin W0^T + b0) * mask0 / keep0 ; ...        (mask NULL: no dropout on that layer; act = pmbrl_mlp_call::act)
  *   (mu, l) = split(h W_L^T + b_L) ;  l <- -softplus(-l + max_log_std) + max_log_std
  *   out_scale/out_shift given:  mu <- mu*out_scale + out_shift ;  l <- l + log(out_scale)
  *   sample = mu + z * exp(l)                              (z NULL: sample = mu)
@@ -543,6 +555,7 @@ typedef struct {
   int32_t B;                  /* rows */
   pmbrl_mlp net;              /* dims[0] = input width, dims[n_layers] = 2 * output width */
   float max_log_std;
+  int32_t act;                /* PMBRL_ACT_*: the hidden layers' activation */
 } pmbrl_mlp_call;
 
 size_t pmbrl_mlp_workspace_bytes(const pmbrl_mlp_call* call);
@@ -599,6 +612,7 @@ typedef struct {
                                           *    return_samples=False): net.dims[n_layers] =
                                           *    (2 n_out + 1) n_components + 1, see pmbrl_config.dyn_components */
   int32_t n_components;                  /* loss_kind 2 only */
+  int32_t act;                           /* PMBRL_ACT_*: the hidden layers' activation */
 } pmbrl_bnn_config;
 typedef struct pmbrl_bnn_plan pmbrl_bnn_plan;
 

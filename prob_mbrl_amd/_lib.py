@@ -22,6 +22,7 @@ FLAG_GMM_EXACT_NOISE_GRAD = 256
 MAX_COMP = 8
 REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
+ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
 INFO_COUNT = 22
 INFO_TAIL_CALLS = 21    # PMBRL_INFO_TAIL_CALLS
 TIMER_COUNT = 8
@@ -35,14 +36,14 @@ class MLP(C.Structure):
 
 
 class MlpCall(C.Structure):
-    _fields_ = [('B', C.c_int32), ('net', MLP), ('max_log_std', C.c_float)]
+    _fields_ = [('B', C.c_int32), ('net', MLP), ('max_log_std', C.c_float), ('act', C.c_int32)]     # act: ACT_*
 
 
 class BnnConfig(C.Structure):
     _fields_ = [('M', C.c_int32), ('N', C.c_int32), ('net', MLP), ('max_log_std', C.c_float),
                 ('temperature', C.c_float * MAX_LAYERS), ('reg_scale', C.c_float * MAX_LAYERS),
                 ('drop_reg', C.c_float * MAX_LAYERS), ('reg_weight', C.c_float), ('loss_kind', C.c_int32),
-                ('n_components', C.c_int32)]
+                ('n_components', C.c_int32), ('act', C.c_int32)]
 
 
 class Reward(C.Structure):
@@ -65,7 +66,8 @@ class Config(C.Structure):
                 ('n_dyn_angle', C.c_int32), ('dyn_angle_dims', C.c_int32 * MAX_ANGLE),
                 ('dyn_components', C.c_int32),
                 ('mm_span_rows', C.c_int32), ('mm_span_offset', C.c_int32),
-                ('mm_span_ranks', C.c_int32), ('mm_span_rank', C.c_int32)]
+                ('mm_span_ranks', C.c_int32), ('mm_span_rank', C.c_int32),
+                ('pol_act', C.c_int32), ('dyn_act', C.c_int32)]     # ACT_* of the two networks' hidden layers
 
 
 # int fn(void* ctx, void* stream, double* buf_d, int64_t n): pmbrl_plan_set_collective

@@ -34,6 +34,7 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     if V.output_density is not None:
         raise NotImplementedError('critic with an output density: not offered on the device path')
     linears, drops, inner = V.model.layer_spec()
+    act = V.model.activation()      # the hidden layers' activation (activations.RELU / TANH / SILU)
     if inner is not None or linears[-1].out_features != 1:
         raise NotImplementedError('the device path fits a critic with one plain output')
     draws = list(_bernoulli) if _bernoulli is not None else None
@@ -107,14 +108,14 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     Xn = ((x0 - V.mx) * V.iSx).contiguous()
     Yn = ((targets - V.my) / V.Sy).contiguous()
     rw_eff = reg_weight * B / (Sy * Sy)
-    key = (id(V), B, tuple(dims), tuple(temps), rw_eff)
+    key = (id(V), B, tuple(dims), tuple(temps), rw_eff, act)
     st = _STEPS.get(key)
     if st is None:
         if len(_STEPS) > 8:
             _STEPS.clear()
         # the step computes  mse_n + (rw'/N) reg ; we want  Sy^2 mse_n + reg_weight reg  -> rw'/N = reg_weight / Sy^2
         st = _STEPS[key] = E.BnnStep(dims, temps, rscale, dreg, B, B, reg_weight=rw_eff, device=dev,
-                                     loss_kind='mse')
+                                     loss_kind='mse', act=act)
     idx = torch.arange(B, dtype=torch.int32, device=dev)
     gpad, loss = st.loss_grad(Xn, Yn, idx, padded, u, bvar)
     grad = torch.cat([gpad[:-(2 * K + 2)], gpad[-(2 * K + 2):-(K + 2)], gpad[-2:-1]]) * (Sy * Sy)

@@ -698,7 +698,7 @@ __global__ __launch_bounds__(PM_MMW_NT) void pm_mmw_bwd_kernel(RolloutArgs A, in
 // ---------------------------------------------------------------------------
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-static int net_plan(const pmbrl_mlp& m, NetPlan& n, int in_expect, int out_expect,
+static int net_plan(const pmbrl_mlp& m, int act, NetPlan& n, int in_expect, int out_expect,
                     const char* name) {
   if (m.n_layers < 1 || m.n_layers > PM_MAXL)
     return fail(-2, std::string(name) + ": n_layers out of range");
@@ -711,6 +711,9 @@ static int net_plan(const pmbrl_mlp& m, NetPlan& n, int in_expect, int out_expec
   }
   if (n.dim[0] != in_expect || n.dim[n.nl] != out_expect)
     return fail(-2, std::string(name) + ": input/output width does not match D/U");
+  if (act != PMBRL_ACT_RELU && act != PMBRL_ACT_TANH && act != PMBRL_ACT_SILU)
+    return fail(-2, std::string(name) + ": unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
+  n.act = act;
   for (int l = 0; l < n.nl; ++l) {
     n.keep[l] = (l < n.nl - 1) ? m.keep[l] : 1.f;
     if (l < n.nl - 1 && !(n.keep[l] > 0.f)) return fail(-2, std::string(name) + ": keep must be > 0");
@@ -857,12 +860,13 @@ static int plan_nets(pmbrl_plan* p) {
   if (p->learned && c.mm_span_rows > 0)
     return fail(-2, "learned reward head: not offered with moment-matching groups spread over ranks (mm_span_rows > 0)");
   if (p->learned && c.D + 1 > PMBRL_MAX_DIM) return fail(-2, "learned reward head: D + 1 exceeds PMBRL_MAX_DIM");
-  int rc = net_plan(c.pol, p->pol, c.D + c.n_pol_angle, 2 * c.U, "policy");
+  int rc = net_plan(c.pol, c.pol_act, p->pol, c.D + c.n_pol_angle, 2 * c.U, "policy");
   // (mixture head: n D means, n D log-stds, n logits, one log-temperature -- examples/deep_pilco_mm.py:117-121;
   //  learned reward: one more mean and log-std for the reward, examples/deep_pilco_mm.py:94-99)
   if (rc == 0)
-    rc = net_plan(c.dyn, p->dyn, c.D + c.U + c.n_dyn_angle,
+    rc = net_plan(c.dyn, c.dyn_act, p->dyn, c.D + c.U + c.n_dyn_angle,
                   gmm ? (2 * c.D + 1) * c.dyn_components + 1 : 2 * (c.D + p->learned), "dynamics");
+  p->act = rc == 0 && (p->pol.act != PMBRL_ACT_RELU || p->dyn.act != PMBRL_ACT_RELU);
   return rc;
 }
 
@@ -1084,7 +1088,7 @@ static int plain_row_tiles(pmbrl_plan* p, const LayoutCalc& L, int cus) {
   // on request (rows_per_wg_hint >= 64): widths <= 512, every narrow width (2U, 2D, D + U) <= 64, no mixture head,
   // no angle features.
   const bool angles = c.n_pol_angle > 0 || c.n_dyn_angle > 0;
-  if (L.gsplit && !angles && c.dyn_components <= 1 && !p->learned && L.maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
+  if (L.gsplit && !angles && c.dyn_components <= 1 && !p->learned && !p->act && L.maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
       c.D + c.U <= PM_IP_NOFF && RT < 4) {
     // every hidden layer 512 wide: the in-place layers of pmbrl_wide.h (compile-time shape, lean epilogue) -- taken by
     // default as soon as 64-row workgroups still give every CU one (PMBRL_WIDE=0: the generic in-place form on
@@ -1111,7 +1115,7 @@ static int plan_layout(pmbrl_plan* p, int cus) {
   // head (its sampling epilogue and head seed are written for that family's sweeps only)
   p->fast = !(c.flags & (PMBRL_FLAG_FORCE_GENERIC | PMBRL_FLAG_INFER_NS | PMBRL_FLAG_POL_MASKS_PER_STEP |
                          PMBRL_FLAG_DYN_MASKS_PER_STEP)) && c.n_pol_angle == 0 && c.n_dyn_angle == 0 && c.dyn_components <= 1 &&
-            !p->learned &&
+            !p->learned && !p->act &&      // (an activation other than ReLU: the general family's ACT instances)
             pm_fast_net_ok(p->pol.dim, p->pol.nt, p->pol.nl) &&
             pm_fast_net_ok(p->dyn.dim, p->dyn.nt, p->dyn.nl);
   LayoutCalc L;
@@ -1484,7 +1488,8 @@ static int plan_workspace(pmbrl_plan* p) {
       if (l < n->nl - 1)
         // u16 (generic) or 4 nibble-bytes (fast); 256 bytes of slack behind it: where the register-resident family's
         // rows past the batch put their (zero) bytes -- lane (< 64) + 4 x tile (< 64) past the end (pmbrl_reg.h)
-        n->abits[l] = take((size_t)c.H * c.B * n->nt[l + 1] * 4 + 256);
+        // (a plan with an activation other than ReLU: act' x mask / keep per unit instead, [H][B][nt * 16] floats)
+        n->abits[l] = take((size_t)c.H * c.B * n->nt[l + 1] * (p->act ? 16 * sizeof(float) : 4) + 256);
     }
   }
   const bool gmm = c.dyn_components > 1;
@@ -1537,7 +1542,9 @@ static int plan_attrs(pmbrl_plan* p, int cus) {
   const pmbrl_config& c = p->cfg;
   int rc = 0;
   if (!p->fast && p->prec) {
-    rc = pm_general_split_set_attr(p);
+    rc = p->act ? pm_general_act_set_attr(p) : pm_general_split_set_attr(p);
+  } else if (!p->fast && p->act) {
+    rc = pm_general_act_set_attr(p);
   } else if (!p->fast) {
     switch (p->RT) {
       case 1: rc = set_attr<1>(p->lds_bytes); break;
@@ -1857,6 +1864,7 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
   memset(&A, 0, sizeof(A));
   A.B = c.B; A.D = c.D; A.U = c.U; A.H = c.H;
   A.Bg = c.B_global; A.row_off = c.row_offset; A.flags = c.flags;
+  A.flags |= (p->pol.act << PM_ACT_POL_SHIFT) | (p->dyn.act << PM_ACT_DYN_SHIFT);   // (read by the ACT instances only)
   // split groups without the statistics exchange (PMBRL_MM_XCH=0): only the generic instances carry the rows + flags form
   if (p->mm_parts > 1 && !p->xch_bytes) A.flags |= PMBRL_FLAG_NO_SHAPED;
   A.G = p->G; A.M = p->M; A.mm_mode = p->mm_mode;
@@ -2008,6 +2016,7 @@ static void launch_fast_rt(const pmbrl_plan* p, const RolloutArgs& A0, hipStream
 }
 static void launch_fwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) {
   if (p->fast) return launch_fast_rt(p, A, s, true);
+  if (p->act) return pm_general_act_launch(p, A, s, true);      // (a network that is not ReLU: pmbrl_general_act.hip)
   if (p->prec) return pm_general_split_launch(p, A, s, true);
   switch (p->RT) {
     case 1: launch_fwd<1>(p, A, s); break;
@@ -2017,6 +2026,7 @@ static void launch_fwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t
 }
 static void launch_bwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) {
   if (p->fast) return launch_fast_rt(p, A, s, false);
+  if (p->act) return pm_general_act_launch(p, A, s, false);
   if (p->prec) return pm_general_split_launch(p, A, s, false);
   switch (p->RT) {
     case 1: launch_bwd<1>(p, A, s); break;
@@ -2730,7 +2740,9 @@ static int mlp_layout(const pmbrl_mlp_call* c, MlpLayout& L) {
   L.bytes = off;
   L.LD = maxnt * 16 + 8;
   L.lds = (2 * (size_t)16 * L.LD + (size_t)PM_NW * PM_KS_NT * 256) * sizeof(float);
-  L.lds_bwd = pm_mlp_bwd_lds_floats(L.nl, L.LD) * sizeof(float);
+  if (c->act != PMBRL_ACT_RELU && c->act != PMBRL_ACT_TANH && c->act != PMBRL_ACT_SILU)
+    return fail(-2, "mlp: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
+  L.lds_bwd = pm_mlp_bwd_lds_floats(L.nl, L.LD, c->act) * sizeof(float);
   if (L.lds > 160 * 1024) return fail(-3, "mlp: network too wide for LDS");
   return 0;
 }
@@ -2778,6 +2790,7 @@ extern "C" int pmbrl_mlp_forward(void* stream, const pmbrl_mlp_call* c, void* wo
   A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
   A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
   A.mls = c->max_log_std;
+  A.act = c->act;
   A.sample = sample_d; A.mean = mean_d; A.log_std = log_std_d;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_fwd_kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
@@ -2829,6 +2842,7 @@ extern "C" int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* c, void*
   A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
   A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
   A.mls = c->max_log_std;
+  A.act = c->act;
   Bw.g_sample = g_sample_d; Bw.g_mean = g_mean_d; Bw.g_log_std = g_log_std_d; Bw.grad_x = grad_x_d;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdx_kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bwd));
@@ -2886,7 +2900,11 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->n_params = po;
   p->LD = maxnt * 16 + 8;
   p->nwg = (cfg->M + 15) / 16;
-  p->lds = pm_bnn_lds_floats(p->nl, p->LD) * sizeof(float);
+  if (cfg->act != PMBRL_ACT_RELU && cfg->act != PMBRL_ACT_TANH && cfg->act != PMBRL_ACT_SILU) {
+    delete p;
+    return fail(-2, "bnn: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
+  }
+  p->lds = pm_bnn_lds_floats(p->nl, p->LD, cfg->act) * sizeof(float);
   if (p->lds > 160 * 1024) { delete p; return fail(-3, "bnn: network too wide / deep for the fused training step's LDS budget"); }
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
@@ -2908,7 +2926,8 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->n_dw_blocks = build_dw_blocks(p->nl, p->nt, blocks, p->dw_wave_first);
   HIPCHK(hipMalloc(&p->dw_blocks_d, blocks.size() * sizeof(DwBlock)));
   HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_bnn_fwd_bwd),
+  HIPCHK(hipFuncSetAttribute(cfg->act ? reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<true>)
+                                   : reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<false>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
   *out = p;
   return 0;
@@ -2962,6 +2981,7 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
     A.n_out = ((p->dim[p->nl] - 1) / A.gmm_n - 1) / 2;
   }
   A.n_in = p->dim[0]; A.sum_h = p->sum_h;
+  A.act = p->cfg.act;
   for (int i = 0; i <= p->nl; ++i) { A.dim[i] = p->dim[i]; A.nt[i] = p->nt[i]; }
   for (int l = 0; l < p->nl; ++l) {
     float* wf = reinterpret_cast<float*>(ws + p->off_wf[l]);
@@ -2992,7 +3012,8 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
     HIPCHK(hipMemsetAsync(grad_flat_d, 0, (size_t)p->n_params * sizeof(float), s));
   } else {
   hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  hipLaunchKernelGGL(pm_bnn_fwd_bwd, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+  if (A.act) hipLaunchKernelGGL(pm_bnn_fwd_bwd<true>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+  else hipLaunchKernelGGL(pm_bnn_fwd_bwd<false>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
   // dW / db of every layer: the policy-gradient GEMM over the same stash layout (one 16-row chunk per split)
   DwArgs W;
   memset(&W, 0, sizeof(W));
@@ -3057,6 +3078,7 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
   memset(&A, 0, sizeof(A));
   A.M = p->cfg.M; A.nl = p->nl; A.LD = p->LD; A.n_out = p->dim[p->nl] / 2; A.nwg = p->nwg;
   A.n_in = p->dim[0]; A.sum_h = p->sum_h;
+  A.act = p->cfg.act;
   BnnTailArgs T;
   memset(&T, 0, sizeof(T));
   T.nl = p->nl; T.n_chunks = p->nwg; T.sum_h = p->sum_h; T.N = p->cfg.N;
@@ -3115,7 +3137,8 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
         A.bvar[l] = bvar_d + (size_t)i * noise + (size_t)p->cfg.M * p->lp_off[l];
       }
     T.loss_out = loss_hist_d ? loss_hist_d + (size_t)3 * i : loss_out_d;
-    hipLaunchKernelGGL(pm_bnn_fwd_bwd, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+    if (A.act) hipLaunchKernelGGL(pm_bnn_fwd_bwd<true>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+    else hipLaunchKernelGGL(pm_bnn_fwd_bwd<false>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
     hipLaunchKernelGGL(pm_bnn_tail, dim3(units), dim3(PM_BNT_NT), 0, s, T);
   }
   if (loss_hist_d)

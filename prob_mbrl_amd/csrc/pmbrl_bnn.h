@@ -42,6 +42,7 @@ struct BnnArgs {
   int rng;
   unsigned rng_k0, rng_k1, rng_step;
   long long* prof;                 // debugging: cycle stamps of workgroup 0 (nullptr: none)
+  int act;                         // PMBRL_ACT_* of the hidden layers (pm_bnn_fwd_bwd<true> when not ReLU)
 };
 
 // 1 / x to an ulp or two: v_rcp_f32 and one Newton step
@@ -51,7 +52,12 @@ __device__ __forceinline__ float pm_fast_rcp(float d) {
 }
 
 // hidden layer forward: out = relu(acc + b) * hard ;  q = relu(.) * d mask / d logit_p
+// ACT: out = act(acc + b) * hard, q = act(.) * d mask / d logit_p, and d_out = act'(acc + b) * hard for the backward pass
+// (pm_act; act = PMBRL_ACT_TANH / PMBRL_ACT_SILU).  The ReLU instance is what it was.
+template <bool ACT = false>
 struct EpiBnnFwd {
+  int act;
+  float* d_out;
   const float* bias;
   const float* logit_p;
   const float *u, *bvar;
@@ -64,7 +70,7 @@ struct EpiBnnFwd {
     const int g = lane >> 4, lrow = lane & 15;
     const int f0 = ot * 16 + 4 * g;
     const f32x4 b = ldg4(bias + f0);
-    f32x4 h, q;
+    f32x4 h, q, dd;
     unsigned ru[4] = {0u, 0u, 0u, 0u}, rv[4] = {0u, 0u, 0u, 0u};
     if (rng && logit_p) {      // 24-bit uniforms in [0, 1), what torch.rand gives a float tensor
       pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer, rstep, rk0, rk1, ru);
@@ -73,7 +79,9 @@ struct EpiBnnFwd {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int f = f0 + r;
-      const float v = fmaxf(acc[r] + b[r], 0.f);
+      float v, dv = 0.f;
+      if constexpr (ACT) pm_act(act, acc[r] + b[r], v, dv);
+      else v = fmaxf(acc[r] + b[r], 0.f);
       float hv = v, qv = 0.f;
       if (logit_p && f < width && lrow < nvalid) {
         const size_t o = (size_t)(row0 + lrow) * width + f;
@@ -89,13 +97,16 @@ struct EpiBnnFwd {
         const bool hard = (rng ? (float)(rv[r] >> 8) * (1.0f / 16777216.0f) : bvar[o]) < pr;
         hv = hard ? v : 0.f;
         qv = v * pr * (1.f - pr) * inv_temp;
+        if (!hard) dv = 0.f;
       }
-      if (f >= width || lrow >= nvalid) { hv = 0.f; qv = 0.f; }
+      if (f >= width || lrow >= nvalid) { hv = 0.f; qv = 0.f; dv = 0.f; }
       h[r] = hv;
       q[r] = qv;
+      dd[r] = dv;
     }
     *reinterpret_cast<f32x4*>(h_out + lrow * ld + f0) = h;
     *reinterpret_cast<f32x4*>(q_out + lrow * ld + f0) = q;
+    if constexpr (ACT) *reinterpret_cast<f32x4*>(d_out + lrow * ld + f0) = dd;
 #pragma unroll
     for (int r = 0; r < 4; ++r) stash[(size_t)(f0 + r) * 16 + lrow] = h[r];
   }
@@ -103,6 +114,8 @@ struct EpiBnnFwd {
 
 // backward through hidden layer l-1's output: acc = dL/d out ; gq = acc * q (dropout-logit term),
 // g_pre = out > 0 ? acc : 0
+// (ACT: g_pre = acc * d, h_in = the d_out of EpiBnnFwd<true>)
+template <bool ACT = false>
 struct EpiBnnBwd {
   const float *h_in, *q_in;   // out and q of that layer
   float *g_out, *gq_out, *stash;
@@ -115,7 +128,8 @@ struct EpiBnnBwd {
     f32x4 gp, gq;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      gp[r] = h[r] > 0.f ? acc[r] : 0.f;
+      if constexpr (ACT) gp[r] = h[r] != 0.f ? acc[r] * h[r] : 0.f;
+      else gp[r] = h[r] > 0.f ? acc[r] : 0.f;
       gq[r] = acc[r] * q[r];
     }
     *reinterpret_cast<f32x4*>(g_out + lrow * ld + f0) = gp;
@@ -127,11 +141,14 @@ struct EpiBnnBwd {
 
 // (A GEMM variant that requests ALL of a wave's weight fragments of a layer at once was measured: pm_bnn_fwd_bwd 27.7 ->
 //  34.3 us -- the first MFMA then waits for 32 loads where gemm_tiles starts on four; the layer chain is not what bounds it.)
-__host__ __device__ inline size_t pm_bnn_lds_floats(int nl, int LD) {
-  // H[0..nl-1], Q[0..nl-2], two gradient buffers, one gq buffer, K-split scratch, loss scratch
-  return ((size_t)nl + (nl - 1) + 3) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256 + PM_NT;
+__host__ __device__ inline size_t pm_bnn_lds_floats(int nl, int LD, int act = 0) {
+  // H[0..nl-1], Q[0..nl-2], two gradient buffers, one gq buffer, K-split scratch, loss scratch; an activation other than
+  // ReLU: one more buffer, the first hidden layer's derivatives (those of hidden layer l >= 1 go where the input of
+  // Linear l - 1 was: the dW stash has it, and the backward pass of these instances does not read H)
+  return ((size_t)nl + (nl - 1) + 3 + (act ? 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256 + PM_NT;
 }
 
+template <bool ACT = false>
 __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 16;
@@ -148,6 +165,8 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   float* GQ = G1 + (size_t)R * LD;
   float* part = GQ + (size_t)R * LD;
   float* red = part + (size_t)PM_NW * PM_KS_NT * 256;
+  float* D0 = red + PM_NT;                              // (ACT only)
+  auto dbuf = [&](int l) { return l == 0 ? D0 : H + (size_t)(l - 1) * R * LD; };
 #define BNN_STAMP(i) do { if (A.prof && wg == 0 && tid == 0) A.prof[i] = (long long)__builtin_readcyclecounter(); } while (0)
   BNN_STAMP(0);
 
@@ -167,7 +186,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   BNN_STAMP(1);
   // ---- forward
   for (int l = 0; l < nl - 1; ++l) {
-    EpiBnnFwd e{A.bias[l], A.logit_p[l], A.u[l], A.bvar[l], A.inv_temp[l],
+    EpiBnnFwd<ACT> e{A.act, ACT ? dbuf(l) : nullptr, A.bias[l], A.logit_p[l], A.u[l], A.bvar[l], A.inv_temp[l],
                 H + (size_t)(l + 1) * R * LD, Q + (size_t)l * R * LD,
                 A.actT[l + 1] + (size_t)wg * A.nt[l + 1] * 16 * 16, LD, row0, nvalid, A.dim[l + 1], lane,
                 A.rng, A.rng_k0, A.rng_k1, A.rng_step, (unsigned)l};
@@ -310,7 +329,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   float* Gin = G0;
   float* Gout = G1;
   for (int l = nl - 1; l >= 1; --l) {
-    EpiBnnBwd e{H + (size_t)l * R * LD, Q + (size_t)(l - 1) * R * LD, Gout, GQ,
+    EpiBnnBwd<ACT> e{ACT ? dbuf(l - 1) : H + (size_t)l * R * LD, Q + (size_t)(l - 1) * R * LD, Gout, GQ,
                 A.gT[l - 1] + (size_t)wg * A.nt[l] * 16 * 16, LD, lane};
     gemm_tiles<1>(A.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
     __syncthreads();

@@ -506,6 +506,30 @@ __device__ __forceinline__ float softplusf(float x) {
 }
 __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x)); }
 
+// Hidden activations (pmbrl_mlp::act).  pm_act gives h = act(a) and d = act'(a); the adjoints multiply by d instead of
+// testing a sign, so a further activation is one more branch here.  Saturation: tanhf is +-1 beyond |a| = 9, and
+// sigmoidf's IEEE division turns the overflowed exp(-a) = inf into 0, not a NaN (a reciprocal with a Newton step would):
+// |a| = 50 and beyond gives tanh = +-1, d = 0 and silu = a or -0, d = 1 or 0.
+// A rollout plan with a network that is not ReLU carries the two activations in bits of RolloutArgs::flags the public
+// PMBRL_FLAG_* do not use: no kernel of another family sees a new argument.
+#define PM_ACT_POL_SHIFT 20
+#define PM_ACT_DYN_SHIFT 22
+#define PM_ACT_MASK 3
+__device__ __forceinline__ void pm_act(int act, float a, float& h, float& d) {
+  if (act == PMBRL_ACT_TANH) {
+    h = tanhf(a);
+    d = 1.f - h * h;
+  } else if (act == PMBRL_ACT_SILU) {
+    const float s = sigmoidf(a);
+    h = a * s;
+    d = s * (1.f + a * (1.f - s));
+  } else {
+    const bool pos = a > 0.f;
+    h = pos ? a : 0.f;
+    d = pos ? 1.f : 0.f;
+  }
+}
+
 // block-wide sum in a fixed order (sm: blockDim.x doubles of LDS); contains barriers
 __device__ __forceinline__ double pm_block_sum(double s, double* sm) {
   sm[threadIdx.x] = s;

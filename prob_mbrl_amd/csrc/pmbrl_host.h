@@ -25,6 +25,7 @@ struct NetPlan {
   int nl;
   int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
   float keep[PM_MAXL];
+  int act;                                 // PMBRL_ACT_* of the hidden layers
   size_t w_off[PM_MAXL], b_off[PM_MAXL];   // offsets (floats) in the flat parameter vector
   size_t n_params;
   // workspace offsets (bytes)
@@ -52,6 +53,7 @@ struct pmbrl_plan {
   size_t lds_bytes;
   NetPlan pol, dyn;
   RewardDev* rew_d;
+  int act;             // a network is not ReLU: the general family's ACT instances, per-unit act' stashes in place of the activity bits
   int learned;         // PMBRL_REWARD_LEARNED: the dynamics head predicts the reward (general family only)
   int rew_k = PMBRL_MAX_TIP;   // tip residuals of the reward (which instance of the reward launch: pm_reward_kernel_for)
   int* wflag_d;        // weight-range flag of the fp16 packer (see RolloutArgs::wflag)
@@ -243,6 +245,9 @@ int pm_fast_split2_mmg_blocks_per_cu(const pmbrl_plan* p);
 // general family on split operands (pmbrl_general_split.hip)
 int pm_general_split_set_attr(const pmbrl_plan* p);
 void pm_general_split_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
+// ... with a network that is not ReLU, exact fp32 and split operands (pmbrl_general_act.hip)
+int pm_general_act_set_attr(const pmbrl_plan* p);
+void pm_general_act_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
 int pm_fast_f32_set_attr(const pmbrl_plan* p);
 void pm_fast_f32_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
 int pm_fast_split1_set_attr(const pmbrl_plan* p);     // PMBRL_PREC_SPLIT

@@ -17,6 +17,37 @@ struct MlpArgs {
   const float *x, *z, *in_shift, *in_iscale, *out_scale, *out_shift, *sq_scale, *sq_bias;
   float mls;
   float *sample, *mean, *log_std;
+  int act;                          // PMBRL_ACT_* of the hidden layers
+};
+
+// The same with act = PMBRL_ACT_TANH / PMBRL_ACT_SILU (pm_act): h = act(v) * mask / keep, and -- d_out given, the input
+// gradient's recomputed forward -- act'(v) * mask / keep next to it.  Padded units (width .. nt * 16) stay 0 in both.
+struct EpiMlpAct {
+  const float* bias;
+  const uint16_t* mask;
+  float keep;
+  float* lds_out;
+  float* d_out;
+  int ld, row0, nvalid, nt, lane, act, width;
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
+    const int g = lane >> 4;
+    const int lrow = rt * 16 + (lane & 15);
+    const int f0 = ot * 16 + 4 * g;
+    const f32x4 b = ldg4(bias + f0);
+    unsigned nib = lrow < nvalid ? 0xFu : 0u;
+    if (mask && lrow < nvalid) nib = ((unsigned)mask[(size_t)(row0 + lrow) * nt + ot] >> (4 * g)) & 0xFu;
+    f32x4 h, d;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float hv, dv;
+      pm_act(act, acc[r] + b[r], hv, dv);
+      const bool m = ((nib >> r) & 1u) && f0 + r < width;
+      h[r] = m ? (keep == 1.f ? hv : hv / keep) : 0.f;
+      d[r] = m ? (keep == 1.f ? dv : dv / keep) : 0.f;
+    }
+    *reinterpret_cast<f32x4*>(lds_out + lrow * ld + f0) = h;
+    if (d_out) *reinterpret_cast<f32x4*>(d_out + lrow * ld + f0) = d;
+  }
 };
 
 struct EpiMlpHidden {
@@ -70,8 +101,13 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_fwd_kernel(const MlpArgs A) {
   }
   __syncthreads();
   for (int l = 0; l < A.nl - 1; ++l) {
-    EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], Y, LD, row0, nvalid, A.nt[l + 1], lane};
-    gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], X, LD, wid, lane, e);
+    if (A.act != PMBRL_ACT_RELU) {
+      EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], Y, nullptr, LD, row0, nvalid, A.nt[l + 1], lane, A.act, A.dim[l + 1]};
+      gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], X, LD, wid, lane, e);
+    } else {
+      EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], Y, LD, row0, nvalid, A.nt[l + 1], lane};
+      gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], X, LD, wid, lane, e);
+    }
     __syncthreads();
     float* t = X; X = Y; Y = t;
   }
@@ -125,8 +161,27 @@ struct EpiMlpBwd {
   }
 };
 
-__host__ __device__ inline size_t pm_mlp_bwd_lds_floats(int nl, int LD) {
-  return ((size_t)nl + 2) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;   // H[0..nl-1], two gradient buffers, K-split scratch
+// ... an activation other than ReLU: g_pre = acc * d with d = act'(v) * mask / keep from the recomputed forward (the
+// layer's OUTPUT does not give SiLU's derivative).  d of hidden layer l - 1 lives where the input of layer l - 2 was -- dead
+// once layer l - 2 has run -- and the first hidden layer's in one more buffer (pm_mlp_bwd_lds_floats).
+struct EpiMlpBwdAct {
+  const float* d_in;
+  float* g_out;
+  int ld, lane;
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
+    const int g = lane >> 4, lrow = lane & 15;
+    const int f0 = ot * 16 + 4 * g;
+    const f32x4 d = *reinterpret_cast<const f32x4*>(d_in + lrow * ld + f0);
+    f32x4 gp;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) gp[r] = d[r] != 0.f ? acc[r] * d[r] : 0.f;
+    *reinterpret_cast<f32x4*>(g_out + lrow * ld + f0) = gp;
+  }
+};
+
+__host__ __device__ inline size_t pm_mlp_bwd_lds_floats(int nl, int LD, int act = 0) {
+  // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: the first hidden layer's derivatives
+  return ((size_t)nl + 2 + (act ? 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
 }
 
 __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs B) {
@@ -142,6 +197,10 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   float* G0 = H + (size_t)nl * R * LD;
   float* G1 = G0 + (size_t)R * LD;
   float* part = G1 + (size_t)R * LD;
+  const bool smooth = A.act != PMBRL_ACT_RELU;
+  float* D0 = part + (size_t)PM_NW * PM_KS_NT * 256;   // (smooth only: pm_mlp_bwd_lds_floats)
+  // derivatives of hidden layer l (the output of Linear l): D0 for l = 0, else the dead input buffer of Linear l - 1
+  auto dbuf = [&](int l) { return l == 0 ? D0 : H + (size_t)(l - 1) * R * LD; };
   const int K0 = A.dim[0];
   for (int i = tid; i < R * A.nt[0] * 16; i += PM_NT) {
     const int r = i / (A.nt[0] * 16), k = i - r * (A.nt[0] * 16);
@@ -154,8 +213,14 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   }
   __syncthreads();
   for (int l = 0; l < nl - 1; ++l) {
-    EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, LD, row0, nvalid, A.nt[l + 1], lane};
-    gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+    if (smooth) {
+      EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, dbuf(l), LD, row0, nvalid, A.nt[l + 1],
+                  lane, A.act, A.dim[l + 1]};
+      gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+    } else {
+      EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, LD, row0, nvalid, A.nt[l + 1], lane};
+      gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+    }
     __syncthreads();
   }
   gemm_narrow<1>(A.wf[nl - 1], A.nt[nl], A.nt[nl - 1], A.bias[nl - 1], H + (size_t)(nl - 1) * R * LD, G1, LD, part,
@@ -194,8 +259,13 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   float* Gin = G0;
   float* Gout = G1;
   for (int l = nl - 1; l >= 1; --l) {
-    EpiMlpBwd e{H + (size_t)l * R * LD, 1.f / A.keep[l - 1], Gout, LD, lane};
-    gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+    if (smooth) {
+      EpiMlpBwdAct e{dbuf(l - 1), Gout, LD, lane};
+      gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+    } else {
+      EpiMlpBwd e{H + (size_t)l * R * LD, 1.f / A.keep[l - 1], Gout, LD, lane};
+      gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+    }
     __syncthreads();
     float* t = Gin; Gin = Gout; Gout = t;
   }

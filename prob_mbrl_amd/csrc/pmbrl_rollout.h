@@ -135,6 +135,107 @@ struct EpiHiddenBwdT {
   }
 };
 
+// Hidden layers of a plan with a network that is not ReLU (pmbrl_mlp::act; the kernels' ACT instances).  Forward:
+//   h = act(acc + b) * mask / keep,   dact = act'(acc + b) * mask / keep
+// dact ([B][nt * 16] floats of step t, in the workspace region the activity bits of a ReLU plan have) is all the adjoint
+// needs of the layer: g_pre = acc * dact.  tanh' could be had from the stashed h, SiLU's cannot (it is not monotone),
+// and the dynamics layers have no stash of h at all: one form for every activation, a ReLU network of a mixed plan
+// included (dact = mask / keep where the pre-activation is positive).  Padded units (width .. nt * 16) get h = 0 and
+// dact = 0 whatever act'(0) is.
+template <int NP = 0, bool F16 = false, int R = 0>
+struct EpiActFwdT {
+  const float* bias;
+  const uint16_t* mask;   // [B][nt]
+  float* dact;            // [B][nt * 16] slice of step t
+  float keep;
+  float* lds_out;
+  float* stash;           // feature-major block [nt*16][Rw] or nullptr
+  int ld, Rw, row0, nvalid, nt, lane, act, width;
+  int* ovf;
+  typedef typename EpiHiddenFwdT<NP, F16, R>::Pre Pre;
+  __device__ __forceinline__ Pre pre(int ot, int rt) const {
+    const int g = lane >> 4;
+    const int lrow = rt * 16 + (lane & 15);
+    Pre p;
+    p.b = ldg4(bias + ot * 16 + 4 * g);
+    p.mw = 0;
+    if (lrow < nvalid) p.mw = mask[(size_t)(row0 + lrow) * nt + ot];
+    return p;
+  }
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) { (*this)(ot, rt, acc, pre(ot, rt)); }
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc, const Pre& pr) {
+    const int g = lane >> 4;
+    const int lrow = rt * 16 + (lane & 15);
+    const int f0 = ot * 16 + 4 * g;
+    const unsigned nib = (pr.mw >> (4 * g)) & 0xFu;   // (rows past the batch: no bit set)
+    f32x4 h, dd;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      float hv, dv;
+      pm_act(act, acc[r] + pr.b[r], hv, dv);
+      const bool m = ((nib >> r) & 1u) && f0 + r < width;
+      // (the reference's division, x / p)
+      h[r] = m ? (keep == 1.f ? hv : hv / keep) : 0.f;
+      dd[r] = m ? (keep == 1.f ? dv : dv / keep) : 0.f;
+    }
+    if constexpr (NP > 0) {
+      pm_store_planes<NP, R, F16>(lds_out, (unsigned)ld, (unsigned)lrow, (unsigned)f0, h);
+      if (ot == nt - 1 && (nt & 1))
+        pm_store_planes<NP, R, F16>(lds_out, (unsigned)ld, (unsigned)lrow, (unsigned)f0 + 16u, f32x4{0.f, 0.f, 0.f, 0.f});
+      if constexpr (F16) {
+        // (SiLU is unbounded above; a NaN pre-activation stays a NaN here and ends the rollout at this step)
+        if (fmaxf(fmaxf(fabsf(h[0]), fabsf(h[1])), fmaxf(fabsf(h[2]), fabsf(h[3]))) > 65504.f) *ovf = 1;
+      }
+    } else {
+      *reinterpret_cast<f32x4*>(lds_out + lrow * ld + f0) = h;
+    }
+    if (stash) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(h[r], stash + (size_t)(f0 + r) * Rw + lrow);
+    }
+    if (lrow < nvalid) *reinterpret_cast<f32x4*>(dact + ((size_t)(row0 + lrow) * nt + ot) * 16 + 4 * g) = dd;
+  }
+};
+
+// ... backward: g_pre = acc * dact (zero where dact is: a dropped, padded or saturated unit passes no NaN on)
+template <int NP = 0, int R = 0>
+struct EpiActBwdT {
+  const float* dact;      // [B][nt * 16] slice of step t
+  float* lds_out;
+  float* stash;           // gT block or nullptr
+  int ld, Rw, row0, nvalid, nt, lane;
+  struct Pre {
+    f32x4 d;
+  };
+  __device__ __forceinline__ Pre pre(int ot, int rt) const {
+    const int lrow = rt * 16 + (lane & 15);
+    Pre p;
+    p.d = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (lrow < nvalid) p.d = ldg4(dact + ((size_t)(row0 + lrow) * nt + ot) * 16 + 4 * (lane >> 4));
+    return p;
+  }
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) { (*this)(ot, rt, acc, pre(ot, rt)); }
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc, const Pre& pr) {
+    const int g = lane >> 4;
+    const int lrow = rt * 16 + (lane & 15);
+    const int f0 = ot * 16 + 4 * g;
+    f32x4 h;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) h[r] = pr.d[r] != 0.f ? acc[r] * pr.d[r] : 0.f;
+    if constexpr (NP > 0) {
+      pm_store_planes<NP, R, false>(lds_out, (unsigned)ld, (unsigned)lrow, (unsigned)f0, h);
+      if (ot == nt - 1 && (nt & 1))
+        pm_store_planes<NP, R, false>(lds_out, (unsigned)ld, (unsigned)lrow, (unsigned)f0 + 16u, f32x4{0.f, 0.f, 0.f, 0.f});
+    } else {
+      *reinterpret_cast<f32x4*>(lds_out + lrow * ld + f0) = h;
+    }
+    if (stash) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) __builtin_nontemporal_store(h[r], stash + (size_t)(f0 + r) * Rw + lrow);
+    }
+  }
+};
+
 // ---------------------------------------------------------------------------
 // reward (envs/<env>/env.py:*Reward.forward); one thread per row
 // ---------------------------------------------------------------------------
@@ -273,9 +374,12 @@ __device__ inline LdsMap pm_lds_carve(float* base, int R, int LD, int D, int U, 
 // PR = 0: exact fp32 MFMA; PR = 2: split operands (pmbrl_gsplit.h) -- two fp16 pieces
 // IP: in-place layers (PR = 2 only; widths <= 512, narrow widths <= PM_IP_NOFF, no mixture head); IP = 2: every hidden
 // layer is 512 wide and runs on pmbrl_wide.h
-template <int RT, int PR = 0, int IP = 0>
+// ACT: a network of the plan is not ReLU (two-buffer layers only) -- the hidden layers run EpiActFwdT with each network's
+// own activation; the ReLU instances (ACT = false) are what they were
+template <int RT, int PR = 0, int IP = 0, bool ACT = false>
 __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  static_assert(!ACT || IP == 0, "activations other than ReLU: the two-buffer layers only");
   constexpr int R = 16 * RT;
   constexpr bool SP = PR != 0;
   const unsigned LDB = (unsigned)A.LD;   // split: elements per row of a piece plane (= floats per row)
@@ -354,7 +458,13 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       EpiHiddenFwdT<SP ? 2 : 0, SP, R> e{P.bias[l], mk, P.abits[l] + (size_t)t * B * nt, P.keep[l], IP ? X : Y,
                                         A.actT[l + 1] + blk * (size_t)nt * 16 * A.Rw, LD, A.Rw, row0, nvalid, nt, lane,
                                         p_ovf};
-      if constexpr (IP >= 2) {
+      if constexpr (ACT) {
+        EpiActFwdT<SP ? 2 : 0, SP, R> ea{P.bias[l], mk, reinterpret_cast<float*>(P.abits[l]) + (size_t)t * B * nt * 16,
+                                        P.keep[l], Y, A.actT[l + 1] + blk * (size_t)nt * 16 * A.Rw, LD, A.Rw, row0, nvalid,
+                                        nt, lane, (A.flags >> PM_ACT_POL_SHIFT) & PM_ACT_MASK, P.dim[l + 1], p_ovf};
+        if constexpr (SP) gemm_tiles_s<RT, true>(P.wf[l], nt, pm_kb32(P.nt[l]), X, LDB, wid, lane, ea);
+        else gemm_tiles<RT>(P.wf[l], nt, P.nt[l], X, LD, wid, lane, ea);
+      } else if constexpr (IP >= 2) {
         const PwFwd w{P.bias[l], mk, P.abits[l] + (size_t)t * B * nt, P.keep[l], X,
                       A.actT[l + 1] + blk * (size_t)nt * 16 * A.Rw, L.tbl, row0, nvalid, p_ovf,
                       (A.prof && wg == 0 && l == 1) ? A.prof + (size_t)t * 32 + 5 : nullptr};
@@ -472,7 +582,13 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       const uint16_t* mk = F.mask[l] + ((A.flags & PMBRL_FLAG_DYN_MASKS_PER_STEP) ? (size_t)t * B * nt : 0);
       EpiHiddenFwdT<SP ? 2 : 0, SP, R> e{F.bias[l], mk, F.abits[l] + (size_t)t * B * nt, F.keep[l], IP ? X : Y,
                                         nullptr, LD, A.Rw, row0, nvalid, nt, lane, p_ovf};
-      if constexpr (IP >= 2) {
+      if constexpr (ACT) {
+        EpiActFwdT<SP ? 2 : 0, SP, R> ea{F.bias[l], mk, reinterpret_cast<float*>(F.abits[l]) + (size_t)t * B * nt * 16,
+                                        F.keep[l], Y, nullptr, LD, A.Rw, row0, nvalid, nt, lane,
+                                        (A.flags >> PM_ACT_DYN_SHIFT) & PM_ACT_MASK, F.dim[l + 1], p_ovf};
+        if constexpr (SP) gemm_tiles_s<RT, true>(F.wf[l], nt, pm_kb32(F.nt[l]), X, LDB, wid, lane, ea);
+        else gemm_tiles<RT>(F.wf[l], nt, F.nt[l], X, LD, wid, lane, ea);
+      } else if constexpr (IP >= 2) {
         const PwFwd w{F.bias[l], mk, F.abits[l] + (size_t)t * B * nt, F.keep[l], X, nullptr, L.tbl, row0, nvalid, p_ovf,
                       (A.prof && wg == 0 && l == 1) ? A.prof + (size_t)t * 32 + 15 : nullptr};
         pw_hidden_fwd<0>(F.wf[l], pm_kb32(F.nt[l]), w, wid, lane);
@@ -692,9 +808,10 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
 // dW GEMM; policy dW/db are NOT accumulated here.
 // ===========================================================================
 // (PR = 2: two bf16 pieces -- the adjoint is linear in the incoming gradient, profiles/r02_split_precision_study.txt)
-template <int RT, int PR = 0, int IP = 0>
+template <int RT, int PR = 0, int IP = 0, bool ACT = false>
 __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const RolloutArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
+  static_assert(!ACT || IP == 0, "activations other than ReLU: the two-buffer layers only");
   constexpr int R = 16 * RT;
   constexpr bool SP = PR != 0;
   const unsigned LDB = (unsigned)A.LD;
@@ -889,7 +1006,12 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
       const int nt = F.nt[l];
       EpiHiddenBwdT<SP ? 2 : 0, R> e{F.abits[l - 1] + (size_t)t * B * nt, F.keep[l - 1], IP ? X : Y, nullptr, LD, A.Rw,
                                     row0, nvalid, nt, lane};
-      if constexpr (IP >= 2) {
+      if constexpr (ACT) {
+        EpiActBwdT<SP ? 2 : 0, R> ea{reinterpret_cast<const float*>(F.abits[l - 1]) + (size_t)t * B * nt * 16, Y, nullptr,
+                                    LD, A.Rw, row0, nvalid, nt, lane};
+        if constexpr (SP) gemm_tiles_s<RT, false>(F.wb[l], nt, pm_kb32(F.nt[l + 1]), X, LDB, wid, lane, ea);
+        else gemm_tiles<RT>(F.wb[l], nt, F.nt[l + 1], X, LD, wid, lane, ea);
+      } else if constexpr (IP >= 2) {
         const PwBwd w{F.abits[l - 1] + (size_t)t * B * nt, F.keep[l - 1], X, nullptr, L.tbl, row0, nvalid,
                       (A.prof && wg == 0 && l == 2) ? A.prof + (size_t)t * 32 + 8 : nullptr};
         pw_hidden_bwd<0>(F.wb[l], pm_kb32(F.nt[l + 1]), w, wid, lane);
@@ -1018,7 +1140,12 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
       const int nt = P.nt[l];
       EpiHiddenBwdT<SP ? 2 : 0, R> e{P.abits[l - 1] + (size_t)t * B * nt, P.keep[l - 1], IP ? X : Y,
                                     A.gT[l - 1] + blk * (size_t)nt * 16 * A.Rw, LD, A.Rw, row0, nvalid, nt, lane};
-      if constexpr (IP >= 2) {
+      if constexpr (ACT) {
+        EpiActBwdT<SP ? 2 : 0, R> ea{reinterpret_cast<const float*>(P.abits[l - 1]) + (size_t)t * B * nt * 16, Y,
+                                    A.gT[l - 1] + blk * (size_t)nt * 16 * A.Rw, LD, A.Rw, row0, nvalid, nt, lane};
+        if constexpr (SP) gemm_tiles_s<RT, false>(P.wb[l], nt, pm_kb32(P.nt[l + 1]), X, LDB, wid, lane, ea);
+        else gemm_tiles<RT>(P.wb[l], nt, P.nt[l + 1], X, LD, wid, lane, ea);
+      } else if constexpr (IP >= 2) {
         const PwBwd w{P.abits[l - 1] + (size_t)t * B * nt, P.keep[l - 1], X,
                       A.gT[l - 1] + blk * (size_t)nt * 16 * A.Rw, L.tbl, row0, nvalid,
                       (A.prof && wg == 0 && l == 2) ? A.prof + (size_t)t * 32 + 18 : nullptr};

@@ -90,7 +90,7 @@ class _MlpCall:
     """Marshalled arguments of one stand-alone network evaluation (kept alive for the backward)."""
 
     def __init__(self, x, params_flat, dims, keep, mask_bits, z, in_shift, in_iscale, out_scale,
-                 out_shift, sq_scale, sq_bias, max_log_std):
+                 out_shift, sq_scale, sq_bias, max_log_std, act=0):
         self.lib = _lib.load()
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
         B = x.shape[0]
@@ -105,6 +105,7 @@ class _MlpCall:
         for l in range(nl - 1):
             call.net.keep[l] = float(keep[l])
         call.max_log_std = float(max_log_std)
+        call.act = int(act)
         self.call = call
         nbytes = self.lib.pmbrl_mlp_workspace_bytes(C.byref(call))
         if nbytes == 0:
@@ -183,16 +184,17 @@ class _MlpFunction(torch.autograd.Function):
 
 def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=None, in_iscale=None,
                 out_scale=None, out_shift=None, sq_scale=None, sq_bias=None, max_log_std=math.log(5.0),
-                want=('sample',)):
+                want=('sample',), act=0):
     """Stand-alone evaluation of one Bayesian MLP with a diagonal-Gaussian head on the rows of x
     (pmbrl_mlp_forward; models/core.py:169-187, 221-248).  dims = [n_in, h..., 2*n_out];
     mask_bits: per hidden layer an int16 bit-row tensor (pack_mask) or None.
+    act: the hidden layers' activation (activations.RELU / TANH / SILU).
     Returns a dict with the requested outputs among 'sample', 'mean', 'log_std' ([B, n_out]).
     If x requires grad the outputs are differentiable with respect to x (pmbrl_mlp_grad_input)."""
     want = tuple(want)
     xc = x.contiguous()
     call = _MlpCall(xc.detach(), params_flat, dims, keep, mask_bits, z, in_shift, in_iscale, out_scale,
-                    out_shift, sq_scale, sq_bias, max_log_std)
+                    out_shift, sq_scale, sq_bias, max_log_std, act=act)
     if x.requires_grad and torch.is_grad_enabled():
         outs = _MlpFunction.apply(xc, call, want)
         return dict(zip(want, outs))
@@ -205,13 +207,14 @@ class BnnStep:
     W0, b0, [logit_p0], W1, b1, [logit_p1], ..., W_L, b_L."""
 
     def __init__(self, dims, temperature, reg_scale, drop_reg, M, N, reg_weight=1.0,
-                 max_log_std=LOG_MAX_STD, device=None, loss_kind='nll', n_components=0):
+                 max_log_std=LOG_MAX_STD, device=None, loss_kind='nll', n_components=0, act=0):
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else 'cuda:0')
         cfg = _lib.BnnConfig()
         cfg.M, cfg.N = int(M), int(N)
         nl = len(dims) - 1
         cfg.net.n_layers = nl
+        cfg.act = int(act)      # the hidden layers' activation (activations.RELU / TANH / SILU)
         for i, d in enumerate(dims):
             cfg.net.dims[i] = int(d)
         for l in range(nl - 1):
@@ -334,7 +337,7 @@ class Engine:
                  max_log_std_pol=LOG_MAX_STD, max_log_std_dyn=LOG_MAX_STD, zmm_per_step=False,
                  force_generic=False, no_shaped=False, infer_ns=False, precision=None,
                  pol_masks_per_step=False, dyn_masks_per_step=False, pol_angle_dims=(), dyn_angle_dims=(),
-                 dyn_components=0, gmm_exact_noise_grad=False, mm_span=None):
+                 dyn_components=0, gmm_exact_noise_grad=False, mm_span=None, pol_act=0, dyn_act=0):
         self.lib = _lib.load()
         if not torch.cuda.is_available():
             raise RuntimeError('prob_mbrl_amd needs a HIP device (no CPU fallback)')
@@ -363,6 +366,9 @@ class Engine:
                 mlp.dims[i] = int(d)
             for i in range(_lib.MAX_LAYERS):
                 mlp.keep[i] = float(keep[i]) if i < len(keep) else 1.0
+        # the hidden layers' activations (activations.RELU / TANH / SILU), one per network: anything but ReLU runs on the
+        # general kernel family
+        cfg.pol_act, cfg.dyn_act = int(pol_act), int(dyn_act)
         cfg.reward = make_reward_struct(reward_spec, D, U)
         cfg.rows_per_wg_hint = rows_per_wg_hint
         cfg.precision = _PRECISIONS[precision if precision is not None else get_precision()]

@@ -391,7 +391,7 @@ class BSequential(nn.Sequential):
         (squashed if `squash=(scale, bias)`) or (mean, log_std)."""
         from . import engine as E
         from .rollout import flat_parameters
-        linears, drops, inner = self.layer_spec()
+        linears, drops, inner, act = self._parse()
         density = inner if inner is not None else density
         if not x.is_cuda:
             raise RuntimeError('the network lives on a HIP device: pass a device tensor (no CPU fallback)')
@@ -429,12 +429,12 @@ class BSequential(nn.Sequential):
         if mixture:
             # the network on the device (raw head rows), the few head formulas of the mixture with torch ops on
             # those rows (stand-alone evaluation is not the hot path; rollouts and training are fused kernels)
-            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',))['mean']
+            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act)['mean']
             return density.from_head(o, out_shift, out_scale, return_samples=return_samples,
                                      resample_noise=resample_noise)
         if plain:
             return E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, out_scale,
-                                 out_shift, want=('mean',))['mean']
+                                 out_shift, want=('mean',), act=act)['mean']
         z = None
         if return_samples:
             z = density.frozen_noise(B, resample_noise, seed).to(device=x.device, dtype=torch.float32)
@@ -442,27 +442,40 @@ class BSequential(nn.Sequential):
                             squash[0] if (squash and return_samples) else None,
                             squash[1] if (squash and return_samples) else None,
                             max_log_std=float(density.max_log_std),
-                            want=('sample',) if return_samples else ('mean', 'log_std'))
+                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act)
         if return_samples:
             return out['sample']
         return out['mean'], out['log_std']
 
     # --- structure the fused kernels understand ---------------------------
     def layer_spec(self):
-        """Parse Linear -> [ReLU] -> [dropout] ... -> Linear [-> density] into
-        (linears, dropouts-per-hidden-layer, density)."""
+        """Parse Linear -> activation -> [dropout] ... -> Linear [-> density] into
+        (linears, dropouts-per-hidden-layer, density).  The activation -- one for all hidden layers -- is
+        activation()."""
+        return self._parse()[:3]
+
+    def activation(self):
+        """PMBRL_ACT_* of the hidden layers (activations.RELU / TANH / SILU)."""
+        return self._parse()[3]
+
+    def _parse(self):
+        from . import activations as ACT
         linears, drops, density = [], [], None
         pending = None
+        acts = []
         for name, m in self._modules.items():
             if isinstance(m, nn.Linear):
                 if pending is not None:
                     drops.append(pending['drop'])
-                    if not pending['relu']:
-                        raise NotImplementedError('hidden layers must use ReLU on the device path')
-                pending = dict(drop=None, relu=False)
+                    if pending['act'] is None:
+                        raise NotImplementedError('every hidden layer needs an activation on the device path: %s are '
+                                                  'offered' % ACT.OFFERED)
+                    acts.append(pending['act'])
+                pending = dict(drop=None, act=None)
                 linears.append(m)
-            elif isinstance(m, nn.ReLU):
-                pending['relu'] = True
+            elif pending is not None and pending['act'] is None and pending['drop'] is None and \
+                    ACT.code_of(m) is not None:
+                pending['act'] = ACT.code_of(m)
             elif isinstance(m, BDropout):
                 if pending is None:
                     raise NotImplementedError('input dropout is not offered on the device path')
@@ -470,11 +483,20 @@ class BSequential(nn.Sequential):
             elif isinstance(m, DiagGaussianDensity):
                 density = m
             else:
-                raise NotImplementedError('module %s (%s) is not offered on the device path' %
-                                          (name, type(m).__name__))
-        if pending is not None and (pending['drop'] is not None or pending['relu']):
+                raise NotImplementedError('module %s (%s) is not offered on the device path; hidden activations '
+                                          'offered: %s' % (name, type(m).__name__, ACT.OFFERED))
+        if pending is not None and (pending['drop'] is not None or pending['act'] is not None):
             raise NotImplementedError('the output layer must be a plain Linear')
-        return linears, drops, density
+        if len(set(acts)) > 1:
+            raise NotImplementedError('mixed activations inside one network are not offered on the device path: one of '
+                                      '%s for all hidden layers (policy and dynamics model choose independently)'
+                                      % ACT.OFFERED)
+        act = acts[0] if acts else ACT.RELU
+        if act != ACT.RELU and any(d is not None and d.unit_inv_keep() is not None for d in drops):
+            raise NotImplementedError('per-unit BDropout rates fold 1 / p_j into the layer in front, which is only valid '
+                                      'for ReLU (positively homogeneous); with Tanh / SiLU use a scalar rate (hidden '
+                                      'activations offered: %s)' % ACT.OFFERED)
+        return linears, drops, density, act
 
 
 def mlp(input_dims, output_dims, hidden_dims=[200, 200], nonlin=nn.ReLU, output_nonlin=None,

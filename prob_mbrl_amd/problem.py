@@ -261,7 +261,9 @@ def engine_from_problem(d, device='cuda:0', rows_per_wg_hint=0, shard=None, B_gl
                    precision=precision, pol_masks_per_step=pol_ps, dyn_masks_per_step=dyn_ps,
                    pol_angle_dims=[int(a) for a in np.asarray(d.get('pol_angle_dims', []))],
                    dyn_angle_dims=[int(a) for a in np.asarray(d.get('dyn_angle_dims', []))],
-                   dyn_components=int(d['dyn_gmm_n']) if 'dyn_gmm_n' in d else 0, mm_span=mm_span)
+                   dyn_components=int(d['dyn_gmm_n']) if 'dyn_gmm_n' in d else 0, mm_span=mm_span,
+                   # the hidden layers' activations (activations.RELU / TANH / SILU), where the problem names them
+                   pol_act=int(d['pol_act']) if 'pol_act' in d else 0, dyn_act=int(d['dyn_act']) if 'dyn_act' in d else 0)
     T = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device=dev)  # noqa: E731
 
     def rows(m):

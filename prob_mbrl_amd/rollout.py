@@ -108,12 +108,12 @@ def _reward_key(spec):
 def get_engine(B, D, U, H, pol_dims, pol_keep, dyn_dims, dyn_keep, spec, mm_states, mm_rewards,
                mm_groups, device, B_global=None, row_offset=0, zmm_per_step=False,
                max_log_std=(E.LOG_MAX_STD, E.LOG_MAX_STD), infer_ns=False, precision=None,
-               masks_per_step=(False, False), angle_dims=((), ()), gmm=(0, False), mm_span=None):
+               masks_per_step=(False, False), angle_dims=((), ()), gmm=(0, False), mm_span=None, acts=(0, 0)):
     precision = precision or E.get_precision()
     key = (str(device), B, D, U, H, tuple(pol_dims), tuple(pol_keep), tuple(dyn_dims),
            tuple(dyn_keep), _reward_key(spec), bool(mm_states), bool(mm_rewards), mm_groups,
            B_global, row_offset, zmm_per_step, max_log_std, bool(infer_ns), precision, tuple(masks_per_step),
-           tuple(angle_dims[0]), tuple(angle_dims[1]), tuple(gmm), tuple(mm_span) if mm_span else None)
+           tuple(angle_dims[0]), tuple(angle_dims[1]), tuple(gmm), tuple(mm_span) if mm_span else None, tuple(acts))
     eng = _ENGINES.get(key)
     if eng is None:
         if len(_ENGINES) > 16:
@@ -125,7 +125,8 @@ def get_engine(B, D, U, H, pol_dims, pol_keep, dyn_dims, dyn_keep, spec, mm_stat
                        max_log_std_dyn=max_log_std[1], infer_ns=infer_ns, precision=precision,
                        pol_masks_per_step=masks_per_step[0], dyn_masks_per_step=masks_per_step[1],
                        pol_angle_dims=angle_dims[0], dyn_angle_dims=angle_dims[1],
-                       dyn_components=gmm[0], gmm_exact_noise_grad=gmm[1], mm_span=mm_span)
+                       dyn_components=gmm[0], gmm_exact_noise_grad=gmm[1], mm_span=mm_span,
+                       pol_act=acts[0], dyn_act=acts[1])
         _ENGINES[key] = eng
     return eng
 
@@ -146,6 +147,8 @@ class Bundle:
                                       'with a learned reward head')
         plin, pdrop, pdens = policy.model.layer_spec()
         dlin, ddrop, ddens_inner = dynamics.model.layer_spec()
+        # the hidden layers' activations (activations.RELU / TANH / SILU): each network has its own
+        self.acts = (policy.model.activation(), dynamics.model.activation())
         ddens = dynamics.output_density
         self.gmm = isinstance(ddens, M.GaussianMixtureDensity)
         if not isinstance(pdens, M.DiagGaussianDensity) or ddens_inner is not None or \
@@ -278,7 +281,7 @@ class Bundle:
                                  masks_per_step=(bool(resample_policy), bool(resample_model)),
                                  angle_dims=self.angle_dims,
                                  gmm=(self.n_comp, bool(getattr(ddens, 'exact_noise_grad', False))),
-                                 mm_span=mm_span if (mm_states or mm_rewards) else None)
+                                 mm_span=mm_span if (mm_states or mm_rewards) else None, acts=self.acts)
         if mm_span and (mm_states or mm_rewards):
             # groups spread over the ranks of process_group: their per-step statistics cross devices
             if process_group is None:

@@ -115,6 +115,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
     N = Xn.shape[0]
     print('train_regressor >', 'Dataset size [%d]' % int(N))
     linears, drops, inner = model.model.layer_spec()
+    act = model.model.activation()      # the hidden layers' activation (activations.RELU / TANH / SILU)
     density = inner if inner is not None else model.output_density
     if density is None:
         raise NotImplementedError('a diagonal-Gaussian output density is required')
@@ -211,7 +212,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
             st = steps.get(M)
             if st is None:
                 st = steps[M] = E.BnnStep(dims, temps, rscale, dreg, M, N, reg_weight,
-                                          max_log_std=float(density.max_log_std), device=dev)
+                                          max_log_std=float(density.max_log_std), device=dev, act=act)
             idx_all = torch.as_tensor(np.stack(take).astype(np.int32), device=dev).contiguous()
             u = bv = None
             if _replay is not None:
@@ -245,7 +246,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
             st = steps[M] = E.BnnStep(dims, temps, rscale, dreg, M, N, reg_weight,
                                       max_log_std=float(density.max_log_std), device=dev,
                                       loss_kind='gmm' if mixture else 'nll',
-                                      n_components=density.n_components if mixture else 0)
+                                      n_components=density.n_components if mixture else 0, act=act)
         idx = device_indices(idx_np)
         if _replay is not None:     # tests: the reference's recorded draws of this step
             f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32), device=dev).reshape(-1)  # noqa: E731
