@@ -44,6 +44,9 @@ def parse(argv=None):
     ap.add_argument('--dyn_opt_iters', type=int, default=2000)
     ap.add_argument('--dyn_batch_size', type=int, default=100)
     ap.add_argument('--dyn_drop_rate', type=float, default=0.1)
+    ap.add_argument('--dyn_dropout', type=str, default='concrete', choices=['concrete', 'bernoulli'],
+                    help='dropout of the dynamics model: concrete (CDropout, rates learned from --dyn_drop_rate) or '
+                         'fixed-rate Bernoulli (BDropout at --dyn_drop_rate, the original Deep-PILCO model)')
     ap.add_argument('--dyn_components', type=int, default=1,
                     help='> 1: GaussianMixtureDensity dynamics head (examples/deep_pilco_mm.py:117-121)')
     ap.add_argument('--dyn_shape', type=lambda s: [int(v) for v in s.split(',')], default=[200, 200])
@@ -97,8 +100,10 @@ def main(argv=None):
     nonlin = module_of(args.nonlin)
     dyn = models.DynamicsModel(
         models.mlp(D + U, dynE, args.dyn_shape,
-                   dropout_layers=[models.CDropout(args.dyn_drop_rate * np.ones(h)) if args.dyn_drop_rate > 0
-                                   else None for h in args.dyn_shape], nonlin=nonlin),
+                   dropout_layers=[None if args.dyn_drop_rate <= 0 else
+                                   (models.BDropout(args.dyn_drop_rate) if args.dyn_dropout == 'bernoulli' else
+                                    models.CDropout(args.dyn_drop_rate * np.ones(h))) for h in args.dyn_shape],
+                   nonlin=nonlin),
         reward_func=reward_func, output_density=density).float()
     pol = models.Policy(
         models.mlp(D, 2 * U, args.pol_shape,

@@ -589,11 +589,20 @@ int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* call, void* workspa
  * dropout with a straight-through Bernoulli sample (models/modules.py:102-118,120-160), Gaussian
  * log-likelihood (losses.py:16-37) and the dropout regulariser (models/modules.py:30-35,88-93,
  * 234-274):   loss = -mean_rows lml + reg_weight * reg / N.
+ * Every hidden layer has a dropout kind: none, concrete (temperature[l] > 0) or fixed-rate
+ * Bernoulli (drop_kind[l] = PMBRL_DROP_BERNOULLI; BDropout.forward, models/modules.py:46-61:
+ * out = act(.) * m / p_j with m = (bvar < p_j); its regulariser on the Linear behind it is
+ * reg_scale_l (sum_j p_j sum_o W[o, j]^2 + sum_o b[o]^2), models/modules.py:30-35).
  * params / grad are flat in the module's parameter order: W0, b0, [logit_p0], W1, b1, [logit_p1],
- * ..., W_L, b_L  (logit_p_l, one per unit of hidden layer l, present iff temperature[l] > 0).
+ * ..., W_L, b_L  (logit_p_l, one per unit of hidden layer l, present iff the layer is CONCRETE:
+ * a Bernoulli layer has no parameter and no slot; pmbrl_bnn_plan_n_params counts accordingly).
  * u / bvar: the uniform noise of the concrete relaxation and the uniform variate of the Bernoulli
- * draw (hard = bvar < probs), per dropout layer a block [M][h_l], blocks concatenated in layer
- * order.  The optimiser step is pmbrl_clip_adam on the same flat vectors. */
+ * draw (hard = bvar < probs; Bernoulli layer: m = bvar < p_j), per dropout layer OF EITHER KIND a
+ * block [M][h_l], blocks concatenated in layer order; a Bernoulli layer's u block is not read (u
+ * may be NULL when no layer is concrete).  For plans whose dropout layers are all concrete both
+ * layouts are what they were.  The optimiser step is pmbrl_clip_adam on the same flat vectors. */
+#define PMBRL_DROP_BY_TEMPERATURE 0   /* none or concrete, as temperature[l] says */
+#define PMBRL_DROP_BERNOULLI 1        /* fixed keep probability bern_keep[l] (or per unit, below) */
 typedef struct {
   int32_t M;                  /* minibatch rows */
   int32_t N;                  /* dataset rows (the regulariser is divided by N) */
@@ -613,11 +622,19 @@ typedef struct {
                                           *    (2 n_out + 1) n_components + 1, see pmbrl_config.dyn_components */
   int32_t n_components;                  /* loss_kind 2 only */
   int32_t act;                           /* PMBRL_ACT_*: the hidden layers' activation */
+  int32_t drop_kind[PMBRL_MAX_LAYERS];   /* PMBRL_DROP_*; zero: today's behaviour.  Any other value: -2 */
+  float bern_keep[PMBRL_MAX_LAYERS];     /* Bernoulli layer l: keep probability p = 1 - rate in (0, 1], else -2;
+                                          * its reg_scale[l] is BDropout.regularizer_scale, temperature / drop_reg unused */
 } pmbrl_bnn_config;
 typedef struct pmbrl_bnn_plan pmbrl_bnn_plan;
 
 int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pmbrl_bnn_plan** out);
 void pmbrl_bnn_plan_destroy(pmbrl_bnn_plan* plan);
+/* Per-unit keep probabilities of Bernoulli layer `layer` (BDropout with a tensor rate): keep_h, n host values in
+ * (0, 1], copied into memory the plan owns (the call waits for the device).  n must be the layer's width; a layer
+ * that is not Bernoulli, a wrong n or a value out of range return -2.  Unlike the rollout plans, which fold 1 / p_j
+ * into ReLU weights, the step divides per unit: every activation is served. */
+int pmbrl_bnn_plan_set_unit_keep(pmbrl_bnn_plan* plan, int32_t layer, const float* keep_h, int32_t n);
 size_t pmbrl_bnn_plan_workspace_bytes(const pmbrl_bnn_plan* plan);
 int64_t pmbrl_bnn_plan_n_params(const pmbrl_bnn_plan* plan);
 int pmbrl_bnn_loss_grad(pmbrl_bnn_plan* plan, void* stream, void* workspace_d,
@@ -643,8 +660,9 @@ int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* plan, void* stream, void* workspace_d
  * torch.optim.Adam's step -- the reference clips nothing here) queued by ONE call, two launches an iteration:
  * forward + backward over the minibatch, then dW / db / regulariser / Adam / re-packed weights / loss in one kernel.
  * Minibatch i = rows idx_all_d[i * M .. (i + 1) * M).  Dropout noise: recorded draws u_d / bvar_d
- * ([n_steps][M * sum_h], the layout of pmbrl_bnn_loss_grad) or, when both are null, drawn inside the kernel (Philox
- * keyed by `seed`, counter = (row, unit, layer, first_step + i)).  exp_avg / exp_avg_sq / step_d: Adam's state (the
+ * ([n_steps][M * sum_h], the layout of pmbrl_bnn_loss_grad, sum_h over the dropout layers of either kind) or, when
+ * both are null, drawn inside the kernel (Philox keyed by `seed`, counter = (row, unit, layer, first_step + i); a
+ * Bernoulli layer draws its variate from the same stream).  exp_avg / exp_avg_sq / step_d: Adam's state (the
  * device-side step counter is advanced by every iteration).  loss_out_d [3]: the last iteration's loss, -E[lml],
  * reg; loss_hist_d (optional) [n_steps][3]: every iteration's.  Replaces eight launches and two torch.rand calls per
  * iteration (train_regressor.py:58-165 runs 2 000 of them per policy-search round). */

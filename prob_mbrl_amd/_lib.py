@@ -23,6 +23,7 @@ MAX_COMP = 8
 REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
+DROP_BY_TEMPERATURE, DROP_BERNOULLI = 0, 1      # pmbrl_bnn_config.drop_kind
 INFO_COUNT = 22
 INFO_TAIL_CALLS = 21    # PMBRL_INFO_TAIL_CALLS
 TIMER_COUNT = 8
@@ -43,7 +44,8 @@ class BnnConfig(C.Structure):
     _fields_ = [('M', C.c_int32), ('N', C.c_int32), ('net', MLP), ('max_log_std', C.c_float),
                 ('temperature', C.c_float * MAX_LAYERS), ('reg_scale', C.c_float * MAX_LAYERS),
                 ('drop_reg', C.c_float * MAX_LAYERS), ('reg_weight', C.c_float), ('loss_kind', C.c_int32),
-                ('n_components', C.c_int32), ('act', C.c_int32)]
+                ('n_components', C.c_int32), ('act', C.c_int32),
+                ('drop_kind', C.c_int32 * MAX_LAYERS), ('bern_keep', C.c_float * MAX_LAYERS)]
 
 
 class Reward(C.Structure):
@@ -97,7 +99,7 @@ EXPORTS = [
     'pmbrl_plan_set_timing', 'pmbrl_plan_read_timing', 'pmbrl_plan_set_prof', 'pmbrl_plan_set_replay', 'pmbrl_plan_replay_count',
     'pmbrl_mlp_workspace_bytes', 'pmbrl_mlp_forward', 'pmbrl_mlp_grad_input',
     'pmbrl_bnn_plan_create', 'pmbrl_bnn_plan_destroy', 'pmbrl_bnn_plan_workspace_bytes',
-    'pmbrl_bnn_plan_n_params', 'pmbrl_bnn_loss_grad', 'pmbrl_bnn_loss_grad_ex', 'pmbrl_bnn_train_steps',
+    'pmbrl_bnn_plan_n_params', 'pmbrl_bnn_plan_set_unit_keep', 'pmbrl_bnn_loss_grad', 'pmbrl_bnn_loss_grad_ex', 'pmbrl_bnn_train_steps',
     'pmbrl_comm_unique_id', 'pmbrl_comm_init', 'pmbrl_allreduce_sum', 'pmbrl_comm_count', 'pmbrl_comm_destroy',
     'pmbrl_plan_set_comm', 'pmbrl_plan_set_collective',
     'pmbrl_p2p_create', 'pmbrl_p2p_handle', 'pmbrl_p2p_open', 'pmbrl_p2p_allreduce_f32', 'pmbrl_p2p_allreduce_f64',
@@ -181,6 +183,8 @@ def load():
     lib.pmbrl_bnn_plan_workspace_bytes.argtypes = [vp]
     lib.pmbrl_bnn_plan_n_params.restype = C.c_int64
     lib.pmbrl_bnn_plan_n_params.argtypes = [vp]
+    lib.pmbrl_bnn_plan_set_unit_keep.restype = C.c_int
+    lib.pmbrl_bnn_plan_set_unit_keep.argtypes = [vp, i32, C.POINTER(f32), i32]
     lib.pmbrl_bnn_loss_grad.restype = C.c_int
     lib.pmbrl_bnn_loss_grad.argtypes = [vp] * 11
     lib.pmbrl_bnn_loss_grad_ex.restype = C.c_int

@@ -2,7 +2,8 @@
 `update_value_function` with the signature and semantics of the function the reference keeps in
 its example script (examples/deep_pilco_no_mm_with_value.py:14-66), on the device:
 
-    V0      = V(states[0])   in training mode (concrete dropout with straight-through samples)
+    V0      = V(states[0])   in training mode (concrete dropout with straight-through samples, or fixed-rate
+                             Bernoulli dropout)
     targets = sum_{j<H} discount(j) r_j + discount(H) V_tgt(states[H])          (constants)
     loss    = mse(V0, targets) + reg_weight * V.regularization_loss()
 
@@ -16,16 +17,17 @@ import torch
 
 from . import engine as E
 from .algorithms import _adam_flat_state, _sync_adam_state
-from .models import CDropout
-from .train_regressor import flat_module_parameters
+from .models import BDropout, CDropout
+from .train_regressor import bernoulli_keep_of, flat_module_parameters, stored_bernoulli_mask
 
 _STEPS = {}
 
 
 def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_target=None, reg_weight=1e-4,
                           resample=False, polyak_averaging=0.005, _bernoulli=None):
-    """`_bernoulli` (tests): the {0,1} outcomes of the concrete-dropout draws, in the order the
-    reference makes them (V0's layers, then V_tgt's), instead of fresh ones."""
+    """`_bernoulli` (tests): the {0,1} outcomes of the dropout layers' Bernoulli draws (concrete layers: the
+    straight-through samples; BDropout layers: the masks), in the order the reference makes them (V0's layers, then
+    V_tgt's), instead of fresh ones."""
     V_tgt = V if V_target is None else V_target
     V.train()
     dev = V.mx.device
@@ -38,7 +40,7 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     if inner is not None or linears[-1].out_features != 1:
         raise NotImplementedError('the device path fits a critic with one plain output')
     draws = list(_bernoulli) if _bernoulli is not None else None
-    n_drop = sum(1 for d in drops if isinstance(d, CDropout))
+    n_drop = sum(1 for d in drops if isinstance(d, BDropout))
     returns = torch.stack([r * discount(j) for j, r in enumerate(rewards[:H])]).sum(0).detach()
     x0 = states[0].detach().to(torch.float32)
     B = x0.shape[0]
@@ -47,7 +49,7 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     #      First: a stand-alone forward re-points the Linear parameters at ITS flat buffer, the fit below
     #      then gathers all parameters (with the dropout logits) into its own.
     if draws is not None:
-        for k, dr in enumerate([d for d in V_tgt.model._modules.values() if isinstance(d, CDropout)]):
+        for k, dr in enumerate([d for d in V_tgt.model._modules.values() if isinstance(d, BDropout)]):
             dr._forced_sample = torch.as_tensor(draws[n_drop + k], dtype=torch.float32, device=dev)
     try:
         VH = V_tgt(states[H].detach(), resample=resample)
@@ -58,13 +60,17 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     targets = (returns + discount(H) * VH.detach()).to(torch.float32).reshape(B, 1)
 
     # ---- parameters in module order, the last layer padded with a zero log-std row for the kernel
-    params, temps, rscale, dreg = [], [], [], []
+    params, temps, rscale, dreg, bern = [], [], [], [], []
     for l, lin in enumerate(linears):
         params += [lin.weight, lin.bias]
         if l < len(linears) - 1:
             dr = drops[l]
+            bern.append(None)
             if dr is None:
                 temps.append(0.0); rscale.append(0.0); dreg.append(0.0)
+            elif type(dr) is BDropout:
+                temps.append(0.0); rscale.append(float(dr.regularizer_scale)); dreg.append(0.0)
+                bern[-1] = bernoulli_keep_of(dr)
             elif isinstance(dr, CDropout):
                 if dr.logit_p.numel() != lin.out_features:
                     dr.logit_p.data = dr.logit_p.data.reshape(-1).expand(lin.out_features).clone()
@@ -72,7 +78,8 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
                 temps.append(float(dr.temp)); rscale.append(float(dr.regularizer_scale))
                 dreg.append(float(dr.dropout_regularizer))
             else:
-                raise NotImplementedError('the critic fit is offered for concrete dropout (CDropout) layers')
+                raise NotImplementedError('the critic fit is offered for concrete (CDropout) and fixed-rate Bernoulli '
+                                          '(BDropout) dropout layers')
     flat = flat_module_parameters(params, V)
     cache = _adam_flat_state(opt, params, flat)
     if cache is None:
@@ -85,9 +92,20 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     # ---- V0's noise: the stored uniform noise (redrawn if it cannot be reused), fresh Bernoulli draws
     us, bvars = [], []
     for l, dr in enumerate(drops):
-        if not isinstance(dr, CDropout):
+        if not isinstance(dr, BDropout):
             continue
         h = linears[l].out_features
+        if type(dr) is BDropout:
+            # the mask itself (mask = bvar < p): recorded, fresh, or the stored one (models/modules.py:46-61)
+            us.append(torch.zeros(B * h, device=dev))
+            if draws is not None:
+                m = torch.as_tensor(draws.pop(0), dtype=torch.float32, device=dev).reshape(B, h)
+                bvars.append((1.0 - m).reshape(-1))
+            elif resample and dr.noise.dim() == 2 and dr.noise.shape[1] == h and dr.noise.shape[0] >= B:
+                bvars.append(torch.rand(B * h, device=dev))
+            else:
+                bvars.append((1.0 - stored_bernoulli_mask(dr, B, h)).reshape(-1))
+            continue
         n = dr.noise
         if resample:
             n = torch.rand(B, h, device=dev)
@@ -108,14 +126,15 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     Xn = ((x0 - V.mx) * V.iSx).contiguous()
     Yn = ((targets - V.my) / V.Sy).contiguous()
     rw_eff = reg_weight * B / (Sy * Sy)
-    key = (id(V), B, tuple(dims), tuple(temps), rw_eff, act)
+    key = (id(V), B, tuple(dims), tuple(temps), rw_eff, act,
+           tuple(None if k is None else (k if isinstance(k, float) else tuple(k.tolist())) for k in bern))
     st = _STEPS.get(key)
     if st is None:
         if len(_STEPS) > 8:
             _STEPS.clear()
         # the step computes  mse_n + (rw'/N) reg ; we want  Sy^2 mse_n + reg_weight reg  -> rw'/N = reg_weight / Sy^2
         st = _STEPS[key] = E.BnnStep(dims, temps, rscale, dreg, B, B, reg_weight=rw_eff, device=dev,
-                                     loss_kind='mse', act=act)
+                                     loss_kind='mse', act=act, bernoulli_keep=bern)
     idx = torch.arange(B, dtype=torch.int32, device=dev)
     gpad, loss = st.loss_grad(Xn, Yn, idx, padded, u, bvar)
     grad = torch.cat([gpad[:-(2 * K + 2)], gpad[-(2 * K + 2):-(K + 2)], gpad[-2:-1]]) * (Sy * Sy)

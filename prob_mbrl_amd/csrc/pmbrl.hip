@@ -2864,7 +2864,29 @@ struct pmbrl_bnn_plan {
   size_t off_part_lp, off_part_loss, off_part, off_reg_part, ws_bytes, lds;
   int part_stride, n_dw_blocks, dw_wave_first[PM_DW_NW + 1];
   DwBlock* dw_blocks_d;
+  // fixed-rate Bernoulli layers (has_drop[l] == 2): noise_off / noise_h count the dropout layers of EITHER kind (the
+  // u / bvar blocks), lp_off / sum_h the concrete ones (the logit gradients); keep_d[l]: the units' keep probabilities
+  int noise_off[PM_MAXL], noise_h, any_bern;
+  float* keep_d[PM_MAXL];
+  float* keep_all_d;
 };
+
+// the instances of a plan: those without a Bernoulli layer are the ones they were
+static const void* bnn_fwd_bwd_fn(const pmbrl_bnn_plan* p) {
+  if (p->any_bern)
+    return p->cfg.act ? reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<true, true>)
+                      : reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<false, true>);
+  return p->cfg.act ? reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<true>) : reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<false>);
+}
+static void bnn_launch_fwd_bwd(const pmbrl_bnn_plan* p, hipStream_t s, const BnnArgs& A) {
+  if (p->any_bern) {
+    if (A.act) hipLaunchKernelGGL((pm_bnn_fwd_bwd<true, true>), dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+    else hipLaunchKernelGGL((pm_bnn_fwd_bwd<false, true>), dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+  } else {
+    if (A.act) hipLaunchKernelGGL(pm_bnn_fwd_bwd<true>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+    else hipLaunchKernelGGL(pm_bnn_fwd_bwd<false>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+  }
+}
 
 extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pmbrl_bnn_plan** out) {
   if (!cfg || !out) return fail(-1, "null argument");
@@ -2883,6 +2905,18 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->nl = m.n_layers;
   int maxnt = 1, po = 0;
   p->sum_h = 0;
+  p->noise_h = 0;
+  p->any_bern = 0;
+  for (int l = 0; l < p->nl - 1; ++l) {
+    if (cfg->drop_kind[l] != PMBRL_DROP_BY_TEMPERATURE && cfg->drop_kind[l] != PMBRL_DROP_BERNOULLI) {
+      delete p;
+      return fail(-2, "bnn: unknown dropout kind (0: by temperature, PMBRL_DROP_BERNOULLI are offered)");
+    }
+    if (cfg->drop_kind[l] == PMBRL_DROP_BERNOULLI && !(cfg->bern_keep[l] > 0.f && cfg->bern_keep[l] <= 1.f)) {
+      delete p;
+      return fail(-2, "bnn: the keep probability of a Bernoulli layer must lie in (0, 1]");
+    }
+  }
   for (int i = 0; i <= p->nl; ++i) {
     if (m.dims[i] < 1 || m.dims[i] > 16 * 64) { delete p; return fail(-2, "bnn: layer width out of range"); }
     p->dim[i] = m.dims[i];
@@ -2892,10 +2926,17 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   for (int l = 0; l < p->nl; ++l) {
     p->w_off[l] = po; po += p->dim[l + 1] * p->dim[l];
     p->b_off[l] = po; po += p->dim[l + 1];
-    p->has_drop[l] = (l < p->nl - 1 && cfg->temperature[l] > 0.f) ? 1 : 0;
+    p->has_drop[l] = 0;
+    if (l < p->nl - 1) {
+      if (cfg->drop_kind[l] == PMBRL_DROP_BERNOULLI) p->has_drop[l] = 2;
+      else if (cfg->temperature[l] > 0.f) p->has_drop[l] = 1;
+    }
     p->lp_poff[l] = po;
     p->lp_off[l] = p->sum_h;
-    if (p->has_drop[l]) { po += p->dim[l + 1]; p->sum_h += p->dim[l + 1]; }
+    p->noise_off[l] = p->noise_h;
+    if (p->has_drop[l] == 1) { po += p->dim[l + 1]; p->sum_h += p->dim[l + 1]; }
+    if (p->has_drop[l]) p->noise_h += p->dim[l + 1];
+    if (p->has_drop[l] == 2) p->any_bern = 1;
   }
   p->n_params = po;
   p->LD = maxnt * 16 + 8;
@@ -2926,9 +2967,22 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->n_dw_blocks = build_dw_blocks(p->nl, p->nt, blocks, p->dw_wave_first);
   HIPCHK(hipMalloc(&p->dw_blocks_d, blocks.size() * sizeof(DwBlock)));
   HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
-  HIPCHK(hipFuncSetAttribute(cfg->act ? reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<true>)
-                                   : reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<false>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
+  if (p->any_bern) {
+    // the Bernoulli layers' keep probabilities, one per unit (a scalar rate repeated; the padding of the last tile keeps 1)
+    std::vector<float> keep;
+    size_t koff[PM_MAXL] = {0};
+    for (int l = 0; l < p->nl - 1; ++l)
+      if (p->has_drop[l] == 2) {
+        koff[l] = keep.size();
+        keep.resize(keep.size() + (size_t)p->nt[l + 1] * 16, 1.f);
+        for (int j = 0; j < p->dim[l + 1]; ++j) keep[koff[l] + j] = cfg->bern_keep[l];
+      }
+    HIPCHK(hipMalloc(&p->keep_all_d, keep.size() * sizeof(float)));
+    HIPCHK(hipMemcpy(p->keep_all_d, keep.data(), keep.size() * sizeof(float), hipMemcpyHostToDevice));
+    for (int l = 0; l < p->nl - 1; ++l)
+      if (p->has_drop[l] == 2) p->keep_d[l] = p->keep_all_d + koff[l];
+  }
+  HIPCHK(hipFuncSetAttribute(bnn_fwd_bwd_fn(p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
   *out = p;
   return 0;
 }
@@ -2936,7 +2990,22 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
 extern "C" void pmbrl_bnn_plan_destroy(pmbrl_bnn_plan* p) {
   if (!p) return;
   if (p->dw_blocks_d) (void)hipFree(p->dw_blocks_d);
+  if (p->keep_all_d) (void)hipFree(p->keep_all_d);
   delete p;
+}
+
+extern "C" int pmbrl_bnn_plan_set_unit_keep(pmbrl_bnn_plan* p, int32_t layer, const float* keep_h, int32_t n) {
+  if (!p || !keep_h) return fail(-1, "null argument");
+  if (layer < 0 || layer >= p->nl - 1 || p->has_drop[layer] != 2)
+    return fail(-2, "pmbrl_bnn_plan_set_unit_keep: not a Bernoulli layer of this plan");
+  if (n != p->dim[layer + 1]) return fail(-2, "pmbrl_bnn_plan_set_unit_keep: n must be the layer's width");
+  for (int j = 0; j < n; ++j)
+    if (!(keep_h[j] > 0.f && keep_h[j] <= 1.f))
+      return fail(-2, "pmbrl_bnn_plan_set_unit_keep: keep probabilities must lie in (0, 1]");
+  HIPCHK(hipSetDevice(p->device));
+  HIPCHK(hipDeviceSynchronize());      // (a step of this plan may still be reading the old values)
+  HIPCHK(hipMemcpy(p->keep_d[layer], keep_h, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
+  return 0;
 }
 extern "C" size_t pmbrl_bnn_plan_workspace_bytes(const pmbrl_bnn_plan* p) { return p ? p->ws_bytes : 0; }
 extern "C" int64_t pmbrl_bnn_plan_n_params(const pmbrl_bnn_plan* p) { return p ? p->n_params : 0; }
@@ -2963,7 +3032,7 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
     return fail(-1, "null argument");
   if (!(terms & 3)) return fail(-1, "bnn: terms must select the likelihood (1), the regulariser (2) or both");
   const bool lik = (terms & 1) != 0, regt = (terms & 2) != 0;
-  if (p->sum_h > 0 && lik && (!u_d || !bvar_d)) return fail(-1, "bnn: dropout layers need u and bvar");
+  if (lik && ((p->sum_h > 0 && !u_d) || (p->noise_h > 0 && !bvar_d))) return fail(-1, "bnn: dropout layers need u and bvar");
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(p->device));
   char* ws = static_cast<char*>(workspace_d);
@@ -2994,11 +3063,14 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
     A.actT[l] = reinterpret_cast<float*>(ws + p->off_actT[l]);
     A.gT[l] = reinterpret_cast<float*>(ws + p->off_gT[l]);
     A.lp_off[l] = p->lp_off[l];
-    if (p->has_drop[l]) {
+    if (p->has_drop[l] == 1) {
       A.logit_p[l] = params_flat_d + p->lp_poff[l];
-      A.u[l] = u_d + (size_t)p->cfg.M * p->lp_off[l];
-      A.bvar[l] = bvar_d + (size_t)p->cfg.M * p->lp_off[l];
+      A.u[l] = u_d + (size_t)p->cfg.M * p->noise_off[l];
+      A.bvar[l] = bvar_d + (size_t)p->cfg.M * p->noise_off[l];
       A.inv_temp[l] = 1.f / p->cfg.temperature[l];
+    } else if (p->has_drop[l] == 2) {
+      A.keep[l] = p->keep_d[l];
+      A.bvar[l] = bvar_d + (size_t)p->cfg.M * p->noise_off[l];
     }
   }
   A.X = Xn_d; A.Y = Yn_d; A.idx = idx_d;
@@ -3012,8 +3084,7 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
     HIPCHK(hipMemsetAsync(grad_flat_d, 0, (size_t)p->n_params * sizeof(float), s));
   } else {
   hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  if (A.act) hipLaunchKernelGGL(pm_bnn_fwd_bwd<true>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-  else hipLaunchKernelGGL(pm_bnn_fwd_bwd<false>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+  bnn_launch_fwd_bwd(p, s, A);
   // dW / db of every layer: the policy-gradient GEMM over the same stash layout (one 16-row chunk per split)
   DwArgs W;
   memset(&W, 0, sizeof(W));
@@ -3038,6 +3109,7 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
   for (int l = 0; l < p->nl; ++l) {
     Fa.w_off[l] = p->w_off[l]; Fa.b_off[l] = p->b_off[l]; Fa.lp_poff[l] = p->lp_poff[l]; Fa.lp_off[l] = p->lp_off[l];
     Fa.has_drop[l] = p->has_drop[l];
+    Fa.keep[l] = p->keep_d[l];
     Fa.reg_scale[l] = p->cfg.reg_scale[l]; Fa.drop_reg[l] = p->cfg.drop_reg[l];
   }
   Fa.reg_weight = regt ? p->cfg.reg_weight : 0.f; Fa.inv_M = A.inv_M;
@@ -3048,7 +3120,8 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
   for (int l = 0; l < p->nl - 1; ++l)
     if (p->has_drop[l]) nfb += (p->dim[l + 1] + PM_BNN_CG - 1) / PM_BNN_CG;
   if (nfb < 1) nfb = 1;
-  hipLaunchKernelGGL(pm_bnn_finish, dim3(nfb), dim3(256), 0, s, Fa);
+  if (p->any_bern) hipLaunchKernelGGL(pm_bnn_finish<true>, dim3(nfb), dim3(256), 0, s, Fa);
+  else hipLaunchKernelGGL(pm_bnn_finish<false>, dim3(nfb), dim3(256), 0, s, Fa);
   hipLaunchKernelGGL(pm_bnn_loss, dim3(1), dim3(64), 0, s, Fa, nfb);
   HIPCHK(hipGetLastError());
   return 0;
@@ -3099,12 +3172,15 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
     A.lp_off[l] = T.lp_off[l] = p->lp_off[l];
     T.w_off[l] = p->w_off[l]; T.b_off[l] = p->b_off[l]; T.lp_poff[l] = p->lp_poff[l];
     T.has_drop[l] = p->has_drop[l];
+    T.keep[l] = p->keep_d[l];
     T.reg_scale[l] = p->cfg.reg_scale[l]; T.drop_reg[l] = p->cfg.drop_reg[l];
     T.unit0[l] = units;
     units += p->nt[l];
-    if (p->has_drop[l]) {
+    if (p->has_drop[l] == 1) {
       A.logit_p[l] = params_flat_d + p->lp_poff[l];
       A.inv_temp[l] = 1.f / p->cfg.temperature[l];
+    } else if (p->has_drop[l] == 2) {
+      A.keep[l] = p->keep_d[l];
     }
   }
   T.unit0[p->nl] = units;
@@ -3127,19 +3203,19 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
   A.rng_k0 = (unsigned)seed; A.rng_k1 = (unsigned)(seed >> 32);
   HIPCHK(hipMemsetAsync(T.counter, 0, sizeof(unsigned), s));
   hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  const size_t noise = (size_t)p->cfg.M * p->sum_h;
+  const size_t noise = (size_t)p->cfg.M * p->noise_h;
   for (int i = 0; i < n_steps; ++i) {
     A.idx = idx_all_d + (size_t)i * p->cfg.M;
     A.rng_step = (unsigned)(first_step + (uint64_t)i);
     for (int l = 0; l < p->nl; ++l)
       if (p->has_drop[l] && u_d) {
-        A.u[l] = u_d + (size_t)i * noise + (size_t)p->cfg.M * p->lp_off[l];
-        A.bvar[l] = bvar_d + (size_t)i * noise + (size_t)p->cfg.M * p->lp_off[l];
+        A.u[l] = u_d + (size_t)i * noise + (size_t)p->cfg.M * p->noise_off[l];
+        A.bvar[l] = bvar_d + (size_t)i * noise + (size_t)p->cfg.M * p->noise_off[l];
       }
     T.loss_out = loss_hist_d ? loss_hist_d + (size_t)3 * i : loss_out_d;
-    if (A.act) hipLaunchKernelGGL(pm_bnn_fwd_bwd<true>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-    else hipLaunchKernelGGL(pm_bnn_fwd_bwd<false>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-    hipLaunchKernelGGL(pm_bnn_tail, dim3(units), dim3(PM_BNT_NT), 0, s, T);
+    bnn_launch_fwd_bwd(p, s, A);
+    if (p->any_bern) hipLaunchKernelGGL(pm_bnn_tail<true>, dim3(units), dim3(PM_BNT_NT), 0, s, T);
+    else hipLaunchKernelGGL(pm_bnn_tail<false>, dim3(units), dim3(PM_BNT_NT), 0, s, T);
   }
   if (loss_hist_d)
     HIPCHK(hipMemcpyAsync(loss_out_d, loss_hist_d + (size_t)3 * (n_steps - 1), 3 * sizeof(float), hipMemcpyDeviceToDevice, s));

@@ -6,6 +6,8 @@
 //   DiagGaussianDensity.forward (mean, clamped log-std)          models/densities.py:87-121
 //   losses.gaussian_log_likelihood                               losses.py:16-37
 //   CDropout / BSequential regularisers                          models/modules.py:88-93,30-35,234-274
+//   BDropout.forward (fixed-rate Bernoulli dropout, x * m / p)   models/modules.py:46-61
+//     and its regulariser on the Linear behind it                models/modules.py:30-35
 //
 // pm_bnn_fwd_bwd: a workgroup (PM_NW waves) owns 16 minibatch rows; all layer inputs and the
 // dropout derivative terms stay in LDS between the forward and the backward pass; the
@@ -43,6 +45,9 @@ struct BnnArgs {
   unsigned rng_k0, rng_k1, rng_step;
   long long* prof;                 // debugging: cycle stamps of workgroup 0 (nullptr: none)
   int act;                         // PMBRL_ACT_* of the hidden layers (pm_bnn_fwd_bwd<true> when not ReLU)
+  // fixed-rate Bernoulli dropout behind hidden layer l (pm_bnn_fwd_bwd<., true>): the units' keep probabilities
+  // [nt[l+1] * 16] (a scalar rate is stored once per unit), nullptr for a layer of another kind.  m = bvar < p_j.
+  const float* keep[PM_MAXL];
 };
 
 // 1 / x to an ulp or two: v_rcp_f32 and one Newton step
@@ -54,12 +59,15 @@ __device__ __forceinline__ float pm_fast_rcp(float d) {
 // hidden layer forward: out = relu(acc + b) * hard ;  q = relu(.) * d mask / d logit_p
 // ACT: out = act(acc + b) * hard, q = act(.) * d mask / d logit_p, and d_out = act'(acc + b) * hard for the backward pass
 // (pm_act; act = PMBRL_ACT_TANH / PMBRL_ACT_SILU).  The ReLU instance is what it was.
-template <bool ACT = false>
+// BERN (plans with a Bernoulli layer; keep != nullptr marks one): m = bvar < p_j, out = act(acc + b) * m / p_j -- divided as
+// BDropout.forward divides, per unit -- q = 0 (there is no logit), d_out = act'(acc + b) * m / p_j.
+template <bool ACT = false, bool BERN = false>
 struct EpiBnnFwd {
   int act;
   float* d_out;
   const float* bias;
   const float* logit_p;
+  const float* keep;
   const float *u, *bvar;
   float inv_temp;
   float *h_out, *q_out, *stash;
@@ -75,6 +83,13 @@ struct EpiBnnFwd {
     if (rng && logit_p) {      // 24-bit uniforms in [0, 1), what torch.rand gives a float tensor
       pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer, rstep, rk0, rk1, ru);
       pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer | 0x100u, rstep, rk0, rk1, rv);
+    }
+    f32x4 kp = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (BERN) {
+      if (keep) {
+        kp = ldg4(keep + f0);
+        if (rng) pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer | 0x100u, rstep, rk0, rk1, rv);
+      }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -99,6 +114,14 @@ struct EpiBnnFwd {
         qv = v * pr * (1.f - pr) * inv_temp;
         if (!hard) dv = 0.f;
       }
+      if constexpr (BERN) {
+        if (keep && f < width && lrow < nvalid) {
+          const size_t o = (size_t)(row0 + lrow) * width + f;
+          const bool hard = (rng ? (float)(rv[r] >> 8) * (1.0f / 16777216.0f) : bvar[o]) < kp[r];
+          hv = hard ? v / kp[r] : 0.f;
+          dv = hard ? dv / kp[r] : 0.f;
+        }
+      }
       if (f >= width || lrow >= nvalid) { hv = 0.f; qv = 0.f; dv = 0.f; }
       h[r] = hv;
       q[r] = qv;
@@ -115,9 +138,12 @@ struct EpiBnnFwd {
 // backward through hidden layer l-1's output: acc = dL/d out ; gq = acc * q (dropout-logit term),
 // g_pre = out > 0 ? acc : 0
 // (ACT: g_pre = acc * d, h_in = the d_out of EpiBnnFwd<true>)
-template <bool ACT = false>
+// BERN, behind a Bernoulli layer (keep != nullptr): out = relu(.) m / p_j, so g_pre = out > 0 ? acc / p_j : 0 (the ACT
+// instances carry m / p_j in d already)
+template <bool ACT = false, bool BERN = false>
 struct EpiBnnBwd {
   const float *h_in, *q_in;   // out and q of that layer
+  const float* keep;
   float *g_out, *gq_out, *stash;
   int ld, lane;
   __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
@@ -126,9 +152,14 @@ struct EpiBnnBwd {
     const f32x4 h = *reinterpret_cast<const f32x4*>(h_in + lrow * ld + f0);
     const f32x4 q = *reinterpret_cast<const f32x4*>(q_in + lrow * ld + f0);
     f32x4 gp, gq;
+    f32x4 kp = {1.f, 1.f, 1.f, 1.f};
+    if constexpr (BERN && !ACT) {
+      if (keep) kp = ldg4(keep + f0);
+    }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if constexpr (ACT) gp[r] = h[r] != 0.f ? acc[r] * h[r] : 0.f;
+      else if constexpr (BERN) gp[r] = h[r] > 0.f ? (keep ? acc[r] / kp[r] : acc[r]) : 0.f;
       else gp[r] = h[r] > 0.f ? acc[r] : 0.f;
       gq[r] = acc[r] * q[r];
     }
@@ -148,7 +179,7 @@ __host__ __device__ inline size_t pm_bnn_lds_floats(int nl, int LD, int act = 0)
   return ((size_t)nl + (nl - 1) + 3 + (act ? 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256 + PM_NT;
 }
 
-template <bool ACT = false>
+template <bool ACT = false, bool BERN = false>
 __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 16;
@@ -186,7 +217,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   BNN_STAMP(1);
   // ---- forward
   for (int l = 0; l < nl - 1; ++l) {
-    EpiBnnFwd<ACT> e{A.act, ACT ? dbuf(l) : nullptr, A.bias[l], A.logit_p[l], A.u[l], A.bvar[l], A.inv_temp[l],
+    EpiBnnFwd<ACT, BERN> e{A.act, ACT ? dbuf(l) : nullptr, A.bias[l], A.logit_p[l], BERN ? A.keep[l] : nullptr, A.u[l], A.bvar[l], A.inv_temp[l],
                 H + (size_t)(l + 1) * R * LD, Q + (size_t)l * R * LD,
                 A.actT[l + 1] + (size_t)wg * A.nt[l + 1] * 16 * 16, LD, row0, nvalid, A.dim[l + 1], lane,
                 A.rng, A.rng_k0, A.rng_k1, A.rng_step, (unsigned)l};
@@ -329,7 +360,8 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   float* Gin = G0;
   float* Gout = G1;
   for (int l = nl - 1; l >= 1; --l) {
-    EpiBnnBwd<ACT> e{ACT ? dbuf(l - 1) : H + (size_t)l * R * LD, Q + (size_t)(l - 1) * R * LD, Gout, GQ,
+    EpiBnnBwd<ACT, BERN> e{ACT ? dbuf(l - 1) : H + (size_t)l * R * LD, Q + (size_t)(l - 1) * R * LD,
+                BERN ? A.keep[l - 1] : nullptr, Gout, GQ,
                 A.gT[l - 1] + (size_t)wg * A.nt[l] * 16 * 16, LD, lane};
     gemm_tiles<1>(A.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
     __syncthreads();
@@ -355,7 +387,8 @@ struct BnnFinishArgs {
   int nl, nwg, sum_h, N;
   int dim[PM_MAXL + 1];
   int w_off[PM_MAXL], b_off[PM_MAXL], lp_poff[PM_MAXL], lp_off[PM_MAXL];
-  int has_drop[PM_MAXL];
+  int has_drop[PM_MAXL];           // 0 none, 1 concrete, 2 Bernoulli (pm_bnn_finish<true>)
+  const float* keep[PM_MAXL];      // Bernoulli layer l: the units' keep probabilities
   float reg_scale[PM_MAXL], drop_reg[PM_MAXL];
   float reg_weight, inv_M;
   int reg_only;      // gradient / loss of the regulariser alone (the likelihood partials are not read)
@@ -372,7 +405,10 @@ struct BnnFinishArgs {
 // adds the weight-decay gradient in place and accumulates the column sums of squares; the
 // slices meet in LDS, slice 0 finishes the unit's logit gradient and regulariser terms.  The
 // group 0 of a layer also handles that layer's biases.
+// BERN: a Bernoulli layer's p_j is its fixed keep probability; reg_scale_l (sum_j p_j sum_o W[o, j]^2 + sum_o b[o]^2)
+// (models/modules.py:30-35), gradient into dW / db, no logit.
 #define PM_BNN_CG 32
+template <bool BERN = false>
 __global__ __launch_bounds__(256) void pm_bnn_finish(const BnnFinishArgs A) {
   __shared__ float s2s[8][PM_BNN_CG + 1];
   __shared__ double sm[256];
@@ -394,8 +430,10 @@ __global__ __launch_bounds__(256) void pm_bnn_finish(const BnnFinishArgs A) {
     const float rs = A.reg_scale[l], dr = A.drop_reg[l];
     const int k = grp * PM_BNN_CG + col;
     float p = 0.f, s2 = 0.f;
+    bool bern = false;
+    if constexpr (BERN) bern = A.has_drop[l] == 2;
     if (k < h) {
-      p = sigmoidf(A.params[A.lp_poff[l] + k]);
+      p = bern ? A.keep[l][k] : sigmoidf(A.params[A.lp_poff[l] + k]);
       const float cw = 2.f * c * rs * p;
       for (int o = sl; o < O; o += 8) {
         const float w = W[(size_t)o * h + k];
@@ -405,7 +443,14 @@ __global__ __launch_bounds__(256) void pm_bnn_finish(const BnnFinishArgs A) {
     }
     s2s[sl][col] = s2;
     __syncthreads();
-    if (sl == 0 && k < h) {
+    if (bern) {
+      if (sl == 0 && k < h) {
+        float tot = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) tot += s2s[q][col];
+        reg += (double)(rs * p * tot);
+      }
+    } else if (sl == 0 && k < h) {
       float tot = 0.f;
 #pragma unroll
       for (int q = 0; q < 8; ++q) tot += s2s[q][col];
@@ -467,7 +512,8 @@ struct BnnTailArgs {
   int nl, n_chunks, sum_h, N;
   int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
   int w_off[PM_MAXL], b_off[PM_MAXL], lp_poff[PM_MAXL], lp_off[PM_MAXL];
-  int has_drop[PM_MAXL];            // dropout behind hidden layer l (the output of Linear l)
+  int has_drop[PM_MAXL];            // dropout behind hidden layer l (the output of Linear l): 1 concrete, 2 Bernoulli
+  const float* keep[PM_MAXL];       // Bernoulli layer l: the units' keep probabilities (pm_bnn_tail<true>)
   int unit0[PM_MAXL + 1];           // first workgroup of layer l (prefix sums of nt[l])
   float reg_scale[PM_MAXL], drop_reg[PM_MAXL];
   float reg_weight, inv_M;
@@ -498,6 +544,7 @@ struct BnnAdam {
   }
 };
 
+template <bool BERN = false>
 __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
   __shared__ float s_s2[PM_BNT_NW][16];
   __shared__ double s_reg[PM_BNT_NT];
@@ -527,7 +574,9 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
   const float rs = drop ? A.reg_scale[q] : 0.f, dr = drop ? A.drop_reg[q] : 0.f;
   const int k = kt * 16 + c16;      // this lane's input column
   float p_k = 0.f;
-  if (drop && k < K) p_k = sigmoidf(A.params[A.lp_poff[q] + k]);
+  bool bern = false;      // (BERN) fixed keep probabilities: the weight decay and its loss term, no logit to update
+  if constexpr (BERN) bern = drop && A.has_drop[q] == 2;
+  if (drop && k < K) p_k = bern ? A.keep[q][k] : sigmoidf(A.params[A.lp_poff[q] + k]);
   const float cw = 2.f * c * rs * p_k;
   double reg = 0.0;
   float s2 = 0.f;
@@ -635,7 +684,14 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
   s2 += __shfl_xor(s2, 32);
   if (g == 0) s_s2[wid][c16] = s2;
   __syncthreads();
-  if (drop && wid == 0 && g == 0 && k < K) {
+  if (bern) {
+    if (wid == 0 && g == 0 && k < K) {
+      float tot = 0.f;
+#pragma unroll
+      for (int w = 0; w < PM_BNT_NW; ++w) tot += s_s2[w][c16];
+      reg += (double)(rs * p_k * tot);
+    }
+  } else if (drop && wid == 0 && g == 0 && k < K) {
     float tot = 0.f;
 #pragma unroll
     for (int w = 0; w < PM_BNT_NW; ++w) tot += s_s2[w][c16];

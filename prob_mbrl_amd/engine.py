@@ -204,10 +204,14 @@ def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=Non
 class BnnStep:
     """Loss + gradient of one BNN training minibatch on the device (pmbrl_bnn_loss_grad;
     utils/train_regressor.py:113-131).  Flat parameter / gradient order = the module's:
-    W0, b0, [logit_p0], W1, b1, [logit_p1], ..., W_L, b_L."""
+    W0, b0, [logit_p0], W1, b1, [logit_p1], ..., W_L, b_L  (logit_p_l for concrete layers only).
+    bernoulli_keep: one entry per hidden layer -- None (the layer is what temperature[l] says), a float or a tensor of
+    the layer's width: fixed-rate Bernoulli dropout with these keep probabilities (BDropout, models/modules.py:14-61;
+    reg_scale[l] is then its regularizer_scale buffer).  u / bvar hold one [M, h_l] block per dropout layer of either
+    kind; a Bernoulli layer's mask is bvar < p, its u block is not read."""
 
     def __init__(self, dims, temperature, reg_scale, drop_reg, M, N, reg_weight=1.0,
-                 max_log_std=LOG_MAX_STD, device=None, loss_kind='nll', n_components=0, act=0):
+                 max_log_std=LOG_MAX_STD, device=None, loss_kind='nll', n_components=0, act=0, bernoulli_keep=None):
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else 'cuda:0')
         cfg = _lib.BnnConfig()
@@ -221,17 +225,34 @@ class BnnStep:
             cfg.temperature[l] = float(temperature[l]) if temperature[l] else 0.0
             cfg.reg_scale[l] = float(reg_scale[l])
             cfg.drop_reg[l] = float(drop_reg[l])
+        unit_keep = {}
+        for l in range(nl - 1):
+            k = bernoulli_keep[l] if bernoulli_keep is not None else None
+            if k is None:
+                continue
+            cfg.drop_kind[l] = _lib.DROP_BERNOULLI
+            cfg.temperature[l] = 0.0
+            k = np.ascontiguousarray(torch.as_tensor(k).detach().cpu().numpy().reshape(-1), dtype=np.float32)
+            if k.size != 1:
+                unit_keep[l] = k            # per-unit rates: handed to the plan once it exists
+                cfg.bern_keep[l] = 1.0
+            else:
+                cfg.bern_keep[l] = float(k[0])
         cfg.max_log_std = float(max_log_std)
         cfg.reg_weight = float(reg_weight)
         # 'gmm': mixture-of-Gaussians NLL (losses.py:40-64), head (2 n_out + 1) n_components + 1 wide
         cfg.loss_kind = {'nll': 0, 'mse': 1, 'gmm': 2}[loss_kind]
         cfg.n_components = int(n_components) if loss_kind == 'gmm' else 0
         self.M, self.N, self.dims = int(M), int(N), list(dims)
-        self.drop_widths = [dims[l + 1] for l in range(nl - 1) if cfg.temperature[l] > 0]
+        self.drop_widths = [dims[l + 1] for l in range(nl - 1)
+                            if cfg.temperature[l] > 0 or cfg.drop_kind[l] == _lib.DROP_BERNOULLI]
         self.sum_h = sum(self.drop_widths)
         self.plan = C.c_void_p()
         _lib.check(self.lib.pmbrl_bnn_plan_create(C.byref(cfg), self.device.index or 0, C.byref(self.plan)),
                    'pmbrl_bnn_plan_create')
+        for l, k in unit_keep.items():
+            _lib.check(self.lib.pmbrl_bnn_plan_set_unit_keep(self.plan, l, k.ctypes.data_as(C.POINTER(C.c_float)),
+                                                             int(k.size)), 'pmbrl_bnn_plan_set_unit_keep')
         self.n_params = int(self.lib.pmbrl_bnn_plan_n_params(self.plan))
         self.ws = torch.empty(self.lib.pmbrl_bnn_plan_workspace_bytes(self.plan), dtype=torch.uint8,
                               device=self.device)

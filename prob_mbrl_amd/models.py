@@ -97,6 +97,9 @@ class BDropout(StochasticModule):
         """The {0,1} mask a stand-alone forward over B rows applies, with the reference's
         rules (models/modules.py:46-61): redraw-and-store when the stored mask cannot be
         reused, a fresh unstored draw when `resample`, else the stored rows."""
+        forced = getattr(self, '_forced_sample', None)      # tests: replay a recorded mask
+        if forced is not None:
+            return forced.reshape(-1, width)[:B]
         n = self.noise
         if n.dim() != 2 or n.shape[1] != width or B > n.shape[0]:
             self.update_noise(torch.empty(B, width), seed)

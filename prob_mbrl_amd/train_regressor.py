@@ -1,6 +1,6 @@
 """`prob_mbrl.utils.train_regressor` (utils/train_regressor.py:58-165): maximum-likelihood
 training of the Bayesian dynamics model.  The iteration body -- forward in train() mode with
-concrete dropout, Gaussian log-likelihood, dropout regulariser, backward -- is one device call
+concrete or fixed-rate Bernoulli dropout, Gaussian log-likelihood, dropout regulariser, backward -- is one device call
 (pmbrl_bnn_loss_grad), the optimiser step is the fused Adam of the policy path (pmbrl_clip_adam)."""
 import os
 
@@ -9,7 +9,7 @@ import torch
 
 from . import engine as E
 from .algorithms import _adam_flat_state, _sync_adam_state
-from .models import CDropout
+from .models import BDropout, CDropout
 
 
 def iterate_minibatches(N, batchsize):
@@ -71,6 +71,18 @@ def flat_module_parameters(params, owner, key='_pmbrl_flat_all'):
     return flat
 
 
+def bernoulli_keep_of(dr):
+    """The keep probabilities 1 - rate of a fixed-rate BDropout layer: a float, or one value per unit (a tensor rate)."""
+    keep = (1 - dr.rate).detach().reshape(-1).float().cpu()
+    return float(keep[0]) if keep.numel() == 1 else keep
+
+
+def stored_bernoulli_mask(dr, M, h):
+    """The leading M rows of a BDropout layer's stored mask, drawn first when its shape does not fit
+    (BDropout.forward without resample, models/modules.py:46-61)."""
+    return dr.hard_mask(M, h)[:M].to(torch.float32)
+
+
 def _is_diag_gaussian_ll(fn):
     """None, losses.gaussian_log_likelihood, or the bound DiagGaussianDensity.log_prob the example
     scripts pass (examples/deep_pilco_mm.py:224; same formula, models/densities.py:123-144)."""
@@ -121,13 +133,18 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
         raise NotImplementedError('a diagonal-Gaussian output density is required')
     dims = [linears[0].in_features] + [l.out_features for l in linears]
     # module parameter order: fc0.weight, fc0.bias, drop0.logit_p, fc1.weight, ...
-    params, temps, rscale, dreg = [], [], [], []
+    params, temps, rscale, dreg, bern = [], [], [], [], []
     for l, lin in enumerate(linears):
         params += [lin.weight, lin.bias]
         if l < len(linears) - 1:
             dr = drops[l]
+            bern.append(None)
             if dr is None:
                 temps.append(0.0); rscale.append(0.0); dreg.append(0.0)
+            elif type(dr) is BDropout:
+                # fixed-rate Bernoulli dropout (models/modules.py:14-61): no parameter, its own regulariser scale
+                temps.append(0.0); rscale.append(float(dr.regularizer_scale)); dreg.append(0.0)
+                bern[-1] = bernoulli_keep_of(dr)
             elif isinstance(dr, CDropout):
                 if dr.logit_p.numel() != lin.out_features:
                     dr.logit_p.data = dr.logit_p.data.reshape(-1).expand(lin.out_features).clone()
@@ -135,12 +152,14 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
                 temps.append(float(dr.temp)); rscale.append(float(dr.regularizer_scale))
                 dreg.append(float(dr.dropout_regularizer))
             else:
-                raise NotImplementedError('BNN training is offered for concrete dropout (CDropout) layers')
+                raise NotImplementedError('BNN training is offered for concrete (CDropout) and fixed-rate Bernoulli '
+                                          '(BDropout) dropout layers')
     if any(not p.requires_grad for p in params):
         raise NotImplementedError('frozen parameters are not offered on the device path')
     model_params = [p for p in model.parameters() if p.requires_grad]
     if len(model_params) != len(params) or any(a is not b for a, b in zip(model_params, params)):
         raise NotImplementedError('the model has trainable parameters outside Linear / CDropout layers')
+    bern_layers = [(l, drops[l]) for l in range(len(bern)) if bern[l] is not None]
     if optimizer is None:
         optimizer = torch.optim.Adam(params, 1e-4)
     flat = flat_module_parameters(params, model)
@@ -150,7 +169,18 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
                                   'model.parameters()')
     steps = {}
     grad = torch.empty_like(flat)
-    sum_h = sum(d for d, t in zip(dims[1:-1], temps) if t > 0)
+    # u / bvar: one [M, h_l] block per dropout layer of either kind, in layer order
+    drop_w = [(l, d) for l, (d, t, k) in enumerate(zip(dims[1:-1], temps, bern)) if t > 0 or k is not None]
+    sum_h = sum(d for _, d in drop_w)
+
+    def stored_masks(bvar, M):
+        # resample=False: a Bernoulli layer applies the leading rows of its stored mask (mask = bvar < p)
+        off = 0
+        for l, h in drop_w:
+            if bern[l] is not None:
+                bvar[off:off + M * h] = (1.0 - stored_bernoulli_mask(drops[l], M, h)).reshape(-1)
+            off += M * h
+        return bvar
     u_fixed = None
     tree = None
     if prioritized_sampling:
@@ -212,12 +242,15 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
             st = steps.get(M)
             if st is None:
                 st = steps[M] = E.BnnStep(dims, temps, rscale, dreg, M, N, reg_weight,
-                                          max_log_std=float(density.max_log_std), device=dev, act=act)
+                                          max_log_std=float(density.max_log_std), device=dev, act=act,
+                                          bernoulli_keep=bern)
             idx_all = torch.as_tensor(np.stack(take).astype(np.int32), device=dev).contiguous()
             u = bv = None
             if _replay is not None:
                 f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32), device=dev).reshape(-1)  # noqa: E731
-                u = torch.cat([f32(a) for a in _replay['u'][done]]).contiguous()
+                # (a Bernoulli layer has no concrete noise: its entry of _replay['u'] may be None)
+                u = torch.cat([f32(a) if a is not None else torch.zeros(M * h, device=dev)
+                               for a, (_, h) in zip(_replay['u'][done], drop_w)]).contiguous()
                 bv = torch.cat([1.0 - f32(a) for a in _replay['hard'][done]]).contiguous()      # hard = (bvar < probs)
             hist = torch.empty(len(take), 3, dtype=torch.float32, device=dev)
             loss = st.train_steps(Xn, Yn, idx_all, flat, cache['m'], cache['v'], step_dev, g['lr'], g['betas'], g['eps'],
@@ -246,16 +279,20 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
             st = steps[M] = E.BnnStep(dims, temps, rscale, dreg, M, N, reg_weight,
                                       max_log_std=float(density.max_log_std), device=dev,
                                       loss_kind='gmm' if mixture else 'nll',
-                                      n_components=density.n_components if mixture else 0, act=act)
+                                      n_components=density.n_components if mixture else 0, act=act,
+                                      bernoulli_keep=bern)
         idx = device_indices(idx_np)
         if _replay is not None:     # tests: the reference's recorded draws of this step
             f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32), device=dev).reshape(-1)  # noqa: E731
-            u_fixed = torch.cat([f32(a) for a in _replay['u'][i]])
+            u_fixed = torch.cat([f32(a) if a is not None else torch.zeros(M * h, device=dev)
+                                 for a, (_, h) in zip(_replay['u'][i], drop_w)])
             bvar = torch.cat([1.0 - f32(a) for a in _replay['hard'][i]])        # hard = (bvar < probs)
         else:
             if resample or u_fixed is None or u_fixed.numel() != M * sum_h:
                 u_fixed = torch.rand(M * sum_h, device=dev, dtype=torch.float32)
             bvar = torch.rand(M * sum_h, device=dev, dtype=torch.float32)
+            if bern_layers and not resample:
+                bvar = stored_masks(bvar, M)
         row_w = row_lp = None
         if prioritized_sampling:
             row_lp = torch.empty(M, dtype=torch.float32, device=dev)

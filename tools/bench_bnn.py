@@ -22,6 +22,11 @@ def main():
     ap.add_argument('--N', type=int, default=1000)
     ap.add_argument('--hidden', type=int, default=200)
     ap.add_argument('--cpu-iters', type=int, default=60)
+    ap.add_argument('--dropout', default='concrete', choices=['concrete', 'bernoulli'],
+                    help='dropout kind of both hidden layers (bernoulli: fixed keep probability 0.9)')
+    ap.add_argument('--n-in', type=int, default=5)
+    ap.add_argument('--n-out', type=int, default=4)
+    ap.add_argument('--repeats', type=int, default=1, help='timed repetitions of the fused leg (all reported)')
     a = ap.parse_args()
     import prob_mbrl_amd as pm
     from prob_mbrl_amd import engine as E
@@ -29,17 +34,21 @@ def main():
     D, U, h = 4, 1, a.hidden
     torch.manual_seed(0)
     np.random.seed(0)
-    dims = [D + U, h, h, 2 * D]
-    Xn = torch.randn(a.N, D + U, device=dev)
-    Yn = torch.randn(a.N, D, device=dev)
+    bern = a.dropout == 'bernoulli'
+    dims = [a.n_in, h, h, 2 * a.n_out]
+    Xn = torch.randn(a.N, a.n_in, device=dev)
+    Yn = torch.randn(a.N, a.n_out, device=dev)
     parts = []
     for l in range(3):
         parts += [torch.randn(dims[l + 1], dims[l], device=dev).reshape(-1) / np.sqrt(dims[l]),
                   torch.zeros(dims[l + 1], device=dev)]
-        if l < 2:
+        if l < 2 and not bern:
             parts.append(torch.full((dims[l + 1],), 1.1, device=dev))
     flat = torch.cat(parts).contiguous()
-    step = E.BnnStep(dims, [0.1, 0.1], [0.5, 0.5], [1.0, 1.0], a.batch, a.N, 1.0, device=dev)
+    if bern:
+        step = E.BnnStep(dims, [0.0, 0.0], [0.5, 0.5], [0.0, 0.0], a.batch, a.N, 1.0, device=dev, bernoulli_keep=[0.9, 0.9])
+    else:
+        step = E.BnnStep(dims, [0.1, 0.1], [0.5, 0.5], [1.0, 1.0], a.batch, a.N, 1.0, device=dev)
     m, v, g = torch.zeros_like(flat), torch.zeros_like(flat), torch.empty_like(flat)
     sum_h = 2 * h
 
@@ -71,21 +80,25 @@ def main():
     chunk(0)
     torch.cuda.synchronize()
     n_chunks = max(1, a.iters // CH)
-    t0 = time.perf_counter()
-    for k in range(n_chunks):
-        chunk(1 + k)
-    torch.cuda.synchronize()
-    dt = time.perf_counter() - t0
+    runs = []
+    for r in range(a.repeats):
+        t0 = time.perf_counter()
+        for k in range(n_chunks):
+            chunk(1 + r * n_chunks + k)
+        torch.cuda.synchronize()
+        runs.append(time.perf_counter() - t0)
+    dt = float(np.median(runs))
     a.iters = n_chunks * CH
-    assert bool(torch.isfinite(flat).all()) and int(stepc.item()) == (n_chunks + 1) * CH
+    assert bool(torch.isfinite(flat).all()) and int(stepc.item()) == (a.repeats * n_chunks + 1) * CH
     # CPU leg: bench.py's cpu_baseline code times the oracle's step on the host (bounded sample)
     from bench import cpu_baseline_bnn
     rate_cpu, cores = cpu_baseline_bnn(dims, h, Xn.cpu(), Yn.cpu(), a.N, a.batch, a.cpu_iters)
     print(json.dumps(dict(metric='bnn_training_iterations_per_sec', value=a.iters / dt, unit='it/s',
                           us_per_iteration=dt / a.iters * 1e6, launches_per_iteration=2,
+                          us_per_iteration_runs=[r / a.iters * 1e6 for r in runs],
                           unfused=dict(value=1.0 / dt_unfused, us_per_iteration=dt_unfused * 1e6, launches_per_iteration=10),
-                          config=dict(workload='dynamics BNN %s, minibatch %d of %d rows, concrete dropout, '
-                                               'Gaussian NLL + regulariser, Adam' % (dims, a.batch, a.N)),
+                          config=dict(workload='dynamics BNN %s, minibatch %d of %d rows, %s dropout, '
+                                               'Gaussian NLL + regulariser, Adam' % (dims, a.batch, a.N, a.dropout)),
                           cpu_baseline=dict(value=rate_cpu, unit='it/s', cores=cores,
                                             kind='port', sample='%d iterations' % a.cpu_iters))))
 
