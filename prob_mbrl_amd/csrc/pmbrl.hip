@@ -1,6 +1,5 @@
-// libpmbrl_hip.so -- C ABI (include/pmbrl.h) over the gfx950 kernels.
-// Host side: shape validation, tiling choice, workspace carve-up, launches.
-#define PM_MAIN_TU
+// libpmbrl_hip.so -- C ABI (include/pmbrl.h) over the gfx950 kernels: the rollout plan and its two calls.
+// Host side: shape validation, tiling choice, workspace carve-up, launches.  (pmbrl_host.h lists the other objects.)
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdio.h>
@@ -17,16 +16,13 @@
 #include "pmbrl_mmx.h"
 #include "pmbrl_mm_wide.h"
 #include "pmbrl_fast.h"
-#include "pmbrl_dw.h"
-#include "pmbrl_mlp.h"
-#include "pmbrl_bnn.h"
+#include "pmbrl_reward.h"
 
 static thread_local std::string g_err;
 int pm_fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
-static int fail(int code, const std::string& msg) { return pm_fail(code, msg); }
 
 extern "C" const char* pmbrl_last_error(void) { return g_err.c_str(); }
 extern "C" int pmbrl_version(void) { return 8; }
@@ -94,7 +90,7 @@ extern "C" const char* pmbrl_build_id(void) {
 }
 
 // ---------------------------------------------------------------------------
-// small kernels
+// small kernels: the fragment packers of the test hook (pmbrl_debug_linear, below), then those of the rollout calls
 // ---------------------------------------------------------------------------
 // fragment packing: dst[((ot*n_kb + kb)*64 + lane)*4 + j] = W[ot*16 + (lane&15)][kb*16 + 4*(lane>>4) + j]
 // (transpose=1: the roles of the two indices of W[O][K] are swapped)
@@ -120,375 +116,16 @@ __global__ void pm_pack_bias(const float* __restrict__ b, int O, int O16, float*
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < O16) dst[i] = i < O ? b[i] : 0.f;
 }
-__global__ void pm_pack_mask_kernel(const float* __restrict__ m, int B, int h, int ld,
-                                    uint16_t* __restrict__ bits) {
-  const int nt = (h + 15) / 16;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= B * nt) return;
-  const int r = i / nt, t = i - r * nt;
-  unsigned w = 0;
-  for (int j = 0; j < 16; ++j) {
-    const int f = t * 16 + j;
-    if (f < h && m[(size_t)r * ld + f] != 0.f) w |= 1u << j;
-  }
-  bits[i] = (uint16_t)w;
-}
-__global__ void pm_set_int(int* p, int v) { *p = v; }
 
-// ---------------------------------------------------------------------------
-// Dropout masks drawn on the device (pmbrl_draw_masks): bit rows straight from a counter-based generator.
-// Philox4x32-10 (Salmon et al., SC'11) keyed by the caller's seed; counter = (row, 16-unit tile, quad + 4 * stream,
-// offset): a draw depends on (seed, offset, row, unit) alone, not on the launch shape.  Stream 0: the uniform noise u;
-// stream 1: the uniform the hard Bernoulli sample is thresholded with.
-// ---------------------------------------------------------------------------
-struct DrawArgs {
-  int kind;              // 0: Bernoulli(keep) -- BDropout.update_noise, models/modules.py:40-44;  1: concrete -- :95-118
-  unsigned long long seed, offset;
-  const float* param;    // kind 0: keep probability; kind 1: logit_p  (param_len 1 or h)
-  int param_len;
-  float temp;
-  int rows, h;
-  const float *u_in, *v_in;     // [rows][h] uniforms to use instead of the generator's (nullptr: generate)
-  uint16_t* bits;        // [rows][ceil(h/16)]
-  int aux_row0, aux_rows;       // rows whose float values are also written (a module keeps its LAST draw as state)
-  float *u_out, *hard_out, *probs_out;   // [aux_rows][h] each, or nullptr
-};
-__global__ __launch_bounds__(256) void pm_draw_masks_kernel(const DrawArgs A) {
-  const int nt = (A.h + 15) / 16;
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long long)A.rows * nt) return;
-  const int r = (int)(i / nt), t = (int)(i - (long long)r * nt);
-  const unsigned k0 = (unsigned)A.seed, k1 = (unsigned)(A.seed >> 32);
-  const unsigned o0 = (unsigned)A.offset, o1 = (unsigned)(A.offset >> 32);
-  unsigned w = 0;
-  const bool aux = r >= A.aux_row0 && r < A.aux_row0 + A.aux_rows;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned ru[4], rv[4];
-    if (!A.u_in) pm_philox((unsigned)r, (unsigned)t, (unsigned)q ^ (o1 << 3), o0, k0, k1, ru);
-    if (A.kind == 1 && !A.v_in) pm_philox((unsigned)r, (unsigned)t, (unsigned)(4 + q) ^ (o1 << 3), o0, k0, k1, rv);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int f = t * 16 + q * 4 + e;
-      if (f >= A.h) continue;
-      const size_t idx = (size_t)r * A.h + f;
-      // 24-bit uniforms in [0, 1) (what torch.rand gives a float tensor)
-      const float u = A.u_in ? A.u_in[idx] : (float)(ru[e] >> 8) * (1.0f / 16777216.0f);
-      const float pr = A.param[A.param_len > 1 ? f : 0];
-      float probs;
-      bool bit;
-      if (A.kind == 0) {
-        probs = pr;
-        bit = u < pr;                                    // torch.bernoulli(p): 1 with probability p
-      } else {
-        // models/modules.py:102-114: probs = sigmoid((logit_p + log((u + 1e-7) / (1 - (u - 1e-7)))) / temp)
-        const float cp = pr + logf((u + 1e-7f) / (1.f - (u - 1e-7f)));
-        probs = 1.f / (1.f + expf(-cp / A.temp));
-        const float v = A.v_in ? A.v_in[idx] : (float)(rv[e] >> 8) * (1.0f / 16777216.0f);
-        bit = v < probs;
-      }
-      if (bit) w |= 1u << (q * 4 + e);
-      if (aux) {
-        const size_t o = (size_t)(r - A.aux_row0) * A.h + f;
-        if (A.u_out) A.u_out[o] = u;
-        if (A.hard_out) A.hard_out[o] = bit ? 1.f : 0.f;
-        if (A.probs_out) A.probs_out[o] = probs;
-      }
-    }
-  }
-  A.bits[i] = (uint16_t)w;
-}
-
-// Small reductions: per-block partial sums in a per-device scratch, finished in FIXED order
-// (bit-reproducible).  The scratch is shared by all calls on a device: calls are expected to
-// be stream-ordered (one optimisation loop per device), like the rest of a plan's work.
-// the reward launch's instance for an action width (pmbrl_fast.h)
+// the reward launch's instance for an action width (pmbrl_reward.h)
 typedef void (*pm_reward_kernel_t)(const RolloutArgs);
 static inline pm_reward_kernel_t pm_reward_kernel_for(int U, int k) {
   if (k <= 2) return U <= 4 ? pm_reward_all_kernel<4, 2> : (U <= 8 ? pm_reward_all_kernel<8, 2> : pm_reward_all_kernel<16, 2>);
   return U <= 4 ? pm_reward_all_kernel<4, PMBRL_MAX_TIP>
                 : (U <= 8 ? pm_reward_all_kernel<8, PMBRL_MAX_TIP> : pm_reward_all_kernel<16, PMBRL_MAX_TIP>);
 }
-static inline int pm_norm_blocks(long long n) { return (int)std::max<long long>(1, std::min<long long>(PM_NORM_MAXB, (n + 255) / 256)); }
-#define PM_RED_MAXB 128
-__device__ double g_red_part[2][PM_RED_MAXB];
-__device__ unsigned g_red_count;
-
-__global__ __launch_bounds__(256) void pm_weighted_sum_kernel(const float* __restrict__ a,
-                                                              const float* __restrict__ w,
-                                                              long long n, float* __restrict__ out,
-                                                              const int* __restrict__ nvalid, long long n_per_step) {
-  __shared__ double sm[256];
-  __shared__ unsigned ticket;
-  if (nvalid) n = min(n, (long long)max(0, *nvalid) * n_per_step);   // truncated horizon
-  double s = 0.0;
-  // (eight elements' loads in flight at a time, added in the order a one-by-one loop adds them: as that loop -- load, wait,
-  //  convert, add -- a thread's eight elements at C2 were eight memory round trips in a row, most of this launch)
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += 8 * stride) {
-    float av[8], wv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      // (beyond n: the last element's address, its value dropped below -- a load under a condition is waited for where
-      //  the branches join, one at a time again)
-      const long long j = min(i + u * stride, n - 1);
-      av[u] = a[j];
-      wv[u] = w[j];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s += i + u * stride < n ? (double)av[u] * (double)wv[u] : 0.0;
-  }
-  const double tot = pm_block_sum(s, sm);
-  if (threadIdx.x == 0) {
-    // (a device-scope store, then the ticket: a release FENCE here is a write-back of this XCD's whole L2 -- the reward
-    //  launch's stash is still in it)
-    __hip_atomic_store(&g_red_part[0][blockIdx.x], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    ticket = __hip_atomic_fetch_add(&g_red_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (ticket == gridDim.x - 1) {          // last block: every partial is published
-    // fixed-shape tree over the published partials (deterministic), not a serial chain of
-    // L2 round trips
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    double t = 0.0;
-    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
-      t += __hip_atomic_load(&g_red_part[0][b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    const double tt = pm_block_sum(t, sm);
-    if (threadIdx.x == 0) {
-      out[0] = (float)tt;
-      __hip_atomic_store(&g_red_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
-}
-
-// clip_grad_norm_ + Adam in two launches: (1) partial sums of g^2 over blocks of 256 elements (pmbrl_dw.h, pm_sq4_wave:
-// the same partial sums the fused iteration's gradient reduction forms on the way), (2) every block adds the partials in
-// the same order (identical norm everywhere) and updates its slice.
-// Guarded form (pmbrl_clip_adam_guarded): block 0 also decides whether the step is taken (the rollout's status word says
-// every horizon step completed) and, if so, advances the device-side step counter; pm_clip_adam_kernel (next launch)
-// reads both.
-__global__ __launch_bounds__(64) void pm_gradnorm_kernel(const float* __restrict__ g, long long n,
-                                                         const int* __restrict__ status, int expect,
-                                                         long long* __restrict__ step, int guarded) {
-  if (guarded && blockIdx.x == 0 && threadIdx.x == 0) pm_adam_decide(status, expect, step);
-  // (one block of 256 elements per workgroup up to PM_NORM_MAXB of them; a longer vector is walked in strides, the
-  //  blocks' sums added in block order)
-  double tot = 0.0;
-  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
-    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
-    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (i0 + 3 < n) t = *reinterpret_cast<const f32x4*>(g + i0);
-    else
-      for (int r = 0; r < 4; ++r) t[r] = i0 + r < n ? g[i0 + r] : 0.f;
-    tot += pm_sq4_wave(t, i0, n);
-  }
-  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
-}
-
-__global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p, float* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v,
-                                                           long long n, int n_part, float lr, float b1,
-                                                           float b2, float omb1, float omb2, float eps,
-                                                           float bc1, float bc2_sqrt, float max_norm,
-                                                           float* __restrict__ norm_out,
-                                                           const long long* __restrict__ step, int guarded,
-                                                           double ln_b1, double ln_b2, double lr_d,
-                                                           float* __restrict__ loss_out, int n_loss_part) {
-  // The first four elements of this thread and the norm's partial sums are requested before anything is decided: as
-  // "go? -> step counter -> partial sums (a loop of dependent loads) -> elements (a loop of four)" this launch was ten
-  // memory round trips in a row around a few hundred instructions.
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  float gq[4], mq[4], vq[4], pq[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    // (beyond n: the last element's address, never used -- loads under a condition are waited for one by one)
-    const long long j = min(i0 + u * stride, n - 1);
-    gq[u] = g[j];
-    mq[u] = m[j];
-    vq[u] = v[j];
-    pq[u] = p[j];
-  }
-  const int lane = threadIdx.x & 63;
-  double part[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const double x = g_norm_part[min(lane + 64 * u, PM_NORM_MAXB - 1)];
-    part[u] = lane + 64 * u < n_part ? x : 0.0;
-  }
-  // the fused iteration's loss: the sums pm_dw_reduce's workgroups left, added in workgroup order by one wave (taken or
-  // not, the step's loss is reported)
-  if (loss_out && blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 128) {
-    double ls = 0.0;
-    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
-    if (lane == 0) loss_out[0] = (float)ls;
-  }
-  if (guarded && !g_adam_go) return;   // the rollout failed: leave parameters and moments alone
-  double step_size_d = lr_d / (double)bc1;
-  if (step) {
-    // guarded form: bias corrections 1 - beta^t of the device-side step counter as -expm1(t ln beta), the exponent formed
-    // and evaluated in double (torch forms them in Python floats; in fp32 the sixth digit of the step size differs and a
-    // five-iteration comparison of the moments notices), ln beta from the host -- two double-precision pow calls were a
-    // thousand instructions at the head of every thread, expm1 is a third of that
-    const double st = (double)step[0];
-    bc1 = (float)-expm1(st * ln_b1);
-    bc2_sqrt = (float)sqrt(-expm1(st * ln_b2));
-    step_size_d = lr_d / -expm1(st * ln_b1);      // (torch: lr / bias_correction1 in Python floats, rounded once)
-  }
-  // the partial sums of squares, block b on lane b mod 64 in block order, and a fixed butterfly: the same bits in every wave
-  // of every block
-  double t = 0.0;
-  {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) t += part[u];                         // (absent: + 0)
-    for (int b = lane + 256; b < n_part; b += 64) t += g_norm_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-  }
-  const float norm = (float)sqrt(t);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
-  float coef = 1.f;
-  if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-  const float step_size = (float)step_size_d;
-  for (long long i = i0;;) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = i + u * stride;
-      if (j < n) {
-        const float gi = gq[u] * coef;
-        const float mi = mq[u] * b1 + omb1 * gi;
-        const float vi = vq[u] * b2 + omb2 * gi * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        g[j] = gi;
-        m[j] = mi;
-        v[j] = vi;
-        p[j] = pq[u] - step_size * (mi / denom);
-      }
-    }
-    i += 4 * stride;
-    if (i >= n) break;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = min(i + u * stride, n - 1);
-      gq[u] = g[j];
-      mq[u] = m[j];
-      vq[u] = v[j];
-      pq[u] = p[j];
-    }
-  }
-}
-
-static void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
-                                long long n_per_step) {
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 2047) / 2048));
-  hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, s, a, w, n, out, nvalid, n_per_step);
-}
-
-// norm_done: the partial sums of squares and the go / no-go decision are already on the device (the fused iteration's
-// gradient reduction formed them: pm_dw_reduce, norm_on)
-static int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
-                                  int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
-                                  double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                                  float* loss_out_d = nullptr, int n_loss_part = 0) {
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
-  const int np = pm_norm_blocks(n);
-  if (!norm_done)
-    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
-                       (long long)n, (const int*)status_d, (int)expect, reinterpret_cast<long long*>(step_d), 1);
-  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
-                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, (float)lr, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, 1.f, 1.f,
-                     (float)max_norm, norm_out_d, reinterpret_cast<const long long*>(step_d), 1, log(beta1), log(beta2), lr,
-                     loss_out_d, n_loss_part);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// the fused iteration tail on a sharded run (pmbrl_plan_set_grad_comm): what pmbrl_rollout_bwd_adam queues around the
-// in-place sum of [flat gradient | loss partial | failure flag] over the ranks
-// ---------------------------------------------------------------------------
-// horizon agreement, 1: this rank's valid steps as entry `rank` of a vector the transport sums (both transports only sum)
-__global__ __launch_bounds__(64) void pm_tail_hvec_kernel(float* __restrict__ hvec, int world, int rank,
-                                                          const int* __restrict__ status, int H) {
-  for (int q = threadIdx.x; q < world; q += blockDim.x) hvec[q] = q == rank ? (float)min(max(status[0], 0), H) : 0.f;
-}
-// 2: the ranks' minimum, written where it is smaller than what this rank's forward sweep left (a rank whose exchange
-// timed out holds zeros for its peers: no step is valid, nothing is stepped)
-__global__ __launch_bounds__(64) void pm_tail_hmin_kernel(const float* __restrict__ hvec, int world,
-                                                          int* __restrict__ status, int H) {
-  if (threadIdx.x != 0) return;
-  int m = H;
-  for (int q = 0; q < world; ++q) m = min(m, (int)hvec[q]);
-  if (m < min(status[0], H)) status[0] = m;
-}
-// behind the gradient reduction: this rank's loss (the reduction's partial sums in workgroup order, as
-// pm_clip_adam_kernel adds them; n_loss_part = 0: already in xb[n], or not asked for) and failure flag next to the gradient
-__global__ __launch_bounds__(64) void pm_tail_pack_kernel(float* __restrict__ xb, int n, int n_loss_part, int loss_here,
-                                                          const int* __restrict__ status, const int* __restrict__ err) {
-  const int lane = threadIdx.x;
-  if (n_loss_part > 0) {
-    double ls = 0.0;
-    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
-    if (lane == 0) xb[n] = (float)ls;
-  } else if (!loss_here && lane == 0) {
-    xb[n] = 0.f;
-  }
-  if (lane == 0) xb[n + 1] = (status[1] != 0 || (err && *err != 0)) ? 1.f : 0.f;
-}
-// behind the exchange: the summed gradient into the caller's vector, the partial sums of ITS squares (pm_gradnorm_kernel's
-// blocks: the separate calls' norm bit for bit), the summed loss where pm_clip_adam_kernel looks for it, and the decision
-__global__ __launch_bounds__(64) void pm_tail_finish_kernel(const float* __restrict__ xb, float* __restrict__ g, long long n,
-                                                            int* __restrict__ status, int expect,
-                                                            long long* __restrict__ step, const int* __restrict__ err) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    // a failure anywhere is a failure everywhere: the host reads it one iteration late.  (A wait of THIS rank that timed
-    // out in the exchange just now is not in the sum -- the flag was packed before it: this rank says so in its own
-    // status word, the others learn it from the sticky error word in the next exchange.)
-    const int bad = (xb[n + 1] != 0.f || (err && *err != 0)) ? 1 : 0;
-    if (bad) status[1] = 1;
-    const int go = (status[0] >= expect && status[1] == 0) ? 1 : 0;
-    g_adam_go = go;
-    if (go && step) step[0] += 1;
-    g_loss_part[0] = (double)xb[n];
-  }
-  double tot = 0.0;
-  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
-    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
-    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (i0 + 3 < n) {
-      t = *reinterpret_cast<const f32x4*>(xb + i0);
-      for (int r = 0; r < 4; ++r) g[i0 + r] = t[r];
-    } else {
-      for (int r = 0; r < 4; ++r)
-        if (i0 + r < n) { t[r] = xb[i0 + r]; g[i0 + r] = t[r]; }
-    }
-    tot += pm_sq4_wave(t, i0, n);
-  }
-  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
-}
 
 // all weight / bias repacking of one forward call in ONE launch (blockIdx.y = job)
-struct PackJob {
-  const float* src;
-  float* dst;
-  int O, K, transpose, mult, is_bias;
-  int planes;   // 0: fp32 fragments of 16-wide k-blocks; 2 / 3: bf16 pieces of K32 blocks (pmbrl_split.h), mult in K32 blocks
-  int f16;      // pieces are fp16 instead of bf16
-};
-struct PackArgs {
-  int n;
-  int* wflag;       // fp16 pieces: set to `gen` when a weight is beyond +-65504 or not finite (nullptr: no check)
-  int gen;
-  int* status;      // reset to "no failure" by the same launch (nullptr: leave alone)
-  PackJob job[6 * PM_MAXL];
-};
 __global__ void pm_pack_all(const PackArgs P) {
   if (P.status && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *P.status = 0x7fffffff;
   const PackJob j = P.job[blockIdx.y];
@@ -554,6 +191,7 @@ __global__ void pm_pack_all(const PackArgs P) {
     j.dst[i] = v;
   }
 }
+void pm_pack_all_launch(const PackArgs& PK, hipStream_t s) { hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK); }
 
 
 // external moment matching (groups larger than a workgroup's rows): one workgroup of PM_MM_NW
@@ -733,71 +371,6 @@ static int set_attr(size_t lds) {
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_rollout_bwd<RT>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return 0;
-}
-
-// dW wave blocks: balanced splits of every layer's output tile grid into <= 4 x 7 tile
-// blocks, dealt to the four SIMDs (waves w and w+4 share SIMD w) by decreasing size so that
-// every SIMD issues the same number of MFMAs.  Returns the number of blocks; `blocks` comes back
-// sorted by wave, wave w owning [wave_first[w], wave_first[w+1]).
-static int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max = PM_DW_TN,
-                           const bool* skip = nullptr) {
-  blocks.clear();
-  auto split = [](int n, int maxsz, std::vector<std::pair<int, int>>& out) {
-    const int parts = (n + maxsz - 1) / maxsz;
-    int lo = 0;
-    for (int i = 0; i < parts; ++i) {
-      const int sz = n / parts + (i < n % parts ? 1 : 0);
-      out.push_back({lo, sz});
-      lo += sz;
-    }
-  };
-  for (int l = 0; l < nl; ++l) {
-    if (skip && skip[l]) continue;      // a wide layer: pm_dw_wide_kernel
-    std::vector<std::pair<int, int>> os, is;
-    split(nt[l + 1], PM_DW_TM, os);
-    split(nt[l], tn_max, is);
-    for (auto& o : os)
-      for (auto& i : is) {
-        DwBlock b;
-        b.layer = (int16_t)l;
-        b.ot0 = (int16_t)o.first;
-        b.n_ot = (int16_t)o.second;
-        b.it0 = (int16_t)i.first;
-        b.n_it = (int16_t)i.second;
-        b.pad = 0;
-        blocks.push_back(b);
-      }
-  }
-  const int n_blocks = (int)blocks.size();
-  // cost of a block = MFMAs per chunk in the shape class it runs in (see pm_dw_kernel)
-  auto cost = [tn_max](const DwBlock& b) {
-    const int ni = b.n_ot <= 1 ? 1 : (b.n_ot <= 3 ? 3 : 4);
-    const int nj = b.n_it <= 1 ? 1 : (b.n_it <= 4 ? 4 : (b.n_it <= 6 ? 6 : 7));
-    return ni * (tn_max <= 4 && nj > 1 ? 4 : nj);
-  };
-  std::stable_sort(blocks.begin(), blocks.end(),
-                   [&](const DwBlock& a, const DwBlock& b) { return cost(a) > cost(b); });
-  std::vector<DwBlock> per_wave[PM_DW_NW];
-  long wave_load[PM_DW_NW] = {0};
-  // waves w and w+4 of a workgroup share SIMD w (measured: pairing (2k, 2k+1) instead is 5% slower)
-  for (const DwBlock& b : blocks) {
-    int best_simd = 0;
-    for (int sm = 1; sm < 4; ++sm)
-      if (wave_load[sm] + wave_load[sm + 4] < wave_load[best_simd] + wave_load[best_simd + 4]) best_simd = sm;
-    const int w = wave_load[best_simd] <= wave_load[best_simd + 4] ? best_simd : best_simd + 4;
-    per_wave[w].push_back(b);
-    wave_load[w] += cost(b);
-  }
-  blocks.clear();
-  // the small blocks are latency-bound (a handful of MFMAs per chunk): the second wave of a SIMD runs
-  // its FIRST, while the SIMD's other wave keeps the MFMA pipe busy with its big block
-  for (int w = 0; w < PM_DW_NW; ++w) {
-    wave_first[w] = (int)blocks.size();
-    if (w >= 4) std::reverse(per_wave[w].begin(), per_wave[w].end());
-    for (const DwBlock& b : per_wave[w]) blocks.push_back(b);
-  }
-  wave_first[PM_DW_NW] = (int)blocks.size();
-  return n_blocks;
 }
 
 // ---------------------------------------------------------------------------
@@ -1315,10 +888,10 @@ static int plan_angles(pmbrl_plan* p) {
 static int plan_dw(pmbrl_plan* p) {
   const pmbrl_config& c = p->cfg;
   std::vector<DwBlock> blocks;
-  // split-operand form of the dW GEMM (pmbrl_dw.h, pm_dw_kernel_s): where the fp32 form is bound by the matrix
+  // split-operand form of the dW GEMM (pmbrl_dw_kernels.h, pm_dw_kernel_s): where the fp32 form is bound by the matrix
   // core -- 32- / 64-row workgroups and the general family's wide networks; the 16-row sweeps' dW is HBM-bound
   p->dw_split = p->prec != 0 && (p->RT >= 2 || !p->fast);
-  // wide layers of the split form go to the LDS-staged tile kernel (pmbrl_dw.h, pm_dw_wide_kernel)
+  // wide layers of the split form go to the LDS-staged tile kernel (pmbrl_dw_kernels.h, pm_dw_wide_kernel)
   bool wide[PM_MAXL] = {false};
   std::vector<DwUnit> units;
   // (layers of at least 128 x 128 on the split-precision plans: also the 200 x 200 layer of the cart-pole shapes,
@@ -1332,15 +905,13 @@ static int plan_dw(pmbrl_plan* p) {
         if (p->dw_layer13 < 0 && p->pol.nt[l + 1] <= PM_DWL_NT && p->pol.nt[l] <= PM_DWL_NT) {
           // a whole layer of up to 13 x 13 tiles per workgroup
           p->dw_layer13 = l;
-          HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_kernel),
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
           continue;
         }
         for (int m0 = 0; m0 < p->pol.nt[l + 1] * 16; m0 += PM_DWW_TM)
           for (int n0 = 0; n0 < p->pol.nt[l] * 16; n0 += PM_DWW_TN) units.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
       }
   // Round 6: the wide sweeps (64-row workgroups, in-place 512-wide layers: pmbrl_wide.h) write the stashes of the 512 x 512
-  // layers PRE-SPLIT, in the layout pm_dw_wide_pre_kernel streams into LDS without touching a register (pmbrl_dw.h).
+  // layers PRE-SPLIT, in the layout pm_dw_wide_pre_kernel streams into LDS without touching a register (pmbrl_dw_kernels.h).
   // Every wide layer 512 x 512 exactly (32 tiles: the stash block's tile count).  (Such a plan has dw_split: the
   // pre-split kernels walk chunk pairs.)
   if (!units.empty() && p->inplace == 2 && p->RT == 4) {
@@ -1367,10 +938,6 @@ static int plan_dw(pmbrl_plan* p) {
           for (int n0 = 0; n0 < 512; n0 += PM_DWP_TN) pre.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
       }
       units = pre;
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<2>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
     } else {
       for (int l = 0; l < PM_MAXL; ++l) p->dw_narrow[l] = 0;
     }
@@ -1379,12 +946,8 @@ static int plan_dw(pmbrl_plan* p) {
   if (p->n_dw_units) {
     HIPCHK(hipMalloc(&p->dw_units_d, units.size() * sizeof(DwUnit)));
     HIPCHK(hipMemcpy(p->dw_units_d, units.data(), units.size() * sizeof(DwUnit), hipMemcpyHostToDevice));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWW_LDS_BYTES));
-    if (p->dw_pre_mask)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_pre_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
   }
+  if (int rc = pm_dw_set_attr(p)) return rc;
   p->n_dw_blocks = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first, p->dw_split ? PM_DW_TN_S : PM_DW_TN, wide);
   p->dw_n_chunks = c.H * p->nwg * p->RT;
   int nsplit = std::min(256, p->dw_n_chunks);   // one 8-wave workgroup per CU
@@ -1631,11 +1194,6 @@ static bool replay_wanted(const pmbrl_plan* p) {
   if (p->replay == 0 || p->span || p->coll) return false;
   return p->replay >= 2 || per_step_launches(p);
 }
-static void replay_drop(pmbrl_plan* p, int slot) {
-  if (p->rp[slot].exec) (void)hipGraphExecDestroy(p->rp[slot].exec);
-  p->rp[slot].exec = nullptr;
-  p->rp[slot].seen = 0;
-}
 // what makes two calls "the same": every argument byte, kept (a hash alone would replay a stale recording on a collision)
 struct ReplayKey {
   unsigned long long h = 1469598103934665603ull;
@@ -1809,34 +1367,6 @@ extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   return 0;
 }
 
-extern "C" int pmbrl_pack_mask(void* stream, const float* mask_d, int32_t B, int32_t h,
-                               int32_t src_ld, uint16_t* bits_d) {
-  if (!mask_d || !bits_d || B < 1 || h < 1 || src_ld < h) return fail(-1, "bad argument");
-  const int nt = (h + 15) / 16;
-  const int n = B * nt;
-  hipLaunchKernelGGL(pm_pack_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
-                     mask_d, B, h, src_ld, bits_d);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int pmbrl_draw_masks(void* stream, int32_t kind, uint64_t seed, uint64_t offset, const float* param_d,
-                                int32_t param_len, float temp, int32_t rows, int32_t h, const float* u_d, const float* v_d,
-                                uint16_t* bits_d, int32_t aux_row0, int32_t aux_rows, float* u_out_d, float* hard_out_d,
-                                float* probs_out_d) {
-  if (!param_d || !bits_d || rows < 1 || h < 1 || (kind != 0 && kind != 1) || (param_len != 1 && param_len != h) ||
-      aux_row0 < 0 || aux_rows < 0 || aux_row0 + aux_rows > rows)
-    return fail(-1, "bad argument");
-  if (kind == 1 && !(temp > 0.f)) return fail(-1, "concrete dropout needs a positive temperature");
-  DrawArgs A;
-  A.kind = kind; A.seed = seed; A.offset = offset; A.param = param_d; A.param_len = param_len; A.temp = temp;
-  A.rows = rows; A.h = h; A.u_in = u_d; A.v_in = v_d; A.bits = bits_d;
-  A.aux_row0 = aux_row0; A.aux_rows = aux_rows; A.u_out = u_out_d; A.hard_out = hard_out_d; A.probs_out = probs_out_d;
-  const long long n = (long long)rows * ((h + 15) / 16);
-  hipLaunchKernelGGL(pm_draw_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
 
 // ---------------------------------------------------------------------------
 // argument assembly
@@ -2139,7 +1669,7 @@ static void launch_pack_all(pmbrl_plan* p, char* ws, const pmbrl_inputs* in, hip
   PK.status = status_d;
   PK.wflag = p->prec == PMBRL_PREC_SPLIT_F16 ? p->wflag_d : nullptr;
   PK.gen = p->wgen;
-  hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
+  pm_pack_all_launch(PK, s);
 }
 
 // the arguments of one pmbrl_rollout_fwd call: filled once by the entry point (which also derives the replay key from them)
@@ -2391,9 +1921,9 @@ static int bwd_args(const pmbrl_plan* p, const BwdCall& C, RolloutArgs& A) {
 static int bwd_agree_horizon(pmbrl_plan* p, const BwdCall& C) {
   hipStream_t s = C.stream;
   float* hvec = p->tail_buf_d + ((size_t)p->pol.n_params + 2 + 3) / 4 * 4;
-  hipLaunchKernelGGL(pm_tail_hvec_kernel, dim3(1), dim3(64), 0, s, hvec, p->tail_world, p->tail_rank, (const int*)C.status, p->cfg.H);
+  pm_tail_hvec_launch(s, hvec, p->tail_world, p->tail_rank, C.status, p->cfg.H);
   if (int rc = tail_allreduce(p, s, hvec, p->tail_world)) return rc;
-  hipLaunchKernelGGL(pm_tail_hmin_kernel, dim3(1), dim3(64), 0, s, (const float*)hvec, p->tail_world, (int*)C.status, p->cfg.H);
+  pm_tail_hmin_launch(s, hvec, p->tail_world, C.status, p->cfg.H);
   return 0;
 }
 
@@ -2429,45 +1959,6 @@ static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutA
   W.nvalid = C.status;
   return W;
 }
-// ... of launch k of the pipelined form: the chunks of step range k, dealt to the partial rows of a grid next to the sweep
-// (the last launch has the chip to itself)
-static DwArgs dw_range_args(const pmbrl_plan* p, const DwArgs& W, int k) {
-  DwArgs Wk = W;
-  const int cps = W.chunks_per_step;
-  Wk.pipe = 1;
-  Wk.pipe_k = k;
-  Wk.nsplit = k + 1 == p->pipe_K ? p->pipe_rows : p->pipe_grid;
-  Wk.rows_before = p->pipe_grid;
-  Wk.c_begin = p->pipe_lo[k] * cps;
-  Wk.c_end = (k ? p->pipe_lo[k - 1] : p->cfg.H) * cps;
-  Wk.chunks_per_split = (Wk.c_end - Wk.c_begin + Wk.nsplit - 1) / Wk.nsplit;
-  if (p->dw_split) Wk.chunks_per_split = (Wk.chunks_per_split + 1) & ~1;
-  return Wk;
-}
-// The dW GEMM over the chunks W describes, one partial row per workgroup: the only place that chooses its kernels.
-// (The pipelined ranges never meet a plan without block-kernel layers or with pre-split stashes: such a plan has
-//  dw_pre_mask -- the first layer's input is at most 40 wide, so only pm_dw_narrow_pre_kernel takes it from the block
-//  kernel -- and plan_dw_pipe leaves the pipeline off for it.)
-static void launch_dw_gemms(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
-  const dim3 rows(W.nsplit), units((W.nsplit + 7) / 8 * 8 * p->n_dw_units);
-  if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
-  else if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, rows, dim3(PM_DW_NT), 0, s, W);
-  else hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W);
-  if (p->dw_pre_mask)
-    for (int l = 0; l < p->pol.nl; ++l) {
-      if (!p->dw_narrow[l]) continue;
-      const int g_wide = p->dw_narrow[l] == 1 ? 1 : 0, nt_n = g_wide ? p->pol.nt[l] : p->pol.nt[l + 1];
-      if (nt_n <= 1) hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<1>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
-      else hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<2>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
-    }
-  if (p->n_dw_units && p->dw_pre_mask)
-    hipLaunchKernelGGL(pm_dw_wide_pre_kernel, units, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
-  else if (p->n_dw_units)
-    hipLaunchKernelGGL(pm_dw_wide_kernel, units, dim3(PM_DW_NT), PM_DWW_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
-  if (p->dw_layer13 >= 0)
-    hipLaunchKernelGGL(pm_dw_layer_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
-}
-
 // stage 4, the groups spanning workgroups (mm_mode 3): dL/dx travels between the steps through two carry buffers.
 // SweepForm::Barrier: one launch, the workgroups meet at a device-wide barrier per step
 static int bwd_sweep_barrier(pmbrl_plan* p, const BwdCall& C, RolloutArgs A) {
@@ -2516,7 +2007,7 @@ static int bwd_sweep_whole(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, const
     if (k + 1 < K) {
       HIPCHK(hipEventRecord(p->pipe_ev[k], s));
       HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[k], 0));
-      launch_dw_gemms(p, dw_range_args(p, W, k), p->pipe_stream);
+      pm_dw_launch_range(p, W, k, p->pipe_stream);
     }
   }
   return 0;
@@ -2549,13 +2040,13 @@ static int bwd_sweep_external(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, fl
 static int bwd_dw(pmbrl_plan* p, const BwdCall& C, const DwArgs& W, bool piped) {
   ScopedTimer tm(p, PMBRL_TIMER_DW, C.stream);
   if (!piped) {
-    launch_dw_gemms(p, W, C.stream);
+    pm_dw_launch(p, W, C.stream);
     return 0;
   }
   // the rows of the last range are added to what the second stream left: join it first
   HIPCHK(hipEventRecord(p->pipe_ev[p->pipe_K - 1], p->pipe_stream));
   HIPCHK(hipStreamWaitEvent(C.stream, p->pipe_ev[p->pipe_K - 1], 0));
-  launch_dw_gemms(p, dw_range_args(p, W, p->pipe_K - 1), C.stream);
+  pm_dw_launch_range(p, W, p->pipe_K - 1, C.stream);
   return 0;
 }
 
@@ -2604,15 +2095,13 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C) {
   {
     ScopedTimer tm(p, PMBRL_TIMER_DW_REDUCE, s);
     if (piped)   // every partial row was written (pm_dw_range)
-      hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, W.part, p->pipe_rows, n,
-                         W.part_stride, red_out, (const int*)nullptr, 0, 1);
+      pm_dw_reduce_launch(s, W.part, p->pipe_rows, n, W.part_stride, red_out, (const int*)nullptr, 0, 1);
     else
-      hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, W.part, p->dw_nsplit, n,
-                         W.part_stride, red_out, (const int*)C.status, W.chunks_per_step, W.chunks_per_split,
-                         norm_fused ? 1 : 0, (const int*)C.status, expect,
-                         opt ? reinterpret_cast<long long*>(opt->step_d) : (long long*)nullptr,
-                         loss_fused ? C.rewards : (const float*)nullptr, C.grad_rewards, (long long)p->cfg.H * p->cfg.B,
-                         (long long)p->cfg.B);
+      pm_dw_reduce_launch(s, W.part, p->dw_nsplit, n, W.part_stride, red_out, (const int*)C.status, W.chunks_per_step,
+                          W.chunks_per_split, norm_fused ? 1 : 0, (const int*)C.status, expect,
+                          opt ? reinterpret_cast<long long*>(opt->step_d) : (long long*)nullptr,
+                          loss_fused ? C.rewards : (const float*)nullptr, C.grad_rewards, (long long)p->cfg.H * p->cfg.B,
+                          (long long)p->cfg.B);
   }
   // the loss asked for with the optimiser step, where the reduction does not form it on the way: a launch of its own
   if (opt && opt->loss_out_d && !loss_fused)
@@ -2623,11 +2112,9 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C) {
   if (tail) {
     // [gradient | loss partial | failure flag] summed over the ranks in place, then the summed gradient's norm and the
     // decision every rank takes alike; the optimiser launch is the one-process one
-    hipLaunchKernelGGL(pm_tail_pack_kernel, dim3(1), dim3(64), 0, s, xb, n, n_loss_part,
-                       opt->loss_out_d && !loss_fused ? 1 : 0, (const int*)C.status, (const int*)p->tail_err_d);
+    pm_tail_pack_launch(s, xb, n, n_loss_part, opt->loss_out_d && !loss_fused ? 1 : 0, C.status, p->tail_err_d);
     if (int rc = tail_allreduce(p, s, xb, (int64_t)n + 2)) return rc;
-    hipLaunchKernelGGL(pm_tail_finish_kernel, dim3(pm_norm_blocks(n)), dim3(64), 0, s, (const float*)xb, C.grad_pol_flat,
-                       (long long)n, (int*)C.status, expect, reinterpret_cast<long long*>(opt->step_d), (const int*)p->tail_err_d);
+    pm_tail_finish_launch(s, xb, C.grad_pol_flat, n, C.status, expect, reinterpret_cast<long long*>(opt->step_d), p->tail_err_d);
     HIPCHK(hipGetLastError());
   }
   // the optimiser step behind it, decided on the device (a form with the reduction, the norm and the update in ONE launch
@@ -2707,713 +2194,9 @@ extern "C" int pmbrl_rollout_bwd_adam(pmbrl_plan* p, void* stream, void* workspa
 }
 
 // ---------------------------------------------------------------------------
-// stand-alone network evaluation
-// ---------------------------------------------------------------------------
-struct MlpLayout {
-  int nl, LD;
-  int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
-  size_t wf[PM_MAXL], wb[PM_MAXL], bias[PM_MAXL], w_off[PM_MAXL], b_off[PM_MAXL], bytes, lds, lds_bwd;
-};
-static int mlp_layout(const pmbrl_mlp_call* c, MlpLayout& L) {
-  if (!c) return fail(-1, "null argument");
-  const pmbrl_mlp& m = c->net;
-  if (m.n_layers < 2 || m.n_layers > PM_MAXL) return fail(-2, "mlp: 2..8 layers");
-  if (c->B < 1) return fail(-2, "mlp: B must be >= 1");
-  if (m.dims[m.n_layers] % 2) return fail(-2, "mlp: the output layer must be 2 x n_out wide");
-  L.nl = m.n_layers;
-  int maxnt = 1;
-  size_t off = 0, po = 0;
-  for (int i = 0; i <= L.nl; ++i) {
-    if (m.dims[i] < 1 || m.dims[i] > 16 * 64) return fail(-2, "mlp: layer width out of range");
-    L.dim[i] = m.dims[i];
-    L.nt[i] = (m.dims[i] + 15) / 16;
-    maxnt = std::max(maxnt, L.nt[i]);
-  }
-  for (int l = 0; l < L.nl; ++l) {
-    L.w_off[l] = po; po += (size_t)L.dim[l + 1] * L.dim[l];
-    L.b_off[l] = po; po += (size_t)L.dim[l + 1];
-    L.wf[l] = off; off += (size_t)L.nt[l + 1] * L.nt[l] * 256 * sizeof(float);
-    L.wb[l] = off; off += (size_t)L.nt[l + 1] * L.nt[l] * 256 * sizeof(float);
-    L.bias[l] = off; off += (size_t)L.nt[l + 1] * 16 * sizeof(float);
-    if (l < L.nl - 1 && !(m.keep[l] > 0.f)) return fail(-2, "mlp: keep must be > 0");
-  }
-  L.bytes = off;
-  L.LD = maxnt * 16 + 8;
-  L.lds = (2 * (size_t)16 * L.LD + (size_t)PM_NW * PM_KS_NT * 256) * sizeof(float);
-  if (c->act != PMBRL_ACT_RELU && c->act != PMBRL_ACT_TANH && c->act != PMBRL_ACT_SILU)
-    return fail(-2, "mlp: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
-  L.lds_bwd = pm_mlp_bwd_lds_floats(L.nl, L.LD, c->act) * sizeof(float);
-  if (L.lds > 160 * 1024) return fail(-3, "mlp: network too wide for LDS");
-  return 0;
-}
-
-extern "C" size_t pmbrl_mlp_workspace_bytes(const pmbrl_mlp_call* c) {
-  MlpLayout L;
-  return mlp_layout(c, L) ? 0 : L.bytes;
-}
-
-extern "C" int pmbrl_mlp_forward(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
-                                 const float* x_d, const float* params_flat_d,
-                                 const uint16_t* const* mask_bits_d, const float* z_d,
-                                 const float* in_shift_d, const float* in_iscale_d,
-                                 const float* out_scale_d, const float* out_shift_d,
-                                 const float* sq_scale_d, const float* sq_bias_d,
-                                 float* sample_d, float* mean_d, float* log_std_d) {
-  MlpLayout L;
-  int rc = mlp_layout(c, L);
-  if (rc) return rc;
-  if (!workspace_d || !x_d || !params_flat_d) return fail(-1, "null argument");
-  if ((in_shift_d == nullptr) != (in_iscale_d == nullptr) || (out_scale_d == nullptr) != (out_shift_d == nullptr) ||
-      (sq_scale_d == nullptr) != (sq_bias_d == nullptr))
-    return fail(-1, "mlp: shift/scale pointers come in pairs");
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace_d);
-  PackArgs PK;
-  PK.wflag = nullptr;
-  PK.gen = 0;
-  PK.n = 0;
-  PK.status = nullptr;
-  MlpArgs A;
-  memset(&A, 0, sizeof(A));
-  A.B = c->B; A.nl = L.nl; A.LD = L.LD; A.n_out = L.dim[L.nl] / 2;
-  for (int i = 0; i <= L.nl; ++i) { A.dim[i] = L.dim[i]; A.nt[i] = L.nt[i]; }
-  for (int l = 0; l < L.nl; ++l) {
-    float* wf = reinterpret_cast<float*>(ws + L.wf[l]);
-    float* bs = reinterpret_cast<float*>(ws + L.bias[l]);
-    PK.job[PK.n++] = PackJob{params_flat_d + L.w_off[l], wf, L.dim[l + 1], L.dim[l], 0, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + L.b_off[l], bs, L.dim[l + 1], L.dim[l], 0, 1, 1, 0, 0};
-    A.wf[l] = wf;
-    A.bias[l] = bs;
-    A.mask[l] = (l < L.nl - 1 && mask_bits_d) ? mask_bits_d[l] : nullptr;
-    A.keep[l] = l < L.nl - 1 ? c->net.keep[l] : 1.f;
-  }
-  A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
-  A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
-  A.mls = c->max_log_std;
-  A.act = c->act;
-  A.sample = sample_d; A.mean = mean_d; A.log_std = log_std_d;
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_fwd_kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
-  hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  hipLaunchKernelGGL(pm_mlp_fwd_kernel, dim3((c->B + 15) / 16), dim3(PM_NT), L.lds, s, A);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
-                                    const float* x_d, const float* params_flat_d,
-                                    const uint16_t* const* mask_bits_d, const float* z_d,
-                                    const float* in_shift_d, const float* in_iscale_d,
-                                    const float* out_scale_d, const float* out_shift_d,
-                                    const float* sq_scale_d, const float* sq_bias_d,
-                                    const float* g_sample_d, const float* g_mean_d,
-                                    const float* g_log_std_d, float* grad_x_d) {
-  MlpLayout L;
-  int rc = mlp_layout(c, L);
-  if (rc) return rc;
-  if (!workspace_d || !x_d || !params_flat_d || !grad_x_d) return fail(-1, "null argument");
-  if (L.lds_bwd > 160 * 1024) return fail(-3, "mlp: network too wide / deep for the input-gradient kernel's LDS budget");
-  if ((in_shift_d == nullptr) != (in_iscale_d == nullptr) || (out_scale_d == nullptr) != (out_shift_d == nullptr) ||
-      (sq_scale_d == nullptr) != (sq_bias_d == nullptr))
-    return fail(-1, "mlp: shift/scale pointers come in pairs");
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace_d);
-  PackArgs PK;
-  PK.wflag = nullptr;
-  PK.gen = 0;
-  PK.n = 0;
-  PK.status = nullptr;
-  MlpBwdArgs Bw;
-  memset(&Bw, 0, sizeof(Bw));
-  MlpArgs& A = Bw.f;
-  A.B = c->B; A.nl = L.nl; A.LD = L.LD; A.n_out = L.dim[L.nl] / 2;
-  for (int i = 0; i <= L.nl; ++i) { A.dim[i] = L.dim[i]; A.nt[i] = L.nt[i]; }
-  for (int l = 0; l < L.nl; ++l) {
-    float* wf = reinterpret_cast<float*>(ws + L.wf[l]);
-    float* wb = reinterpret_cast<float*>(ws + L.wb[l]);
-    float* bs = reinterpret_cast<float*>(ws + L.bias[l]);
-    PK.job[PK.n++] = PackJob{params_flat_d + L.w_off[l], wf, L.dim[l + 1], L.dim[l], 0, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + L.w_off[l], wb, L.dim[l + 1], L.dim[l], 1, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + L.b_off[l], bs, L.dim[l + 1], L.dim[l], 0, 1, 1, 0, 0};
-    A.wf[l] = wf; Bw.wb[l] = wb; A.bias[l] = bs;
-    A.mask[l] = (l < L.nl - 1 && mask_bits_d) ? mask_bits_d[l] : nullptr;
-    A.keep[l] = l < L.nl - 1 ? c->net.keep[l] : 1.f;
-  }
-  A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
-  A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
-  A.mls = c->max_log_std;
-  A.act = c->act;
-  Bw.g_sample = g_sample_d; Bw.g_mean = g_mean_d; Bw.g_log_std = g_log_std_d; Bw.grad_x = grad_x_d;
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdx_kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bwd));
-  hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  hipLaunchKernelGGL(pm_mlp_bwdx_kernel, dim3((c->B + 15) / 16), dim3(PM_NT), L.lds_bwd, s, Bw);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// BNN training step
-// ---------------------------------------------------------------------------
-struct pmbrl_bnn_plan {
-  pmbrl_bnn_config cfg;
-  int device, nl, LD, nwg, sum_h, n_params;
-  int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
-  int w_off[PM_MAXL], b_off[PM_MAXL], lp_poff[PM_MAXL], lp_off[PM_MAXL], has_drop[PM_MAXL];
-  size_t off_wf[PM_MAXL], off_wb[PM_MAXL], off_bias[PM_MAXL], off_actT[PM_MAXL], off_gT[PM_MAXL];
-  size_t off_part_lp, off_part_loss, off_part, off_reg_part, ws_bytes, lds;
-  int part_stride, n_dw_blocks, dw_wave_first[PM_DW_NW + 1];
-  DwBlock* dw_blocks_d;
-  // fixed-rate Bernoulli layers (has_drop[l] == 2): noise_off / noise_h count the dropout layers of EITHER kind (the
-  // u / bvar blocks), lp_off / sum_h the concrete ones (the logit gradients); keep_d[l]: the units' keep probabilities
-  int noise_off[PM_MAXL], noise_h, any_bern;
-  float* keep_d[PM_MAXL];
-  float* keep_all_d;
-};
-
-// the instances of a plan: those without a Bernoulli layer are the ones they were
-static const void* bnn_fwd_bwd_fn(const pmbrl_bnn_plan* p) {
-  if (p->any_bern)
-    return p->cfg.act ? reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<true, true>)
-                      : reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<false, true>);
-  return p->cfg.act ? reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<true>) : reinterpret_cast<const void*>(&pm_bnn_fwd_bwd<false>);
-}
-static void bnn_launch_fwd_bwd(const pmbrl_bnn_plan* p, hipStream_t s, const BnnArgs& A) {
-  if (p->any_bern) {
-    if (A.act) hipLaunchKernelGGL((pm_bnn_fwd_bwd<true, true>), dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-    else hipLaunchKernelGGL((pm_bnn_fwd_bwd<false, true>), dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-  } else {
-    if (A.act) hipLaunchKernelGGL(pm_bnn_fwd_bwd<true>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-    else hipLaunchKernelGGL(pm_bnn_fwd_bwd<false>, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-  }
-}
-
-extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pmbrl_bnn_plan** out) {
-  if (!cfg || !out) return fail(-1, "null argument");
-  const pmbrl_mlp& m = cfg->net;
-  if (m.n_layers < 2 || m.n_layers > PM_MAXL) return fail(-2, "bnn: 2..8 layers");
-  if (cfg->M < 1 || cfg->N < 1) return fail(-2, "bnn: M, N must be >= 1");
-  if (cfg->loss_kind == 2) {
-    const int n = cfg->n_components;
-    if (n < 2 || n > PMBRL_MAX_COMP) return fail(-2, "bnn: mixture loss needs 2..PMBRL_MAX_COMP components");
-    if ((m.dims[m.n_layers] - 1) % n || ((m.dims[m.n_layers] - 1) / n - 1) % 2 || (m.dims[m.n_layers] - 1) / n < 3)
-      return fail(-2, "bnn: mixture head must be (2 n_out + 1) n_components + 1 wide");
-  } else if (m.dims[m.n_layers] % 2) return fail(-2, "bnn: the output layer must be 2 x n_out wide");
-  pmbrl_bnn_plan* p = new pmbrl_bnn_plan();
-  p->cfg = *cfg;
-  p->device = device;
-  p->nl = m.n_layers;
-  int maxnt = 1, po = 0;
-  p->sum_h = 0;
-  p->noise_h = 0;
-  p->any_bern = 0;
-  for (int l = 0; l < p->nl - 1; ++l) {
-    if (cfg->drop_kind[l] != PMBRL_DROP_BY_TEMPERATURE && cfg->drop_kind[l] != PMBRL_DROP_BERNOULLI) {
-      delete p;
-      return fail(-2, "bnn: unknown dropout kind (0: by temperature, PMBRL_DROP_BERNOULLI are offered)");
-    }
-    if (cfg->drop_kind[l] == PMBRL_DROP_BERNOULLI && !(cfg->bern_keep[l] > 0.f && cfg->bern_keep[l] <= 1.f)) {
-      delete p;
-      return fail(-2, "bnn: the keep probability of a Bernoulli layer must lie in (0, 1]");
-    }
-  }
-  for (int i = 0; i <= p->nl; ++i) {
-    if (m.dims[i] < 1 || m.dims[i] > 16 * 64) { delete p; return fail(-2, "bnn: layer width out of range"); }
-    p->dim[i] = m.dims[i];
-    p->nt[i] = (m.dims[i] + 15) / 16;
-    maxnt = std::max(maxnt, p->nt[i]);
-  }
-  for (int l = 0; l < p->nl; ++l) {
-    p->w_off[l] = po; po += p->dim[l + 1] * p->dim[l];
-    p->b_off[l] = po; po += p->dim[l + 1];
-    p->has_drop[l] = 0;
-    if (l < p->nl - 1) {
-      if (cfg->drop_kind[l] == PMBRL_DROP_BERNOULLI) p->has_drop[l] = 2;
-      else if (cfg->temperature[l] > 0.f) p->has_drop[l] = 1;
-    }
-    p->lp_poff[l] = po;
-    p->lp_off[l] = p->sum_h;
-    p->noise_off[l] = p->noise_h;
-    if (p->has_drop[l] == 1) { po += p->dim[l + 1]; p->sum_h += p->dim[l + 1]; }
-    if (p->has_drop[l]) p->noise_h += p->dim[l + 1];
-    if (p->has_drop[l] == 2) p->any_bern = 1;
-  }
-  p->n_params = po;
-  p->LD = maxnt * 16 + 8;
-  p->nwg = (cfg->M + 15) / 16;
-  if (cfg->act != PMBRL_ACT_RELU && cfg->act != PMBRL_ACT_TANH && cfg->act != PMBRL_ACT_SILU) {
-    delete p;
-    return fail(-2, "bnn: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
-  }
-  p->lds = pm_bnn_lds_floats(p->nl, p->LD, cfg->act) * sizeof(float);
-  if (p->lds > 160 * 1024) { delete p; return fail(-3, "bnn: network too wide / deep for the fused training step's LDS budget"); }
-  size_t off = 0;
-  auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
-  for (int l = 0; l < p->nl; ++l) {
-    p->off_wf[l] = take((size_t)p->nt[l + 1] * p->nt[l] * 256 * sizeof(float));
-    p->off_wb[l] = take((size_t)p->nt[l + 1] * p->nt[l] * 256 * sizeof(float));
-    p->off_bias[l] = take((size_t)p->nt[l + 1] * 16 * sizeof(float));
-    p->off_actT[l] = take((size_t)p->nwg * p->nt[l] * 16 * 16 * sizeof(float));
-    p->off_gT[l] = take((size_t)p->nwg * p->nt[l + 1] * 16 * 16 * sizeof(float));
-  }
-  p->part_stride = (p->n_params + 3) / 4 * 4;
-  p->off_part_lp = take((size_t)p->nwg * std::max(p->sum_h, 1) * sizeof(float));
-  p->off_part_loss = take((size_t)p->nwg * sizeof(float));
-  p->off_part = take((size_t)p->nwg * p->part_stride * sizeof(float));
-  p->off_reg_part = take(1024 * sizeof(float));
-  p->ws_bytes = off;
-  HIPCHK(hipSetDevice(device));
-  std::vector<DwBlock> blocks;
-  p->n_dw_blocks = build_dw_blocks(p->nl, p->nt, blocks, p->dw_wave_first);
-  HIPCHK(hipMalloc(&p->dw_blocks_d, blocks.size() * sizeof(DwBlock)));
-  HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
-  if (p->any_bern) {
-    // the Bernoulli layers' keep probabilities, one per unit (a scalar rate repeated; the padding of the last tile keeps 1)
-    std::vector<float> keep;
-    size_t koff[PM_MAXL] = {0};
-    for (int l = 0; l < p->nl - 1; ++l)
-      if (p->has_drop[l] == 2) {
-        koff[l] = keep.size();
-        keep.resize(keep.size() + (size_t)p->nt[l + 1] * 16, 1.f);
-        for (int j = 0; j < p->dim[l + 1]; ++j) keep[koff[l] + j] = cfg->bern_keep[l];
-      }
-    HIPCHK(hipMalloc(&p->keep_all_d, keep.size() * sizeof(float)));
-    HIPCHK(hipMemcpy(p->keep_all_d, keep.data(), keep.size() * sizeof(float), hipMemcpyHostToDevice));
-    for (int l = 0; l < p->nl - 1; ++l)
-      if (p->has_drop[l] == 2) p->keep_d[l] = p->keep_all_d + koff[l];
-  }
-  HIPCHK(hipFuncSetAttribute(bnn_fwd_bwd_fn(p), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds));
-  *out = p;
-  return 0;
-}
-
-extern "C" void pmbrl_bnn_plan_destroy(pmbrl_bnn_plan* p) {
-  if (!p) return;
-  if (p->dw_blocks_d) (void)hipFree(p->dw_blocks_d);
-  if (p->keep_all_d) (void)hipFree(p->keep_all_d);
-  delete p;
-}
-
-extern "C" int pmbrl_bnn_plan_set_unit_keep(pmbrl_bnn_plan* p, int32_t layer, const float* keep_h, int32_t n) {
-  if (!p || !keep_h) return fail(-1, "null argument");
-  if (layer < 0 || layer >= p->nl - 1 || p->has_drop[layer] != 2)
-    return fail(-2, "pmbrl_bnn_plan_set_unit_keep: not a Bernoulli layer of this plan");
-  if (n != p->dim[layer + 1]) return fail(-2, "pmbrl_bnn_plan_set_unit_keep: n must be the layer's width");
-  for (int j = 0; j < n; ++j)
-    if (!(keep_h[j] > 0.f && keep_h[j] <= 1.f))
-      return fail(-2, "pmbrl_bnn_plan_set_unit_keep: keep probabilities must lie in (0, 1]");
-  HIPCHK(hipSetDevice(p->device));
-  HIPCHK(hipDeviceSynchronize());      // (a step of this plan may still be reading the old values)
-  HIPCHK(hipMemcpy(p->keep_d[layer], keep_h, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-  return 0;
-}
-extern "C" size_t pmbrl_bnn_plan_workspace_bytes(const pmbrl_bnn_plan* p) { return p ? p->ws_bytes : 0; }
-extern "C" int64_t pmbrl_bnn_plan_n_params(const pmbrl_bnn_plan* p) { return p ? p->n_params : 0; }
-
-extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* workspace_d, const float* Xn_d,
-                                      const float* Yn_d, const int32_t* idx_d, const float* params_flat_d,
-                                      const float* u_d, const float* bvar_d, float* grad_flat_d,
-                                      float* loss_out_d, const float* row_weight_d, float* row_logprob_d,
-                                      int32_t terms);
-extern "C" int pmbrl_bnn_loss_grad(pmbrl_bnn_plan* p, void* stream, void* workspace_d, const float* Xn_d,
-                                   const float* Yn_d, const int32_t* idx_d, const float* params_flat_d,
-                                   const float* u_d, const float* bvar_d, float* grad_flat_d,
-                                   float* loss_out_d) {
-  return pmbrl_bnn_loss_grad_ex(p, stream, workspace_d, Xn_d, Yn_d, idx_d, params_flat_d, u_d, bvar_d,
-                                grad_flat_d, loss_out_d, nullptr, nullptr, 3);
-}
-
-extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* workspace_d, const float* Xn_d,
-                                      const float* Yn_d, const int32_t* idx_d, const float* params_flat_d,
-                                      const float* u_d, const float* bvar_d, float* grad_flat_d,
-                                      float* loss_out_d, const float* row_weight_d, float* row_logprob_d,
-                                      int32_t terms) {
-  if (!p || !workspace_d || !Xn_d || !Yn_d || !idx_d || !params_flat_d || !grad_flat_d || !loss_out_d)
-    return fail(-1, "null argument");
-  if (!(terms & 3)) return fail(-1, "bnn: terms must select the likelihood (1), the regulariser (2) or both");
-  const bool lik = (terms & 1) != 0, regt = (terms & 2) != 0;
-  if (lik && ((p->sum_h > 0 && !u_d) || (p->noise_h > 0 && !bvar_d))) return fail(-1, "bnn: dropout layers need u and bvar");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipSetDevice(p->device));
-  char* ws = static_cast<char*>(workspace_d);
-  PackArgs PK;
-  PK.wflag = nullptr;
-  PK.gen = 0;
-  PK.n = 0;
-  PK.status = nullptr;
-  BnnArgs A;
-  memset(&A, 0, sizeof(A));
-  A.M = p->cfg.M; A.nl = p->nl; A.LD = p->LD; A.n_out = p->dim[p->nl] / 2; A.nwg = p->nwg;
-  A.gmm_n = 0;
-  if (p->cfg.loss_kind == 2) {
-    A.gmm_n = p->cfg.n_components;
-    A.n_out = ((p->dim[p->nl] - 1) / A.gmm_n - 1) / 2;
-  }
-  A.n_in = p->dim[0]; A.sum_h = p->sum_h;
-  A.act = p->cfg.act;
-  for (int i = 0; i <= p->nl; ++i) { A.dim[i] = p->dim[i]; A.nt[i] = p->nt[i]; }
-  for (int l = 0; l < p->nl; ++l) {
-    float* wf = reinterpret_cast<float*>(ws + p->off_wf[l]);
-    float* wb = reinterpret_cast<float*>(ws + p->off_wb[l]);
-    float* bs = reinterpret_cast<float*>(ws + p->off_bias[l]);
-    PK.job[PK.n++] = PackJob{params_flat_d + p->w_off[l], wf, p->dim[l + 1], p->dim[l], 0, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + p->w_off[l], wb, p->dim[l + 1], p->dim[l], 1, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + p->b_off[l], bs, p->dim[l + 1], p->dim[l], 0, 1, 1, 0, 0};
-    A.wf[l] = wf; A.wb[l] = wb; A.bias[l] = bs;
-    A.actT[l] = reinterpret_cast<float*>(ws + p->off_actT[l]);
-    A.gT[l] = reinterpret_cast<float*>(ws + p->off_gT[l]);
-    A.lp_off[l] = p->lp_off[l];
-    if (p->has_drop[l] == 1) {
-      A.logit_p[l] = params_flat_d + p->lp_poff[l];
-      A.u[l] = u_d + (size_t)p->cfg.M * p->noise_off[l];
-      A.bvar[l] = bvar_d + (size_t)p->cfg.M * p->noise_off[l];
-      A.inv_temp[l] = 1.f / p->cfg.temperature[l];
-    } else if (p->has_drop[l] == 2) {
-      A.keep[l] = p->keep_d[l];
-      A.bvar[l] = bvar_d + (size_t)p->cfg.M * p->noise_off[l];
-    }
-  }
-  A.X = Xn_d; A.Y = Yn_d; A.idx = idx_d;
-  A.mls = p->cfg.max_log_std;
-  A.mse = p->cfg.loss_kind == 1;
-  A.row_w = row_weight_d; A.row_lp = row_logprob_d;
-  A.inv_M = 1.f / (float)p->cfg.M;
-  A.part_lp = reinterpret_cast<float*>(ws + p->off_part_lp);
-  A.part_loss = reinterpret_cast<float*>(ws + p->off_part_loss);
-  if (!lik) {
-    HIPCHK(hipMemsetAsync(grad_flat_d, 0, (size_t)p->n_params * sizeof(float), s));
-  } else {
-  hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  bnn_launch_fwd_bwd(p, s, A);
-  // dW / db of every layer: the policy-gradient GEMM over the same stash layout (one 16-row chunk per split)
-  DwArgs W;
-  memset(&W, 0, sizeof(W));
-  W.nl = p->nl; W.nsplit = p->nwg; W.n_chunks = p->nwg; W.chunks_per_split = 1;
-  W.RT = 1; W.Rw = 16; W.n_params = p->n_params; W.part_stride = p->part_stride;
-  for (int i = 0; i <= p->nl; ++i) { W.dim[i] = p->dim[i]; W.nt[i] = p->nt[i]; }
-  for (int l = 0; l < p->nl; ++l) {
-    W.w_off[l] = p->w_off[l]; W.b_off[l] = p->b_off[l];
-    W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l];
-  }
-  W.blocks = p->dw_blocks_d;
-  for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first[w];
-  W.part = reinterpret_cast<float*>(ws + p->off_part);
-  hipLaunchKernelGGL(pm_dw_kernel, dim3(p->nwg), dim3(PM_DW_NT), 0, s, W);
-  hipLaunchKernelGGL(pm_dw_reduce, dim3((p->n_params + 255) / 256), dim3(512), 0, s, W.part, p->nwg, p->n_params,
-                     p->part_stride, grad_flat_d, (const int*)nullptr, 0, 1);
-  }
-  BnnFinishArgs Fa;
-  memset(&Fa, 0, sizeof(Fa));
-  Fa.nl = p->nl; Fa.nwg = p->nwg; Fa.sum_h = p->sum_h; Fa.N = p->cfg.N;
-  for (int i = 0; i <= p->nl; ++i) Fa.dim[i] = p->dim[i];
-  for (int l = 0; l < p->nl; ++l) {
-    Fa.w_off[l] = p->w_off[l]; Fa.b_off[l] = p->b_off[l]; Fa.lp_poff[l] = p->lp_poff[l]; Fa.lp_off[l] = p->lp_off[l];
-    Fa.has_drop[l] = p->has_drop[l];
-    Fa.keep[l] = p->keep_d[l];
-    Fa.reg_scale[l] = p->cfg.reg_scale[l]; Fa.drop_reg[l] = p->cfg.drop_reg[l];
-  }
-  Fa.reg_weight = regt ? p->cfg.reg_weight : 0.f; Fa.inv_M = A.inv_M;
-  Fa.reg_only = lik ? 0 : 1;
-  Fa.params = params_flat_d; Fa.grad = grad_flat_d; Fa.part_lp = A.part_lp; Fa.part_loss = A.part_loss;
-  Fa.loss_out = loss_out_d; Fa.reg_part = reinterpret_cast<float*>(ws + p->off_reg_part);
-  int nfb = 0;
-  for (int l = 0; l < p->nl - 1; ++l)
-    if (p->has_drop[l]) nfb += (p->dim[l + 1] + PM_BNN_CG - 1) / PM_BNN_CG;
-  if (nfb < 1) nfb = 1;
-  if (p->any_bern) hipLaunchKernelGGL(pm_bnn_finish<true>, dim3(nfb), dim3(256), 0, s, Fa);
-  else hipLaunchKernelGGL(pm_bnn_finish<false>, dim3(nfb), dim3(256), 0, s, Fa);
-  hipLaunchKernelGGL(pm_bnn_loss, dim3(1), dim3(64), 0, s, Fa, nfb);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// Whole training iterations of utils/train_regressor.py:113-131 (likelihood + regulariser, Adam, no clipping) in TWO
-// launches each: pm_bnn_fwd_bwd, pm_bnn_tail (pmbrl_bnn.h).  n_steps iterations are queued by ONE call: minibatch i takes
-// rows idx_all_d[i * M ..]; the dropout noise comes from the in-kernel generator (seed, first_step + i) unless recorded
-// draws are handed in (u_d / bvar_d: [n_steps][M * sum_h]).  The weights' fragments are packed once at the start of the
-// call (the parameters may have changed outside) and kept current by the tail of every iteration.
-extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* workspace_d, const float* Xn_d, const float* Yn_d,
-                                     const int32_t* idx_all_d, int32_t n_steps, float* params_flat_d, float* exp_avg_d,
-                                     float* exp_avg_sq_d, int64_t* step_d, double lr, double beta1, double beta2, double eps,
-                                     uint64_t seed, uint64_t first_step, const float* u_d, const float* bvar_d,
-                                     float* loss_out_d, float* loss_hist_d) {
-  if (!p || !workspace_d || !Xn_d || !Yn_d || !idx_all_d || !params_flat_d || !exp_avg_d || !exp_avg_sq_d || !step_d ||
-      !loss_out_d || n_steps < 1)
-    return fail(-1, "bad argument");
-  if (p->cfg.loss_kind != 0) return fail(-3, "pmbrl_bnn_train_steps: the diagonal-Gaussian likelihood only (use pmbrl_bnn_loss_grad_ex)");
-  if ((u_d == nullptr) != (bvar_d == nullptr)) return fail(-1, "bnn: u and bvar come together");
-  hipStream_t s = (hipStream_t)stream;
-  HIPCHK(hipSetDevice(p->device));
-  char* ws = static_cast<char*>(workspace_d);
-  PackArgs PK;
-  PK.wflag = nullptr; PK.gen = 0; PK.n = 0; PK.status = nullptr;
-  BnnArgs A;
-  memset(&A, 0, sizeof(A));
-  A.M = p->cfg.M; A.nl = p->nl; A.LD = p->LD; A.n_out = p->dim[p->nl] / 2; A.nwg = p->nwg;
-  A.n_in = p->dim[0]; A.sum_h = p->sum_h;
-  A.act = p->cfg.act;
-  BnnTailArgs T;
-  memset(&T, 0, sizeof(T));
-  T.nl = p->nl; T.n_chunks = p->nwg; T.sum_h = p->sum_h; T.N = p->cfg.N;
-  int units = 0;
-  for (int i = 0; i <= p->nl; ++i) { A.dim[i] = T.dim[i] = p->dim[i]; A.nt[i] = T.nt[i] = p->nt[i]; }
-  for (int l = 0; l < p->nl; ++l) {
-    float* wf = reinterpret_cast<float*>(ws + p->off_wf[l]);
-    float* wb = reinterpret_cast<float*>(ws + p->off_wb[l]);
-    float* bs = reinterpret_cast<float*>(ws + p->off_bias[l]);
-    PK.job[PK.n++] = PackJob{params_flat_d + p->w_off[l], wf, p->dim[l + 1], p->dim[l], 0, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + p->w_off[l], wb, p->dim[l + 1], p->dim[l], 1, 1, 0, 0, 0};
-    PK.job[PK.n++] = PackJob{params_flat_d + p->b_off[l], bs, p->dim[l + 1], p->dim[l], 0, 1, 1, 0, 0};
-    A.wf[l] = wf; A.wb[l] = wb; A.bias[l] = bs;
-    T.wf[l] = wf; T.wb[l] = wb; T.bias[l] = bs;
-    A.actT[l] = reinterpret_cast<float*>(ws + p->off_actT[l]);
-    A.gT[l] = reinterpret_cast<float*>(ws + p->off_gT[l]);
-    T.actT[l] = A.actT[l]; T.gT[l] = A.gT[l];
-    A.lp_off[l] = T.lp_off[l] = p->lp_off[l];
-    T.w_off[l] = p->w_off[l]; T.b_off[l] = p->b_off[l]; T.lp_poff[l] = p->lp_poff[l];
-    T.has_drop[l] = p->has_drop[l];
-    T.keep[l] = p->keep_d[l];
-    T.reg_scale[l] = p->cfg.reg_scale[l]; T.drop_reg[l] = p->cfg.drop_reg[l];
-    T.unit0[l] = units;
-    units += p->nt[l];
-    if (p->has_drop[l] == 1) {
-      A.logit_p[l] = params_flat_d + p->lp_poff[l];
-      A.inv_temp[l] = 1.f / p->cfg.temperature[l];
-    } else if (p->has_drop[l] == 2) {
-      A.keep[l] = p->keep_d[l];
-    }
-  }
-  T.unit0[p->nl] = units;
-  if (units > 512) return fail(-3, "pmbrl_bnn_train_steps: network too wide for the fused tail");
-  A.X = Xn_d; A.Y = Yn_d;
-  A.mls = p->cfg.max_log_std;
-  A.inv_M = T.inv_M = 1.f / (float)p->cfg.M;
-  A.part_lp = reinterpret_cast<float*>(ws + p->off_part_lp);
-  A.part_loss = reinterpret_cast<float*>(ws + p->off_part_loss);
-  T.part_lp = A.part_lp; T.part_loss = A.part_loss; T.n_part_loss = p->nwg;
-  T.reg_weight = p->cfg.reg_weight;
-  T.params = params_flat_d; T.m = exp_avg_d; T.v = exp_avg_sq_d;
-  T.reg_part = reinterpret_cast<float*>(ws + p->off_reg_part);
-  T.counter = reinterpret_cast<unsigned*>(ws + p->off_reg_part) + 1000;
-  T.step = reinterpret_cast<long long*>(step_d);
-  T.lr = (float)lr; T.b1 = (float)beta1; T.b2 = (float)beta2; T.eps = (float)eps;
-  T.ln_b1 = log(beta1); T.ln_b2 = log(beta2);
-  A.rng = u_d ? 0 : 1;
-  A.prof = getenv("PMBRL_BNN_PROF") ? reinterpret_cast<long long*>(ws + p->off_reg_part) + 256 : nullptr;      // (debugging: stamps at floats 512.. of the scratch)
-  A.rng_k0 = (unsigned)seed; A.rng_k1 = (unsigned)(seed >> 32);
-  HIPCHK(hipMemsetAsync(T.counter, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(pm_pack_all, dim3(32, PK.n), dim3(256), 0, s, PK);
-  const size_t noise = (size_t)p->cfg.M * p->noise_h;
-  for (int i = 0; i < n_steps; ++i) {
-    A.idx = idx_all_d + (size_t)i * p->cfg.M;
-    A.rng_step = (unsigned)(first_step + (uint64_t)i);
-    for (int l = 0; l < p->nl; ++l)
-      if (p->has_drop[l] && u_d) {
-        A.u[l] = u_d + (size_t)i * noise + (size_t)p->cfg.M * p->noise_off[l];
-        A.bvar[l] = bvar_d + (size_t)i * noise + (size_t)p->cfg.M * p->noise_off[l];
-      }
-    T.loss_out = loss_hist_d ? loss_hist_d + (size_t)3 * i : loss_out_d;
-    bnn_launch_fwd_bwd(p, s, A);
-    if (p->any_bern) hipLaunchKernelGGL(pm_bnn_tail<true>, dim3(units), dim3(PM_BNT_NT), 0, s, T);
-    else hipLaunchKernelGGL(pm_bnn_tail<false>, dim3(units), dim3(PM_BNT_NT), 0, s, T);
-  }
-  if (loss_hist_d)
-    HIPCHK(hipMemcpyAsync(loss_out_d, loss_hist_d + (size_t)3 * (n_steps - 1), 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// gradient all-reduce: RCCL through dlopen (no link-time dependency)
-// ---------------------------------------------------------------------------
-#include <dlfcn.h>
-namespace {
-struct RcclId { char internal[PMBRL_COMM_ID_BYTES]; };          // = ncclUniqueId (rccl.h:43)
-struct RcclApi {
-  void* lib = nullptr;
-  int (*GetUniqueId)(RcclId*) = nullptr;
-  int (*CommInitRank)(void**, int, RcclId, int) = nullptr;      // ncclCommInitRank(comm*, nranks, id BY VALUE, rank)
-  int (*AllReduce)(const void*, void*, size_t, int, int, void*, hipStream_t) = nullptr;
-  int (*CommDestroy)(void*) = nullptr;
-  int (*CommCount)(void*, int*) = nullptr;                       // ncclCommCount(comm, int* count)
-  const char* (*GetErrorString)(int) = nullptr;
-};
-RcclApi g_rccl;
-int rccl_load() {
-  if (g_rccl.lib) return 0;
-  void* h = dlopen("librccl.so.1", RTLD_NOW | RTLD_NOLOAD);      // the copy torch.distributed already loaded
-  if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_NOLOAD);
-  if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-  if (!h) h = dlopen("librccl.so", RTLD_NOW | RTLD_LOCAL);
-  if (!h) h = dlopen("/opt/rocm/lib/librccl.so.1", RTLD_NOW | RTLD_LOCAL);
-  if (!h) return fail(-4, std::string("librccl not found: ") + dlerror());
-  RcclApi a;
-  a.lib = h;
-  a.GetUniqueId = reinterpret_cast<decltype(a.GetUniqueId)>(dlsym(h, "ncclGetUniqueId"));
-  a.CommInitRank = reinterpret_cast<decltype(a.CommInitRank)>(dlsym(h, "ncclCommInitRank"));
-  a.AllReduce = reinterpret_cast<decltype(a.AllReduce)>(dlsym(h, "ncclAllReduce"));
-  a.CommDestroy = reinterpret_cast<decltype(a.CommDestroy)>(dlsym(h, "ncclCommDestroy"));
-  a.CommCount = reinterpret_cast<decltype(a.CommCount)>(dlsym(h, "ncclCommCount"));
-  a.GetErrorString = reinterpret_cast<decltype(a.GetErrorString)>(dlsym(h, "ncclGetErrorString"));
-  if (!a.GetUniqueId || !a.CommInitRank || !a.AllReduce || !a.CommDestroy)
-    return fail(-4, "librccl lacks ncclGetUniqueId / ncclCommInitRank / ncclAllReduce / ncclCommDestroy");
-  g_rccl = a;
-  return 0;
-}
-int rccl_fail(const char* what, int rc) {
-  return fail(-200 - rc, std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(rc) : "RCCL error"));
-}
-}  // namespace
-struct pmbrl_comm {
-  void* comm;
-  int rank, nranks, device;
-};
-extern "C" int pmbrl_comm_unique_id(void* id_out) {
-  if (!id_out) return fail(-1, "null argument");
-  if (int rc = rccl_load()) return rc;
-  RcclId id;
-  if (int rc = g_rccl.GetUniqueId(&id)) return rccl_fail("ncclGetUniqueId", rc);
-  memcpy(id_out, &id, sizeof(id));
-  return 0;
-}
-extern "C" int pmbrl_comm_init(const void* id_in, int32_t rank, int32_t nranks, int32_t device, pmbrl_comm** out) {
-  if (!id_in || !out || nranks < 1 || rank < 0 || rank >= nranks) return fail(-1, "bad argument");
-  if (int rc = rccl_load()) return rc;
-  HIPCHK(hipSetDevice(device));
-  RcclId id;
-  memcpy(&id, id_in, sizeof(id));
-  void* c = nullptr;
-  if (int rc = g_rccl.CommInitRank(&c, nranks, id, rank)) return rccl_fail("ncclCommInitRank", rc);
-  *out = new pmbrl_comm{c, rank, nranks, device};
-  return 0;
-}
-extern "C" int pmbrl_allreduce_sum(pmbrl_comm* comm, void* stream, float* buf_d, int64_t n) {
-  if (!comm || !buf_d || n < 0) return fail(-1, "bad argument");
-  // ncclFloat32 = 7, ncclSum = 0 (rccl.h: ncclDataType_t, ncclRedOp_t)
-  if (int rc = g_rccl.AllReduce(buf_d, buf_d, (size_t)n, 7, 0, comm->comm, (hipStream_t)stream))
-    return rccl_fail("ncclAllReduce", rc);
-  return 0;
-}
-extern "C" int pmbrl_comm_count(pmbrl_comm* comm, int32_t* nranks_out) {
-  if (!comm || !nranks_out) return fail(-1, "null argument");
-  if (!g_rccl.CommCount) return fail(-4, "librccl lacks ncclCommCount");
-  int n = 0;
-  if (int rc = g_rccl.CommCount(comm->comm, &n)) return rccl_fail("ncclCommCount", rc);
-  *nranks_out = n;
-  return 0;
-}
-extern "C" void pmbrl_comm_destroy(pmbrl_comm* comm) {
-  if (!comm) return;
-  if (g_rccl.CommDestroy) (void)g_rccl.CommDestroy(comm->comm);
-  delete comm;
-}
-
-static int pm_coll_rccl(void* ctx, void* stream, double* buf_d, int64_t n) {
-  pmbrl_comm* comm = static_cast<pmbrl_comm*>(ctx);
-  return g_rccl.AllReduce(buf_d, buf_d, (size_t)n, 8 /* ncclDouble */, 0 /* ncclSum */, comm->comm, (hipStream_t)stream);
-}
-extern "C" int pmbrl_plan_set_comm(pmbrl_plan* plan, pmbrl_comm* comm) {
-  if (!plan || !comm) return fail(-1, "null argument");
-  plan->coll = pm_coll_rccl;
-  plan->coll_ctx = comm;
-  return 0;
-}
-extern "C" int pmbrl_plan_set_collective(pmbrl_plan* plan, pmbrl_collective_fn fn, void* ctx) {
-  if (!plan) return fail(-1, "null argument");
-  plan->coll = fn;
-  plan->coll_ctx = ctx;
-  return 0;
-}
-
-extern "C" int pmbrl_plan_set_grad_comm(pmbrl_plan* plan, pmbrl_comm* comm, pmbrl_p2p* p2p) {
-  if (!plan) return fail(-1, "null argument");
-  if (comm && p2p) return fail(-1, "pmbrl_plan_set_grad_comm: at most one of the two transports");
-  HIPCHK(hipSetDevice(plan->device));
-  // whatever follows, the plan first lets go of the transport it had (a refusal leaves it without one)
-  for (int k = 0; k < 2; ++k) replay_drop(plan, k);     // (a recording holds the transport it was made with)
-  if (plan->tail_buf_d) {
-    HIPCHK(hipDeviceSynchronize());                       // (calls still queued may read it)
-    HIPCHK(hipFree(plan->tail_buf_d));
-    plan->tail_buf_d = nullptr;
-  }
-  plan->grad_comm = nullptr;
-  plan->grad_p2p = nullptr;
-  plan->tail_err_d = nullptr;
-  // (a plan of LOCAL groups that runs the span form with one rank -- plan_layout: groups beyond the CU count -- is fine)
-  if ((comm || p2p) && plan->span && plan->cfg.mm_span_ranks > 1)
-    return fail(-3, "pmbrl_plan_set_grad_comm: not offered with moment-matching groups spread over ranks (mm_span_rows)");
-  int rank = 0, world = 1;
-  int* err_d = nullptr;
-  const size_t n = plan->pol.n_params;
-  if (comm) { rank = comm->rank; world = comm->nranks; }
-  if (p2p) {
-    size_t cap = 0;
-    pm_p2p_describe(p2p, &rank, &world, &cap, &err_d);
-    if ((n + 2) * sizeof(float) > cap)
-      return fail(-2, "pmbrl_plan_set_grad_comm: the flat gradient is larger than the peer-to-peer slots (max_bytes of pmbrl_p2p_create)");
-  }
-  if (!comm && !p2p) return 0;
-  const size_t nx = (n + 2 + 3) / 4 * 4 + (size_t)world;
-  HIPCHK(hipMalloc(&plan->tail_buf_d, nx * sizeof(float)));
-  HIPCHK(hipMemset(plan->tail_buf_d, 0, nx * sizeof(float)));
-  plan->grad_comm = comm;
-  plan->grad_p2p = p2p;
-  plan->tail_rank = rank;
-  plan->tail_world = world;
-  plan->tail_err_d = err_d;
-  return 0;
-}
-
-extern "C" int pmbrl_weighted_sum(void* stream, const float* a_d, const float* w_d, int64_t n,
-                                  float* out_d) {
-  if (!a_d || !w_d || !out_d || n < 0) return fail(-1, "bad argument");
-  launch_weighted_sum((hipStream_t)stream, a_d, w_d, n, out_d, nullptr, 0);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int pmbrl_weighted_sum_steps(void* stream, const float* a_d, const float* w_d, int64_t n_per_step,
-                                        int32_t n_steps, const int32_t* status_d, float* out_d) {
-  if (!a_d || !w_d || !out_d || n_per_step < 0 || n_steps < 0) return fail(-1, "bad argument");
-  launch_weighted_sum((hipStream_t)stream, a_d, w_d, (long long)n_per_step * n_steps, out_d, status_d, n_per_step);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int pmbrl_clip_adam(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
-                               float* exp_avg_sq_d, int64_t n, int64_t step, double lr, double beta1,
-                               double beta2, double eps, double max_norm, float* norm_out_d) {
-  if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || n < 1 || step < 1)
-    return fail(-1, "bad argument");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
-  const int np = pm_norm_blocks(n);
-  // without clipping and without a norm to report there is nothing for the norm kernel to do
-  const bool need_norm = max_norm > 0.0 || norm_out_d != nullptr;
-  if (need_norm)
-    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
-                       (long long)n, (const int*)nullptr, 0, (long long*)nullptr, 0);
-  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
-                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, need_norm ? np : 0, (float)lr, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                     (float)bc1, (float)sqrt(bc2), (float)max_norm, norm_out_d, (const long long*)nullptr, 0, 0.0, 0.0, lr,
-                     (float*)nullptr, 0);
-  HIPCHK(hipGetLastError());
-  return 0;
-}
-
-extern "C" int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
-                                       float* exp_avg_sq_d, int64_t n, int64_t* step_d, double lr,
-                                       double beta1, double beta2, double eps, double max_norm,
-                                       float* norm_out_d, const int32_t* status_d, int32_t expect) {
-  if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || !step_d || !status_d || n < 1)
-    return fail(-1, "bad argument");
-  return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, lr, beta1, beta2, eps, max_norm,
-                                norm_out_d, status_d, expect, false);
-}
-// ---------------------------------------------------------------------------
-// test hook: y = x W^T + b through gemm_tiles / gemm_narrow
+// test hook: y = x W^T + b through gemm_tiles / gemm_narrow, with the fragment packers only it launches.  gemm_tiles<RT> and
+// gemm_narrow<RT> are not __forceinline__, so how the compiler inlines them depends on their other users in the module:
+// the hook is compiled in this object, with the general family's exact-fp32 instances, to keep the code it is there to test.
 // ---------------------------------------------------------------------------
 template <int RT>
 __global__ __launch_bounds__(PM_NT, 1) void pm_debug_linear_kernel(const float* x, const float* wf,

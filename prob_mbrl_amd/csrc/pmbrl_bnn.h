@@ -12,7 +12,7 @@
 // pm_bnn_fwd_bwd: a workgroup (PM_NW waves) owns 16 minibatch rows; all layer inputs and the
 // dropout derivative terms stay in LDS between the forward and the backward pass; the
 // pre-activation gradients and layer inputs are stashed feature-major, exactly the layout the
-// policy-gradient dW GEMM (pmbrl_dw.h) consumes, so dW / db come from the same kernel.
+// policy-gradient dW GEMM (pmbrl_dw_kernels.h) consumes, so dW / db come from the same kernel.
 // pm_bnn_finish adds the regulariser, reduces the dropout-logit gradients and the loss.
 #pragma once
 #include "pmbrl_dev.h"

@@ -18,7 +18,7 @@ int pm_general_split_set_attr(const pmbrl_plan* p) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_rollout_bwd<4, 2, 2>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
-    // (<4, 2, 3>: the wide layers with every 512-wide stash pre-split for the dW GEMM -- pmbrl_dw.h, pm_dw_wide_pre_kernel)
+    // (<4, 2, 3>: the wide layers with every 512-wide stash pre-split for the dW GEMM -- pmbrl_dw_kernels.h, pm_dw_wide_pre_kernel)
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_rollout_fwd<4, 2, 3>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_rollout_bwd<4, 2, 3>),

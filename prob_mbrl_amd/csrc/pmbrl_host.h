@@ -1,8 +1,20 @@
-// Host-side declarations shared by the translation units of libpmbrl_hip.so.  The library is built from
-// several .hip files so that the kernel families compile in parallel: pmbrl.hip (C ABI, plan, small kernels,
-// general kernel family), pmbrl_general_split.hip (the general family on split operands), pmbrl_fast_f32.hip
-// (latency-optimised sweeps, exact fp32 MFMA), pmbrl_fast_split.hip (the same on split bf16 / fp16 operands; compiled
-// once per precision), pmbrl_reg.hip (register-resident family) and pmbrl_p2p.hip (peer-to-peer transport): seven objects.
+// Host-side declarations shared by the translation units of libpmbrl_hip.so: the plan, the records the launchers take
+// and the launchers themselves.  A kernel is compiled in exactly one object, the one that holds its launcher; another
+// object that needs it calls the launcher declared here.  The objects:
+//   pmbrl.hip                error string, version, build id, graph capture, the rollout plan, argument assembly and the two
+//                            rollout calls, with the kernels only they launch (the general family in exact fp32, external
+//                            moment matching, the reward kernels, pm_pack_all), and the GEMM test hook
+//   pmbrl_general_split.hip  the general family on split operands
+//   pmbrl_general_act.hip    the general family for networks that are not ReLU
+//   pmbrl_fast_f32.hip       latency-optimised sweeps, exact fp32 MFMA
+//   pmbrl_fast_split.hip     the same on split bf16 / fp16 operands; compiled once per precision (two objects)
+//   pmbrl_reg.hip            register-resident family
+//   pmbrl_dw.hip             the policy-gradient dW GEMMs
+//   pmbrl_tail.hip           mask packing / drawing, weighted sum, dW reduction, gradient norm, clip + Adam, sharded tail
+//   pmbrl_bnn.hip            BNN training step
+//   pmbrl_mlp.hip            stand-alone network evaluation
+//   pmbrl_comm.hip           RCCL through dlopen, the plan's transports (host code only)
+//   pmbrl_p2p.hip            peer-to-peer transport
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -14,6 +26,7 @@
 #include "pmbrl_dw.h"
 
 int pm_fail(int code, const std::string& msg);
+static inline int fail(int code, const std::string& msg) { return pm_fail(code, msg); }
 #define HIPCHK(expr)                                                               \
   do {                                                                             \
     hipError_t _e = (expr);                                                        \
@@ -138,6 +151,13 @@ static inline SweepForm sweep_form(const pmbrl_plan* p) {
   return p->mm_mode == 2 ? SweepForm::StepExternal : SweepForm::Whole;
 }
 
+// forget what a replay slot has recorded (pmbrl_plan_set_replay)
+static inline void replay_drop(pmbrl_plan* p, int slot) {
+  if (p->rp[slot].exec) (void)hipGraphExecDestroy(p->rp[slot].exec);
+  p->rp[slot].exec = nullptr;
+  p->rp[slot].seen = 0;
+}
+
 struct ScopedTimer {
   pmbrl_plan* p; int slot; hipStream_t s;
   ScopedTimer(pmbrl_plan* p_, int slot_, hipStream_t s_) : p(p_), slot(slot_), s(s_) {
@@ -219,6 +239,47 @@ static inline int fast_variant(int RT, const RolloutArgs& A) {
   return mmg ? PF_VAR_MMG : mm ? PF_VAR_MM : (ext ? PF_VAR_EXT : PF_VAR_LEAN);
 }
 
+// all weight / bias repacking of one forward call in ONE launch (blockIdx.y = job)
+struct PackJob {
+  const float* src;
+  float* dst;
+  int O, K, transpose, mult, is_bias;
+  int planes;   // 0: fp32 fragments of 16-wide k-blocks; 2 / 3: bf16 pieces of K32 blocks (pmbrl_split.h), mult in K32 blocks
+  int f16;      // pieces are fp16 instead of bf16
+};
+struct PackArgs {
+  int n;
+  int* wflag;       // fp16 pieces: set to `gen` when a weight is beyond +-65504 or not finite (nullptr: no check)
+  int gen;
+  int* status;      // reset to "no failure" by the same launch (nullptr: leave alone)
+  PackJob job[6 * PM_MAXL];
+};
+void pm_pack_all_launch(const PackArgs& PK, hipStream_t s);   // (pmbrl.hip)
+
+// the dW GEMMs (pmbrl_dw.hip)
+int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max = PM_DW_TN,
+                    const bool* skip = nullptr);
+int pm_dw_set_attr(const pmbrl_plan* p);
+void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s);
+void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s);   // launch k of the pipelined form
+void pm_dw_blocks_launch(const DwArgs& W, hipStream_t s);
+// the kernels around the sweeps (pmbrl_tail.hip); pm_dw_reduce's arguments are the kernel's
+#define PM_NORM_MAXB 8192      // blocks of 256 elements: gradients of up to 2 M parameters (beyond: pm_gradnorm_kernel strides)
+void pm_dw_reduce_launch(hipStream_t s, const float* part, int nsplit, int n, int stride, float* grad,
+                         const int* nvalid = nullptr, int chunks_per_step = 0, int chunks_per_split = 1, int norm_on = 0,
+                         const int* status = nullptr, int expect = 0, long long* step = nullptr, const float* loss_r = nullptr,
+                         const float* loss_w = nullptr, long long loss_n = 0, long long loss_per_step = 0);
+void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
+                         long long n_per_step);
+int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, int64_t n,
+                           int64_t* step_d, double lr, double beta1, double beta2, double eps, double max_norm,
+                           float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
+                           float* loss_out_d = nullptr, int n_loss_part = 0);
+void pm_tail_hvec_launch(hipStream_t s, float* hvec, int world, int rank, const int* status, int H);
+void pm_tail_hmin_launch(hipStream_t s, const float* hvec, int world, int* status, int H);
+void pm_tail_pack_launch(hipStream_t s, float* xb, int n, int n_loss_part, int loss_here, const int* status, const int* err);
+void pm_tail_finish_launch(hipStream_t s, const float* xb, float* g, long long n, int* status, int expect, long long* step,
+                           const int* err);
 // peer-to-peer transport (pmbrl_p2p.hip): what the fused iteration tail needs to know of one
 void pm_p2p_describe(const pmbrl_p2p* p, int* rank, int* nranks, size_t* cap_bytes, int** err_d);
 // register-resident family (pmbrl_reg.hip)

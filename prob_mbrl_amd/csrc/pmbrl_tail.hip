@@ -1,0 +1,581 @@
+// The small kernels around the sweeps and their stand-alone entry points: mask packing and drawing, the weighted sum,
+// the dW GEMM's reduction, the gradient norm, clip + Adam, and the sharded iteration tail.  pm_dw_reduce lives here and not
+// with the dW GEMMs: it leaves the norm's and the loss' partial sums and the go / no-go decision in the device globals
+// (g_norm_part, g_loss_part, g_adam_go) that pm_clip_adam_kernel and the pm_tail_* kernels read, and a device global is
+// one object's.  The rollout adjoint call (pmbrl.hip) and the BNN step (pmbrl_bnn.hip) reach them through the launchers
+// declared in pmbrl_host.h.
+#include <hip/hip_runtime.h>
+#include <math.h>
+
+#include <algorithm>
+#include <string>
+
+#include "pmbrl_host.h"
+
+__global__ void pm_pack_mask_kernel(const float* __restrict__ m, int B, int h, int ld,
+                                    uint16_t* __restrict__ bits) {
+  const int nt = (h + 15) / 16;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * nt) return;
+  const int r = i / nt, t = i - r * nt;
+  unsigned w = 0;
+  for (int j = 0; j < 16; ++j) {
+    const int f = t * 16 + j;
+    if (f < h && m[(size_t)r * ld + f] != 0.f) w |= 1u << j;
+  }
+  bits[i] = (uint16_t)w;
+}
+__global__ void pm_set_int(int* p, int v) { *p = v; }
+
+// ---------------------------------------------------------------------------
+// Dropout masks drawn on the device (pmbrl_draw_masks): bit rows straight from a counter-based generator.
+// Philox4x32-10 (Salmon et al., SC'11) keyed by the caller's seed; counter = (row, 16-unit tile, quad + 4 * stream,
+// offset): a draw depends on (seed, offset, row, unit) alone, not on the launch shape.  Stream 0: the uniform noise u;
+// stream 1: the uniform the hard Bernoulli sample is thresholded with.
+// ---------------------------------------------------------------------------
+struct DrawArgs {
+  int kind;              // 0: Bernoulli(keep) -- BDropout.update_noise, models/modules.py:40-44;  1: concrete -- :95-118
+  unsigned long long seed, offset;
+  const float* param;    // kind 0: keep probability; kind 1: logit_p  (param_len 1 or h)
+  int param_len;
+  float temp;
+  int rows, h;
+  const float *u_in, *v_in;     // [rows][h] uniforms to use instead of the generator's (nullptr: generate)
+  uint16_t* bits;        // [rows][ceil(h/16)]
+  int aux_row0, aux_rows;       // rows whose float values are also written (a module keeps its LAST draw as state)
+  float *u_out, *hard_out, *probs_out;   // [aux_rows][h] each, or nullptr
+};
+__global__ __launch_bounds__(256) void pm_draw_masks_kernel(const DrawArgs A) {
+  const int nt = (A.h + 15) / 16;
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long long)A.rows * nt) return;
+  const int r = (int)(i / nt), t = (int)(i - (long long)r * nt);
+  const unsigned k0 = (unsigned)A.seed, k1 = (unsigned)(A.seed >> 32);
+  const unsigned o0 = (unsigned)A.offset, o1 = (unsigned)(A.offset >> 32);
+  unsigned w = 0;
+  const bool aux = r >= A.aux_row0 && r < A.aux_row0 + A.aux_rows;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    unsigned ru[4], rv[4];
+    if (!A.u_in) pm_philox((unsigned)r, (unsigned)t, (unsigned)q ^ (o1 << 3), o0, k0, k1, ru);
+    if (A.kind == 1 && !A.v_in) pm_philox((unsigned)r, (unsigned)t, (unsigned)(4 + q) ^ (o1 << 3), o0, k0, k1, rv);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int f = t * 16 + q * 4 + e;
+      if (f >= A.h) continue;
+      const size_t idx = (size_t)r * A.h + f;
+      // 24-bit uniforms in [0, 1) (what torch.rand gives a float tensor)
+      const float u = A.u_in ? A.u_in[idx] : (float)(ru[e] >> 8) * (1.0f / 16777216.0f);
+      const float pr = A.param[A.param_len > 1 ? f : 0];
+      float probs;
+      bool bit;
+      if (A.kind == 0) {
+        probs = pr;
+        bit = u < pr;                                    // torch.bernoulli(p): 1 with probability p
+      } else {
+        // models/modules.py:102-114: probs = sigmoid((logit_p + log((u + 1e-7) / (1 - (u - 1e-7)))) / temp)
+        const float cp = pr + logf((u + 1e-7f) / (1.f - (u - 1e-7f)));
+        probs = 1.f / (1.f + expf(-cp / A.temp));
+        const float v = A.v_in ? A.v_in[idx] : (float)(rv[e] >> 8) * (1.0f / 16777216.0f);
+        bit = v < probs;
+      }
+      if (bit) w |= 1u << (q * 4 + e);
+      if (aux) {
+        const size_t o = (size_t)(r - A.aux_row0) * A.h + f;
+        if (A.u_out) A.u_out[o] = u;
+        if (A.hard_out) A.hard_out[o] = bit ? 1.f : 0.f;
+        if (A.probs_out) A.probs_out[o] = probs;
+      }
+    }
+  }
+  A.bits[i] = (uint16_t)w;
+}
+
+// Small reductions: per-block partial sums in a per-device scratch, finished in FIXED order
+// (bit-reproducible).  The scratch is shared by all calls on a device: calls are expected to
+// be stream-ordered (one optimisation loop per device), like the rest of a plan's work.
+#define PM_RED_MAXB 128
+__device__ double g_red_part[2][PM_RED_MAXB];
+__device__ unsigned g_red_count;
+
+__global__ __launch_bounds__(256) void pm_weighted_sum_kernel(const float* __restrict__ a,
+                                                              const float* __restrict__ w,
+                                                              long long n, float* __restrict__ out,
+                                                              const int* __restrict__ nvalid, long long n_per_step) {
+  __shared__ double sm[256];
+  __shared__ unsigned ticket;
+  if (nvalid) n = min(n, (long long)max(0, *nvalid) * n_per_step);   // truncated horizon
+  double s = 0.0;
+  // (eight elements' loads in flight at a time, added in the order a one-by-one loop adds them: as that loop -- load, wait,
+  //  convert, add -- a thread's eight elements at C2 were eight memory round trips in a row, most of this launch)
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += 8 * stride) {
+    float av[8], wv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      // (beyond n: the last element's address, its value dropped below -- a load under a condition is waited for where
+      //  the branches join, one at a time again)
+      const long long j = min(i + u * stride, n - 1);
+      av[u] = a[j];
+      wv[u] = w[j];
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += i + u * stride < n ? (double)av[u] * (double)wv[u] : 0.0;
+  }
+  const double tot = pm_block_sum(s, sm);
+  if (threadIdx.x == 0) {
+    // (a device-scope store, then the ticket: a release FENCE here is a write-back of this XCD's whole L2 -- the reward
+    //  launch's stash is still in it)
+    __hip_atomic_store(&g_red_part[0][blockIdx.x], tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    ticket = __hip_atomic_fetch_add(&g_red_count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  if (ticket == gridDim.x - 1) {          // last block: every partial is published
+    // fixed-shape tree over the published partials (deterministic), not a serial chain of
+    // L2 round trips
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    double t = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += blockDim.x)
+      t += __hip_atomic_load(&g_red_part[0][b], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const double tt = pm_block_sum(t, sm);
+    if (threadIdx.x == 0) {
+      out[0] = (float)tt;
+      __hip_atomic_store(&g_red_count, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
+// Squared norm of the gradient for clip_grad_norm_ (algorithms/mc_pilco.py:199-200): partial sums over blocks of 256
+// consecutive elements, ONE definition for the two kernels that form them -- pm_gradnorm_kernel (its own launch) and
+// pm_dw_reduce (round 6: the fused iteration's reduction forms them on the way, one launch less) -- so that the two
+// forms of an iteration walk the same trajectory bit for bit.  Lane c of a wave holds elements 4 c .. 4 c + 3 of the
+// block: squares added in element order, then a fixed butterfly over the 64 lanes.
+__device__ double g_norm_part[PM_NORM_MAXB];
+__device__ double g_loss_part[PM_NORM_MAXB];   // the loss' partial sums, one per workgroup of pm_dw_reduce (loss_r != nullptr)
+__device__ int g_adam_go;
+__device__ __forceinline__ double pm_sq4_wave(const f32x4& t, long long i0, long long n) {
+  double s = 0.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const double x = i0 + r < n ? (double)t[r] : 0.0;
+    s += x * x;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  return s;
+}
+// the optimiser step of a guarded iteration is taken if the rollout completed: status[0] = steps the forward sweep
+// completed, status[1] = set by the adjoint sweep when one of its exchanges timed out (the gradient is garbage then)
+__device__ __forceinline__ void pm_adam_decide(const int* status, int expect, long long* step) {
+  const int go = (!status || (status[0] >= expect && status[1] == 0)) ? 1 : 0;
+  g_adam_go = go;
+  if (go && step) step[0] += 1;
+}
+
+// grad[i] = sum_s part[s][i] in fixed order.  A workgroup = 64 float4 columns x 8 slices of the
+// split range: every wave reads whole 1 KiB rows, a thread keeps 16 independent loads in flight.
+// norm_on: also the partial sums of squares of ITS 256 elements and (block 0) the decision whether the guarded optimiser
+// step is taken -- what pm_gradnorm_kernel does in a launch of its own.
+__global__ __launch_bounds__(512) void pm_dw_reduce(const float* __restrict__ part, int nsplit, int n,
+                                                    int stride, float* __restrict__ grad,
+                                                    const int* __restrict__ nvalid = nullptr, int chunks_per_step = 0,
+                                                    int chunks_per_split = 1, int norm_on = 0,
+                                                    const int* __restrict__ status = nullptr, int expect = 0,
+                                                    long long* __restrict__ step = nullptr,
+                                                    const float* __restrict__ loss_r = nullptr,
+                                                    const float* __restrict__ loss_w = nullptr, long long loss_n = 0,
+                                                    long long loss_per_step = 0) {
+  __shared__ f32x4 sm[8][64];
+  __shared__ double sl_[8];
+  // loss_r: the fused iteration's loss on the way -- this workgroup's slice of sum_i r_i w_i over the valid steps (requested
+  // here, added below: pm_clip_adam_kernel adds the workgroups' sums in workgroup order).  One launch less per iteration.
+  float lr4[4] = {0.f, 0.f, 0.f, 0.f}, lw4[4] = {0.f, 0.f, 0.f, 0.f};
+  long long l_n = 0;
+  const long long l_i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, l_st = (long long)gridDim.x * blockDim.x;
+  if (loss_r) {
+    l_n = nvalid ? min(loss_n, (long long)max(0, *nvalid) * loss_per_step) : loss_n;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = min(l_i0 + u * l_st, loss_n - 1);
+      lr4[u] = loss_r[j];
+      lw4[u] = loss_w[j];
+    }
+  }
+  if (nvalid) {   // truncated horizon: only the splits that own a chunk of a valid step wrote a partial
+    const long long nc = (long long)max(0, *nvalid) * chunks_per_step;
+    nsplit = (int)min((long long)nsplit, (nc + chunks_per_split - 1) / chunks_per_split);
+  }
+  const int col = threadIdx.x & 63, sl = threadIdx.x >> 6;
+  const int c4 = blockIdx.x * 64 + col;            // float4 column
+  const int per = (nsplit + 7) / 8;
+  const int k_lo = sl * per, k_hi = min(nsplit, k_lo + per);
+  f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (c4 * 4 < n) {
+    const float* p = part + (size_t)c4 * 4;
+    // (sixteen rows in flight per thread, the tail as one predicated batch of eight: at C2 a slice is 33 rows -- as
+    //  8 + 8 + 8 + 8 + 1 it was five memory round trips in a row, now three; the order of the additions is the rows')
+    int k = k_lo;
+    for (; k + 16 <= k_hi; k += 16) {
+      f32x4 v[16];
+#pragma unroll
+      for (int u = 0; u < 16; ++u) v[u] = ldg4(p + (size_t)(k + u) * stride);
+#pragma unroll
+      for (int u = 0; u < 16; ++u) s += v[u];
+    }
+    for (; k < k_hi; k += 8) {
+      f32x4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) v[u] = ldg4(p + (size_t)min(k + u, k_hi - 1) * stride);   // (beyond: dropped below)
+#pragma unroll
+      for (int u = 0; u < 8; ++u) s += k + u < k_hi ? v[u] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+  }
+  sm[sl][col] = s;
+  if (loss_r) {
+    double ls = 0.0;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) ls += l_i0 + u * l_st < l_n ? (double)lr4[u] * (double)lw4[u] : 0.0;
+    for (long long j = l_i0 + 4 * l_st; j < l_n; j += l_st) ls += (double)loss_r[j] * (double)loss_w[j];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    if (col == 0) sl_[sl] = ls;
+  }
+  __syncthreads();
+  if (loss_r && threadIdx.x == 0) {
+    double t = sl_[0];
+#pragma unroll
+    for (int k = 1; k < 8; ++k) t += sl_[k];
+    g_loss_part[blockIdx.x] = t;
+  }
+  if (sl == 0) {
+    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (c4 * 4 < n) {
+      t = sm[0][col];
+#pragma unroll
+      for (int k = 1; k < 8; ++k) t += sm[k][col];
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (c4 * 4 + r < n) grad[c4 * 4 + r] = t[r];
+    }
+    if (norm_on) {
+      const double s2 = pm_sq4_wave(t, (long long)c4 * 4, n);
+      if (col == 0) {
+        g_norm_part[blockIdx.x] = s2;
+        if (blockIdx.x == 0) pm_adam_decide(status, expect, step);
+      }
+    }
+  }
+}
+
+static inline int pm_norm_blocks(long long n) { return (int)std::max<long long>(1, std::min<long long>(PM_NORM_MAXB, (n + 255) / 256)); }
+// clip_grad_norm_ + Adam in two launches: (1) partial sums of g^2 over blocks of 256 elements (pm_sq4_wave above:
+// the same partial sums the fused iteration's gradient reduction forms on the way), (2) every block adds the partials in
+// the same order (identical norm everywhere) and updates its slice.
+// Guarded form (pmbrl_clip_adam_guarded): block 0 also decides whether the step is taken (the rollout's status word says
+// every horizon step completed) and, if so, advances the device-side step counter; pm_clip_adam_kernel (next launch)
+// reads both.
+__global__ __launch_bounds__(64) void pm_gradnorm_kernel(const float* __restrict__ g, long long n,
+                                                         const int* __restrict__ status, int expect,
+                                                         long long* __restrict__ step, int guarded) {
+  if (guarded && blockIdx.x == 0 && threadIdx.x == 0) pm_adam_decide(status, expect, step);
+  // (one block of 256 elements per workgroup up to PM_NORM_MAXB of them; a longer vector is walked in strides, the
+  //  blocks' sums added in block order)
+  double tot = 0.0;
+  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
+    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
+    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (i0 + 3 < n) t = *reinterpret_cast<const f32x4*>(g + i0);
+    else
+      for (int r = 0; r < 4; ++r) t[r] = i0 + r < n ? g[i0 + r] : 0.f;
+    tot += pm_sq4_wave(t, i0, n);
+  }
+  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
+}
+
+__global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           long long n, int n_part, float lr, float b1,
+                                                           float b2, float omb1, float omb2, float eps,
+                                                           float bc1, float bc2_sqrt, float max_norm,
+                                                           float* __restrict__ norm_out,
+                                                           const long long* __restrict__ step, int guarded,
+                                                           double ln_b1, double ln_b2, double lr_d,
+                                                           float* __restrict__ loss_out, int n_loss_part) {
+  // The first four elements of this thread and the norm's partial sums are requested before anything is decided: as
+  // "go? -> step counter -> partial sums (a loop of dependent loads) -> elements (a loop of four)" this launch was ten
+  // memory round trips in a row around a few hundred instructions.
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  float gq[4], mq[4], vq[4], pq[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    // (beyond n: the last element's address, never used -- loads under a condition are waited for one by one)
+    const long long j = min(i0 + u * stride, n - 1);
+    gq[u] = g[j];
+    mq[u] = m[j];
+    vq[u] = v[j];
+    pq[u] = p[j];
+  }
+  const int lane = threadIdx.x & 63;
+  double part[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const double x = g_norm_part[min(lane + 64 * u, PM_NORM_MAXB - 1)];
+    part[u] = lane + 64 * u < n_part ? x : 0.0;
+  }
+  // the fused iteration's loss: the sums pm_dw_reduce's workgroups left, added in workgroup order by one wave (taken or
+  // not, the step's loss is reported)
+  if (loss_out && blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 128) {
+    double ls = 0.0;
+    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    if (lane == 0) loss_out[0] = (float)ls;
+  }
+  if (guarded && !g_adam_go) return;   // the rollout failed: leave parameters and moments alone
+  double step_size_d = lr_d / (double)bc1;
+  if (step) {
+    // guarded form: bias corrections 1 - beta^t of the device-side step counter as -expm1(t ln beta), the exponent formed
+    // and evaluated in double (torch forms them in Python floats; in fp32 the sixth digit of the step size differs and a
+    // five-iteration comparison of the moments notices), ln beta from the host -- two double-precision pow calls were a
+    // thousand instructions at the head of every thread, expm1 is a third of that
+    const double st = (double)step[0];
+    bc1 = (float)-expm1(st * ln_b1);
+    bc2_sqrt = (float)sqrt(-expm1(st * ln_b2));
+    step_size_d = lr_d / -expm1(st * ln_b1);      // (torch: lr / bias_correction1 in Python floats, rounded once)
+  }
+  // the partial sums of squares, block b on lane b mod 64 in block order, and a fixed butterfly: the same bits in every wave
+  // of every block
+  double t = 0.0;
+  {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t += part[u];                         // (absent: + 0)
+    for (int b = lane + 256; b < n_part; b += 64) t += g_norm_part[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  }
+  const float norm = (float)sqrt(t);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+  float coef = 1.f;
+  if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
+  const float step_size = (float)step_size_d;
+  for (long long i = i0;;) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = i + u * stride;
+      if (j < n) {
+        const float gi = gq[u] * coef;
+        const float mi = mq[u] * b1 + omb1 * gi;
+        const float vi = vq[u] * b2 + omb2 * gi * gi;
+        const float denom = sqrtf(vi) / bc2_sqrt + eps;
+        g[j] = gi;
+        m[j] = mi;
+        v[j] = vi;
+        p[j] = pq[u] - step_size * (mi / denom);
+      }
+    }
+    i += 4 * stride;
+    if (i >= n) break;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = min(i + u * stride, n - 1);
+      gq[u] = g[j];
+      mq[u] = m[j];
+      vq[u] = v[j];
+      pq[u] = p[j];
+    }
+  }
+}
+
+void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
+                                long long n_per_step) {
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 2047) / 2048));
+  hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, s, a, w, n, out, nvalid, n_per_step);
+}
+
+// norm_done: the partial sums of squares and the go / no-go decision are already on the device (the fused iteration's
+// gradient reduction formed them: pm_dw_reduce, norm_on)
+int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
+                                  int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
+                                  double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
+                                  float* loss_out_d, int n_loss_part) {
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
+  const int np = pm_norm_blocks(n);
+  if (!norm_done)
+    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
+                       (long long)n, (const int*)status_d, (int)expect, reinterpret_cast<long long*>(step_d), 1);
+  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
+                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, (float)lr, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, 1.f, 1.f,
+                     (float)max_norm, norm_out_d, reinterpret_cast<const long long*>(step_d), 1, log(beta1), log(beta2), lr,
+                     loss_out_d, n_loss_part);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// the fused iteration tail on a sharded run (pmbrl_plan_set_grad_comm): what pmbrl_rollout_bwd_adam queues around the
+// in-place sum of [flat gradient | loss partial | failure flag] over the ranks
+// ---------------------------------------------------------------------------
+// horizon agreement, 1: this rank's valid steps as entry `rank` of a vector the transport sums (both transports only sum)
+__global__ __launch_bounds__(64) void pm_tail_hvec_kernel(float* __restrict__ hvec, int world, int rank,
+                                                          const int* __restrict__ status, int H) {
+  for (int q = threadIdx.x; q < world; q += blockDim.x) hvec[q] = q == rank ? (float)min(max(status[0], 0), H) : 0.f;
+}
+// 2: the ranks' minimum, written where it is smaller than what this rank's forward sweep left (a rank whose exchange
+// timed out holds zeros for its peers: no step is valid, nothing is stepped)
+__global__ __launch_bounds__(64) void pm_tail_hmin_kernel(const float* __restrict__ hvec, int world,
+                                                          int* __restrict__ status, int H) {
+  if (threadIdx.x != 0) return;
+  int m = H;
+  for (int q = 0; q < world; ++q) m = min(m, (int)hvec[q]);
+  if (m < min(status[0], H)) status[0] = m;
+}
+// behind the gradient reduction: this rank's loss (the reduction's partial sums in workgroup order, as
+// pm_clip_adam_kernel adds them; n_loss_part = 0: already in xb[n], or not asked for) and failure flag next to the gradient
+__global__ __launch_bounds__(64) void pm_tail_pack_kernel(float* __restrict__ xb, int n, int n_loss_part, int loss_here,
+                                                          const int* __restrict__ status, const int* __restrict__ err) {
+  const int lane = threadIdx.x;
+  if (n_loss_part > 0) {
+    double ls = 0.0;
+    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    if (lane == 0) xb[n] = (float)ls;
+  } else if (!loss_here && lane == 0) {
+    xb[n] = 0.f;
+  }
+  if (lane == 0) xb[n + 1] = (status[1] != 0 || (err && *err != 0)) ? 1.f : 0.f;
+}
+// behind the exchange: the summed gradient into the caller's vector, the partial sums of ITS squares (pm_gradnorm_kernel's
+// blocks: the separate calls' norm bit for bit), the summed loss where pm_clip_adam_kernel looks for it, and the decision
+__global__ __launch_bounds__(64) void pm_tail_finish_kernel(const float* __restrict__ xb, float* __restrict__ g, long long n,
+                                                            int* __restrict__ status, int expect,
+                                                            long long* __restrict__ step, const int* __restrict__ err) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    // a failure anywhere is a failure everywhere: the host reads it one iteration late.  (A wait of THIS rank that timed
+    // out in the exchange just now is not in the sum -- the flag was packed before it: this rank says so in its own
+    // status word, the others learn it from the sticky error word in the next exchange.)
+    const int bad = (xb[n + 1] != 0.f || (err && *err != 0)) ? 1 : 0;
+    if (bad) status[1] = 1;
+    const int go = (status[0] >= expect && status[1] == 0) ? 1 : 0;
+    g_adam_go = go;
+    if (go && step) step[0] += 1;
+    g_loss_part[0] = (double)xb[n];
+  }
+  double tot = 0.0;
+  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
+    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
+    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (i0 + 3 < n) {
+      t = *reinterpret_cast<const f32x4*>(xb + i0);
+      for (int r = 0; r < 4; ++r) g[i0 + r] = t[r];
+    } else {
+      for (int r = 0; r < 4; ++r)
+        if (i0 + r < n) { t[r] = xb[i0 + r]; g[i0 + r] = t[r]; }
+    }
+    tot += pm_sq4_wave(t, i0, n);
+  }
+  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
+}
+
+// the launches of the kernels above that the rollout adjoint call and the BNN step queue (pmbrl_host.h)
+void pm_dw_reduce_launch(hipStream_t s, const float* part, int nsplit, int n, int stride, float* grad, const int* nvalid,
+                         int chunks_per_step, int chunks_per_split, int norm_on, const int* status, int expect, long long* step,
+                         const float* loss_r, const float* loss_w, long long loss_n, long long loss_per_step) {
+  hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, part, nsplit, n, stride, grad, nvalid,
+                     chunks_per_step, chunks_per_split, norm_on, status, expect, step, loss_r, loss_w, loss_n, loss_per_step);
+}
+void pm_tail_hvec_launch(hipStream_t s, float* hvec, int world, int rank, const int* status, int H) {
+  hipLaunchKernelGGL(pm_tail_hvec_kernel, dim3(1), dim3(64), 0, s, hvec, world, rank, status, H);
+}
+void pm_tail_hmin_launch(hipStream_t s, const float* hvec, int world, int* status, int H) {
+  hipLaunchKernelGGL(pm_tail_hmin_kernel, dim3(1), dim3(64), 0, s, hvec, world, status, H);
+}
+void pm_tail_pack_launch(hipStream_t s, float* xb, int n, int n_loss_part, int loss_here, const int* status, const int* err) {
+  hipLaunchKernelGGL(pm_tail_pack_kernel, dim3(1), dim3(64), 0, s, xb, n, n_loss_part, loss_here, status, err);
+}
+void pm_tail_finish_launch(hipStream_t s, const float* xb, float* g, long long n, int* status, int expect, long long* step,
+                           const int* err) {
+  hipLaunchKernelGGL(pm_tail_finish_kernel, dim3(pm_norm_blocks(n)), dim3(64), 0, s, xb, g, n, status, expect, step, err);
+}
+
+extern "C" int pmbrl_pack_mask(void* stream, const float* mask_d, int32_t B, int32_t h,
+                               int32_t src_ld, uint16_t* bits_d) {
+  if (!mask_d || !bits_d || B < 1 || h < 1 || src_ld < h) return fail(-1, "bad argument");
+  const int nt = (h + 15) / 16;
+  const int n = B * nt;
+  hipLaunchKernelGGL(pm_pack_mask_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
+                     mask_d, B, h, src_ld, bits_d);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pmbrl_draw_masks(void* stream, int32_t kind, uint64_t seed, uint64_t offset, const float* param_d,
+                                int32_t param_len, float temp, int32_t rows, int32_t h, const float* u_d, const float* v_d,
+                                uint16_t* bits_d, int32_t aux_row0, int32_t aux_rows, float* u_out_d, float* hard_out_d,
+                                float* probs_out_d) {
+  if (!param_d || !bits_d || rows < 1 || h < 1 || (kind != 0 && kind != 1) || (param_len != 1 && param_len != h) ||
+      aux_row0 < 0 || aux_rows < 0 || aux_row0 + aux_rows > rows)
+    return fail(-1, "bad argument");
+  if (kind == 1 && !(temp > 0.f)) return fail(-1, "concrete dropout needs a positive temperature");
+  DrawArgs A;
+  A.kind = kind; A.seed = seed; A.offset = offset; A.param = param_d; A.param_len = param_len; A.temp = temp;
+  A.rows = rows; A.h = h; A.u_in = u_d; A.v_in = v_d; A.bits = bits_d;
+  A.aux_row0 = aux_row0; A.aux_rows = aux_rows; A.u_out = u_out_d; A.hard_out = hard_out_d; A.probs_out = probs_out_d;
+  const long long n = (long long)rows * ((h + 15) / 16);
+  hipLaunchKernelGGL(pm_draw_masks_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, A);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pmbrl_weighted_sum(void* stream, const float* a_d, const float* w_d, int64_t n,
+                                  float* out_d) {
+  if (!a_d || !w_d || !out_d || n < 0) return fail(-1, "bad argument");
+  launch_weighted_sum((hipStream_t)stream, a_d, w_d, n, out_d, nullptr, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pmbrl_weighted_sum_steps(void* stream, const float* a_d, const float* w_d, int64_t n_per_step,
+                                        int32_t n_steps, const int32_t* status_d, float* out_d) {
+  if (!a_d || !w_d || !out_d || n_per_step < 0 || n_steps < 0) return fail(-1, "bad argument");
+  launch_weighted_sum((hipStream_t)stream, a_d, w_d, (long long)n_per_step * n_steps, out_d, status_d, n_per_step);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pmbrl_clip_adam(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
+                               float* exp_avg_sq_d, int64_t n, int64_t step, double lr, double beta1,
+                               double beta2, double eps, double max_norm, float* norm_out_d) {
+  if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || n < 1 || step < 1)
+    return fail(-1, "bad argument");
+  const double bc1 = 1.0 - pow(beta1, (double)step);
+  const double bc2 = 1.0 - pow(beta2, (double)step);
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
+  const int np = pm_norm_blocks(n);
+  // without clipping and without a norm to report there is nothing for the norm kernel to do
+  const bool need_norm = max_norm > 0.0 || norm_out_d != nullptr;
+  if (need_norm)
+    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
+                       (long long)n, (const int*)nullptr, 0, (long long*)nullptr, 0);
+  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
+                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, need_norm ? np : 0, (float)lr, (float)beta1,
+                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
+                     (float)bc1, (float)sqrt(bc2), (float)max_norm, norm_out_d, (const long long*)nullptr, 0, 0.0, 0.0, lr,
+                     (float*)nullptr, 0);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
+                                       float* exp_avg_sq_d, int64_t n, int64_t* step_d, double lr,
+                                       double beta1, double beta2, double eps, double max_norm,
+                                       float* norm_out_d, const int32_t* status_d, int32_t expect) {
+  if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || !step_d || !status_d || n < 1)
+    return fail(-1, "bad argument");
+  return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, lr, beta1, beta2, eps, max_norm,
+                                norm_out_d, status_d, expect, false);
+}

@@ -290,7 +290,7 @@ __device__ __forceinline__ float pw_row_share(float v) {
 // synchronises behind it.  Everything but the LDS writes happens IN FRONT of that barrier: a wave that leaves the K
 // loop early (of a SIMD's two waves one does) runs its epilogue while its partner still feeds the matrix core, and the
 // results wait for the barrier as packed pieces in the accumulators' registers.
-// STASH: 0 none; 1 fp32, feature-major [512][Rw] (what the fp32-stash kernels of pmbrl_dw.h read); 2 PRE-SPLIT for
+// STASH: 0 none; 1 fp32, feature-major [512][Rw] (what the fp32-stash kernels of pmbrl_dw_kernels.h read); 2 PRE-SPLIT for
 // pm_dw_wide_pre_kernel / pm_dw_narrow_pre_kernel: [piece][tile][row (64)][16 features] bf16 -- a lane's four features of a
 // row are one 8-byte store per piece (pw_stash_pre).  One form per kernel instance (pm_rollout_fwd / _bwd <4, 2, 2 | 3>).
 __device__ __forceinline__ void pw_stash_pre(const pw_rsrc& srd, int vo, int so, const pm_u32x2& hi, const pm_u32x2& lo) {

@@ -348,6 +348,52 @@ def test_all_concrete_plan_keeps_its_bits():
     assert np.allclose(out[0][1], d['losses'][0], rtol=3e-5, atol=2e-6)
 
 
+def test_calls_alternating_on_one_plan_are_those_of_fresh_plans():
+    """Both BNN calls start from a copy of the records their plan filled when it was created.  Seven calls alternating on ONE
+    BnnStep against the same calls each on a FRESH one, started from the state the shared sequence had: every output
+    bit-equal.  Calls 5 and 6 would read a field call 4 (row weights) or call 5 (the generator switch) left in the plan."""
+    from prob_mbrl_amd import activations
+    from prob_mbrl_amd import engine as E
+    rs = np.random.RandomState(11)
+    dims, M, N, h = [3, 20, 20, 4], 24, 60, 40
+    CALLS = (1, 2, 1, 2, 1, 2, 1)      # iterations per call: 1 is a loss_grad, 2 a train_steps
+    fresh = lambda: E.BnnStep(dims, [0.7, 0.0], [0.5, 0.5], [1.0, 0.0], M, N, device=torch.device(DEV),  # noqa: E731
+                              act=activations.SILU, bernoulli_keep=[None, 0.8])
+    n = (3 * 20 + 20 + 20) + (20 * 20 + 20) + (20 * 4 + 4)
+    Xn, Yn = T(rs.randn(N, 3)), T(rs.randn(N, 2))
+    idx = [torch.tensor(np.stack([rs.permutation(N)[:M] for _ in range(k)]).astype(np.int32), device=DEV).contiguous()
+           for k in CALLS]
+    u = [T(rs.rand(k * M * h)) for k in CALLS]
+    bvar = [T(rs.rand(k * M * h)) for k in CALLS]
+    row_w = T(rs.rand(M) + 0.5)
+
+    def call(i, step, flat, m, v, stepc):
+        """Call i on `step`; the state is updated in place.  Returns every output of the call."""
+        if CALLS[i] == 2:
+            kw = dict(seed=7, first_step=3 + i) if i in (1, 5) else dict(u=u[i], bvar=bvar[i])
+            out = [step.train_steps(Xn, Yn, idx[i], flat, m, v, stepc, 1e-2, **kw)]
+        else:
+            lp = torch.zeros(M, device=DEV)
+            kw = {0: {}, 2: dict(terms=2), 4: dict(row_weight=row_w, row_logprob=lp), 6: {}}[i]
+            out = list(step.loss_grad(Xn, Yn, idx[i].reshape(-1), flat, u[i], bvar[i], **kw)) + [lp]
+        return [t.clone() for t in out + [flat, m, v, stepc]]
+
+    shared = fresh()
+    assert shared.n_params == n
+    state = [T(rs.randn(n) * 0.3), torch.zeros(n, device=DEV), torch.zeros(n, device=DEV),
+             torch.zeros(1, dtype=torch.int64, device=DEV)]
+    for i in range(len(CALLS)):
+        start, before = [t.clone() for t in state], state[0].clone()
+        got = call(i, shared, *state)
+        want = call(i, fresh(), *start)
+        bits = lambda t: t.view(torch.int32) if t.dtype == torch.float32 else t  # noqa: E731
+        assert all(torch.isfinite(t).all() for t in got), i
+        assert len(got) == len(want) and all(torch.equal(bits(a), bits(b)) for a, b in zip(got, want)), i
+        if CALLS[i] == 2:
+            assert not torch.equal(state[0], before)      # the iterations did step
+    assert int(state[3].item()) == 6
+
+
 def test_bad_bernoulli_fields_are_rejected():
     from prob_mbrl_amd import _lib
     from prob_mbrl_amd import engine as E

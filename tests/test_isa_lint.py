@@ -1,5 +1,5 @@
 """The fast sweep kernels and the dW GEMM issue some loads through inline asm and wait for them
-with explicit s_waitcnt (prob_mbrl_amd/csrc/pmbrl_fast.h, pmbrl_dw.h).  This compiles the
+with explicit s_waitcnt (prob_mbrl_amd/csrc/pmbrl_fast.h, pmbrl_dw_kernels.h).  This compiles the
 device code to ISA and checks that no instruction touches a register whose load is still in
 flight (tools/check_inflight.py) -- a register-allocator copy or spill there would be a silent
 data corruption that only shows on some shapes."""
@@ -19,8 +19,9 @@ HIPCC = '/opt/rocm/bin/hipcc'
 def test_no_instruction_touches_in_flight_registers(tmp_path):
     csrc = os.path.join(ROOT, 'prob_mbrl_amd', 'csrc')
     # the translation units that hold inline-asm loads, compiled to ISA side by side
-    units = [('pmbrl.hip', []), ('pmbrl_fast_f32.hip', []), ('pmbrl_fast_split.hip', ['-DPM_SPLIT_PR=1']),
-             ('pmbrl_fast_split.hip', ['-DPM_SPLIT_PR=2']), ('pmbrl_general_split.hip', [])]
+    # (pmbrl_dw.hip: the dW kernel; pmbrl.hip: the general family's exact-fp32 instances)
+    units = [('pmbrl_dw.hip', []), ('pmbrl_fast_f32.hip', []), ('pmbrl_fast_split.hip', ['-DPM_SPLIT_PR=1']),
+             ('pmbrl_fast_split.hip', ['-DPM_SPLIT_PR=2']), ('pmbrl_general_split.hip', []), ('pmbrl.hip', [])]
     procs = []
     for k, (src, extra) in enumerate(units):
         out = str(tmp_path / ('u%d.s' % k))
@@ -46,7 +47,7 @@ def test_no_instruction_touches_in_flight_registers(tmp_path):
     assert len(names) >= 19 + 16 + 6 + 8, len(names)     # fp32 instantiations + the dW kernel + the split-precision ones
     assert total_loads > 500
     # pm_rollout_fwd / bwd <1|2|4, 2, 0>, the in-place <4, 2, 1>, the in-place wide layers <4, 2, 2> (pmbrl_wide.h) and the
-    # same with pre-split stashes <4, 2, 3> (round 6: pmbrl_dw.h, pm_dw_wide_pre_kernel)
+    # same with pre-split stashes <4, 2, 3> (round 6: pmbrl_dw_kernels.h, pm_dw_wide_pre_kernel)
     assert general_split == 12, general_split
     # register spills of the default-precision instances that run the cart-pole shapes: none without moment matching,
     # none with 25-row groups split over two 16-row workgroups (statistics exchange: the rows + flags form is no
