@@ -216,6 +216,12 @@ enum {
   PMBRL_INFO_N_POL_PARAMS = 4,
   PMBRL_INFO_N_DYN_PARAMS = 5,
   PMBRL_INFO_DW_SPLITS = 6,
+  PMBRL_INFO_MM_MODE = 7,
+  PMBRL_INFO_LD = 8,
+  PMBRL_INFO_DW_BLOCKS = 9,
+  PMBRL_INFO_FAST = 10,      /* 1: the latency-optimised kernel family */
+  PMBRL_INFO_STAGES = 11,    /* ... its stage pair: 16 CA + CB */
+  PMBRL_INFO_MM_GRID = 12,
   PMBRL_INFO_PRECISION = 13, /* PMBRL_PREC_* actually in use */
   PMBRL_INFO_DW_PIPE = 14,   /* launches the adjoint sweep is cut into so that the dW GEMM runs behind it (1: no) */
   PMBRL_INFO_MM_PARTS = 15,  /* workgroups a moment-matching group is split over (in-kernel moment matching; 1: whole groups) */
@@ -257,6 +263,14 @@ void pmbrl_plan_destroy(pmbrl_plan* plan);
  * activation / gradient stashes, bit masks, dW partial sums. */
 size_t pmbrl_plan_workspace_bytes(const pmbrl_plan* plan);
 int pmbrl_plan_info(const pmbrl_plan* plan, int32_t* info /* [PMBRL_INFO_COUNT] */);
+/* Which sweep kernels the plan resolved when it was created: *name = the runtime's name (hipKernelNameRefByPtr) of the
+ * forward (adjoint = 0) or adjoint sweep kernel.  Latency-optimised family (pmbrl_plan_info: fast = 1): variant = 0 plain
+ * and lean, 1 plain with optional outputs or a step range, 2 moment matching inside the sweep, 3 the same as one launch
+ * with a device-wide barrier per step -- the call picks among them by its arguments; "" where the plan has no instance
+ * for that variant.  General family: variant is ignored.  PMBRL_SWEEP_REG: the register-resident family's pair
+ * (PMBRL_INFO_REG; "" where it does not serve the plan).  The string belongs to the runtime. */
+#define PMBRL_SWEEP_REG 4
+int pmbrl_plan_sweep_kernel(const pmbrl_plan* plan, int variant, int adjoint, const char** name);
 
 /* {0,1} float mask [B, h] -> bit rows [B, ceil(h/16)] uint16 (little-endian bit
  * order).  Replaces the per-step fp32 mask multiply of models/modules.py:61,160

@@ -24,8 +24,12 @@ REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
 DROP_BY_TEMPERATURE, DROP_BERNOULLI = 0, 1      # pmbrl_bnn_config.drop_kind
-INFO_COUNT = 22
-INFO_TAIL_CALLS = 21    # PMBRL_INFO_TAIL_CALLS
+# pmbrl_plan_info indices (PMBRL_INFO_* of include/pmbrl.h)
+(INFO_ROWS_PER_WG, INFO_N_WG, INFO_ROW_TILES, INFO_LDS_BYTES, INFO_N_POL_PARAMS, INFO_N_DYN_PARAMS, INFO_DW_SPLITS,
+ INFO_MM_MODE, INFO_LD, INFO_DW_BLOCKS, INFO_FAST, INFO_STAGES, INFO_MM_GRID, INFO_PRECISION, INFO_DW_PIPE, INFO_MM_PARTS,
+ INFO_REG, INFO_REPLAY, INFO_INPLACE, INFO_REG_FWD_CALLS, INFO_REG_BWD_CALLS, INFO_TAIL_CALLS, INFO_COUNT) = range(23)
+# pmbrl_plan_sweep_kernel: the variants of the latency-optimised family (PF_VAR_*), then PMBRL_SWEEP_REG
+SWEEP_VARIANTS = ('lean', 'ext', 'mm', 'mmg', 'reg')
 TIMER_COUNT = 8
 TIMER_NAMES = ['pack', 'fwd', 'bwd', 'dw', 'dw_reduce', 'reward']
 
@@ -92,7 +96,7 @@ class Inputs(C.Structure):
 EXPORTS = [
     'pmbrl_last_error', 'pmbrl_version', 'pmbrl_build_id', 'pmbrl_plan_create',
     'pmbrl_graph_capture_begin', 'pmbrl_graph_capture_end', 'pmbrl_graph_launch', 'pmbrl_graph_num_nodes', 'pmbrl_graph_destroy',
-    'pmbrl_plan_destroy', 'pmbrl_plan_workspace_bytes', 'pmbrl_plan_info',
+    'pmbrl_plan_destroy', 'pmbrl_plan_workspace_bytes', 'pmbrl_plan_info', 'pmbrl_plan_sweep_kernel',
     'pmbrl_pack_mask', 'pmbrl_draw_masks', 'pmbrl_rollout_fwd', 'pmbrl_rollout_bwd', 'pmbrl_rollout_bwd_adam',
     'pmbrl_plan_set_loss',
     'pmbrl_weighted_sum', 'pmbrl_weighted_sum_steps', 'pmbrl_clip_adam', 'pmbrl_clip_adam_guarded', 'pmbrl_debug_linear',
@@ -152,6 +156,8 @@ def load():
     lib.pmbrl_plan_workspace_bytes.argtypes = [vp]
     lib.pmbrl_plan_info.restype = C.c_int
     lib.pmbrl_plan_info.argtypes = [vp, C.POINTER(i32)]
+    lib.pmbrl_plan_sweep_kernel.restype = C.c_int
+    lib.pmbrl_plan_sweep_kernel.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_char_p)]
     lib.pmbrl_pack_mask.restype = C.c_int
     lib.pmbrl_pack_mask.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.pmbrl_rollout_fwd.restype = C.c_int

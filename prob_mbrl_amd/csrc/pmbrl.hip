@@ -364,14 +364,12 @@ static int net_plan(const pmbrl_mlp& m, int act, NetPlan& n, int in_expect, int 
   return 0;
 }
 
-template <int RT>
-static int set_attr(size_t lds) {
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_rollout_fwd<RT>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_rollout_bwd<RT>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return 0;
-}
+// the general family in exact fp32: the instantiations of PM_GENERAL_F32_INSTANCES
+#define PM_INST(RT, CA, CB, VAR, D, U, LD, NL, NT, TREE) \
+  {reinterpret_cast<const void*>(&pm_rollout_fwd<RT>), reinterpret_cast<const void*>(&pm_rollout_bwd<RT>)},
+static const PmInst general_f32_fns[] = {PM_GENERAL_F32_INSTANCES};
+#undef PM_INST
+static_assert(sizeof(general_f32_fns) / sizeof(general_f32_fns[0]) == pm_general_f32_n, "one kernel pair per key");
 
 // ---------------------------------------------------------------------------
 // plan creation: pmbrl_plan_create runs the stages below in order; each one fills its part of the plan from the
@@ -445,7 +443,6 @@ static int plan_nets(pmbrl_plan* p) {
 
 // stage 2: the layout of the sweeps.  What a choice of row tiles RT (16 rows each) asks for, as functions of the
 // networks, the precision asked for and what is given
-struct StagePair { int ca, cb; };
 struct LayoutCalc {
   const pmbrl_plan* p;
   int maxnt;             // widest activation (any layer of either net), in 16-wide tiles
@@ -456,7 +453,7 @@ struct LayoutCalc {
   // 64-row workgroups on split operands: two fp16 piece planes fit the LDS (three bf16 planes do not), and
   // only the shape-specialised instance keeps its inline-asm loads clear of register-allocator copies
   // (tools/check_inflight.py; the generic 64-row split instances fail that lint and are not compiled):
-  // the double cart-pole shape with in-kernel moment matching (PM_SPLIT_SHAPED_RT4), fp32 otherwise
+  // the double cart-pole shape with in-kernel moment matching (the 64-row row of PM_SPLIT2_INSTANCES), fp32 otherwise
   bool rt4_split;
   // LDS leading dimension of the general family: widest activation, +8 so that LD % 16 == 8 (conflict-free
   // ds_read_b128 for the MFMA B operand)
@@ -476,18 +473,13 @@ struct LayoutCalc {
     return w;
   }
   // stage sizes (k-blocks) of the weight stream: every streamed layer is padded to a whole number
-  // of stage PAIRS (CA + CB k-blocks); pick, among the instantiated pairs, the one that pads least
+  // of stage PAIRS (CA + CB k-blocks); pick, among the pairs the family has instances of for RT, the one that pads
+  // least (pmbrl_instances.h).  (The general family streams no stage pairs: on split operands its plans report the pair
+  // of the 32-row instances, as they always have.)
   StagePair stages(int RT) const {
-    static const StagePair cand1[] = {{8, 8}, {7, 6}, {4, 4}, {2, 2}}, cand2[] = {{4, 4}, {4, 3}, {2, 2}}, cand4[] = {{2, 2}, {1, 1}};
-    static const StagePair cands[] = {{4, 3}, {1, 1}};
-    const bool sp = prec(RT) != 0;
-    const StagePair* cand = sp ? cands : RT == 1 ? cand1 : (RT == 2 ? cand2 : cand4);
-    const int nc = sp ? 2 : RT == 1 ? 4 : (RT == 2 ? 3 : 2);
-    const int kdiv = sp ? 2 : 1;
-    StagePair best = cand[0];
-    for (int i = 1; i < nc; ++i)
-      if (stream_work(cand[i].ca + cand[i].cb, kdiv) < stream_work(best.ca + best.cb, kdiv)) best = cand[i];
-    return best;
+    const int pr = prec(RT);
+    return pm_inst_best_stages(pm_fast_keys(pr), pr && !p->fast ? std::min(RT, 2) : RT,
+                               [&](int m) { return stream_work(m, pr ? 2 : 1); });
   }
   // split path: elements per row of a bf16 piece plane = padded K + 16 (conflict-free ds_read_b128)
   int ldb(int RT) const {
@@ -609,11 +601,12 @@ static int plan_groups(pmbrl_plan* p, LayoutCalc& L, int cus) {
   }
   // A group beyond 8 parts of 32 rows -- ONE group over the whole batch, the reference's default (mm_groups=None,
   // examples/deep_pilco_mm.py:31): 16-row parts whose sums travel over two levels (pm_xch_get_tree), every workgroup
-  // resident.  Only where the instance that exchanges sums runs (compile-time state width, the cart-pole shape:
-  // PM_SPLIT_SHAPED_CASES) -- the rows + flags form of the generic instances keeps the whole group's rows in LDS.
+  // resident.  Only where the instance that exchanges sums runs (compile-time state width, the cart-pole shape: the
+  // PfShapeTree row of PM_SPLIT2_INSTANCES) -- the rows + flags form of the generic instances keeps the whole group's rows in LDS.
   // 2 500 rows: 157 parts, 13 collectors; against the device-wide-barrier form (every workgroup re-reads and
   // re-reduces the whole group's rows every step) 3.0 -> see profiles/r04*_single_group.txt.  PMBRL_MM_TREE=0: off.
-  const bool shaped_mm1 = p->fast && L.prec(1) == PMBRL_PREC_SPLIT_F16 && c.D == 4 && c.U == 1 && hidden_tiles_3l(p) == 13 &&
+  const bool shaped_mm1 = p->fast && L.prec(1) == PMBRL_PREC_SPLIT_F16 &&
+                          pm_inst_any(pm_fast_keys(L.prec(1)), 1, PF_VAR_MM, c.D, c.U, 3, hidden_tiles_3l(p), 1) &&
                           !(c.flags & PMBRL_FLAG_NO_SHAPED) && sw.lds_tiles && sw.mm_xch;
   if (p->mm_mode == 2 && !p->span && !sw.mm_parts_set && shaped_mm1 && (c.flags & PMBRL_FLAG_MM_STATES) && sw.mm_tree) {
     const int parts = (p->M + 15) / 16;
@@ -698,8 +691,11 @@ static int plan_layout(pmbrl_plan* p, int cus) {
   for (int i = 0; i <= p->dyn.nl; ++i) L.maxnt = std::max(L.maxnt, p->dyn.nt[i]);
   L.gsplit = !p->fast && c.precision == PMBRL_PREC_SPLIT_F16;
   L.want_split = (c.precision == PMBRL_PREC_SPLIT || c.precision == PMBRL_PREC_SPLIT_F16) && p->fast;
-  L.rt4_split = c.precision == PMBRL_PREC_SPLIT_F16 && mm && c.D == 6 && c.U == 1 && hidden_tiles_3l(p) == 13 &&
+  L.rt4_split = c.precision == PMBRL_PREC_SPLIT_F16 && mm &&
+                pm_inst_any(pm_fast_keys(c.precision), 4, PF_VAR_MM, c.D, c.U, 3, hidden_tiles_3l(p)) &&
                 !(c.flags & PMBRL_FLAG_NO_SHAPED);
+  for (int RT : {1, 2, 4})
+    if (!L.stages(RT).ca) return fail(-3, "no stage pair instantiated for " + std::to_string(16 * RT) + "-row workgroups");
   p->G = 1;
   p->M = c.B;
   p->mm_mode = 0;
@@ -753,7 +749,7 @@ static int plan_layout(pmbrl_plan* p, int cus) {
 
   // LDS-resident tiles of the sweeps' second streamed layer (pmbrl_fast.h, lds_tile_s): the shape-specialised 16-row
   // split-precision instances (two streamed layers of 13 or 14 tiles, stage pair = one tile) keep 8 tiles of it in the
-  // LDS the workgroup has to itself anyway; the launch decides per kernel variant (pmbrl_fast_split.hip).
+  // LDS the workgroup has to itself anyway; which variants use them is settled with the plan's kernels (resolve_sweeps).
   // PMBRL_LDS_TILES=0: off.
   const int ht = hidden_tiles_3l(p);
   if (p->fast && p->RT == 1 && p->prec == PMBRL_PREC_SPLIT_F16 && p->CA + p->CB == 7 && (ht == 13 || ht == 14) &&
@@ -1100,24 +1096,65 @@ static int plan_workspace(pmbrl_plan* p) {
   return 0;
 }
 
-// stage 8: kernel attributes, and the residency the barrier form relies on
+// stage 8: the plan's sweep kernels, kernel attributes, and the residency the barrier form relies on
+static PmInstTable sweep_table(const pmbrl_plan* p) {
+  if (p->fast)
+    return p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_instances() : p->prec ? pm_fast_split1_instances() : pm_fast_f32_instances();
+  if (p->act) return pm_general_act_instances();
+  return p->prec ? pm_general_split_instances() : PmInstTable{pm_general_f32_keys, general_f32_fns, pm_general_f32_n};
+}
+// do the shape-specialised 16-row instances of this plan's stage pair hold tiles of the second streamed layer in LDS
+// (pmbrl_fast.h, lds_tile_s; plan_layout reserved them: wlds_off)?  Two fp16 pieces, a tile exactly one stage pair wide,
+// two hidden layers of more than 8 tiles -- whose second stream entry (fill_args: add_stream) is then 7 K32 blocks x 2
+// pieces and more than 8 tiles, which the kernels count on.  Worked out for 13 tiles, the only such rows (sd.n = 2,
+// n_kb[1] = 14, n_ot[1] = 12 or 13); a shaped row of another width or depth has to establish it again.
+static bool lds_tiles_row(const pmbrl_plan* p, const PmInstKey& k) {
+  return p->prec == PMBRL_PREC_SPLIT_F16 && p->RT == 1 && p->CA + p->CB == 7 && k.var != PF_VAR_MMG && k.nl == 3 && k.nt > 8;
+}
+// p->sweep / p->sweep_key: per variant the shape-specialised row of the plan's shape if there is one and it may run, else
+// the generic row.  A plan whose calls will ask for a variant that has neither is refused.
+static int resolve_sweeps(pmbrl_plan* p) {
+  const pmbrl_config& c = p->cfg;
+  const PmInstTable T = sweep_table(p);
+  auto take = [&](int slot, const PmInstKey& k) {
+    const int i = pm_inst_find(T, k);
+    if (i >= 0) { p->sweep[slot] = T.fn[i]; p->sweep_key[slot] = k; }
+    return i >= 0;
+  };
+  if (!p->fast) {
+    // the table of the networks that are not ReLU is keyed by piece planes, the split one by the in-place form (3: the
+    // wide layers with pre-split stashes), the exact-fp32 one by row tiles alone
+    const int wide_form = (p->inplace == 2 && p->dw_pre_mask) ? 3 : p->inplace;
+    const PmInstKey k = pm_general_key(p->RT, p->act ? (p->prec ? 2 : 0) : p->prec ? wide_form : 0);
+    return take(0, k) ? 0 : fail(-3, "no general-family instance for " + pm_inst_name(k));
+  }
+  // not on request (tests), and not for split groups without the statistics exchange (PMBRL_MM_XCH=0): only the generic
+  // instances carry the rows + flags form
+  const bool shaped_ok = !(c.flags & PMBRL_FLAG_NO_SHAPED) && !(p->mm_parts > 1 && !p->xch_bytes);
+  for (int var = 0; var < PF_VAR_COUNT; ++var) {
+    const bool mm_in = p->mm_mode == 1 || p->mm_mode == 3;
+    const bool needed = var == PF_VAR_MMG ? p->mm_grid != 0 : (var == PF_VAR_MM) == mm_in;
+    PmInstKey k = {p->RT, p->CA, p->CB, var, c.D, c.U, p->LD, 3, hidden_tiles_3l(p), 0};
+    // groups split over more than 8 workgroups: the two-level exchange, which only that instance has
+    k.tree = var == PF_VAR_MM && p->mm_mode == 1 && p->mm_parts > 8;
+    if (shaped_ok && (!lds_tiles_row(p, k) || p->wlds_off > 0) && take(var, k)) continue;
+    if (k.tree) return fail(-3, "no instance for a moment-matching group split over more than 8 workgroups: " + pm_inst_name(k));
+    k = PmInstKey{p->RT, p->CA, p->CB, var, 0, 0, 0, 0, 0, 0};
+    if (!take(var, k) && needed) return fail(-3, "no latency-optimised instance for " + pm_inst_name(k));
+  }
+  return 0;
+}
 static int plan_attrs(pmbrl_plan* p, int cus) {
   const pmbrl_config& c = p->cfg;
-  int rc = 0;
-  if (!p->fast && p->prec) {
-    rc = p->act ? pm_general_act_set_attr(p) : pm_general_split_set_attr(p);
-  } else if (!p->fast && p->act) {
-    rc = pm_general_act_set_attr(p);
-  } else if (!p->fast) {
-    switch (p->RT) {
-      case 1: rc = set_attr<1>(p->lds_bytes); break;
-      case 2: rc = set_attr<2>(p->lds_bytes); break;
-      default: rc = set_attr<4>(p->lds_bytes); break;
-    }
-  } else if (p->prec) {
-    rc = p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_set_attr(p) : pm_fast_split1_set_attr(p);
-  } else {
-    rc = pm_fast_f32_set_attr(p);
+  if (int rc = resolve_sweeps(p)) return rc;
+  // the LDS the plan asks for: on the general family's pair, on every latency-optimised instance of the plan's (row
+  // tiles, stage pair)
+  const PmInstTable T = sweep_table(p);
+  for (int i = 0; i < T.n; ++i) {
+    const PmInstKey& k = T.key[i];
+    if (p->fast ? k.rt != p->RT || k.ca != p->CA || k.cb != p->CB : T.fn[i].fwd != p->sweep[0].fwd) continue;
+    HIPCHK(hipFuncSetAttribute(T.fn[i].fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
+    HIPCHK(hipFuncSetAttribute(T.fn[i].bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p->lds_bytes));
   }
   if (p->mm_wide) {
     const int smem = (int)pm_mmw_lds_bytes(p->M, c.D, true);
@@ -1142,15 +1179,17 @@ static int plan_attrs(pmbrl_plan* p, int cus) {
       return fail(-3, "hipFuncSetAttribute(moment-matching kernels) failed");
     }
   }
-  if (!rc && p->reg) rc = pm_reg_set_attr(p);
-  if (rc) return rc;
+  if (p->reg)
+    if (int rc = pm_reg_resolve(p)) return rc;
   if (p->mm_grid) {
-    // the barrier-form sweep needs every workgroup resident at once: ask the runtime how many of THIS
-    // kernel (registers, LDS) fit a CU instead of assuming one
-    const int per_cu = p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_mmg_blocks_per_cu(p)
-                       : p->prec                        ? pm_fast_split1_mmg_blocks_per_cu(p)
-                                                        : pm_fast_f32_mmg_blocks_per_cu(p);
-    if (per_cu < 1 || p->nwg > cus) p->mm_grid = 0;     // (one per CU is all that is relied upon)
+    // the barrier-form sweep needs every workgroup resident at once: ask the runtime how many of the generic barrier-form
+    // kernel of this stage pair (registers, LDS) fit a CU instead of assuming one (min over forward / adjoint)
+    const int i = pm_inst_find(T, {1, p->CA, p->CB, PF_VAR_MMG, 0, 0, 0, 0, 0, 0});
+    int a = 0, b = 0;
+    if (i < 0 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&a, T.fn[i].fwd, PF_NT, p->lds_bytes) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, T.fn[i].bwd, PF_NT, p->lds_bytes) != hipSuccess)
+      a = b = 0;
+    if (std::min(a, b) < 1 || p->nwg > cus) p->mm_grid = 0;     // (one per CU is all that is relied upon)
   }
   return 0;
 }
@@ -1337,6 +1376,19 @@ extern "C" void pmbrl_plan_destroy(pmbrl_plan* p) {
   delete p;
 }
 
+extern "C" int pmbrl_plan_sweep_kernel(const pmbrl_plan* p, int variant, int adjoint, const char** name) {
+  if (!p || !name) return fail(-1, "null argument");
+  PmInst k{};
+  if (variant == PMBRL_SWEEP_REG) k = p->reg ? p->reg_k[0] : k;
+  else if (!p->fast) k = p->sweep[0];
+  else if (variant >= 0 && variant < PF_VAR_COUNT) k = p->sweep[variant];
+  else return fail(-1, "variant out of range");
+  const void* f = adjoint ? k.bwd : k.fwd;
+  *name = f ? hipKernelNameRefByPtr(f, nullptr) : "";
+  if (!*name) *name = "";
+  return 0;
+}
+
 extern "C" size_t pmbrl_plan_workspace_bytes(const pmbrl_plan* p) { return p ? p->ws_bytes : 0; }
 
 extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
@@ -1349,12 +1401,12 @@ extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   info[PMBRL_INFO_N_POL_PARAMS] = (int32_t)p->pol.n_params;
   info[PMBRL_INFO_N_DYN_PARAMS] = (int32_t)p->dyn.n_params;
   info[PMBRL_INFO_DW_SPLITS] = p->dw_nsplit;
-  info[7] = p->mm_mode;
-  info[8] = p->LD;
-  info[9] = p->n_dw_blocks;
-  info[10] = p->fast;
-  info[11] = p->CA * 16 + p->CB;
-  info[12] = p->mm_grid;
+  info[PMBRL_INFO_MM_MODE] = p->mm_mode;
+  info[PMBRL_INFO_LD] = p->LD;
+  info[PMBRL_INFO_DW_BLOCKS] = p->n_dw_blocks;
+  info[PMBRL_INFO_FAST] = p->fast;
+  info[PMBRL_INFO_STAGES] = p->CA * 16 + p->CB;
+  info[PMBRL_INFO_MM_GRID] = p->mm_grid;
   info[PMBRL_INFO_PRECISION] = p->prec;
   info[PMBRL_INFO_DW_PIPE] = p->pipe_K;
   info[PMBRL_INFO_MM_PARTS] = p->mm_parts;
@@ -1395,8 +1447,6 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
   A.B = c.B; A.D = c.D; A.U = c.U; A.H = c.H;
   A.Bg = c.B_global; A.row_off = c.row_offset; A.flags = c.flags;
   A.flags |= (p->pol.act << PM_ACT_POL_SHIFT) | (p->dyn.act << PM_ACT_DYN_SHIFT);   // (read by the ACT instances only)
-  // split groups without the statistics exchange (PMBRL_MM_XCH=0): only the generic instances carry the rows + flags form
-  if (p->mm_parts > 1 && !p->xch_bytes) A.flags |= PMBRL_FLAG_NO_SHAPED;
   A.G = p->G; A.M = p->M; A.mm_mode = p->mm_mode;
   A.t0 = 0; A.t1 = c.H;
   A.rows_per_wg = p->rows_per_wg; A.nwg = p->nwg; A.Rw = 16 * p->RT; A.LD = p->LD; A.LDB = p->LDB;
@@ -1496,6 +1546,10 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
     A.pol_first_w = in->pol_params_d + p->pol.w_off[0];
     A.dyn_first_w = in->dyn_params_d + p->dyn.w_off[0];
   }
+  // (plan_attrs resolved every variant the plan's calls can ask for -- LEAN and EXT, or MM / MMG; never a null launch)
+  const int var = p->fast ? fast_variant(p->RT, A) : 0;
+  if (!p->sweep[var].fwd || (var == PF_VAR_LEAN && p->fast && !p->sweep[PF_VAR_EXT].fwd))
+    return fail(-3, "the plan resolved no sweep kernel for this call's variant");
   return 0;
 }
 
@@ -1524,46 +1578,51 @@ static void pack_jobs(const NetPlan& n, char* ws, const float* params, int pair_
   }
 }
 
-template <int RT>
-static void launch_fwd(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(pm_rollout_fwd<RT>, dim3(p->nwg), dim3(PM_NT), p->lds_bytes, s, A);
+// Tiles of the streamed layers that a 16-row split-precision sweep holds outside the weight stream, whose table then
+// starts behind them.  k: the instance that will run.
+static void resident_tiles(const pmbrl_plan* p, const PmInstKey& k, RolloutArgs& A, bool fwd) {
+  StreamDesc& sd = fwd ? A.sd_fwd : A.sd_bwd;
+  const int np = (fwd && p->prec != PMBRL_PREC_SPLIT_F16) ? 3 : 2;
+  if (!p->prec || p->RT != 1 || p->CA + p->CB != 7 || np != 2) return;
+  // Register-resident first tiles (pmbrl_fast.h, resident_tile_s): the plain variants keep output tile `wave` of the
+  // sweep's first streamed layer in registers when a tile is exactly one stage pair and two pieces wide; the stream
+  // table then starts at tile 8 of that layer.
+  if ((k.var == PF_VAR_LEAN || k.var == PF_VAR_EXT) && sd.n >= 1 && sd.n_kb[0] == 7 * np && sd.n_ot[0] > 8) {
+    A.res_tiles = 8;
+    A.res_w = sd.wf[0];
+    sd.wf[0] += (size_t)8 * sd.n_kb[0] * 256;
+    sd.n_ot[0] -= 8;
+  }
+  // LDS-resident tiles (lds_tile_s): tiles 0..7 of the SECOND streamed layer, in the LDS the plan reserved
+  if (lds_tiles_row(p, k)) {
+    A.lds_w = sd.wf[1];
+    A.wlds_off = p->wlds_off;
+    A.lds_last_lanes = p->lds_last_lanes;
+    sd.wf[1] += (size_t)8 * sd.n_kb[1] * 256;
+    sd.n_ot[1] -= 8;
+  }
 }
-template <int RT>
-static void launch_bwd(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) {
-  hipLaunchKernelGGL(pm_rollout_bwd<RT>, dim3(p->nwg), dim3(PM_NT), p->lds_bytes, s, A);
-}
-static void launch_fast_rt(const pmbrl_plan* p, const RolloutArgs& A0, hipStream_t s, bool fwd) {
+// one sweep on the kernels the plan resolved (plan_attrs); the latency-optimised family picks the variant per call
+static void launch_sweep(const pmbrl_plan* p, const RolloutArgs& A0, hipStream_t s, bool fwd) {
+  const int var = p->fast ? fast_variant(p->RT, A0) : 0;
+  const void* k = fwd ? p->sweep[var].fwd : p->sweep[var].bwd;
+  RolloutArgs A = A0;
+  void* args[] = {&A};
+  if (!p->fast) {
+    (void)hipLaunchKernel(k, dim3(p->nwg), dim3(PM_NT), args, p->lds_bytes, s);
+    return;
+  }
+  resident_tiles(p, p->sweep_key[var], A, fwd);
   // (more groups than fit the chip at once: batches of whole groups, one launch each -- pmbrl_host.h, mm_gpb)
   const int per = (p->mm_gpb > 0 && A0.mm_mode == 1) ? p->mm_gpb * p->mm_parts : p->nwg;
   for (int w0 = 0; w0 < p->nwg; w0 += per) {
-    RolloutArgs A = A0;
     A.wg0 = w0;
     A.launch_wg = std::min(per, p->nwg - w0);
-    if (p->prec == PMBRL_PREC_SPLIT_F16) pm_fast_split2_launch(p, A, s, fwd);
-    else if (p->prec) pm_fast_split1_launch(p, A, s, fwd);
-    else pm_fast_f32_launch(p, A, s, fwd);
+    (void)hipLaunchKernel(k, dim3(A.launch_wg), dim3(PF_NT), args, p->lds_bytes, s);
   }
 }
-static void launch_fwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) {
-  if (p->fast) return launch_fast_rt(p, A, s, true);
-  if (p->act) return pm_general_act_launch(p, A, s, true);      // (a network that is not ReLU: pmbrl_general_act.hip)
-  if (p->prec) return pm_general_split_launch(p, A, s, true);
-  switch (p->RT) {
-    case 1: launch_fwd<1>(p, A, s); break;
-    case 2: launch_fwd<2>(p, A, s); break;
-    default: launch_fwd<4>(p, A, s); break;
-  }
-}
-static void launch_bwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) {
-  if (p->fast) return launch_fast_rt(p, A, s, false);
-  if (p->act) return pm_general_act_launch(p, A, s, false);
-  if (p->prec) return pm_general_split_launch(p, A, s, false);
-  switch (p->RT) {
-    case 1: launch_bwd<1>(p, A, s); break;
-    case 2: launch_bwd<2>(p, A, s); break;
-    default: launch_bwd<4>(p, A, s); break;
-  }
-}
+static void launch_fwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) { launch_sweep(p, A, s, true); }
+static void launch_bwd_rt(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s) { launch_sweep(p, A, s, false); }
 
 // groups spread over ranks (pmbrl_mmx.h): the in-place fp64 sum of the statistics buffer over the ranks
 static int mmx_exchange(pmbrl_plan* p, hipStream_t s, double* buf, size_t n) {

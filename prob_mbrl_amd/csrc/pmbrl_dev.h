@@ -174,11 +174,7 @@ struct RolloutArgs {
   long long* prof;              // debug: cycle stamps [H][32] of workgroup 0 (nullptr = off)
 };
 
-// kernel variants of the latency-optimised family (pmbrl_fast.h)
-#define PF_VAR_LEAN 0
-#define PF_VAR_EXT 1
-#define PF_VAR_MM 2
-#define PF_VAR_MMG 3   // mm_mode 3 as ONE launch: the workgroups meet at a device-wide barrier every step
+#include "pmbrl_instances.h"   // PF_VAR_*: the kernel variants of the latency-optimised family (pmbrl_fast.h)
 
 #define PM_MARK(slot)                                                        \
   do {                                                                        \

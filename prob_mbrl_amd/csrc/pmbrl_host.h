@@ -1,14 +1,16 @@
 // Host-side declarations shared by the translation units of libpmbrl_hip.so: the plan, the records the launchers take
-// and the launchers themselves.  A kernel is compiled in exactly one object, the one that holds its launcher; another
-// object that needs it calls the launcher declared here.  The objects:
+// and the launchers themselves.  A kernel is compiled in exactly one object; another object that needs it calls the
+// launcher declared here, or, for the sweep kernels, takes it from the instance table that object exports
+// (pmbrl_instances.h).  The objects:
 //   pmbrl.hip                error string, version, build id, graph capture, the rollout plan, argument assembly and the two
 //                            rollout calls, with the kernels only they launch (the general family in exact fp32, external
 //                            moment matching, the reward kernels, pm_pack_all), and the GEMM test hook
-//   pmbrl_general_split.hip  the general family on split operands
-//   pmbrl_general_act.hip    the general family for networks that are not ReLU
-//   pmbrl_fast_f32.hip       latency-optimised sweeps, exact fp32 MFMA
+//                            (it also resolves a plan's sweep kernels from the tables and launches them)
+//   pmbrl_general_split.hip  the general family on split operands: instances and table, nothing else
+//   pmbrl_general_act.hip    the general family for networks that are not ReLU: the same
+//   pmbrl_fast_f32.hip       latency-optimised sweeps, exact fp32 MFMA: the same
 //   pmbrl_fast_split.hip     the same on split bf16 / fp16 operands; compiled once per precision (two objects)
-//   pmbrl_reg.hip            register-resident family
+//   pmbrl_reg.hip            register-resident family: instances, resolution, packer and launch
 //   pmbrl_dw.hip             the policy-gradient dW GEMMs
 //   pmbrl_tail.hip           mask packing / drawing, weighted sum, dW reduction, gradient norm, clip + Adam, sharded tail
 //   pmbrl_bnn.hip            BNN training step
@@ -24,6 +26,7 @@
 #include "pmbrl.h"
 #include "pmbrl_dev.h"
 #include "pmbrl_dw.h"
+#include "pmbrl_instances.h"
 
 int pm_fail(int code, const std::string& msg);
 static inline int fail(int code, const std::string& msg) { return pm_fail(code, msg); }
@@ -111,6 +114,12 @@ struct pmbrl_plan {
                  // statistics exchange needs a group's workgroups resident together
   int mm_fan;    // ... more than 8: parts per collector of the two-level sum exchange (0: one level)
   size_t off_ztab;   // ... and the noise standardisation of the whole group per step (pm_mm_ztable_kernel)
+  // the sweep kernels, resolved from the instance tables when the plan is created (plan_attrs): one pair per PF_VAR_* for
+  // the latency-optimised family ({nullptr, nullptr}: this plan has none for that variant), sweep[0] for the general one;
+  // sweep_key: the table rows they came from
+  PmInst sweep[PF_VAR_COUNT];
+  PmInstKey sweep_key[PF_VAR_COUNT];
+  PmInst reg_k[2];   // ... and the register-resident family's: [0] plain, [1] with cycle stamps (pm_reg_resolve)
   int reg;       // the register-resident family (pmbrl_reg.h) serves this plan's plain whole-horizon launches
   mutable int reg_calls[2];   // sweeps it has served: [0] forward, [1] adjoint (pmbrl_plan_info)
   int reg_mm;    // ... including the sweeps that moment-match the states of split groups (pmbrl_reg_mm.h): state width, 0 = no
@@ -168,63 +177,15 @@ struct ScopedTimer {
   }
 };
 
-// the instantiated (row tiles, stage pair) combinations -- keep in sync with LayoutCalc::stages (pmbrl.hip)
-#define PM_FAST_CASES                                                                  \
-  PM_FAST_CASE(1, 8, 8) PM_FAST_CASE(1, 7, 6) PM_FAST_CASE(1, 4, 4) PM_FAST_CASE(1, 2, 2) \
-  PM_FAST_CASE(2, 4, 4) PM_FAST_CASE(2, 4, 3) PM_FAST_CASE(2, 2, 2) PM_FAST_CASE(4, 2, 2) PM_FAST_CASE(4, 1, 1)
-// shape-specialised instantiations (pmbrl_fast.h: PfShape): RT, CA, CB, variant, D, U, LD, layers,
-// 16-wide tiles per hidden layer.
-// The shipped configurations: cart-pole (D=4) and double cart-pole (D=6) states, one action,
-// 2 x 200 hidden units; plain / per-step / in-kernel moment matching.
-#define PM_FAST_SHAPED_CASES                                  \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_LEAN, 4, 1, 216, 3, 13)      \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_EXT, 4, 1, 216, 3, 13)       \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_LEAN, 5, 1, 216, 3, 13)      \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_LEAN, 6, 1, 216, 3, 13)      \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_EXT, 5, 1, 216, 3, 13)       \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_EXT, 6, 1, 216, 3, 13)       \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_MM, 5, 1, 216, 3, 13)        \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_MM, 6, 1, 216, 3, 13)        \
-  PM_FAST_SHAPED(2, 4, 3, PF_VAR_MM, 4, 1, 232, 3, 13)        \
-  PM_FAST_SHAPED(2, 4, 3, PF_VAR_MM, 6, 1, 232, 3, 13)        \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_MM, 4, 1, 216, 3, 13)        \
-  PM_FAST_SHAPED(4, 1, 1, PF_VAR_MM, 6, 1, 232, 3, 13)        \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_MMG, 4, 1, 216, 3, 13)       \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_MMG, 5, 1, 216, 3, 13)       \
-  PM_FAST_SHAPED(1, 7, 6, PF_VAR_MMG, 6, 1, 216, 3, 13)
-
-// split-bf16 instantiations (pmbrl_split.h): stage pairs in K32 blocks
-// (64-row workgroups exist with two fp16 piece planes only: PM_SPLIT_PR == 2)
-#define PM_SPLIT_CASES_12 PM_SPLIT_CASE(1, 4, 3) PM_SPLIT_CASE(1, 1, 1) PM_SPLIT_CASE(2, 4, 3) PM_SPLIT_CASE(2, 1, 1)
-#if defined(PM_SPLIT_PR) && PM_SPLIT_PR == 2
-#define PM_SPLIT_CASES PM_SPLIT_CASES_12 PM_SPLIT_CASE(4, 4, 3)
-#define PM_SPLIT_SHAPED_RT4(LDV) PM_FAST_SHAPED(4, 4, 3, PF_VAR_MM, 6, 1, LDV, 3, 13)
-#else
-#define PM_SPLIT_CASES PM_SPLIT_CASES_12
-#define PM_SPLIT_SHAPED_RT4(LDV)
-#endif
-// shape-specialised split instantiations; LDV: floats per row of an activation buffer = piece planes x 240 / 2
-// (three bf16 planes: 360, two fp16 planes: 240)
-#define PM_SPLIT_SHAPED_CASES(LDV)                             \
-  PM_FAST_SHAPED(1, 4, 3, PF_VAR_LEAN, 4, 1, LDV, 3, 13)       \
-  PM_FAST_SHAPED(1, 4, 3, PF_VAR_EXT, 4, 1, LDV, 3, 13)        \
-  PM_FAST_SHAPED(1, 4, 3, PF_VAR_LEAN, 5, 1, LDV, 3, 13)       \
-  PM_FAST_SHAPED(1, 4, 3, PF_VAR_LEAN, 6, 1, LDV, 3, 13)       \
-  PM_FAST_SHAPED(2, 4, 3, PF_VAR_MM, 4, 1, LDV, 3, 13)         \
-  PM_FAST_SHAPED(1, 4, 3, PF_VAR_MM, 4, 1, LDV, 3, 13)         \
-  PM_FAST_SHAPED(2, 4, 3, PF_VAR_MM, 6, 1, LDV, 3, 13)         \
-  PM_FAST_SHAPED(1, 4, 3, PF_VAR_MMG, 5, 1, LDV, 3, 13)         \
-  PM_SPLIT_SHAPED_RT4(LDV)
-
-// 16-wide tiles of the hidden layers if every hidden layer of both nets has the same width, else -1
-static inline int hidden_tiles(const RolloutArgs& A) {
-  const int nt = A.pol.nt[1];
-  for (int l = 1; l < A.pol.nl; ++l) if (A.pol.nt[l] != nt) return -1;
-  for (int l = 1; l < A.dyn.nl; ++l) if (A.dyn.nt[l] != nt) return -1;
-  return nt;
+// a key as text, for the message of a plan that asks for an instance no table has
+static inline std::string pm_inst_name(const PmInstKey& k) {
+  std::string s;
+  for (int v : {k.rt, k.ca, k.cb, k.var, k.d, k.u, k.ld, k.nl, k.nt, k.tree}) s += (s.empty() ? "(" : ", ") + std::to_string(v);
+  return s + ") [row tiles, stage pair, variant, D, U, LD, layers, hidden tiles, tree]";
 }
-// ... the plan-side twin for the shape-specialised instances' networks (two hidden layers each): -1 also if a net has
-// another depth
+
+// 16-wide tiles of the hidden layers of the shape-specialised instances' networks (two hidden layers each, all of one
+// width); -1 for any other pair of networks
 static inline int hidden_tiles_3l(const pmbrl_plan* p) {
   if (p->pol.nl != 3 || p->dyn.nl != 3) return -1;
   const int nt = p->pol.nt[1];
@@ -288,7 +249,7 @@ bool pm_reg_shape_ok(const pmbrl_plan* p, int prec1);
 bool pm_reg_mm_shape_ok(const pmbrl_plan* p, int prec1);
 int pm_reg_mm_width(const pmbrl_plan* p);
 size_t pm_reg_pack_bytes();
-int pm_reg_set_attr(const pmbrl_plan* p);
+int pm_reg_resolve(pmbrl_plan* p);
 bool pm_reg_can_run(const pmbrl_plan* p, const RolloutArgs& A, bool fwd);
 struct ZtabArgs;   // (pmbrl_mm.h: the noise table of split moment-matching groups, formed by extra workgroups of the pack launch)
 void pm_reg_pack_launch(const pmbrl_plan* p, char* ws, const float* pol_params, const float* dyn_params, int* wflag, int gen,
@@ -296,22 +257,9 @@ void pm_reg_pack_launch(const pmbrl_plan* p, char* ws, const float* pol_params, 
 void pm_reg_unpack_abits(const pmbrl_plan* p, char* ws, hipStream_t s);
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,
                    hipStream_t s, bool fwd);
-// per-family entry points (defined in pmbrl_fast_f32.hip / pmbrl_fast_split.hip)
-// *_mmg_blocks_per_cu: workgroups of the barrier-form sweep (PF_VAR_MMG) the runtime says can be resident
-// per CU with this plan's LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor, min over forward / adjoint;
-// 0 = no such instantiation): the one-launch form is selected only if every workgroup can be resident
-int pm_fast_f32_mmg_blocks_per_cu(const pmbrl_plan* p);
-int pm_fast_split1_mmg_blocks_per_cu(const pmbrl_plan* p);
-int pm_fast_split2_mmg_blocks_per_cu(const pmbrl_plan* p);
-// general family on split operands (pmbrl_general_split.hip)
-int pm_general_split_set_attr(const pmbrl_plan* p);
-void pm_general_split_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
-// ... with a network that is not ReLU, exact fp32 and split operands (pmbrl_general_act.hip)
-int pm_general_act_set_attr(const pmbrl_plan* p);
-void pm_general_act_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
-int pm_fast_f32_set_attr(const pmbrl_plan* p);
-void pm_fast_f32_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
-int pm_fast_split1_set_attr(const pmbrl_plan* p);     // PMBRL_PREC_SPLIT
-void pm_fast_split1_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
-int pm_fast_split2_set_attr(const pmbrl_plan* p);     // PMBRL_PREC_SPLIT_F16
-void pm_fast_split2_launch(const pmbrl_plan* p, const RolloutArgs& A, hipStream_t s, bool fwd);
+// the sweep kernels' instance tables, one per object (pmbrl_instances.h; pmbrl.hip holds the general family's in exact fp32)
+PmInstTable pm_fast_f32_instances();
+PmInstTable pm_fast_split1_instances();     // PMBRL_PREC_SPLIT
+PmInstTable pm_fast_split2_instances();     // PMBRL_PREC_SPLIT_F16
+PmInstTable pm_general_split_instances();
+PmInstTable pm_general_act_instances();

@@ -54,26 +54,24 @@ size_t pm_reg_pack_bytes() { return (size_t)PR_PACK_FLOATS * sizeof(float); }
 // state width of the moment-matching instance this plan's sweeps run on (0: the plain instance)
 int pm_reg_mm_width(const pmbrl_plan* p) { return (p->reg && p->mm_mode == 1) ? p->cfg.D : 0; }
 
-template <int MMD, bool TREE = false>
-static int reg_set_attr_mm() {
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_reg_fwd_kernel<false, MMD, TREE>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PR_LDS_FLOATS * sizeof(float))));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_reg_fwd_kernel<true, MMD, TREE>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PR_LDS_FLOATS * sizeof(float))));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_reg_bwd_kernel<false, MMD, TREE>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PRB_LDS_FLOATS * sizeof(float))));
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_reg_bwd_kernel<true, MMD, TREE>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PRB_LDS_FLOATS * sizeof(float))));
-  return 0;
-}
-int pm_reg_set_attr(const pmbrl_plan* p) {
-  if (p->reg_mm == 4 && p->mm_fan) return reg_set_attr_mm<4, true>();
-  switch (p->reg_mm) {
-    case 4: return reg_set_attr_mm<4>();
-    case 5: return reg_set_attr_mm<5>();
-    case 6: return reg_set_attr_mm<6>();
-    default: return reg_set_attr_mm<0>();
+// the instantiations of PM_REG_INSTANCES and their table
+#define PM_INST(RT, CA, CB, VAR, D, U, LD, NL, NT, TREE)                       \
+  {reinterpret_cast<const void*>(&pm_reg_fwd_kernel<VAR != 0, D, TREE != 0>), \
+   reinterpret_cast<const void*>(&pm_reg_bwd_kernel<VAR != 0, D, TREE != 0>)},
+static const PmInst fns[] = {PM_REG_INSTANCES};
+#undef PM_INST
+static_assert(sizeof(fns) / sizeof(fns[0]) == pm_reg_n, "one kernel pair per key");
+// the plan's two pairs (p->reg_k: plain, with cycle stamps), their LDS attributes set
+int pm_reg_resolve(pmbrl_plan* p) {
+  for (int prof = 0; prof < 2; ++prof) {
+    const PmInstKey k = pm_reg_key(p->reg_mm, p->reg_mm == 4 && p->mm_fan, prof != 0);
+    const int i = pm_inst_find({pm_reg_keys, fns, pm_reg_n}, k);
+    if (i < 0) return pm_fail(-3, "no register-resident instance for " + pm_inst_name(k));
+    p->reg_k[prof] = fns[i];
+    HIPCHK(hipFuncSetAttribute(fns[i].fwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PR_LDS_FLOATS * sizeof(float))));
+    HIPCHK(hipFuncSetAttribute(fns[i].bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(PRB_LDS_FLOATS * sizeof(float))));
   }
+  return 0;
 }
 
 static void reg_net(const pmbrl_plan* p, int net, const NetPlan& n, const NetDev& d, RegNet& r) {
@@ -181,17 +179,6 @@ void pm_reg_unpack_abits(const pmbrl_plan* p, char* ws, hipStream_t s) {
   hipLaunchKernelGGL(pm_reg_unpack_abits_kernel, dim3(p->nwg, p->cfg.H), dim3(PR_NTHR), 0, s, U);
 }
 
-template <int MMD, bool TREE = false>
-static void reg_launch_mm(int nwg, const RegArgs& R, hipStream_t s, bool fwd) {
-  if (fwd) {
-    if (R.prof) hipLaunchKernelGGL((pm_reg_fwd_kernel<true, MMD, TREE>), dim3(nwg), dim3(PR_NTHR), PR_LDS_FLOATS * sizeof(float), s, R);
-    else hipLaunchKernelGGL((pm_reg_fwd_kernel<false, MMD, TREE>), dim3(nwg), dim3(PR_NTHR), PR_LDS_FLOATS * sizeof(float), s, R);
-  } else {
-    if (R.prof) hipLaunchKernelGGL((pm_reg_bwd_kernel<true, MMD, TREE>), dim3(nwg), dim3(PR_NTHR), PRB_LDS_FLOATS * sizeof(float), s, R);
-    else hipLaunchKernelGGL((pm_reg_bwd_kernel<false, MMD, TREE>), dim3(nwg), dim3(PR_NTHR), PRB_LDS_FLOATS * sizeof(float), s, R);
-  }
-}
-
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,
                    hipStream_t s, bool fwd) {
   ++p->reg_calls[fwd ? 0 : 1];
@@ -207,15 +194,11 @@ void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const fl
   const int total = R.mm.xcd == 2 ? 8 * 2 * p->mm_fan : R.mm.xcd ? (p->G + 7) / 8 * 8 * p->mm_parts : p->nwg;
   int per = (p->reg_mm && p->mm_gpb > 0) ? p->mm_gpb * p->mm_parts : total;
   if (R.mm.xcd == 1 && per < total) per = (p->mm_gpb + 7) / 8 * 8 * p->mm_parts;
+  const PmInst& K = p->reg_k[R.prof ? 1 : 0];
   for (int w0 = 0; w0 < total; w0 += per) {
     R.wg0 = w0;
-    const int n = std::min(per, total - w0);
-    if (p->reg_mm == 4 && p->mm_fan) { reg_launch_mm<4, true>(n, R, s, fwd); continue; }
-    switch (p->reg_mm) {
-      case 4: reg_launch_mm<4>(n, R, s, fwd); break;
-      case 5: reg_launch_mm<5>(n, R, s, fwd); break;
-      case 6: reg_launch_mm<6>(n, R, s, fwd); break;
-      default: reg_launch_mm<0>(n, R, s, fwd); break;
-    }
+    void* args[] = {&R};
+    (void)hipLaunchKernel(fwd ? K.fwd : K.bwd, dim3(std::min(per, total - w0)), dim3(PR_NTHR), args,
+                          (fwd ? PR_LDS_FLOATS : PRB_LDS_FLOATS) * sizeof(float), s);
   }
 }

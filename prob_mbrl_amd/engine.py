@@ -427,14 +427,18 @@ class Engine:
         self.plan = plan
         info = (C.c_int32 * _lib.INFO_COUNT)()
         _lib.check(self.lib.pmbrl_plan_info(plan, info), 'pmbrl_plan_info')
-        self.info = dict(rows_per_wg=info[0], n_wg=info[1], row_tiles=info[2],
-                         lds_bytes=info[3], n_pol_params=info[4], n_dyn_params=info[5],
-                         dw_splits=info[6], mm_mode=info[7], LD=info[8], dw_blocks=info[9],
-                         fast=info[10], stages=(info[11] >> 4, info[11] & 15), mm_grid=info[12],
-                         precision={_lib.PREC_SPLIT: 'split', _lib.PREC_SPLIT_F16: 'split_f16'}.get(info[13], 'f32'),
-                         dw_pipe=info[14], mm_parts=info[15], reg=info[16], replay=info[17], inplace=info[18])
-        self.n_pol_params = info[4]
-        self.n_dyn_params = info[5]
+        L = _lib
+        self.info = dict(rows_per_wg=info[L.INFO_ROWS_PER_WG], n_wg=info[L.INFO_N_WG], row_tiles=info[L.INFO_ROW_TILES],
+                         lds_bytes=info[L.INFO_LDS_BYTES], n_pol_params=info[L.INFO_N_POL_PARAMS],
+                         n_dyn_params=info[L.INFO_N_DYN_PARAMS], dw_splits=info[L.INFO_DW_SPLITS],
+                         mm_mode=info[L.INFO_MM_MODE], LD=info[L.INFO_LD], dw_blocks=info[L.INFO_DW_BLOCKS],
+                         fast=info[L.INFO_FAST], stages=(info[L.INFO_STAGES] >> 4, info[L.INFO_STAGES] & 15),
+                         mm_grid=info[L.INFO_MM_GRID],
+                         precision={L.PREC_SPLIT: 'split', L.PREC_SPLIT_F16: 'split_f16'}.get(info[L.INFO_PRECISION], 'f32'),
+                         dw_pipe=info[L.INFO_DW_PIPE], mm_parts=info[L.INFO_MM_PARTS], reg=info[L.INFO_REG],
+                         replay=info[L.INFO_REPLAY], inplace=info[L.INFO_INPLACE])
+        self.n_pol_params = info[L.INFO_N_POL_PARAMS]
+        self.n_dyn_params = info[L.INFO_N_DYN_PARAMS]
         ws_bytes = self.lib.pmbrl_plan_workspace_bytes(plan)
         self.ws_bytes = ws_bytes
         self.workspace = torch.empty(ws_bytes + 256, dtype=torch.uint8, device=self.device)
@@ -710,13 +714,30 @@ class Engine:
         _lib.check(self.lib.pmbrl_plan_set_replay(self.plan, int(on)), 'set_replay')
         info = (C.c_int32 * _lib.INFO_COUNT)()
         _lib.check(self.lib.pmbrl_plan_info(self.plan, info), 'plan_info')
-        self.info['replay'] = int(info[17])
+        self.info['replay'] = int(info[_lib.INFO_REPLAY])
 
     def reg_calls(self):
         """(forward sweeps, adjoint sweeps) of this plan that ran on the register-resident family (csrc/pmbrl_reg.h)."""
         info = (C.c_int32 * _lib.INFO_COUNT)()
         _lib.check(self.lib.pmbrl_plan_info(self.plan, info), 'plan_info')
-        return int(info[19]), int(info[20])
+        return int(info[_lib.INFO_REG_FWD_CALLS]), int(info[_lib.INFO_REG_BWD_CALLS])
+
+    def sweep_kernels(self):
+        """The sweep kernels the plan resolved when it was created (pmbrl_plan_sweep_kernel): {variant: (forward, adjoint)}
+        by the runtime's names, the variants of _lib.SWEEP_VARIANTS the plan has an instance for.  A plan on the general
+        family has one pair, under 'lean'."""
+        out = {}
+        for v, key in enumerate(_lib.SWEEP_VARIANTS):
+            if key in ('ext', 'mm', 'mmg') and not self.info['fast']:
+                continue
+            names = []
+            for adjoint in (0, 1):
+                name = C.c_char_p()
+                _lib.check(self.lib.pmbrl_plan_sweep_kernel(self.plan, v, adjoint, C.byref(name)), 'plan_sweep_kernel')
+                names.append((name.value or b'').decode())
+            if names[0]:
+                out[key] = tuple(names)
+        return out
 
     def replay_count(self):
         """(forward calls, adjoint calls) that went out as one graph launch so far."""

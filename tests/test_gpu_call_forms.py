@@ -18,6 +18,7 @@ DEV = 'cuda:0'
 ONE_GROUP = dict(mm_groups=0)      # one moment-matching group over all rows: it spans workgroups
 # ... of the cart-pole shape (2 x 200 units: the sweeps' prologue form needs their wide activation rows), 80 rows, 6 steps
 SPANNING = ('synthetic/cartpole_mm', dict(P=1, S=80, H=6))
+NO_REG = {'PMBRL_REG': '0'}        # the latency-optimised family where the register-resident one would serve the plan
 # id: (fixture, fixture overrides, environment, engine arguments, optimiser in the call, what plan_info must say)
 FORMS = {
     'reg_plain': ('full200_nomm', {}, {}, {}, True, dict(reg=1, mm_mode=0)),
@@ -35,6 +36,16 @@ FORMS = {
     'pipelined_dw': ('nomm_d4', {}, {'PMBRL_DW_PIPE': '5,4,3'}, {}, True, dict(dw_pipe=3)),
     'loss_launch': ('full200_nomm', {}, {'PMBRL_FUSE_LOSS': '0'}, {}, True, dict(reg=1)),
     'no_optimiser': ('full200_nomm', {}, {}, {}, False, dict(reg=1)),
+    # ... and one form per instance table that the forms above leave out, shape-specialised and generic (KERNELS below)
+    'lo_shaped_lean': ('full200_nomm', {}, NO_REG, {}, True, dict(fast=1, reg=0, mm_mode=0, precision='split_f16', stages=(4, 3))),
+    'lo_shaped_mm_parts2': ('full200_mmg', {}, NO_REG, {}, True, dict(fast=1, reg=0, mm_mode=1, mm_parts=2, precision='split_f16')),
+    'lo_split_bf16': ('full200_nomm', {}, {}, dict(precision='split'), True, dict(fast=1, reg=0, precision='split', stages=(4, 3))),
+    'lo_f32_shaped': ('full200_nomm', {}, {}, dict(precision='f32'), True, dict(fast=1, reg=0, precision='f32', stages=(7, 6))),
+    'lo_f32_generic': ('nomm_d4', {}, {}, dict(precision='f32'), True, dict(fast=1, precision='f32', stages=(2, 2))),
+    'general_f32': ('nomm_d4', {}, {}, dict(force_generic=True, precision='f32'), True, dict(fast=0, mm_mode=0, precision='f32')),
+    'general_tanh': ('activations/act_tanh_d4', {}, {}, {}, True, dict(fast=0, mm_mode=0, precision='split_f16')),
+    'lo_rows64_split': ('dcp200_mmg50', {}, {'PMBRL_MM_PARTS': '1'}, {}, True, dict(fast=1, row_tiles=4, mm_mode=1, mm_parts=1, precision='split_f16')),
+    'lo_tree': ('synthetic/cartpole_mm', dict(P=1, S=144, H=6), NO_REG, {}, True, dict(fast=1, reg=0, mm_mode=1, mm_parts=9, precision='split_f16')),
 }
 # graph nodes of (forward call, adjoint call), measured on the commit before the split: exact, no margin
 NODES = {
@@ -53,11 +64,84 @@ NODES = {
     'spanning_barrier': (6, 8),
     'spanning_perstep': (11, 12),
     'wide_ext': (24, 25),
+    # (the forms added with the instance tables: counted on the commit before them)
+    'general_f32': (4, 4),
+    'general_tanh': (4, 4),
+    'lo_f32_generic': (4, 4),
+    'lo_f32_shaped': (4, 4),
+    'lo_rows64_split': (5, 6),
+    'lo_shaped_lean': (4, 5),
+    'lo_shaped_mm_parts2': (7, 8),
+    'lo_split_bf16': (4, 5),
+    'lo_tree': (8, 8),
 }
+# The sweep kernels of each form's forward and adjoint call, (variant of Engine.sweep_kernels(), name) each: what the
+# commit before the instance tables launched, from a rocprofv3 --kernel-trace of every form there (mangled names; the
+# trace names the kernel descriptor, NAME.kd, the runtime the kernel, NAME)
+KERNELS = {
+    'external_perstep': (('ext', '_Z19pm_rollout_fwd_fastILi1ELi1ELi1ELi1E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                          ('ext', '_Z19pm_rollout_bwd_fastILi1ELi1ELi1ELi1E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'fast_mm': (('mm', '_Z19pm_rollout_fwd_fastILi1ELi1ELi1ELi2E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                 ('mm', '_Z19pm_rollout_bwd_fastILi1ELi1ELi1ELi2E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'fast_mm_parts2': (('mm', '_Z19pm_rollout_fwd_fastILi1ELi1ELi1ELi2E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                        ('mm', '_Z19pm_rollout_bwd_fastILi1ELi1ELi1ELi2E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'fast_plain': (('lean', '_Z19pm_rollout_fwd_fastILi1ELi1ELi1ELi0E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                    ('lean', '_Z19pm_rollout_bwd_fastILi1ELi1ELi1ELi0E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'general': (('lean', '_Z14pm_rollout_fwdILi1ELi2ELi0ELb0EEv11RolloutArgs'),
+                 ('lean', '_Z14pm_rollout_bwdILi1ELi2ELi0ELb0EEv11RolloutArgs')),
+    'general_f32': (('lean', '_Z14pm_rollout_fwdILi1ELi0ELi0ELb0EEv11RolloutArgs'),
+                     ('lean', '_Z14pm_rollout_bwdILi1ELi0ELi0ELb0EEv11RolloutArgs')),
+    'general_tanh': (('lean', '_Z14pm_rollout_fwdILi1ELi2ELi0ELb1EEv11RolloutArgs'),
+                      ('lean', '_Z14pm_rollout_bwdILi1ELi2ELi0ELb1EEv11RolloutArgs')),
+    'learned_reward': (('lean', '_Z14pm_rollout_fwdILi1ELi2ELi0ELb0EEv11RolloutArgs'),
+                        ('lean', '_Z14pm_rollout_bwdILi1ELi2ELi0ELb0EEv11RolloutArgs')),
+    'lo_f32_generic': (('lean', '_Z19pm_rollout_fwd_fastILi1ELi2ELi2ELi0E7PfShapeILi0ELi0ELi0ELi0ELi0EELi0EEv11RolloutArgs'),
+                        ('lean', '_Z19pm_rollout_bwd_fastILi1ELi2ELi2ELi0E7PfShapeILi0ELi0ELi0ELi0ELi0EELi0EEv11RolloutArgs')),
+    'lo_f32_shaped': (('lean', '_Z19pm_rollout_fwd_fastILi1ELi7ELi6ELi0E7PfShapeILi5ELi1ELi216ELi3ELi13EELi0EEv11RolloutArgs'),
+                       ('lean', '_Z19pm_rollout_bwd_fastILi1ELi7ELi6ELi0E7PfShapeILi5ELi1ELi216ELi3ELi13EELi0EEv11RolloutArgs')),
+    'lo_rows64_split': (('mm', '_Z19pm_rollout_fwd_fastILi4ELi4ELi3ELi2E7PfShapeILi6ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs'),
+                         ('mm', '_Z19pm_rollout_bwd_fastILi4ELi4ELi3ELi2E7PfShapeILi6ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs')),
+    'lo_shaped_lean': (('lean', '_Z19pm_rollout_fwd_fastILi1ELi4ELi3ELi0E7PfShapeILi5ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs'),
+                        ('lean', '_Z19pm_rollout_bwd_fastILi1ELi4ELi3ELi0E7PfShapeILi5ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs')),
+    'lo_shaped_mm_parts2': (('mm', '_Z19pm_rollout_fwd_fastILi1ELi4ELi3ELi2E7PfShapeILi4ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs'),
+                             ('mm', '_Z19pm_rollout_bwd_fastILi1ELi4ELi3ELi2E7PfShapeILi4ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs')),
+    'lo_split_bf16': (('lean', '_Z19pm_rollout_fwd_fastILi1ELi4ELi3ELi0E7PfShapeILi5ELi1ELi360ELi3ELi13EELi1EEv11RolloutArgs'),
+                       ('lean', '_Z19pm_rollout_bwd_fastILi1ELi4ELi3ELi0E7PfShapeILi5ELi1ELi360ELi3ELi13EELi1EEv11RolloutArgs')),
+    'lo_tree': (('mm', '_Z19pm_rollout_fwd_fastILi1ELi4ELi3ELi2E11PfShapeTreeILi4ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs'),
+                 ('mm', '_Z19pm_rollout_bwd_fastILi1ELi4ELi3ELi2E11PfShapeTreeILi4ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs')),
+    'loss_launch': (('reg', '_Z17pm_reg_fwd_kernelILb0ELi0ELb0EEv7RegArgs'),
+                     ('reg', '_Z17pm_reg_bwd_kernelILb0ELi0ELb0EEv7RegArgs')),
+    'no_optimiser': (('reg', '_Z17pm_reg_fwd_kernelILb0ELi0ELb0EEv7RegArgs'),
+                      ('reg', '_Z17pm_reg_bwd_kernelILb0ELi0ELb0EEv7RegArgs')),
+    'perstep_switches_d4': (('mm', '_Z19pm_rollout_fwd_fastILi1ELi1ELi1ELi2E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                             ('mm', '_Z19pm_rollout_bwd_fastILi1ELi1ELi1ELi2E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'pipelined_dw': (('lean', '_Z19pm_rollout_fwd_fastILi1ELi1ELi1ELi0E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                      ('ext', '_Z19pm_rollout_bwd_fastILi1ELi1ELi1ELi1E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'reg_plain': (('reg', '_Z17pm_reg_fwd_kernelILb0ELi0ELb0EEv7RegArgs'),
+                   ('reg', '_Z17pm_reg_bwd_kernelILb0ELi0ELb0EEv7RegArgs')),
+    'reg_split_groups': (('reg', '_Z17pm_reg_fwd_kernelILb0ELi4ELb0EEv7RegArgs'),
+                          ('reg', '_Z17pm_reg_bwd_kernelILb0ELi4ELb0EEv7RegArgs')),
+    'spanning_barrier': (('mmg', '_Z19pm_rollout_fwd_fastILi1ELi4ELi3ELi3E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs'),
+                          ('mmg', '_Z19pm_rollout_bwd_fastILi1ELi4ELi3ELi3E7PfShapeILi0ELi0ELi0ELi0ELi0EELi2EEv11RolloutArgs')),
+    'spanning_perstep': (('mm', '_Z19pm_rollout_fwd_fastILi1ELi4ELi3ELi2E7PfShapeILi4ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs'),
+                          ('mm', '_Z19pm_rollout_bwd_fastILi1ELi4ELi3ELi2E7PfShapeILi4ELi1ELi240ELi3ELi13EELi2EEv11RolloutArgs')),
+    'wide_ext': (('lean', '_Z14pm_rollout_fwdILi1ELi2ELi0ELb0EEv11RolloutArgs'),
+                  ('lean', '_Z14pm_rollout_bwdILi1ELi2ELi0ELb0EEv11RolloutArgs')),
+}
+
+
+def check_kernels(form, eng):
+    """The plan resolved the sweep kernels that the parent of the instance tables launched for this form.  The names
+    are what plan creation resolved (pmbrl_plan_sweep_kernel), not what a launch used: that the launches use the resolved
+    pointer was checked once, by tracing every form on both trees (DESIGN_LOG.md)."""
+    got = eng.sweep_kernels()
+    for adjoint, (variant, name) in enumerate(KERNELS[form]):
+        assert got.get(variant, ('', ''))[adjoint] == name, (form, variant, got)
 
 
 def build(form, monkeypatch):
     name, over, env, kw, with_adam, want = FORMS[form] if isinstance(form, str) else form
+    from tests import act_oracle as AO
     from tests import lr_oracle as LR
     from prob_mbrl_amd import engine as E
     from prob_mbrl_amd import problem as PB
@@ -65,7 +149,8 @@ def build(form, monkeypatch):
     if name.startswith('synthetic/'):
         d = PB.synthetic_problem(name.split('/')[1], seed=0, data_seed=0, **over)
     else:
-        d = dict(LR.load(name.split('/')[1]) if learned else common.load(name))
+        d = dict(LR.load(name.split('/')[1]) if learned else AO.load(name.split('/')[1]) if name.startswith('activations/')
+                 else common.load(name))
         for k, v in over.items():
             d[k] = np.asarray(v)
     for k, v in env.items():
@@ -115,6 +200,7 @@ def test_call_form_records_the_same_launches_and_replays_bit_equal(form, monkeyp
     from prob_mbrl_amd import engine as E
     want = eager(form, monkeypatch)
     eng, st, fwd, bwd = build(form, monkeypatch)
+    check_kernels(form, eng)
     p0 = st['params'].clone()
     gf = E.Graph(fwd, warmup=1)
     gb = E.Graph(bwd, warmup=1)
