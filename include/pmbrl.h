@@ -181,7 +181,11 @@ typedef struct pmbrl_config {
  *   PMBRL_MM_MODE2          groups that span workgroups: separate moment-matching kernels between per-step launches
  *                           instead of the in-sweep form (mm_mode 3)
  *   PMBRL_MM_NO_BATCH       no batches of whole groups beyond the CU count: split groups keep every workgroup resident
- *   PMBRL_DW_NO_WIDE        no LDS-staged tile kernels for the dW GEMM of layers >= 128 x 128 (the block kernel instead)
+ *   PMBRL_DW_NO_WIDE        no LDS-staged tile kernels for the dW GEMM of layers >= 128 x 128 (the block kernel instead).
+ *                           On a plan of the register-resident family the ADJOINT sweep then goes to the
+ *                           latency-optimised family (the forward sweep stays): the register-resident adjoint stashes no
+ *                           delta of the second hidden layer, and only the whole-layer kernel rebuilds it -- slower, and
+ *                           the adjoint call needs the parameter pointers in its inputs
  *   PMBRL_REG_DEBUG         the register-resident family prints its workspace offsets at every launch
  * Off when set to 0 (on when unset or any other number):
  *   PMBRL_LDS_TILES         LDS-resident weight tiles (pmbrl_fast.h, lds_tile_s): the shape-specialised 16-row

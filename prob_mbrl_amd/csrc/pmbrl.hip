@@ -1268,7 +1268,10 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
   if (R.exec && same) {
     HIPCHK(hipGraphLaunch(R.exec, s));
     ++R.launches;
-    if (slot == 0) { p->old_pack_stale = R.aux & 1; p->abits_packed = (R.aux >> 1) & 1; }   // (the host-side notes the recorded call left: which families' weights it packed, the form of its activity bits)
+    // (the host-side notes the recorded call left -- forward: which families' weights it packed, the form of its activity
+    //  bits; adjoint: whether its sweep left the second hidden layer's delta to the dW GEMM)
+    if (slot == 0) { p->old_pack_stale = R.aux & 1; p->abits_packed = (R.aux >> 1) & 1; }
+    else p->dw_g1_rebuilt = (R.aux >> 2) & 1;
     return 0;
   }
   if (!same || R.seen == 0) {      // first sight of these arguments: as usual, remember them
@@ -1307,7 +1310,7 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
     return body(s);
   }
   R.exec = ex;
-  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1);
+  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1) | ((p->dw_g1_rebuilt & 1) << 2);
   HIPCHK(hipGraphLaunch(R.exec, s));
   ++R.launches;
   return 0;
@@ -2016,6 +2019,10 @@ static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutA
   for (int l = 0; l < p->pol.nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
   W.part = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_part);
   W.nvalid = C.status;
+  if (p->dw_g1_rebuilt) {      // (gT[1] does not exist: the layer kernel rebuilds it)
+    pm_reg_dw_rebuild_args(p, static_cast<char*>(C.workspace), W);
+    W.rc_inv_keep = A.pol.inv_keep[1];
+  }
   return W;
 }
 // stage 4, the groups spanning workgroups (mm_mode 3): dL/dx travels between the steps through two carry buffers.
@@ -2109,12 +2116,17 @@ static int bwd_dw(pmbrl_plan* p, const BwdCall& C, const DwArgs& W, bool piped) 
   return 0;
 }
 
-static int rollout_bwd(pmbrl_plan* p, const BwdCall& C) {
+// A0, reg_bwd: the call's sweep arguments (bwd_args) and the family they go to, assembled once by rollout_bwd_replay --
+// its replay key holds the family too
+static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, bool reg_bwd) {
   hipStream_t s = C.stream;
-  RolloutArgs A;
-  if (int rc = bwd_args(p, C, A)) return rc;
-  const bool reg_bwd = pm_reg_can_run(p, A, false);
+  RolloutArgs A = A0;
   if (int rc = check_bwd(p, C, reg_bwd)) return rc;
+  // the register-resident adjoint (always over its own family's forward stashes: the forward call takes the family
+  // whenever the adjoint call can) stashes no delta of the policy's second hidden layer -- every dW launch of THIS call,
+  // pipelined ranges and the sharded tail's included, rebuilds it; the other family's adjoint on the same forward
+  // (optional outputs, PMBRL_REG_BWD=0) writes gT[1] and keeps the classic kernel
+  p->dw_g1_rebuilt = reg_bwd ? 1 : 0;
   const pmbrl_adam* opt = C.opt;
   const bool tail = bwd_tail(p, C);
   float* const xb = p->tail_buf_d;
@@ -2187,7 +2199,7 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C) {
 }
 
 // what makes two adjoint calls "the same" (pmbrl_plan_set_replay)
-static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C) {
+static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
   const pmbrl_adam* opt = C.opt;
   ReplayKey K;
   K.val(C.stream); K.val(C.workspace); K.add(C.in, sizeof(*C.in));
@@ -2206,6 +2218,9 @@ static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C) {
   // what the forward call left behind decides which conversions the adjoint call queues (weights repacked for the other
   // family, activity words unpacked): a recording is only good for the state it was recorded in
   K.val(p->old_pack_stale); K.val(p->abits_packed);
+  // ... and the family this call's sweep takes decides which form of the layer's dW kernel follows it (dw_g1_rebuilt)
+  const int g1_rebuilt = reg_bwd ? 1 : 0;
+  K.val(g1_rebuilt);
   return K;
 }
 
@@ -2213,18 +2228,21 @@ static int rollout_bwd_replay(pmbrl_plan* p, const BwdCall& C) {
   if (!p || !C.workspace || !C.in || !C.states || !C.actions || !C.rewards || !C.grad_rewards || !C.grad_pol_flat)
     return fail(-1, "null argument");
   HIPCHK(hipSetDevice(p->device));
+  RolloutArgs A;      // (no stream in it: the same for the eager call, the recording and the key)
+  if (int rc = bwd_args(p, C, A)) return rc;
+  const bool reg_bwd = pm_reg_can_run(p, A, false);
   const bool tail = bwd_tail(p, C);
   if (tail) ++p->tail_calls;
   if (tail && p->grad_p2p) {
     // the peer-to-peer exchange cannot be recorded (its generation is a kernel argument): eagerly, whatever
     // pmbrl_plan_set_replay says
     if (p->rp[1].exec || p->rp[1].seen) replay_drop(p, 1);
-    return rollout_bwd(p, C);
+    return rollout_bwd(p, C, A, reg_bwd);
   }
-  return replay_call(p, 1, bwd_key(p, C), C.stream, [&](hipStream_t on) {
+  return replay_call(p, 1, bwd_key(p, C, reg_bwd), C.stream, [&](hipStream_t on) {
     BwdCall Con = C;
     Con.stream = on;
-    return rollout_bwd(p, Con);
+    return rollout_bwd(p, Con, A, reg_bwd);
   });
 }
 

@@ -45,6 +45,13 @@ struct DwArgs {
   int pipe_k;                            // index of this launch, 0 = the highest steps
   int c_begin, c_end;                    // chunk range of this launch (c_end = the previous launch's c_begin)
   int rows_before;                       // partial rows the earlier launches own (the last launch has more)
+  // Rebuilding form of the whole-layer kernel (pm_dw_layer_rc_kernel: behind a register-resident adjoint sweep, which
+  // stashes no delta of the policy's second hidden layer; a call fills these, dw_call_args).  RT = 1: chunk c is the
+  // (step, workgroup) block c of every stash and of the activity words -- chunks_per_step is the sweep's nwg
+  const unsigned* rc_abits;              // (nullptr: the classic form, the delta is fetched) the forward sweep's activity words of that layer: [chunk][sweep wave (4)][lane]
+  const float* rc_head;                  // the adjoint pack's transposed head weights: [tile][2 blocks][lane][4]
+  float rc_inv_keep;                     // 1 / keep of the layer's dropout
+  int rc_D, rc_U;                        // state and action widths: which rows of a gT[l + 1] block a lane group holds
 };
 
 // tile sizes of the kernels of whole layers, which the plan's choice of them reads (pmbrl_dw_kernels.h)

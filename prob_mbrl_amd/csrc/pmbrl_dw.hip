@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <vector>
 
 #include "pmbrl_host.h"
@@ -75,9 +76,12 @@ int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wa
 
 // dynamic LDS of the kernels plan_dw chose for this plan
 int pm_dw_set_attr(const pmbrl_plan* p) {
-  if (p->dw_layer13 >= 0)
+  if (p->dw_layer13 >= 0) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rc_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
+  }
   if (p->dw_pre_mask) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
@@ -129,7 +133,14 @@ void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
     hipLaunchKernelGGL(pm_dw_wide_pre_kernel, units, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
   else if (p->n_dw_units)
     hipLaunchKernelGGL(pm_dw_wide_kernel, units, dim3(PM_DW_NT), PM_DWW_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
-  if (p->dw_layer13 >= 0)
+  // (W carries what rebuilds the delta operand -- dw_call_args, behind a register-resident adjoint sweep, which left no
+  //  stash of it: the rebuilding form.  It is written for 16-row chunks and the policy's second hidden layer, which is
+  //  all pm_reg_can_run lets reach it)
+  const bool rebuild = W.rc_abits != nullptr;
+  assert(!rebuild || (W.RT == 1 && p->dw_layer13 == PM_REG_DW_LAYER));
+  if (p->dw_layer13 >= 0 && rebuild)
+    hipLaunchKernelGGL(pm_dw_layer_rc_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
+  else if (p->dw_layer13 >= 0)
     hipLaunchKernelGGL(pm_dw_layer_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
 }
 void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s) { pm_dw_launch(p, dw_range_args(p, W, k), s); }

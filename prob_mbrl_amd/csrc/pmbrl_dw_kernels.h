@@ -25,6 +25,7 @@
 #pragma once
 #include "pmbrl_dw.h"
 #include "pmbrl_split.h"
+#include "pmbrl_reg_head.h"
 
 #include <utility>
 #include <type_traits>
@@ -955,11 +956,152 @@ __global__ __launch_bounds__(PM_DWP_NT, 1) void pm_dw_narrow_pre_kernel(const Dw
 // the 128 x 128 tiles above leave a workgroup a dozen steps of one exposed memory round trip each, in two rounds
 // over the chip (65 us for 173 MB at the cart-pole shape).  One workgroup per row-step range and CU instead:
 // 53 KB per step in flight per CU, every stash byte fetched once, wave w accumulates tile rows w and w + 8.
+//
+// RC (pm_dw_layer_rc_kernel): the delta operand is REBUILT, not fetched.  Behind a register-resident adjoint sweep
+// (pmbrl_reg.h) gT[l] does not exist: delta_l of a 16-feature tile and a 16-row chunk is one MFMA pair -- the adjoint
+// pack's transposed head weights (A.rc_head: [tile][2 blocks][lane][4]) times the head gradient of the chunk (the
+// [16][16] block of gT[l + 1], as bf16 pieces: PR_HEAD_BFRAGS) -- times the {0, 1 / keep} multipliers of the tile's
+// activity nibble (A.rc_abits: the forward sweep's words [chunk][sweep wave][lane], nibble q = tile 4 q + wave, nibble 3
+// = tile 12 on wave pr_xwave(0)).  The same instructions on the same operand bytes as the sweep's head_adjoint: the same
+// bits the sweep used to stash.  Each wave builds the A tiles it alone consumes (tile rows wid, wid + 8; both chunks of
+// a step): ~0.4 KB of loads per chunk where the stash tile rows were 26.6 KB per step, 8 small MFMAs beside the step's
+// 78.  The result comes out in accumulator layout (lane (row, g): features 4 g + r of chunk row `row`) and goes into
+// the stage's [piece][feature][k] image by 2-byte LDS stores, into rows only this wave reads back; rows and features past
+// the batch or the width are zero through their nibbles and the zero rows of the pack.  RT = 1 only (a chunk is one
+// (step, workgroup) block of every stash), which is all the register-resident family runs.
 #define PM_DWL_F (PM_DWL_NT * 16)
 #define PM_DWL_STAGE (2 * PM_DWL_F * 2 * PM_DWW_LDK)
 #define PM_DWL_LDS_BYTES (2 * PM_DWL_STAGE * 2)
 #define PM_DWL_Q ((PM_DWL_F * 8 + PM_DW_NT - 1) / PM_DW_NT)      // float4 quads per thread and operand: 4
-__global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A, int l) {
+// What a wave of the rebuilding form holds of its operand, and the three things it does with it.  Lane (c16, g) is the
+// sweep's lane (row, g): chunk row c16, the head pairs of network inputs 2 g + s, i.e. actions j = 2 g + s - D -- rows j
+// (mean) and U + j (log-std) of the gT[l + 1] block, zero where there is no such action (what the sweep's registers held
+// there).  The form that does not need a state holds PmDwNone.
+struct PmDwNone {};
+// ... and what a thread of the classic form holds of the FETCHED operand: the raw quads of a step, their offsets, the
+// bias sums
+struct PmDwFetched {
+  f32x4 ra[PM_DWL_Q];
+  float bs[PM_DWL_Q];
+  unsigned offA[PM_DWL_Q];
+};
+struct PmDwRc {
+  f32x4 hw[2][2];                  // transposed head weights of this wave's two tiles: [tile][block]
+  float hgm[2][2], hgl[2][2];      // head gradient of the step's two chunks: [chunk][slot]
+  unsigned abw[2][2];              // activity words: [chunk][tile]
+  float rbs[2][4];                 // bias sums of this lane's row: [tile][accumulator register]
+  unsigned hoff_m[2], hoff_l[2], ab_off[2], ab_sh[2];
+  bool hok[2], two;                // two: this wave owns tile rows wid and wid + 8 (waves 0 .. 4)
+  size_t hblk;
+  int row0;                        // first feature row of the wave's first tile
+
+  __device__ __forceinline__ void init(const DwArgs& A, int l, int wid, int lane) {
+    const int g = lane >> 4, c16 = lane & 15;
+    two = wid + 8 < PM_DWL_NT;
+    row0 = wid * 16;
+    hblk = (size_t)A.nt[l + 2] * 16 * A.Rw;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int tr = (i == 0 || two) ? wid + 8 * i : wid;
+#pragma unroll
+      for (int b = 0; b < 2; ++b) hw[i][b] = *reinterpret_cast<const f32x4*>(A.rc_head + (size_t)(tr * 2 + b) * PR_FRAG + lane * 4);
+      ab_off[i] = (unsigned)((tr == PR_XT ? pr_xwave(0) : (tr & (PR_NW - 1))) * 64 + lane);
+      ab_sh[i] = tr == PR_XT ? 4u * PR_SLOTS : 4u * (unsigned)(tr >> 2);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) rbs[i][r] = 0.f;
+    }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      const int j = 2 * g + s - A.rc_D;
+      hok[s] = j >= 0 && j < A.rc_U;
+      hoff_m[s] = (unsigned)((hok[s] ? j : 0) * 16 + c16);
+      hoff_l[s] = (unsigned)((A.rc_U + (hok[s] ? j : 0)) * 16 + c16);
+    }
+  }
+  // the inputs of step (c, c + 1): requested with the B operand's loads, a step ahead; an odd range's last step has no
+  // second chunk: zeros -- a zero nibble makes the tile zero
+  __device__ __forceinline__ void fetch(const DwArgs& A, int l, int c, bool second) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const bool live = h == 0 || second;
+      const float* hb = A.gT[l + 1] + (size_t)(c + h) * hblk;
+      const unsigned* ap = A.rc_abits + (size_t)(c + h) * (PR_NW * 64);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        hgm[h][s] = (live && hok[s]) ? hb[hoff_m[s]] : 0.f;
+        hgl[h][s] = (live && hok[s]) ? hb[hoff_l[s]] : 0.f;
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) abw[h][i] = live ? ap[ab_off[i]] : 0u;
+    }
+  }
+  // the sweep's head_adjoint on this wave's tiles -> the A planes `sa` of a stage: B fragments of the two chunks, per
+  // (chunk, tile) the pack's block 0 x the means' fragment, then block 1 x the log-stds', in one accumulator chain; x the
+  // nibble's multipliers.  (Waves 5 .. 7 own one tile: their second chain repeats the first and is dropped.)
+  __device__ __forceinline__ void stage(unsigned short* sa, float inv_keep, int lane) {
+    const int g = lane >> 4, c16 = lane & 15;
+    f32x4 bf[2][2], dl[2][2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { PR_HEAD_BFRAGS(hgm[h], hgl[h], bf[h]) }
+    pr_mfma_open();
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) pr_mfma0<false, false, true>(dl[h][i], hw[i][0], bf[h][0]);
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int i = 0; i < 2; ++i) pr_mfma<false, false, true>(dl[h][i], hw[i][1], bf[h][1]);
+    asm volatile("s_nop 7\n\ts_nop 7" : "+v"(dl[0][0]), "+v"(dl[0][1]), "+v"(dl[1][0]), "+v"(dl[1][1]));
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (i == 0 || two) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          // (the product ROUNDED to fp32, as the sweep stashed it: pinned, or the compiler contracts it into the
+          //  subtractions and additions below)
+          f32x4 gq = dl[h][i] * pr_nibble_mult((abw[h][i] >> ab_sh[i]) & 15u, inv_keep);
+          asm volatile("" : "+v"(gq));
+          // bias gradient: this lane's row, chunk by chunk in the order of the range -- one fixed order; the rows are added
+          // up once, at the end (bias_out).  (In the classic form's order -- four rows of a quad summed per step -- it is
+          // the parent's bits and 80 more vector instructions a wave and step: 3 us of the kernel's 56 at the cart-pole shape.)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) rbs[i][r] += gq[r];
+          // put()'s arithmetic on the four features of this lane's row: k = 16 h + c16 of feature rows 4 g + r
+          pm_u32x2 pc[2];
+          pm_split4<2, false>(gq, pc);
+          unsigned short* q = sa + (row0 + 128 * i + 4 * g) * PM_DWW_LDK + 16 * h + c16;
+#pragma unroll
+          for (int pz = 0; pz < 2; ++pz, q += PM_DWL_F * PM_DWW_LDK) {
+            q[0] = (unsigned short)(pc[pz][0] & 0xffffu);
+            q[PM_DWW_LDK] = (unsigned short)(pc[pz][0] >> 16);
+            q[2 * PM_DWW_LDK] = (unsigned short)(pc[pz][1] & 0xffffu);
+            q[3 * PM_DWW_LDK] = (unsigned short)(pc[pz][1] >> 16);
+          }
+        }
+      }
+  }
+  // bias gradient of the range: the sixteen rows of a lane group, a four-level tree in a fixed order
+  __device__ __forceinline__ void bias_out(float* pb, int O, int lane, bool add) {
+    const int g = lane >> 4, c16 = lane & 15;
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+      if (i == 0 || two) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          float v = rbs[i][r];
+          v += __shfl_xor(v, 1);
+          v += __shfl_xor(v, 2);
+          v += __shfl_xor(v, 4);
+          v += __shfl_xor(v, 8);
+          const int o = row0 + 128 * i + 4 * g + r;
+          if (c16 == 0 && o < O) pm_dw_put(pb + o, v, add);
+        }
+      }
+  }
+};
+template <bool RC>
+__device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
   extern __shared__ __attribute__((aligned(16))) unsigned short dww_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -978,10 +1120,16 @@ __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A
   const float* gbase = A.gT[l];
   const float* abase = A.actT[l];
   const size_t gblk = (size_t)Fo16 * A.Rw, ablk = (size_t)Fi16 * A.Rw;
-  f32x4 ra[PM_DWL_Q], rb[PM_DWL_Q];
-  float bs[PM_DWL_Q];
+  f32x4 rb[PM_DWL_Q];
+  // the delta operand: fetched (the classic form's raw quads, their offsets, the bias sums) or rebuilt -- one of the two
+  // states, the other an empty struct
+  std::conditional_t<RC, PmDwNone, PmDwFetched> cl;
+  std::conditional_t<RC, PmDwRc, PmDwNone> rc;
+  if constexpr (RC) rc.init(A, l, wid, lane);
+  else {
 #pragma unroll
-  for (int j = 0; j < PM_DWL_Q; ++j) bs[j] = 0.f;
+    for (int j = 0; j < PM_DWL_Q; ++j) cl.bs[j] = 0.f;
+  }
   auto fetch1 = [&](f32x4& dst, const float* base, size_t blk, int F16, int idx, int c, bool second) {
     const int f = idx >> 3, kq = idx & 7;
     const float* p;
@@ -1001,27 +1149,30 @@ __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A
   // instructions and a branch per load, eight loads a thread and step (as in pm_dw_wide_kernel).
   const bool pow2 = (A.RT & (A.RT - 1)) == 0;
   const int rt_sh = A.RT >= 4 ? 2 : (A.RT >= 2 ? 1 : 0);
-  unsigned offA[PM_DWL_Q], offB[PM_DWL_Q];
+  unsigned offB[PM_DWL_Q];
 #pragma unroll
   for (int j = 0; j < PM_DWL_Q; ++j) {
     const int idx = tid + PM_DW_NT * j, f = idx >> 3, kq = idx & 7;
     const int fa = min(f, Fo16 - 1), fb = min(f, Fi16 - 1);
     if (A.RT >= 2) {
-      offA[j] = (unsigned)(fa * A.Rw + kq * 4);
+      if constexpr (!RC) cl.offA[j] = (unsigned)(fa * A.Rw + kq * 4);
       offB[j] = (unsigned)(fb * A.Rw + kq * 4);
     } else {
-      offA[j] = (unsigned)((kq >> 2) * (int)gblk + fa * 16 + (kq & 3) * 4);
+      if constexpr (!RC) cl.offA[j] = (unsigned)((kq >> 2) * (int)gblk + fa * 16 + (kq & 3) * 4);
       offB[j] = (unsigned)((kq >> 2) * (int)ablk + fb * 16 + (kq & 3) * 4);
     }
   }
   auto fetch = [&](int c) {
     const bool second = c + 1 < R.c_hi;
+    if constexpr (RC) rc.fetch(A, l, c, second);
     if (second && pow2) {
       const int b = A.RT >= 2 ? c >> rt_sh : c, rt = A.RT >= 2 ? (c & (A.RT - 1)) : 0;
       const float* pg = gbase + (size_t)b * gblk + rt * 16;
       const float* pa = abase + (size_t)b * ablk + rt * 16;
+      if constexpr (!RC) {
 #pragma unroll
-      for (int j = 0; j < PM_DWL_Q; ++j) ra[j] = *reinterpret_cast<const f32x4*>(pg + offA[j]);
+        for (int j = 0; j < PM_DWL_Q; ++j) cl.ra[j] = *reinterpret_cast<const f32x4*>(pg + cl.offA[j]);
+      }
 #pragma unroll
       for (int j = 0; j < PM_DWL_Q; ++j) rb[j] = *reinterpret_cast<const f32x4*>(pa + offB[j]);
       return;
@@ -1029,7 +1180,7 @@ __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A
 #pragma unroll
     for (int j = 0; j < PM_DWL_Q; ++j) {
       const int idx = tid + PM_DW_NT * j;      // (idx >= 13 * 16 * 8: feature >= 208 >= F16 -> zeros, never staged)
-      fetch1(ra[j], gbase, gblk, Fo16, idx, c, second);
+      if constexpr (!RC) fetch1(cl.ra[j], gbase, gblk, Fo16, idx, c, second);
       fetch1(rb[j], abase, ablk, Fi16, idx, c, second);
     }
   };
@@ -1048,11 +1199,12 @@ __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A
     for (int j = 0; j < PM_DWL_Q; ++j) {
       const int idx = tid + PM_DW_NT * j;
       if (idx < PM_DWL_F * 8) {
-        put(sa, idx >> 3, idx & 7, ra[j]);
+        if constexpr (!RC) put(sa, idx >> 3, idx & 7, cl.ra[j]);
         put(sb, idx >> 3, idx & 7, rb[j]);
-        bs[j] += (ra[j][0] + ra[j][1]) + (ra[j][2] + ra[j][3]);
+        if constexpr (!RC) cl.bs[j] += (cl.ra[j][0] + cl.ra[j][1]) + (cl.ra[j][2] + cl.ra[j][3]);
       }
     }
+    if constexpr (RC) rc.stage(sa, A.rc_inv_keep, lane);
   };
   f32x4 acc[2][PM_DWL_NT];
 #pragma unroll
@@ -1138,14 +1290,20 @@ __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A
       __syncthreads();
     }
   }
-  // bias gradient: the eight threads that staged one delta feature hold its partial row sums
+  if constexpr (RC) {
+    rc.bias_out(part + A.b_off[l], O, lane, R.add);
+  } else {
+    // bias gradient: the eight threads that staged one delta feature hold its partial row sums
 #pragma unroll
-  for (int j = 0; j < PM_DWL_Q; ++j) {
-    float v = bs[j];
-    v += __shfl_xor(v, 1);
-    v += __shfl_xor(v, 2);
-    v += __shfl_xor(v, 4);
-    const int idx = tid + PM_DW_NT * j, o = idx >> 3;
-    if ((idx & 7) == 0 && o < O) pm_dw_put(part + A.b_off[l] + o, v, R.add);
+    for (int j = 0; j < PM_DWL_Q; ++j) {
+      float v = cl.bs[j];
+      v += __shfl_xor(v, 1);
+      v += __shfl_xor(v, 2);
+      v += __shfl_xor(v, 4);
+      const int idx = tid + PM_DW_NT * j, o = idx >> 3;
+      if ((idx & 7) == 0 && o < O) pm_dw_put(part + A.b_off[l] + o, v, R.add);
+    }
   }
 }
+__global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A, int l) { pm_dw_layer_body<false>(A, l); }
+__global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_rc_kernel(const DwArgs A, int l) { pm_dw_layer_body<true>(A, l); }

@@ -128,6 +128,9 @@ struct pmbrl_plan {
   size_t off_reg_ab[2][2];   // its activity words [net][hidden layer]: [step][workgroup][wave][lane] x 32 bits (pmbrl_reg.h)
   int abits_packed;      // the last forward call left the activity bits in that form only (pm_reg_unpack_abits: -> NetPlan::abits)
   int old_pack_stale;    // the last forward call packed the register-resident family's weights only
+  int dw_g1_rebuilt;     // the latest adjoint call's sweep ran on this family over its own forward stashes: gT[1] is NOT written,
+                         // that call's dW GEMM rebuilds the operand (dw_call_args hands it the inputs: DwArgs::rc_abits; a note for the record
+                         // a replayed call leaves behind, as abits_packed is -- the launches read DwArgs)
   // Replay (pmbrl_plan_set_replay): a call whose arguments equal the previous call's is recorded as a hipGraph the second
   // time it is seen and launched as one graph from then on.  Slot 0: pmbrl_rollout_fwd, slot 1: pmbrl_rollout_bwd(_adam).
   int replay;            // 0 off, 1 the one-launch-per-step forms, 2 every form
@@ -255,6 +258,8 @@ struct ZtabArgs;   // (pmbrl_mm.h: the noise table of split moment-matching grou
 void pm_reg_pack_launch(const pmbrl_plan* p, char* ws, const float* pol_params, const float* dyn_params, int* wflag, int gen,
                         hipStream_t s, int* status_reset, const ZtabArgs* ztab);
 void pm_reg_unpack_abits(const pmbrl_plan* p, char* ws, hipStream_t s);
+#define PM_REG_DW_LAYER 1      // the policy layer whose delta the family's adjoint does not stash: the second hidden one (200 x 200)
+void pm_reg_dw_rebuild_args(const pmbrl_plan* p, char* ws, DwArgs& W);   // what pm_dw_layer_rc_kernel reads of the family's workspace
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,
                    hipStream_t s, bool fwd);
 // the sweep kernels' instance tables, one per object (pmbrl_instances.h; pmbrl.hip holds the general family's in exact fp32)

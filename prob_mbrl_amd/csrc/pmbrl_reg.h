@@ -32,17 +32,13 @@
 #include <utility>
 #include "pmbrl_dev.h"
 #include "pmbrl_split.h"
+#include "pmbrl_reg_head.h"      // PR_NW, PR_SLOTS, PR_XT, PR_FRAG, pr_xwave, the inline-asm MFMAs, the head adjoint's fragments
 #include "pmbrl_reg_mm.h"
 
-#define PR_NW 4                 // waves per workgroup: one per SIMD
 #define PR_NTHR (PR_NW * 64)
 #define PR_NT 13                // output tiles of a hidden layer (hidden width 193 .. 208: net_plan, nt = (width + 15) / 16)
 #define PR_KB 7                 // K32 blocks of a hidden width
-#define PR_SLOTS 3              // register-resident tiles per wave and hidden->hidden layer: tile 4 s + w
-#define PR_XT 12                // the tile that lives in LDS (run by wave pr_xwave(net))
-#define PR_FRAG 256             // floats of one fragment (64 lanes x 16 bytes)
 #define PM_GLOBAL_ __attribute__((address_space(1)))
-typedef unsigned pr_u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // floats of the packed sections of ONE network and direction (pm_reg_pack_kernel writes them, the sweeps read them)
@@ -58,9 +54,6 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #define PR_OFF_HEAD (PR_RES_FLOATS + PR_XT_FLOATS + PR_L0P_FLOATS)
 // the whole packed buffer: [direction (0 forward, 1 adjoint)][net (0 policy, 1 dynamics)][PR_NET_FLOATS]
 #define PR_PACK_FLOATS (4 * PR_NET_FLOATS)
-
-// the wave that runs the LDS-resident tile of a network (two different ones: they balance over a step)
-__host__ __device__ constexpr int pr_xwave(int net) { return net; }
 
 // LDS map (floats)
 #define PR_LDS_ACT 0                                   // [kb][piece][lane][4]: hidden activations as B fragments
@@ -339,44 +332,6 @@ __global__ __launch_bounds__(256) void pm_reg_pack_kernel(const RegPackArgs P) {
   }
 }
 
-// ---------------------------------------------------------------------------
-// MFMA with the A operand (weights) in the accumulator file or in a VGPR.  Inline asm: the compiler schedules the
-// statement as one opaque instruction and pads nothing around it -- pr_mfma_fence() supplies the wait states
-// between a chain's last MFMA and the first VALU read of its accumulator (8-pass XDL: 12 states), pr_mfma_open()
-// those between a VALU write of an operand and the first MFMA of a group.
-// ---------------------------------------------------------------------------
-// NOP: two wait states in front of the instruction, INSIDE the statement.  A VGPR written by a VALU instruction may
-// not be read as an MFMA operand in the next two issue slots (hipcc pads that for its own MFMAs, not for asm), and
-// the compiler is free to schedule the VALU that builds an operand -- a cvt_pk of a fragment -- right in front of
-// the statement that consumes it: measured as garbage head / tail products before this was here.  The big hidden
-// layers need none (B operands come from ds_read, weights from the prologue).
-template <bool F16, bool AG, bool NOP = false>
-__device__ __forceinline__ void pr_mfma(f32x4& acc, const f32x4& w, const f32x4& b) {
-  if constexpr (NOP) {
-    if constexpr (F16) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
-    else asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
-  } else if constexpr (F16) {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
-  } else {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
-  }
-}
-// first product of a chain: C = 0 (inline constant), the accumulator is a pure output
-template <bool F16, bool AG, bool NOP = false>
-__device__ __forceinline__ void pr_mfma0(f32x4& acc, const f32x4& w, const f32x4& b) {
-  if constexpr (NOP) {
-    if constexpr (F16) asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(b));
-    else asm volatile("s_nop 1\n\tv_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(b));
-  } else if constexpr (F16) {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(b));
-  } else {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "a"(w), "v"(b));
-    else asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, 0" : "=&v"(acc) : "v"(w), "v"(b));
-  }
-}
 // Workgroup barrier that waits for this wave's LDS traffic only.  __syncthreads() also drains vmcnt: every stash store of
 // the phase would be waited for at every barrier of the horizon loop, and nothing a barrier orders here goes through
 // global memory.
@@ -423,8 +378,6 @@ __device__ __forceinline__ void pr_aload4_b8(unsigned (&d)[4], const pr_i32x4& s
                : "v"(voff), "s"(srd), "s"(s0), "s"(s1), "s"(s2), "s"(s3)
                : "memory");
 }
-__device__ __forceinline__ void pr_mfma_open() { asm volatile("s_nop 3"); }
-__device__ __forceinline__ void pr_mfma_fence() { asm volatile("s_nop 7\n\ts_nop 7"); }
 
 // Register-resident weights of one sweep direction: both networks' hidden->hidden layers, PR_SLOTS tiles per wave
 // and network, PR_KB blocks x 2 pieces each = 84 fragments.  The first 64 go to the accumulator file ("a": all 256
@@ -1244,7 +1197,6 @@ __global__ __launch_bounds__(PR_NTHR, 1) void pm_reg_bwd_kernel(const RegArgs A)
   const unsigned x_step = (unsigned)B * D * 4u, a_step = (unsigned)B * U * 4u;
   const int st_step = A.nwg * (PR_NT * 1024), st_step2 = A.nwg * 1024;
   int so_g0 = (int)A.gT[0] + ((T1 - 1) * A.nwg + wg) * (PR_NT * 1024);
-  int so_g1 = (int)A.gT[1] + ((T1 - 1) * A.nwg + wg) * (PR_NT * 1024);
   int so_g2 = (int)A.gT[2] + ((T1 - 1) * A.nwg + wg) * 1024;
 
   // ---- per-row inputs of a step, staged through LDS.  The 16 rows of a step need dL/dr~, the reward Jacobian Jx | Ja,
@@ -1328,25 +1280,15 @@ __global__ __launch_bounds__(PR_NTHR, 1) void pm_reg_bwd_kernel(const RegArgs A)
   };
 
   // head adjoint of network NET: inputs gm (x the means' rows), gl (x the log-stds' rows) of the lane's two slots;
-  // result x activity of the second hidden layer -> LDS (+ stash)
-  auto head_adjoint = [&](auto netc, const float (&gm)[2], const float (&gl)[2], const unsigned abw, int so_st) {
+  // result x activity of the second hidden layer -> LDS.  The policy's (delta of its second hidden layer) is NOT stashed:
+  // the dW GEMM of that layer rebuilds it from the head-gradient stash gT[2], the activity words and the pack's PR_OFF_L0
+  // section with the same two MFMAs on the same fragments (pmbrl_dw_kernels.h, the RC form of pm_dw_layer_kernel) --
+  // 80 MB less written here and read there at the cart-pole shape
+  auto head_adjoint = [&](auto netc, const float (&gm)[2], const float (&gl)[2], const unsigned abw) {
     constexpr int NET = decltype(netc)::value;
     // B fragments: slots 3 s + {0, 1, 2} = g.hi, g.lo, g.hi
     f32x4 bf[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      unsigned short hh[2], hl[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const float v = k == 0 ? gm[s] : gl[s];
-        const unsigned a = pm_pk_bf16(v, 0.f) & 0xffffu;
-        hh[s] = (unsigned short)a;
-        hl[s] = (unsigned short)(pm_pk_bf16(v - pm_bf_lo(a), 0.f) & 0xffffu);
-      }
-      const pr_u32x4 u = {(unsigned)hh[0] | ((unsigned)hl[0] << 16), (unsigned)hh[0] | ((unsigned)hh[1] << 16),
-                          (unsigned)hl[1] | ((unsigned)hh[1] << 16), 0u};
-      bf[k] = __builtin_bit_cast(f32x4, u);
-    }
+    PR_HEAD_BFRAGS(gm, gl, bf)
     const float* l0w = smem + PRB_LDS_L0(NET) + lane * 4;
     const bool xw = NET == 0 ? xw_pol : xw_dyn;
     f32x4 acc[PR_SLOTS + 1], wf[PR_SLOTS + 1][2], mfv[PR_SLOTS + 1];
@@ -1375,11 +1317,6 @@ __global__ __launch_bounds__(PR_NTHR, 1) void pm_reg_bwd_kernel(const RegArgs A)
       float* dst = act_w + (size_t)((ot >> 1) * 2) * PR_FRAG + 2 * (ot & 1);
       *reinterpret_cast<pm_u32x2*>(dst) = pc[0];
       *reinterpret_cast<pm_u32x2*>(dst + PR_FRAG) = pc[1];
-      if constexpr (NET == 0) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          PR_EXP_STASH(__builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(gq[r]), srd, lane_st + r * 64, pr_uni(so_st + ot * 1024), 0);)
-      }
     };
     pr_for<PR_SLOTS>([&](auto qc) {
       constexpr int q = decltype(qc)::value;
@@ -1536,7 +1473,7 @@ __global__ __launch_bounds__(PR_NTHR, 1) void pm_reg_bwd_kernel(const RegArgs A)
       gm[s] = gg * c_sy[s];
       gl[s] = gg * In.td[s];
     }
-    head_adjoint(std::integral_constant<int, 1>{}, gm, gl, abc[0], 0);
+    head_adjoint(std::integral_constant<int, 1>{}, gm, gl, abc[0]);
     pr_barrier();
     if (PROF && wg == 0 && tid == 0) A.prof[(size_t)t * 32 + 1] = (long long)__builtin_readcyclecounter();
     f32x4 o;
@@ -1571,30 +1508,31 @@ __global__ __launch_bounds__(PR_NTHR, 1) void pm_reg_bwd_kernel(const RegArgs A)
     } else if (wid == 3) {
       for (int k = 2 * U * 16 + lane; k < 256; k += 64) __builtin_amdgcn_raw_buffer_store_b32(0u, srd, k * 4, pr_uni(so_g2), 0);
     }
-    head_adjoint(std::integral_constant<int, 0>{}, pm_, pl_, abc[2], so_g1);
+    head_adjoint(std::integral_constant<int, 0>{}, pm_, pl_, abc[2]);
     pr_barrier();
     if (PROF && wg == 0 && tid == 0) A.prof[(size_t)t * 32 + 3] = (long long)__builtin_readcyclecounter();
     // (between the step's third and fourth barrier: every lane has read this step's inputs, none reads the next one's
-    //  before the fourth.  Behind the two staged loads: the 4 activity-word loads and at least the 12 stash stores of the
-    //  policy's head adjoint)
+    //  before the fourth.  Behind the two staged loads EVERY wave has issued the 4 activity-word loads and nothing else it
+    //  can count on: the dynamics model stashes nothing, the policy's head adjoint no longer does (its 12 stores made this
+    //  16), and the head-gradient stores in between are wave 2's and wave 3's alone, a number that depends on U -- so 4.
+    //  No PR_EXP_NOSTASH variant here, unlike ab_landed below, and on purpose: this count holds loads only, and the
+    //  activity-word loads are not under PR_EXP_STASH; ab_landed counts the first layer's stores, which are)
     hidden_adjoint_and_tail(std::integral_constant<int, 0>{}, abc[3], so_g0, o, [&]() {
-#ifdef PR_EXP_NOSTASH
-      stage_landed(std::integral_constant<int, 0>{}, sv);
-#else
-      stage_landed(std::integral_constant<int, 16>{}, sv);
-#endif
+      stage_landed(std::integral_constant<int, 4>{}, sv);
       stage_park();
     });
     if (PROF && wg == 0 && tid == 0) A.prof[(size_t)t * 32 + 4] = (long long)__builtin_readcyclecounter();
 #pragma unroll
     for (int s = 0; s < 2; ++s) gx[s] = ok_x[s] ? gxn[s] + o[2 * s] : 0.f;
-    so_g0 -= st_step; so_g1 -= st_step; so_g2 -= st_step2;
-    // the next step's activity words: requested a step ago; behind them this step issued at least the 24 stash stores of
-    // the policy's two hidden layers (3 tiles x 4 registers each, every wave)
+    so_g0 -= st_step; so_g2 -= st_step2;
+    // the next step's activity words: requested a step ago; behind them this step issued at least the 12 stash stores of
+    // the policy's first hidden layer (3 tiles x 4 registers, every wave; 16 on the wave that also runs tile 12).  The
+    // second hidden layer's 12 are gone with its stash (they made this 24), wave 2's / wave 3's head-gradient stores are
+    // not every wave's.  A count above what a wave really issued would read a word whose load has not landed.
 #ifdef PR_EXP_NOSTASH
     ab_landed(std::integral_constant<int, 0>{}, abn);
 #else
-    ab_landed(std::integral_constant<int, 24>{}, abn);
+    ab_landed(std::integral_constant<int, 12>{}, abn);
 #endif
 #pragma unroll
     for (int k = 0; k < 4; ++k) abc[k] = abn[k];

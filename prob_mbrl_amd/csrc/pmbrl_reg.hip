@@ -136,6 +136,9 @@ static void reg_args(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const 
 bool pm_reg_can_run(const pmbrl_plan* p, const RolloutArgs& A, bool fwd) {
   if (!p->reg || (A.mm_mode != 0) != (p->reg_mm != 0)) return false;
   if (!fwd && !p->sw.reg_bwd) return false;
+  // (the adjoint sweep stashes no delta of the policy's second hidden layer: only behind the whole-layer dW kernel,
+  //  which rebuilds it -- PMBRL_DW_NO_WIDE sends the adjoint to the other family)
+  if (!fwd && p->dw_layer13 != PM_REG_DW_LAYER) return false;
   const bool ext = A.grad_states || A.grad_actions || A.agn || A.zpol_ss != 0 || A.zdyn_ss != 0 ||
                    (((A.flags & PMBRL_FLAG_MM_STATES) != 0) != (p->reg_mm != 0)) || A.t0 != 0 || A.t1 != A.H || A.gx_from_carry;
   if (p->reg_mm && p->mm_parts > 1 && !A.xch) return false;
@@ -177,6 +180,16 @@ void pm_reg_unpack_abits(const pmbrl_plan* p, char* ws, hipStream_t s) {
       U.dst[n][l] = reinterpret_cast<unsigned char*>(ws + nets[n]->abits[l]);
     }
   hipLaunchKernelGGL(pm_reg_unpack_abits_kernel, dim3(p->nwg, p->cfg.H), dim3(PR_NTHR), 0, s, U);
+}
+
+// the dW GEMM of the policy's second hidden layer behind this family's adjoint sweep rebuilds the delta the sweep does not
+// stash (pmbrl_dw_kernels.h, pm_dw_layer_rc_kernel): the activity words of that layer, the transposed head weights of the
+// adjoint pack (direction 1, policy), the dropout's 1 / keep
+void pm_reg_dw_rebuild_args(const pmbrl_plan* p, char* ws, DwArgs& W) {
+  W.rc_abits = reinterpret_cast<const unsigned*>(ws + p->off_reg_ab[0][1]);
+  W.rc_head = reinterpret_cast<const float*>(ws + p->off_reg_pack) + (size_t)2 * PR_NET_FLOATS + PR_OFF_L0;
+  W.rc_D = p->cfg.D;
+  W.rc_U = p->cfg.U;
 }
 
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,
