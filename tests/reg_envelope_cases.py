@@ -15,6 +15,7 @@ import torch
 
 from oracle import ref_torch as R
 from prob_mbrl_amd import problem as PB
+from tests.common import rel  # noqa: F401  (the envelope tests use it through this module too)
 
 # the project's bars (tests/test_gpu_kernels.py: TOL_TRAJ, TOL_GRAD)
 TOL_TRAJ = 2e-5
@@ -218,11 +219,6 @@ def split_drift(o):
     o['drift'] = o['states'][..., DRIFT_DIM]
     o['states'] = o['states'][..., keep]
     return o
-
-
-def rel(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
 
 
 def param_slices(d):

@@ -1,22 +1,22 @@
-"""CPU: the fp64 oracle for Tanh / SiLU hidden layers (tests/act_oracle.py) against the reference's own fp32 and fp64
+"""CPU: the fp64 oracle (oracle/ref_torch.py) on Tanh / SiLU hidden layers -- the activation is the `act` entry of a
+network's dict, filled from the fixture's pol_act / dyn_act / val_act / act -- against the reference's own fp32 and fp64
 outputs recorded in tests/golden/activations/ (tools/make_golden_activations.py); the Python layer's parsing of the
 activation and its refusals, which need no device."""
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from tests import act_oracle as AO
+from oracle import ref_torch
+from tests import common
+from tests.common import rel
 
 
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-300))
-
-
-@pytest.mark.parametrize('name', AO.ITER)
+@pytest.mark.parametrize('name', common.ACT_ITER)
 def test_oracle_reproduces_reference(name):
-    d = AO.load(name)
-    loss, g, (S, A, R) = AO.iteration(d)
+    d = common.load(name)
+    loss, g, (S, A, R) = common.oracle_iteration(d)
     states, rewards = torch.stack(S).detach().numpy(), torch.stack(R).detach().numpy()
     # the 1e-6 of tests/test_oracle_golden.py against the reference's fp64 run
     assert rel(states, d['ref64_states']) < 1e-6
@@ -25,20 +25,20 @@ def test_oracle_reproduces_reference(name):
     assert abs(float(loss) - float(d['ref64_loss'])) <= 1e-6 * abs(float(d['ref64_loss']))
     assert rel(g.numpy(), d['ref64_grad']) < 1e-6
     if name == 'act_tanh_sat':      # what the fixture is for: pre-activations of 50 and beyond
-        assert AO.dyn_first_layer_max(d, [s.detach() for s in S], [a.detach() for a in A]) >= 50.0
+        assert common.dyn_first_layer_max(d, [s.detach() for s in S], [a.detach() for a in A]) >= 50.0
 
 
-@pytest.mark.parametrize('name', AO.MCP)
+@pytest.mark.parametrize('name', common.ACT_MCP)
 def test_oracle_first_mc_pilco_loss(name):
-    d = AO.load(name)
-    loss, _, _ = AO.iteration(d, with_value=True, cvar_eps=float(d['mcp_cvar_eps']), reg_weight=float(d['mcp_reg_weight']))
+    d = common.load(name)
+    loss, _, _ = common.oracle_iteration(d, with_value=True, cvar_eps=float(d['mcp_cvar_eps']), reg_weight=float(d['mcp_reg_weight']))
     assert abs(float(loss) - float(d['ref32_mcp_losses'][0])) <= 2e-6 * abs(float(d['ref32_mcp_losses'][0]))
 
 
-@pytest.mark.parametrize('name', AO.BNN)
+@pytest.mark.parametrize('name', common.ACT_BNN)
 def test_oracle_bnn_training(name):
-    d = AO.load(name)
-    params, losses, g0 = AO.bnn_train(d)
+    d = common.load(name)
+    params, losses, g0 = ref_torch.bnn_train(d, torch.float64)
     assert np.allclose(np.asarray(losses), d['losses'], rtol=1e-5, atol=1e-7)
     nl = int(d['n_layers'])
     k = 0
@@ -48,11 +48,11 @@ def test_oracle_bnn_training(name):
 
 
 def test_fixtures_hold_numeric_arrays_only():
-    import os
-    names = sorted(f[:-4] for f in os.listdir(AO.GOLDEN) if f.endswith('.npz'))
-    assert set(names) == set(AO.ITER + AO.MCP + AO.BNN)
+    golden = os.path.join(common.GOLDEN, 'activations')
+    names = sorted(f[:-4] for f in os.listdir(golden) if f.endswith('.npz'))
+    assert set(names) == set(common.ACT_ITER + common.ACT_MCP + common.ACT_BNN)
     for name in names:
-        raw = np.load(os.path.join(AO.GOLDEN, name + '.npz'), allow_pickle=False)
+        raw = np.load(os.path.join(golden, name + '.npz'), allow_pickle=False)
         for k in raw.files:
             assert raw[k].dtype.kind in 'biufU', (name, k, raw[k].dtype)     # (U: the reward's kind, a name)
 

@@ -5,7 +5,6 @@ the HIP kernels, which need a GPU -- scaled by 1/B_global with the global cyclic
 index, and ONE sum all-reduce reproduces the full-batch gradient.  The device-side twin
 is tests/test_gpu_kernels.py::test_sharded_rows_reproduce_full_gradient."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,14 +13,6 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from tests import common
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _worker(rank, world, port, name, out):
@@ -55,7 +46,7 @@ def test_two_rank_shards_allreduce_to_full_gradient(name):
     world = 2
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_worker, args=(r, world, port, name, out)) for r in range(world)]
     for p in procs:
         p.start()
@@ -106,7 +97,7 @@ def test_ints_over_ranks_min_and_max_on_two_gloo_ranks():
     world = 2
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_ints_worker, args=(r, world, port, out)) for r in range(world)]
     for p in procs:
         p.start()

@@ -11,11 +11,6 @@ pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
 
-def _flat_grad(pol):
-    lins = [m for m in pol.model._modules.values() if isinstance(m, torch.nn.Linear)]
-    return torch.cat([t.grad.reshape(-1) for l in lins for t in (l.weight, l.bias)]).cpu().numpy()
-
-
 def test_rollout_resamples_masks_every_step(monkeypatch):
     """rollout(resample_model=True, resample_policy=True): new dropout masks at every step
     (utils/rollout.py:95-98,110-115).  Fixture from the reference's own rollout, whose draws were
@@ -48,7 +43,7 @@ def test_rollout_resamples_masks_every_step(monkeypatch):
     loss.backward()
     assert common.rel(torch.stack(states).detach().cpu().numpy(), d['ref64_states']) < 2e-5
     assert abs(float(loss) - float(d['ref64_loss'])) <= 2e-5 * abs(float(d['ref64_loss']))
-    assert common.rel(_flat_grad(pol), d['ref64_grad']) < 1e-4
+    assert common.rel(common.flat_grad(pol), d['ref64_grad']) < 1e-4
     monkeypatch.undo()
     # and with the modules' own draws: runs, finite, different masks at different steps
     s2, _, _ = pm.utils.rollout(x0, dyn, pol, H, resample_model=True, resample_policy=True)
@@ -114,7 +109,7 @@ def test_rollout_autograd_matches_reference(name):
     loss.backward()
     assert common.rel(torch.stack(states).detach().cpu().numpy(), d['ref64_states']) < 2e-5
     assert abs(float(loss) - float(d['ref64_loss'])) <= 2e-5 * abs(float(d['ref64_loss']))
-    assert common.rel(_flat_grad(pol), d['ref64_grad']) < 1e-4
+    assert common.rel(common.flat_grad(pol), d['ref64_grad']) < 1e-4
     # frozen buffers were used, not redrawn
     assert torch.equal(pol.model.fc_nonlin.z.cpu(), torch.tensor(d['pol_z']))
 
@@ -153,33 +148,18 @@ def test_mc_pilco_matches_reference_iterations(name):
         assert (n, n) in deltas, deltas
     lins = [m for m in pol.model._modules.values() if isinstance(m, torch.nn.Linear)]
     final = torch.cat([t.detach().reshape(-1) for l in lins for t in (l.weight, l.bias)]).cpu().numpy()
-    # Adam divides by |g_i|: an element whose gradient is tiny against the gradient's rms moves by up to lr per step on
-    # the SIGN of rounding noise -- in any fp32-class arithmetic, the reference's own included.  The bar per element is
-    # the north star's 1e-4 (of the gradient's rms) pushed through Adam's normalisation: n lr eps_g / (|g_i| + eps),
-    # capped at n lr; |g_i| from the reference's second-moment estimate.  (The 32-unit fixtures never need the term:
-    # 2e-6 covers them; of the 41 602 parameters of the 2 x 200 policy a few dozen have |g_i| < 1e-3 rms.)
-    n_it, lr = int(d['mcp_n_iters']), float(d['mcp_lr'])
-    g_abs = np.sqrt(np.asarray(d['ref32_mcp_exp_avg_sq'], np.float64) / (1.0 - 0.999 ** n_it))
-    eps_g = 1e-4 * np.sqrt(np.mean(g_abs ** 2))
-    tol = 1e-4 * np.abs(d['ref32_mcp_final']) + 2e-6 + n_it * lr * np.minimum(1.0, eps_g / (g_abs + 1e-8))
-    err = np.abs(final.astype(np.float64) - d['ref32_mcp_final'])
+    # the per-element Adam bar and the update-cosine bar
+    from prob_mbrl_amd.problem import flat_params
+    err, g_abs, cos = common.assert_mcp_update(final, flat_params(d, 'pol'), d)      # (from the policy the fixture's run started from)
     plain = 1e-4 * np.abs(d['ref32_mcp_final']) + 2e-6
     print('%s: parameters beyond the plain bar %d of %d (worst %.2e at |g| = %.2e, gradient rms %.2e)' %
-          (name, int((err > plain).sum()), err.size, float(err.max()), float(g_abs[np.argmax(err)]), float(eps_g * 1e4)))
-    assert np.all(err <= tol), (int((err > tol).sum()), float((err - tol).max()), float(err.max()))
-    # FROZEN (round 6): these bars may only tighten.  The per-element bar above admits whatever Adam can reach for an element
-    # whose gradient is rounding noise; what guards against a systematic error is (a) the COUNT of elements beyond the plain
-    # bar -- a regression threshold, measured 0 in all seven fixtures on the round-6 build -- and (b) the update direction,
-    # a quantity rounding does not move: the cosine between this run's total parameter update and the reference's.
+          (name, int((err > plain).sum()), err.size, float(err.max()), float(g_abs[np.argmax(err)]),
+           float(np.sqrt(np.mean(g_abs ** 2)))))
+    print('%s: cosine of the total update 1 - %.2e' % (name, 1.0 - cos))
+    # FROZEN (round 6): may only tighten.  Beside the two bars above, what guards against a systematic error is the COUNT of
+    # elements beyond the plain bar -- a regression threshold, measured 0 in all seven fixtures on the round-6 build
     n_beyond = int((err > plain).sum())
     assert n_beyond <= (4 if err.size > 40000 else 0), n_beyond
-    from prob_mbrl_amd.problem import flat_params
-    init = flat_params(d, 'pol').astype(np.float64)          # the policy the fixture's run started from
-    upd = final.astype(np.float64) - init
-    upd_ref = np.asarray(d['ref32_mcp_final'], np.float64) - init
-    cos = float(upd @ upd_ref / (np.linalg.norm(upd) * np.linalg.norm(upd_ref)))
-    print('%s: cosine of the total update 1 - %.2e' % (name, 1.0 - cos))
-    assert cos > 1.0 - 1e-7, cos          # (measured: 1 - 6.3e-9 at worst, mcp_mm1)
     # Adam state is visible through the torch optimiser object (drop-in: same opt reused later)
     st = opt.state[lins[0].weight]
     assert int(st['step']) == int(d['mcp_n_iters'])
@@ -231,7 +211,7 @@ def test_rollout_truncated_horizon_matches_reference(monkeypatch):
     loss.backward()
     assert common.rel(torch.stack(states).detach().cpu().numpy(), d['ref64_states']) < 2e-5
     assert abs(float(loss) - float(d['ref64_loss'])) <= 2e-5 * abs(float(d['ref64_loss']))
-    g = _flat_grad(pol)
+    g = common.flat_grad(pol)
     assert np.all(np.isfinite(g)) and common.rel(g, d['ref64_grad']) < 1e-4
     # five steps or fewer: the reference re-raises (utils/rollout.py:155-157)
     monkeypatch.setattr(E.Engine, 'valid_steps', lambda self: 5)
@@ -481,7 +461,7 @@ def test_mixture_head_trains_and_rolls_out():
     loss = -torch.stack(rewards).sum(0).mean()
     pol.zero_grad()
     loss.backward()
-    g = _flat_grad(pol)
+    g = common.flat_grad(pol)
     assert np.isfinite(g).all() and np.abs(g).max() > 0
     # the Gumbel noise is frozen across rollouts, the component draws and the Gaussian noise are not
     s2, _, _ = pm.utils.rollout(x0, dyn, pol, H, resample_state_noise=False, resample_action_noise=False)
@@ -495,31 +475,6 @@ def test_mixture_head_trains_and_rolls_out():
     assert samples.shape == (64, D) and bool(torch.isfinite(samples).all())
 
 
-def _value_from_fixture(d):
-    """The critic of examples/deep_pilco_no_mm_with_value.py:269-278 (no output density,
-    concrete dropout, eval mode) holding the fixture's weights and masks."""
-    import prob_mbrl_amd as pm
-    n = int(d['val_n_layers'])
-    hid = [d['val_W%d' % i].shape[0] for i in range(n - 1)]
-    D = d['val_W0'].shape[1]
-    V = pm.models.Regressor(pm.models.mlp(
-        D, 1, hid, dropout_layers=[pm.models.CDropout(0.1 * np.ones(h)) for h in hid],
-        nonlin=torch.nn.ReLU)).float()
-    T = lambda a: torch.tensor(np.asarray(a, dtype=np.float32))  # noqa: E731
-    with torch.no_grad():
-        lins = [m for m in V.model._modules.values() if isinstance(m, torch.nn.Linear)]
-        for i, lin in enumerate(lins):
-            lin.weight.copy_(T(d['val_W%d' % i]))
-            lin.bias.copy_(T(d['val_b%d' % i]))
-        for i in range(n - 1):
-            dr = getattr(V.model, 'drop%d' % i)
-            dr.noise.data = torch.rand(d['val_mask%d' % i].shape)
-            dr.concrete_noise = T(d['val_mask%d' % i])
-        for k in ('mx', 'iSx', 'my', 'Sy'):
-            getattr(V, k).data = T(d['val_' + k]).reshape(1, -1)
-    return V.to(DEV).eval()
-
-
 def _flat_params(pol):
     lins = [m for m in pol.model._modules.values() if isinstance(m, torch.nn.Linear)]
     return torch.cat([t.detach().reshape(-1) for l in lins for t in (l.weight, l.bias)]).cpu().numpy()
@@ -531,7 +486,7 @@ def test_mc_pilco_value_bootstrap_matches_reference():
     import prob_mbrl_amd as pm
     d = common.load('ext_value')
     dyn, pol = common.modules_from_fixture(d, 'ext_value', DEV)
-    V = _value_from_fixture(d)
+    V = common.value_from_fixture(d, DEV)
     x0 = torch.tensor(d['x0'], device=DEV)
     # the critic alone: value and input gradient against the oracle
     from oracle import ref_torch as R
@@ -680,7 +635,7 @@ def test_mc_pilco_with_value_function_and_critic_hook():
     from prob_mbrl_amd.critic import update_value_function
     d = common.load('ext_value')
     dyn, pol = common.modules_from_fixture(d, 'ext_value', DEV)
-    V = _value_from_fixture(d)
+    V = common.value_from_fixture(d, DEV)
     optV = torch.optim.Adam(V.parameters(), 1e-3)
     opt = torch.optim.Adam(pol.parameters(), 1e-3)
     H = int(d['H'])

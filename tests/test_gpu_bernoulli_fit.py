@@ -1,6 +1,6 @@
 """GPU (-m gpu): fits of networks with fixed-rate Bernoulli dropout (BDropout), alone and mixed with concrete dropout and
 with layers that have none: pmbrl_bnn_loss_grad, pmbrl_bnn_train_steps, train_regressor and the critic fit against the
-reference's fixtures (tests/golden/bdropout, tools/make_golden_bdropout.py) and the fp64 oracle tests/bdrop_oracle.py.
+reference's fixtures (tests/golden/bdropout, tools/make_golden_bdropout.py) and the fp64 oracle (oracle/ref_torch.py).
 Bars: those of tests/test_gpu_activations.py::test_bnn_loss_grad_matches_reference / test_bnn_train_steps_matches_reference
 and of tests/test_gpu_api.py::test_critic_fit_matches_reference."""
 import ctypes
@@ -12,7 +12,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests import bdrop_oracle as BO
+from oracle import ref_torch as R
+from tests import common
+from tests.common import rel
 from tests.test_bernoulli_fit_oracle import STAT, binomial_moments, example_width_case
 
 pytestmark = pytest.mark.gpu
@@ -24,7 +26,7 @@ def keeps(d):
     """BnnStep's bernoulli_keep of a fixture: None, a float, or a tensor of the layer's width."""
     out = []
     for l in range(int(d['n_layers']) - 1):
-        k = np.asarray(d['keep%d' % l], np.float32) if int(d['kind%d' % l]) == BO.BERNOULLI else None
+        k = np.asarray(d['keep%d' % l], np.float32) if int(d['kind%d' % l]) == R.BERNOULLI else None
         out.append(None if k is None else (float(k[0]) if k.size == 1 else torch.tensor(k)))
     return out
 
@@ -35,16 +37,16 @@ def bnn_step(d, M, **kw):
     dims = [d['W0_init'].shape[1]] + [d['W%d_init' % l].shape[0] for l in range(nl)]
     kind = [int(d['kind%d' % l]) for l in range(nl - 1)]
     n_comp = int(d['n_components']) if 'n_components' in d else 0
-    return E.BnnStep(dims, [float(d['temp%d' % l]) if kind[l] == BO.CONCRETE else 0.0 for l in range(nl - 1)],
+    return E.BnnStep(dims, [float(d['temp%d' % l]) if kind[l] == R.CONCRETE else 0.0 for l in range(nl - 1)],
                      [float(d['reg_scale%d' % l]) if kind[l] else 0.0 for l in range(nl - 1)],
-                     [float(d['drop_reg%d' % l]) if kind[l] == BO.CONCRETE else 0.0 for l in range(nl - 1)], M, int(d['N']),
+                     [float(d['drop_reg%d' % l]) if kind[l] == R.CONCRETE else 0.0 for l in range(nl - 1)], M, int(d['N']),
                      float(d['reg_weight']), max_log_std=float(d['max_log_std']), device=torch.device(DEV),
                      loss_kind='gmm' if n_comp > 1 else 'nll', n_components=n_comp, act=int(d['act']),
                      bernoulli_keep=kw.get('bernoulli_keep', keeps(d)))
 
 
 def flat_params(d, suffix='_init'):
-    keys = BO.param_keys(d)
+    keys = R.fit_problem_from_npz(d)[3]
     parts = [T(d[k + suffix]).reshape(-1) for k in keys]
     return torch.cat(parts).contiguous(), keys, [p.numel() for p in parts]
 
@@ -54,10 +56,10 @@ def noise(d, it):
     us, bs = [], []
     for l in range(int(d['n_layers']) - 1):
         kind = int(d['kind%d' % l])
-        if kind == BO.NONE:
+        if kind == R.NONE:
             continue
         hard = T(d['hard%d_it%d' % (l, it)]).reshape(-1)
-        us.append(T(d['u%d_it%d' % (l, it)]).reshape(-1) if kind == BO.CONCRETE else torch.full_like(hard, 0.5))
+        us.append(T(d['u%d_it%d' % (l, it)]).reshape(-1) if kind == R.CONCRETE else torch.full_like(hard, 0.5))
         bs.append(1.0 - hard)
     return torch.cat(us).contiguous(), torch.cat(bs).contiguous()
 
@@ -85,26 +87,27 @@ def replay_loss_grad(d, want_losses, want_g0, want_final):
         assert np.allclose(loss.cpu().numpy(), want_losses[it], rtol=3e-5, atol=2e-6), (it, loss, want_losses[it])
         if it == 0:
             for key, g in blocks(grad, keys, sizes):
-                print(key, BO.rel(g, want_g0[key]))
-                assert BO.rel(g, want_g0[key]) < 5e-5, key
+                want = np.asarray(want_g0[key]).reshape(-1)
+                print(key, rel(g, want))
+                assert rel(g, want) < 5e-5, key
         E.clip_adam(flat, grad, m, v, it + 1, float(d['lr']), max_norm=None)
     for key, p in blocks(flat, keys, sizes):
         assert np.allclose(p, np.asarray(want_final[key]).reshape(-1), rtol=2e-5, atol=5e-7), (key, np.abs(p - np.asarray(want_final[key]).reshape(-1)).max())
 
 
-@pytest.mark.parametrize('name', BO.FIT)
+@pytest.mark.parametrize('name', common.BD_FIT)
 def test_loss_grad_matches_reference(name):
     """pmbrl_bnn_loss_grad + pmbrl_clip_adam replaying every nll / mixture fixture (a plan per minibatch size: the third
     minibatch of an epoch is short)."""
-    d = BO.load(name)
-    keys = BO.param_keys(d)
+    d = common.load(name)
+    keys = R.fit_problem_from_npz(d)[3]
     replay_loss_grad(d, d['losses'], {k: d['g%s_it0' % k] for k in keys}, {k: d[k + '_final'] for k in keys})
 
 
 @pytest.mark.parametrize('name', ['bd_nll_relu', 'bd_unit_tanh', 'bd_mixed_silu'])
 def test_train_steps_match_reference(name):
     """pmbrl_bnn_train_steps with the recorded draws, one iteration per call."""
-    d = BO.load(name)
+    d = common.load(name)
     flat, keys, sizes = flat_params(d)
     Xn, Yn = T(d['Xn']), T(d['Yn'])
     m, v = torch.zeros_like(flat), torch.zeros_like(flat)
@@ -126,20 +129,19 @@ def test_train_steps_match_reference(name):
 
 def dynamics_from_fixture(d):
     import prob_mbrl_amd as pm
-    from prob_mbrl_amd import activations as ACT
     n = int(d['n_layers'])
     hid = [d['W%d_init' % i].shape[0] for i in range(n - 1)]
     Din, Dout = d['W0_init'].shape[1], d['W%d_init' % (n - 1)].shape[0] // 2
     drops = []
     for l, h in enumerate(hid):
         kind = int(d['kind%d' % l])
-        if kind == BO.BERNOULLI:
+        if kind == R.BERNOULLI:
             k = np.asarray(d['keep%d' % l], np.float32)
             drops.append(pm.models.BDropout(float(1 - k[0]) if k.size == 1 else torch.tensor(1 - k)))
         else:
-            drops.append(pm.models.CDropout(0.1 * np.ones(h)) if kind == BO.CONCRETE else None)
-    nonlin = {BO.RELU: torch.nn.ReLU, BO.TANH: torch.nn.Tanh, BO.SILU: ACT.Swish}[int(d['act'])]
-    dyn = pm.models.DynamicsModel(pm.models.mlp(Din, 2 * Dout, hid, dropout_layers=drops, nonlin=nonlin), reward_func=None,
+            drops.append(pm.models.CDropout(0.1 * np.ones(h)) if kind == R.CONCRETE else None)
+    dyn = pm.models.DynamicsModel(pm.models.mlp(Din, 2 * Dout, hid, dropout_layers=drops, nonlin=common.act_module(d['act'])),
+                                  reward_func=None,
                                   output_density=pm.models.DiagGaussianDensity(Dout)).float()
     lins = [m for m in dyn.model._modules.values() if isinstance(m, torch.nn.Linear)]
     with torch.no_grad():
@@ -164,7 +166,7 @@ def test_train_regressor_matches_reference(name):
     bd_nll_relu on the fused path, resample=False, decoupled_reg and prioritized_sampling."""
     import prob_mbrl_amd as pm
     from prob_mbrl_amd import train_regressor as TR
-    d = BO.load(name)
+    d = common.load(name)
     dyn, lins = dynamics_from_fixture(d)
     opt = torch.optim.Adam([p for p in dyn.parameters() if p.requires_grad], float(d['lr']))
     dyn = dyn.to(DEV)
@@ -204,7 +206,7 @@ def test_train_regressor_applies_the_stored_mask_without_resample():
     """resample=False and no replay: the leading rows of the modules' stored masks serve every iteration (set here to the
     fixture's), and are still there afterwards."""
     import prob_mbrl_amd as pm
-    d = BO.load('bd_resample_off')
+    d = common.load('bd_resample_off')
     dyn, lins = dynamics_from_fixture(d)
     opt = torch.optim.Adam([p for p in dyn.parameters() if p.requires_grad], float(d['lr']))
     dyn = dyn.to(DEV)
@@ -222,7 +224,7 @@ def test_critic_fit_matches_reference():
     """critic.update_value_function on a critic with Bernoulli layers, the recorded masks through _bernoulli."""
     import prob_mbrl_amd as pm
     from prob_mbrl_amd.critic import update_value_function
-    d = BO.load('bd_critic')
+    d = common.load('bd_critic')
     C = lambda a: torch.tensor(np.asarray(a, dtype=np.float32))  # noqa: E731
     n = int(d['n_layers'])
     hid = [d['W%d_init' % i].shape[0] for i in range(n - 1)]
@@ -255,8 +257,10 @@ def test_example_width_against_the_oracle():
     """6 -> 200 -> 200 -> 10, B(0.1) twice, M = 100, N = 300, two iterations: no fixture, the fp64 oracle is the reference.
     (The seeds keep every kept pre-activation clear of ReLU's kink: tests/test_bernoulli_fit_oracle.py says how far and why.)"""
     d = example_width_case()
-    params, losses, g0 = BO.train(d)
-    replay_loss_grad(d, losses, {k: g.numpy() for k, g in g0.items()}, {k: p.detach().numpy() for k, p in params.items()})
+    params, losses, g0 = R.bnn_train(d, torch.float64)
+    keys = R.fit_problem_from_npz(d)[3]
+    replay_loss_grad(d, np.asarray(losses), {k: g.numpy() for k, g in zip(keys, g0)},
+                     {k: p.detach().numpy() for k, p in zip(keys, params)})
 
 
 def _two_layer(keep, seed, n_steps=3, u=False):
@@ -322,8 +326,7 @@ def test_all_concrete_plan_keeps_its_bits():
     """A concrete plan created through the old BnnStep call and one created with explicit (empty) Bernoulli fields give
     bit-identical pmbrl_bnn_loss_grad output on act_bnn_tanh."""
     from prob_mbrl_amd import engine as E
-    from tests import act_oracle as AO
-    d = AO.load('act_bnn_tanh')
+    d = common.load('act_bnn_tanh')
     nl = int(d['n_layers'])
     parts = []
     for l in range(nl):

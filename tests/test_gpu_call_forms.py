@@ -141,16 +141,13 @@ def check_kernels(form, eng):
 
 def build(form, monkeypatch):
     name, over, env, kw, with_adam, want = FORMS[form] if isinstance(form, str) else form
-    from tests import act_oracle as AO
-    from tests import lr_oracle as LR
     from prob_mbrl_amd import engine as E
     from prob_mbrl_amd import problem as PB
     learned = name.startswith('learned_reward/')
     if name.startswith('synthetic/'):
         d = PB.synthetic_problem(name.split('/')[1], seed=0, data_seed=0, **over)
     else:
-        d = dict(LR.load(name.split('/')[1]) if learned else AO.load(name.split('/')[1]) if name.startswith('activations/')
-                 else common.load(name))
+        d = dict(common.load(name.split('/')[-1]))
         for k, v in over.items():
             d[k] = np.asarray(v)
     for k, v in env.items():

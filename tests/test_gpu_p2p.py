@@ -3,7 +3,6 @@ PROCESSES on one device -- IPC-mapped buffers work where RCCL refuses two ranks 
 run of the statistics exchange of moment-matching groups spread over ranks through a device-side transport with more
 than one rank.  Bootstrap (the 64-byte IPC handles) over a gloo group."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -12,14 +11,6 @@ import torch
 from tests import common
 
 pytestmark = pytest.mark.gpu
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _allreduce_worker(rank, world, port, out):
@@ -54,7 +45,7 @@ def test_p2p_allreduce_between_processes_on_one_device(world):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_allreduce_worker, args=(r, world, port, out)) for r in range(world)]
     for p in procs:
         p.start()
@@ -117,7 +108,7 @@ def test_groups_spread_over_two_processes_through_the_p2p_transport(name):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_span_worker, args=(r, 2, port, name, out)) for r in range(2)]
     for p in procs:
         p.start()

@@ -6,7 +6,6 @@ branch is covered by the one-rank case below).  Shapes: D = 4, U = 1, H = 8; 2 x
 (general family) and 2 x 200 networks with one row a rank (register-resident family: tests/reg_envelope_cases.py
 'rows1')."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -19,14 +18,6 @@ H = 8
 LR, CLIP = 1e-3, 0.05
 N_IT = 3
 SMALL, REG = 32, 200        # hidden widths of the two shapes
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _problem(width, rows, groups=0, seed=3):
@@ -175,7 +166,7 @@ def _run(world, case, target=_worker):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=target, args=(r, world, port, case, out)) for r in range(world)]
     for p in procs:
         p.start()

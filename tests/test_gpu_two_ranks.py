@@ -5,7 +5,6 @@ cannot be checked on CPU: every rank issues the same sequence of collectives aro
 launches, and the sharded iteration reproduces the reference's single-process result."""
 import json
 import os
-import socket
 import subprocess
 import sys
 
@@ -19,17 +18,9 @@ pytestmark = pytest.mark.gpu
 ROOT = common.ROOT
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
 def test_bench_two_ranks_one_device():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-           '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
+           '--master-addr', '127.0.0.1', '--master-port', str(common.free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1',
            '--timing-steps', '2', '--dist-backend', 'gloo', '--one-device', '--repeats', '1']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -74,7 +65,7 @@ def test_bench_launches_itself_without_a_launcher():
 def test_bench_three_ranks_uneven_strong_split():
     """100 moment-matching groups over 3 ranks: 34 / 33 / 33 whole groups (strong curve), 3 x 2500 rows (weak)."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '3',
-           '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
+           '--master-addr', '127.0.0.1', '--master-port', str(common.free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '3', '--steps', '2', '--warmup', '1', '--config', 'cartpole_mm',
            '--timing-steps', '1', '--dist-backend', 'gloo', '--one-device', '--repeats', '1']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -88,7 +79,7 @@ def test_bench_two_ranks_strong_scaling():
     """--scaling strong: the SAME 100 x 25 rows divided over the ranks (what BASELINE.json's metric at
     N GPUs means); the JSON line says which it was."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-           '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
+           '--master-addr', '127.0.0.1', '--master-port', str(common.free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--scaling', 'strong',
            '--timing-steps', '2', '--dist-backend', 'gloo', '--one-device', '--repeats', '1']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -101,7 +92,7 @@ def test_bench_two_ranks_strong_scaling():
 def test_bench_two_ranks_one_global_moment_matching_group():
     """--mm-global: one moment-matching group over the rows of both ranks, statistics exchanged every step."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-           '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
+           '--master-addr', '127.0.0.1', '--master-port', str(common.free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--config', 'cartpole_mm',
            '--mm-global', '--timing-steps', '1', '--dist-backend', 'gloo', '--one-device', '--repeats', '1']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -152,7 +143,7 @@ def test_mc_pilco_two_ranks_match_reference():
     name = 'mcp_nomm'
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_mcp_worker, args=(r, 2, port, name, out)) for r in range(2)]
     for p in procs:
         p.start()
@@ -178,7 +169,7 @@ def test_mc_pilco_one_global_moment_matching_group_over_ranks(world):
     name = 'mcp_mm1'
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_mcp_worker, args=(r, world, port, name, out)) for r in range(world)]
     for p in procs:
         p.start()
@@ -233,7 +224,7 @@ def test_rollout_autograd_with_one_group_over_two_processes():
     name = 'mm1_b100_h40'
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_rollout_worker, args=(r, 2, port, name, out)) for r in range(2)]
     for p in procs:
         p.start()
@@ -258,7 +249,7 @@ def test_mc_pilco_two_ranks_cvar_and_regulariser(name):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_mcp_worker, args=(r, 2, port, name, out)) for r in range(2)]
     for p in procs:
         p.start()
@@ -281,7 +272,6 @@ def _n3_worker(rank, world, port, name, out):
     try:
         import prob_mbrl_amd as pm
         from prob_mbrl_amd import algorithms as ALG
-        from tests.test_gpu_api import _value_from_fixture
         d = dict(common.load(name))
         B = d['x0'].shape[0]
         lo, hi = rank * B // world, (rank + 1) * B // world
@@ -296,7 +286,7 @@ def _n3_worker(rank, world, port, name, out):
         exp = None
         if name == 'ext_value':
             full = dict(common.load(name))
-            V = _value_from_fixture(full)
+            V = common.value_from_fixture(full)
             # the critic's frozen masks / noise are per row: this rank's rows of them
             for m in V.modules():
                 for attr in ('noise', 'concrete_noise', 'z'):
@@ -340,7 +330,7 @@ def test_mc_pilco_two_ranks_value_bootstrap_and_prioritised_replay(name):
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_n3_worker, args=(r, 2, port, name, out)) for r in range(2)]
     for p in procs:
         p.start()
@@ -365,7 +355,7 @@ def test_bench_two_ranks_p2p_transport_one_device():
     """bench.py --transport p2p with both ranks on one device: the gradient all-reduce of every iteration really runs on
     the device between two processes (IPC-mapped slots), which RCCL cannot do on a one-GPU box."""
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
-           '--master-addr', '127.0.0.1', '--master-port', str(_free_port()),
+           '--master-addr', '127.0.0.1', '--master-port', str(common.free_port()),
            os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '5', '--warmup', '2', '--transport', 'p2p',
            '--timing-steps', '2', '--dist-backend', 'gloo', '--one-device', '--repeats', '1', '--no-second-curve']
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
@@ -419,7 +409,7 @@ def test_ranks_agree_on_a_truncated_horizon_and_all_enter_p2p_check():
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
     out = ctx.Queue()
-    port = _free_port()
+    port = common.free_port()
     procs = [ctx.Process(target=_agree_worker, args=(r, 2, port, out)) for r in range(2)]
     for p in procs:
         p.start()
