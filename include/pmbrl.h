@@ -205,6 +205,9 @@ typedef struct pmbrl_config {
  *   PMBRL_MM_PARTS=n        moment-matching groups split over n workgroups where that can be done (1: whole groups)
  *   PMBRL_REPLAY=0|1|2      default of pmbrl_plan_set_replay (1)
  *   PMBRL_DW_PIPE=off | n0,n1,...   dW GEMM behind the adjoint sweep on a second stream: never / these step ranges
+ *   PMBRL_DW_STREAM=off | steps[,workgroups]   dW GEMM of the policy's second hidden layer BESIDE the one-launch
+ *                           register-resident adjoint sweep (pmbrl_plan_dw_stream): never / this many of the highest steps
+ *                           on this many consumer workgroups, on any plan whose sweep can publish for it
  * Read by the Python layer: PMBRL_PRECISION (default arithmetic: f32 | split | split_f16), PMBRL_LIB_PATH (the shared
  * library to load), PMBRL_SHARDED_TAIL=0 (mc_pilco keeps the separate calls on a sharded run even where the gradient
  * exchange could run inside pmbrl_rollout_bwd_adam), PMBRL_TORCH_ALLREDUCE=1 (gradient all-reduce through torch.distributed instead of the C ABI). */
@@ -275,6 +278,10 @@ int pmbrl_plan_info(const pmbrl_plan* plan, int32_t* info /* [PMBRL_INFO_COUNT] 
  * (PMBRL_INFO_REG; "" where it does not serve the plan).  The string belongs to the runtime. */
 #define PMBRL_SWEEP_REG 4
 int pmbrl_plan_sweep_kernel(const pmbrl_plan* plan, int variant, int adjoint, const char** name);
+/* Does the plan run the dW GEMM of the policy's second hidden layer BESIDE its one-launch adjoint sweep, on the CUs the
+ * sweep leaves idle (the streamed form)?  out[0]: steps of the horizon that are streamed (-1: the form is off), out[1]:
+ * consumer workgroups.  Environment PMBRL_DW_STREAM=off | <steps>[,<workgroups>] (read when the plan is created). */
+int pmbrl_plan_dw_stream(const pmbrl_plan* plan, int32_t* out /* [2] */);
 
 /* {0,1} float mask [B, h] -> bit rows [B, ceil(h/16)] uint16 (little-endian bit
  * order).  Replaces the per-step fp32 mask multiply of models/modules.py:61,160

@@ -412,6 +412,14 @@ static PlanSwitches read_switches() {
       if (*q == ',') ++q;
     }
   }
+  if (const char* e = getenv("PMBRL_DW_STREAM")) {
+    s.dw_stream_off = !strcmp(e, "off");
+    s.dw_stream_set = e[0] >= '0' && e[0] <= '9';
+    if (s.dw_stream_set) {
+      s.dw_stream_steps = atoi(e);
+      if (const char* q = strchr(e, ',')) s.dw_stream_wgs = std::max(0, atoi(q + 1));
+    }
+  }
   return s;
 }
 
@@ -1027,11 +1035,61 @@ static int plan_dw_pipe(pmbrl_plan* p, int cus) {
   return 0;
 }
 
+// The second hidden layer's dW GEMM BESIDE the adjoint sweep (the streamed form).  Cutting the sweep into ranges (above)
+// costs ~15 us a cut at the cart-pole shapes, more than it hides.  Behind a register-resident adjoint sweep the layer's
+// kernel REBUILDS its delta operand from the forward sweep's stashes and the policy head's gradient -- 2 U floats a row,
+// the only input the adjoint sweep produces.  So the sweep stays ONE launch and publishes that gradient step by step
+// (tagged granules, RegArgs::pub); st_wgs consumer workgroups (pm_dw_layer_st_kernel), one per CU the sweep leaves idle,
+// launched on the second stream next to it, follow it down the steps [st_cut, H); the steps below the cut go to the
+// layer's kernel behind the sweep, over the whole chip, which adds to the consumers' partial rows.  The sweep waits for
+// nothing; the consumers wait (bounded) for sweep workgroups only and are fewer than the CUs the sweep leaves: serialised
+// in submission order the form is merely not faster.
+//   PMBRL_DW_STREAM=off | <steps streamed>[,<consumer workgroups>] (the second: any plan that meets the first four
+//   conditions -- tests, tuning)
+static int plan_dw_stream(pmbrl_plan* p, int cus) {
+  const pmbrl_config& c = p->cfg;
+  const PlanSwitches& sw = p->sw;
+  p->st_on = 0;
+  const int n_free = cus >= 64 && cus % 8 == 0 ? 8 * (cus / 8 - (p->nwg + 7) / 8) : 0;
+  // the plain register-resident instance serves the adjoint in one launch, and its dW GEMM rebuilds the delta
+  const bool fam = p->reg && !p->reg_mm && sw.reg_bwd && p->dw_layer13 == PM_REG_DW_LAYER && p->RT == 1;
+  const bool single = sweep_form(p) == SweepForm::Whole && p->mm_parts <= 1 && p->pipe_K <= 1;
+  if (!fam || !single || n_free < 1 || n_free < cus / 8 || sw.dw_stream_off || c.H >= 4095) return 0;
+  // Large enough to hide something: every consumer gets at least a chunk of every sweep step (fewer, and it runs single
+  // chunks on half-empty K = 32 MFMAs or idles), and the layer's GEMM over the whole chip -- ~3.5 us per chunk pair and
+  // workgroup -- is worth more than what the form adds behind the sweep (the consumers' write-out and a launch, ~12 us):
+  // H nwg / (2 cus) pairs x 3.5 us >= 2 x 12 us
+  const bool large = p->nwg >= n_free && (long long)c.H * p->nwg >= 14ll * cus;
+  if (!large && !sw.dw_stream_set) return 0;
+  // The cut.  A consumer's share of a sweep step is ceil(nwg / n_free) chunks, taken in pairs.  With at most one pair a
+  // step -- nwg <= 2 n_free -- the consumers wait for the sweep at every step (2 us of work against a 4 us step at the
+  // cart-pole shape) and finish a write-out behind it, hidden behind the block kernel: EVERY step is streamed and no
+  // launch of the layer's kernel follows.  (Measured, DESIGN_LOG.md "dW beside the sweep": 40 of 40 steps 410 us an
+  // iteration, 38: 426, 35: 428, 30: 432, 20: 442, off: 430 -- a launch behind the sweep costs ~25 us before its first
+  // chunk; 64 consumers with two pairs a step fall behind: 494 us.)  More than a pair: the consumers do the share they can
+  // keep up with, the highest steps, and the launch behind the sweep takes the rest
+  int steps = p->nwg <= 2 * n_free ? c.H : (int)((long long)c.H * 2 * n_free / p->nwg);
+  int wgs = n_free;
+  if (sw.dw_stream_set) {
+    steps = sw.dw_stream_steps;
+    if (sw.dw_stream_wgs > 0) wgs = std::min(wgs, sw.dw_stream_wgs);
+  }
+  steps = std::max(0, std::min(c.H, steps));
+  p->st_on = 1;
+  p->st_cut = c.H - steps;
+  p->st_wgs = wgs;
+  if (!p->pipe_stream) HIPCHK(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
+  for (int k = 0; k < 2; ++k)
+    if (!p->pipe_ev[k]) HIPCHK(hipEventCreateWithFlags(&p->pipe_ev[k], hipEventDisableTiming));
+  return 0;
+}
+
 // stage 7: the register-resident family, and the workspace carve-up
-static int plan_workspace(pmbrl_plan* p) {
+static int plan_workspace(pmbrl_plan* p, int cus) {
   const pmbrl_config& c = p->cfg;
   p->reg = pm_reg_plan_ok(p) ? 1 : 0;
   p->reg_mm = pm_reg_mm_width(p);
+  if (int rc = plan_dw_stream(p, cus)) return rc;
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
@@ -1091,8 +1149,11 @@ static int plan_workspace(pmbrl_plan* p) {
     for (int l = 0; l < 2; ++l) p->off_reg_ab[n][l] = take(p->reg ? (size_t)c.H * p->nwg * 1024 : 0);
   p->off_part = take((size_t)std::max(p->dw_nsplit, p->pipe_K > 1 ? p->pipe_rows : 0) *
                      ((p->pol.n_params + 3) / 4 * 4) * sizeof(float));
+  // the policy head's gradient as the adjoint sweep publishes it for the streamed dW GEMM: [H][nwg][2 U][16] granules
+  p->pub_bytes = p->st_on ? (size_t)c.H * p->nwg * 2 * c.U * 16 * sizeof(unsigned long long) : 0;
+  p->off_pub = take(p->pub_bytes);
   p->ws_bytes = off;
-  if (p->ws_bytes >= ((size_t)1 << 32)) p->reg = p->reg_mm = 0;      // (the family addresses its stashes with 32-bit workspace offsets)
+  if (p->ws_bytes >= ((size_t)1 << 32)) p->reg = p->reg_mm = p->st_on = 0;      // (the family addresses its stashes with 32-bit workspace offsets)
   return 0;
 }
 
@@ -1216,7 +1277,7 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
   if (int rc = plan_angles(p.get())) return rc;
   if (int rc = plan_dw(p.get())) return rc;
   if (int rc = plan_dw_pipe(p.get(), cus)) return rc;
-  if (int rc = plan_workspace(p.get())) return rc;
+  if (int rc = plan_workspace(p.get(), cus)) return rc;
   if (int rc = plan_attrs(p.get(), cus)) return rc;
   *out = p.release();
   return 0;
@@ -1271,7 +1332,7 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
     // (the host-side notes the recorded call left -- forward: which families' weights it packed, the form of its activity
     //  bits; adjoint: whether its sweep left the second hidden layer's delta to the dW GEMM)
     if (slot == 0) { p->old_pack_stale = R.aux & 1; p->abits_packed = (R.aux >> 1) & 1; }
-    else p->dw_g1_rebuilt = (R.aux >> 2) & 1;
+    else { p->dw_g1_rebuilt = (R.aux >> 2) & 1; p->dw_streamed = (R.aux >> 3) & 1; }
     return 0;
   }
   if (!same || R.seen == 0) {      // first sight of these arguments: as usual, remember them
@@ -1310,7 +1371,7 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
     return body(s);
   }
   R.exec = ex;
-  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1) | ((p->dw_g1_rebuilt & 1) << 2);
+  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1) | ((p->dw_g1_rebuilt & 1) << 2) | ((p->dw_streamed & 1) << 3);
   HIPCHK(hipGraphLaunch(R.exec, s));
   ++R.launches;
   return 0;
@@ -1374,7 +1435,8 @@ extern "C" void pmbrl_plan_destroy(pmbrl_plan* p) {
   if (p->tail_buf_d) (void)hipFree(p->tail_buf_d);
   if (p->pipe_stream) {
     (void)hipStreamDestroy(p->pipe_stream);
-    for (int k = 0; k < p->pipe_K; ++k) (void)hipEventDestroy(p->pipe_ev[k]);
+    for (int k = 0; k < PM_PIPE_MAX; ++k)
+      if (p->pipe_ev[k]) (void)hipEventDestroy(p->pipe_ev[k]);
   }
   delete p;
 }
@@ -1393,6 +1455,13 @@ extern "C" int pmbrl_plan_sweep_kernel(const pmbrl_plan* p, int variant, int adj
 }
 
 extern "C" size_t pmbrl_plan_workspace_bytes(const pmbrl_plan* p) { return p ? p->ws_bytes : 0; }
+
+extern "C" int pmbrl_plan_dw_stream(const pmbrl_plan* p, int32_t* out) {
+  if (!p || !out) return fail(-1, "null argument");
+  out[0] = p->st_on ? p->cfg.H - p->st_cut : -1;
+  out[1] = p->st_on ? p->st_wgs : 0;
+  return 0;
+}
 
 extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   if (!p || !info) return fail(-1, "null argument");
@@ -2014,8 +2083,18 @@ static int bwd_reward_adjoint(pmbrl_plan* p, const BwdCall& C, RolloutArgs& A, f
 }
 
 // the dW GEMM's arguments: the plan's part (plan_dw) + this call's stashes, partial rows and status word
-static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A) {
+static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A, bool streamed) {
   DwArgs W = p->dw_args;
+  if (streamed) {
+    // the streamed form of the layer's GEMM: the granules the sweep of THIS call publishes, under its launch generation
+    // (generation + step + 1, never 0: xch_prepare's rule)
+    W.st_on = 1;
+    W.st_cut = p->st_cut;
+    W.st_wgs = p->st_wgs;
+    W.st_pub = reinterpret_cast<const unsigned long long*>(static_cast<char*>(C.workspace) + p->off_pub);
+    W.st_tag = ((++p->pub_gen) << 12) + 1u;
+    W.st_fail = C.status ? C.status + 1 : nullptr;
+  }
   for (int l = 0; l < p->pol.nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
   W.part = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_part);
   W.nvalid = C.status;
@@ -2055,9 +2134,21 @@ static int bwd_sweep_steps(pmbrl_plan* p, const BwdCall& C, RolloutArgs A) {
 // SweepForm::Whole as K launches over the descending step ranges [lo[k], lo[k-1]) (lo[-1] = H; one range: [0, H)).  More
 // than one (the plan's pipe_lo): the dW GEMM of range k goes out on the second stream behind the sweep of that range, next
 // to the sweep of range k+1; the last range's GEMM is bwd_dw's
+// (W.st_on, the streamed form -- one range: the sweep publishes the policy head's gradient and the layer's consumers go
+//  out on the second stream next to it, behind everything the call's stream held in front of the sweep; bwd_dw joins them)
 static int bwd_sweep_whole(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, const DwArgs& W, bool reg_bwd, int K, const int* lo) {
   hipStream_t s = C.stream;
   char* ws = static_cast<char*>(C.workspace);
+  if (W.st_on) {
+    // the granules' tags: zeroed once per workspace; a RECORDED launch carries the fill -- its replays repeat its generation
+    // and would meet their own tags of the replay before
+    const bool rec = pm_stream_recording(s);
+    if (p->pub_ws != C.workspace || rec) {
+      HIPCHK(hipMemsetAsync(ws + p->off_pub, 0, p->pub_bytes, s));
+      p->pub_ws = rec ? nullptr : C.workspace;
+    }
+    HIPCHK(hipEventRecord(p->pipe_ev[0], s));
+  }
   if (p->mm_parts > 1) {
     // groups split over workgroups: their own flags, and two buffers for the rows of dL/dx they exchange
     A.gsync += 1024;
@@ -2068,8 +2159,13 @@ static int bwd_sweep_whole(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, const
     A.t0 = lo[k];
     A.t1 = k ? lo[k - 1] : p->cfg.H;
     A.gx_from_carry = k > 0;
-    if (reg_bwd) pm_reg_launch(p, ws, A, C.in->pol_params_d, C.in->dyn_params_d, s, false);
+    if (reg_bwd) pm_reg_launch(p, ws, A, C.in->pol_params_d, C.in->dyn_params_d, s, false, W.st_on ? (unsigned)p->off_pub : 0u, W.st_tag);
     else launch_bwd_rt(p, A, s);
+    if (W.st_on) {
+      HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[0], 0));
+      pm_dw_stream_launch(p, W, p->pipe_stream);
+      HIPCHK(hipEventRecord(p->pipe_ev[1], p->pipe_stream));
+    }
     if (k + 1 < K) {
       HIPCHK(hipEventRecord(p->pipe_ev[k], s));
       HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[k], 0));
@@ -2106,7 +2202,8 @@ static int bwd_sweep_external(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, fl
 static int bwd_dw(pmbrl_plan* p, const BwdCall& C, const DwArgs& W, bool piped) {
   ScopedTimer tm(p, PMBRL_TIMER_DW, C.stream);
   if (!piped) {
-    pm_dw_launch(p, W, C.stream);
+    // (streamed: the layer's kernel takes the steps below the cut and adds to the consumers' rows -- behind them)
+    pm_dw_launch(p, W, C.stream, W.st_on ? p->pipe_ev[1] : nullptr);
     return 0;
   }
   // the rows of the last range are added to what the second stream left: join it first
@@ -2116,6 +2213,11 @@ static int bwd_dw(pmbrl_plan* p, const BwdCall& C, const DwArgs& W, bool piped) 
   return 0;
 }
 
+// does this call's dW GEMM of the second hidden layer run beside its sweep (plan_dw_stream)?  The plan's form, on the family
+// that publishes; not with the cycle stamps, nor with the exchange inside (one form of the sharded tail)
+static bool bwd_streamed(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
+  return p->st_on && reg_bwd && sweep_form(p) == SweepForm::Whole && p->pipe_K <= 1 && !p->prof_bwd && !bwd_tail(p, C);
+}
 // A0, reg_bwd: the call's sweep arguments (bwd_args) and the family they go to, assembled once by rollout_bwd_replay --
 // its replay key holds the family too
 static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, bool reg_bwd) {
@@ -2135,9 +2237,11 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   if (p->reg && !reg_bwd) bwd_convert_family(p, C);
   float* grt = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_grt);
   if (int rc = bwd_reward_adjoint(p, C, A, grt)) return rc;
-  const DwArgs W = dw_call_args(p, C, A);
   const SweepForm form = sweep_form(p);
   const bool piped = form == SweepForm::Whole && p->pipe_K > 1 && !p->prof_bwd;
+  const bool streamed = bwd_streamed(p, C, reg_bwd);
+  p->dw_streamed = streamed ? 1 : 0;
+  const DwArgs W = dw_call_args(p, C, A, streamed);
   {
     ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
     static const int whole[1] = {0};
@@ -2221,6 +2325,9 @@ static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
   // ... and the family this call's sweep takes decides which form of the layer's dW kernel follows it (dw_g1_rebuilt)
   const int g1_rebuilt = reg_bwd ? 1 : 0;
   K.val(g1_rebuilt);
+  // ... and whether the layer's GEMM runs beside the sweep (bwd_streamed)
+  const int streamed = bwd_streamed(p, C, reg_bwd) ? 1 : 0;
+  K.val(streamed);
   return K;
 }
 

@@ -52,6 +52,18 @@ struct DwArgs {
   const float* rc_head;                  // the adjoint pack's transposed head weights: [tile][2 blocks][lane][4]
   float rc_inv_keep;                     // 1 / keep of the layer's dropout
   int rc_D, rc_U;                        // state and action widths: which rows of a gT[l + 1] block a lane group holds
+  // Streamed form of the rebuilding kernel (pmbrl.hip: "the layer's dW GEMM beside the adjoint sweep").  The steps
+  // [st_cut, valid steps) go to st_wgs consumer workgroups (pm_dw_layer_st_kernel) that run NEXT TO the one-launch sweep, on
+  // the CUs it leaves idle, and follow it step by step: of the three inputs only the head gradient comes from the adjoint
+  // sweep, which publishes it as tagged granules (st_pub: [H][chunks per step][2 U][16] x {tag, 32 bits}, step t's tag
+  // st_tag + t).  Consumer w owns partial row w; pm_dw_layer_rc_kernel then takes the steps below the cut, dealt to the
+  // rows the reduction reads, and adds to the consumers' rows (pm_dw_range_st).  Only the layer's W / b columns of the
+  // partial rows are concerned: the other kernels run as without it.
+  int st_on;                             // 0: off (fields below unused)
+  int st_cut, st_wgs;
+  const unsigned long long* st_pub;
+  unsigned st_tag;
+  int* st_fail;                          // the adjoint sweep's failure word (status[1]): set when a wait for a granule gives up
 };
 
 // tile sizes of the kernels of whole layers, which the plan's choice of them reads (pmbrl_dw_kernels.h)

@@ -81,6 +81,10 @@ int pm_dw_set_attr(const pmbrl_plan* p) {
                                hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rc_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_st_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rcb_kernel),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
   }
   if (p->dw_pre_mask) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>),
@@ -117,7 +121,9 @@ static DwArgs dw_range_args(const pmbrl_plan* p, const DwArgs& W, int k) {
 // (The pipelined ranges never meet a plan without block-kernel layers or with pre-split stashes: such a plan has
 //  dw_pre_mask -- the first layer's input is at most 40 wide, so only pm_dw_narrow_pre_kernel takes it from the block
 //  kernel -- and plan_dw_pipe leaves the pipeline off for it.)
-void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
+// (W.st_on, the streamed form: the layer's kernel is the launch behind the consumers -- it adds to their partial rows, so
+//  `after`, the event behind them, is waited for in front of it; the other kernels neither read nor write those columns)
+void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s, hipEvent_t after) {
   const dim3 rows(W.nsplit), units((W.nsplit + 7) / 8 * 8 * p->n_dw_units);
   if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
   else if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, rows, dim3(PM_DW_NT), 0, s, W);
@@ -138,12 +144,22 @@ void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
   //  all pm_reg_can_run lets reach it)
   const bool rebuild = W.rc_abits != nullptr;
   assert(!rebuild || (W.RT == 1 && p->dw_layer13 == PM_REG_DW_LAYER));
-  if (p->dw_layer13 >= 0 && rebuild)
+  assert(!W.st_on || rebuild);
+  if (after) (void)hipStreamWaitEvent(s, after, 0);
+  if (W.st_on && W.st_cut == 0) return;      // (every step streamed: the consumers wrote every row the reduction reads)
+  if (p->dw_layer13 >= 0 && rebuild && W.st_on)
+    hipLaunchKernelGGL(pm_dw_layer_rcb_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
+  else if (p->dw_layer13 >= 0 && rebuild)
     hipLaunchKernelGGL(pm_dw_layer_rc_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
   else if (p->dw_layer13 >= 0)
     hipLaunchKernelGGL(pm_dw_layer_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
 }
 void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s) { pm_dw_launch(p, dw_range_args(p, W, k), s); }
+// the streamed form's consumers (W.st_on): one workgroup per CU the adjoint sweep leaves idle, next to it
+void pm_dw_stream_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
+  assert(W.st_on && W.rc_abits && W.RT == 1 && p->dw_layer13 == PM_REG_DW_LAYER);
+  hipLaunchKernelGGL(pm_dw_layer_st_kernel, dim3(W.st_wgs), dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
+}
 // the block kernel alone, one partial row per workgroup: the BNN step's dW / db (its stashes have the same layout)
 void pm_dw_blocks_launch(const DwArgs& W, hipStream_t s) {
   hipLaunchKernelGGL(pm_dw_kernel, dim3(W.nsplit), dim3(PM_DW_NT), 0, s, W);

@@ -74,6 +74,42 @@ __device__ __forceinline__ bool pm_dw_range(const DwArgs& A, int row, DwRange& r
 }
 __device__ __forceinline__ void pm_dw_put(float* q, float v, bool add) { *q = add ? *q + v : v; }
 
+// Streamed form (DwArgs::st_on): what every launch of it derives from the plan's fields and the status word -- and from
+// nothing else, so which chunk lands in which partial row, and in what order, is the same on every run
+struct DwStream {
+  int steps;      // valid steps of the horizon
+  int rows;       // partial rows the reduction reads: the ones that own a chunk of a valid step in the one-launch deal (pm_dw_reduce)
+  int nc;         // consumer workgroups that own a partial row: rows [0, nc)
+  bool any;       // a streamed step is valid: the consumers define their rows, the launch behind the sweep adds to them
+};
+__device__ __forceinline__ DwStream pm_dw_stream(const DwArgs& A) {
+  long long nv = 0x7fffffffll;
+  if (A.nvalid) nv = max(0, __builtin_amdgcn_readfirstlane(*A.nvalid));
+  const long long n_chunks = min((long long)A.n_chunks, nv * A.chunks_per_step);
+  DwStream S;
+  S.steps = (int)(n_chunks / A.chunks_per_step);
+  S.rows = (int)((n_chunks + A.chunks_per_split - 1) / A.chunks_per_split);
+  S.nc = min(A.st_wgs, S.rows);
+  S.any = A.st_cut < S.steps;
+  return S;
+}
+// ... the launch behind the sweep: the chunks of the steps below the cut, dealt in whole pairs to the rows the reduction
+// reads -- under the pipelined form's rules: a row a consumer defined is added to, any other is written, zeros if it got
+// no chunk
+__device__ __forceinline__ bool pm_dw_range_st(const DwArgs& A, int row, DwRange& r) {
+  const DwStream S = pm_dw_stream(A);
+  r.add = r.zero = false;
+  if (row >= S.rows) return false;
+  const int c_end = min(A.st_cut, S.steps) * A.chunks_per_step;
+  const int per = ((c_end + S.rows - 1) / S.rows + 1) & ~1;
+  r.add = S.any && row < S.nc;
+  r.c_lo = row * per;
+  r.c_hi = min(c_end, r.c_lo + per);
+  if (r.c_lo < r.c_hi) return true;
+  r.zero = !r.add;
+  return r.zero;
+}
+
 template <int NI, int NJ>
 __device__ __forceinline__ void pm_dw_block(const DwArgs& A, const DwBlock& blk, int c_lo, int c_hi,
                                             float* part, int lane, bool add) {
@@ -1100,14 +1136,127 @@ struct PmDwRc {
       }
   }
 };
-template <bool RC>
+// The streamed form's operand state: the head gradient comes from the granules the adjoint sweep publishes while this kernel
+// runs.  They are asked for with the step-ahead prefetch, whether they are there yet or not, and their tags are looked at
+// when the values are consumed: a granule that has not arrived is asked for again, in a wait bounded as pmbrl_xch.h's.  A
+// wait that gives up sets the sweep's failure word (the guarded optimiser step is not taken) and ends all waiting of this
+// wave: nothing here waits without a bound.
+typedef __attribute__((address_space(1))) const unsigned long long pm_dw_gu64;
+struct PmDwRcSt : PmDwRc {
+  unsigned long long gr[2][2][2];      // granules of the step's two chunks: [chunk][slot][mean | log-std]
+  const unsigned long long* gp;        // the first chunk's block of them
+  unsigned want;                       // the tag of their step
+  int gblk;
+  bool gsecond, dead;
+
+  __device__ __forceinline__ void init_st(const DwArgs& A) {
+    gblk = 2 * A.rc_U * 16;
+    dead = false;
+  }
+  // (every lane asks, without a branch: a lane group without an action asks for action 0's granules, a step without a
+  //  second chunk for the first one's again -- both inside the buffer, both ignored)
+  __device__ __forceinline__ void load() {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      pm_dw_gu64* q = (pm_dw_gu64*)gp + ((h == 1 && gsecond) ? gblk : 0);
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        gr[h][s][0] = __hip_atomic_load(q + hoff_m[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gr[h][s][1] = __hip_atomic_load(q + hoff_l[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  }
+  // the inputs of step (c, c + 1) of sweep step t
+  __device__ __forceinline__ void fetch_st(const DwArgs& A, int c, bool second, int t) {
+    gp = A.st_pub + (size_t)c * gblk;
+    want = A.st_tag + (unsigned)t;
+    gsecond = second;
+    load();
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const unsigned* ap = A.rc_abits + (size_t)(c + h) * (PR_NW * 64);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) abw[h][i] = (h == 0 || second) ? ap[ab_off[i]] : 0u;
+    }
+  }
+  // before stage(): the granules have arrived -> the head gradient
+  __device__ __forceinline__ void settle(const DwArgs& A, int lane) {
+    for (int spins = 0;;) {
+      bool here = true;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+          const bool live = (h == 0 || gsecond) && hok[s];
+          here = here && (!live || ((unsigned)(gr[h][s][0] >> 32) == want && (unsigned)(gr[h][s][1] >> 32) == want));
+        }
+      if (__all(here) || dead) break;
+      // not there yet: this wave is ahead of the sweep.  It polls ONE granule of the step (every lane the same 8 bytes:
+      // the first row's first mean) between long sleeps, then asks for its own again -- hundreds of waves re-reading all
+      // their granules every few hundred cycles were a flood of uncached reads next to a latency-bound sweep
+      for (;;) {
+        if (++spins > (1 << 19)) {
+          dead = true;
+          if (lane == 0 && A.st_fail) atomicMax(A.st_fail, 1);
+          break;
+        }
+        __builtin_amdgcn_s_sleep(32);
+        const unsigned long long g1 = __hip_atomic_load((pm_dw_gu64*)gp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if ((unsigned)(g1 >> 32) == want) break;
+      }
+      if (dead) break;
+      load();
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const bool live = (h == 0 || gsecond) && hok[s];
+        hgm[h][s] = live ? __uint_as_float((unsigned)gr[h][s][0]) : 0.f;
+        hgl[h][s] = live ? __uint_as_float((unsigned)gr[h][s][1]) : 0.f;
+      }
+  }
+};
+// ST (pm_dw_layer_st_kernel): the streamed form's consumer, one of DwArgs::st_wgs workgroups next to the adjoint sweep.  It
+// walks the streamed steps in DESCENDING order, as the sweep produces them, and takes at each its fixed slice of the step's
+// chunks -- workgroup w of nc: chunks [w n / nc, (w + 1) n / nc) of the step's n, in pairs from the slice's first chunk
+// (a pair never straddles two steps; an odd slice ends in a single chunk).  Same rebuild, same MFMA order inside a pair, same
+// write-out; its partial row is its own (never added to: it defines the row, zeros if its slices are empty).
+// (ST = 2, pm_dw_layer_rcb_kernel: the launch of the streamed form BEHIND the sweep -- the rebuilding kernel over the steps below
+//  the cut, pm_dw_range_st; an instance of its own, so that pm_dw_layer_rc_kernel stays the code it was)
+template <bool RC, int ST = 0>
 __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
+  static_assert(RC || ST == 0, "the streamed form rebuilds its operand");
   extern __shared__ __attribute__((aligned(16))) unsigned short dww_lds[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row = blockIdx.x;
   DwRange R;
-  if (!pm_dw_range(A, row, R)) return;
+  int st_steps = 0, k_lo = 0, k_hi = 0;      // (ST) valid steps; this workgroup's slice of a step's chunks
+  if constexpr (ST == 1) {
+    const DwStream S = pm_dw_stream(A);
+    if (!S.any || row >= S.nc) return;
+    st_steps = S.steps;
+    k_lo = (int)((long long)row * A.chunks_per_step / S.nc);
+    k_hi = (int)((long long)(row + 1) * A.chunks_per_step / S.nc);
+    R.add = false;
+    R.zero = k_lo >= k_hi;
+    R.c_lo = R.c_hi = 0;
+    if (A.st_cut == 0) {
+      // every step is streamed and no launch follows behind the sweep: the rows the reduction reads beyond the consumers'
+      // hold no chunk -- zeros, written here, while the sweep is still in its prologue
+      const int O_ = A.dim[l + 1], K_ = A.dim[l];
+      for (int r = S.nc + row; r < S.rows; r += S.nc) {
+        float* pz = A.part + (size_t)r * A.part_stride;
+        for (int e = tid; e < O_ * K_; e += PM_DW_NT) pz[A.w_off[l] + e] = 0.f;
+        for (int e = tid; e < O_; e += PM_DW_NT) pz[A.b_off[l] + e] = 0.f;
+      }
+    }
+  } else if constexpr (ST == 2) {
+    if (!pm_dw_range_st(A, row, R)) return;
+  } else {
+    if (!pm_dw_range(A, row, R)) return;
+  }
   const int Fo16 = A.nt[l + 1] * 16, Fi16 = A.nt[l] * 16;
   const int O = A.dim[l + 1], K = A.dim[l];
   float* part = A.part + (size_t)row * A.part_stride;
@@ -1124,7 +1273,8 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
   // the delta operand: fetched (the classic form's raw quads, their offsets, the bias sums) or rebuilt -- one of the two
   // states, the other an empty struct
   std::conditional_t<RC, PmDwNone, PmDwFetched> cl;
-  std::conditional_t<RC, PmDwRc, PmDwNone> rc;
+  std::conditional_t<RC, std::conditional_t<ST == 1, PmDwRcSt, PmDwRc>, PmDwNone> rc;
+  if constexpr (ST == 1) rc.init_st(A);
   if constexpr (RC) rc.init(A, l, wid, lane);
   else {
 #pragma unroll
@@ -1162,9 +1312,9 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
       offB[j] = (unsigned)((kq >> 2) * (int)ablk + fb * 16 + (kq & 3) * 4);
     }
   }
-  auto fetch = [&](int c) {
-    const bool second = c + 1 < R.c_hi;
-    if constexpr (RC) rc.fetch(A, l, c, second);
+  auto fetch = [&](int c, bool second, int t) {      // (t: the sweep step of the pair, the streamed form's)
+    if constexpr (ST == 1) rc.fetch_st(A, c, second, t);
+    else if constexpr (RC) rc.fetch(A, l, c, second);
     if (second && pow2) {
       const int b = A.RT >= 2 ? c >> rt_sh : c, rt = A.RT >= 2 ? (c & (A.RT - 1)) : 0;
       const float* pg = gbase + (size_t)b * gblk + rt * 16;
@@ -1204,6 +1354,7 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
         if constexpr (!RC) cl.bs[j] += (cl.ra[j][0] + cl.ra[j][1]) + (cl.ra[j][2] + cl.ra[j][3]);
       }
     }
+    if constexpr (ST == 1) rc.settle(A, lane);
     if constexpr (RC) rc.stage(sa, A.rc_inv_keep, lane);
   };
   f32x4 acc[2][PM_DWL_NT];
@@ -1237,16 +1388,35 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
       if (two) acc[1][j] = pm_mfma_bf<false>(ah[1], bh, acc[1][j]);
     }
   };
-  fetch(R.c_lo);
-  stage(0);
-  __syncthreads();
-  int st = 0;
-  for (int c = R.c_lo; c < R.c_hi; c += 2, st ^= 1) {
-    const bool more = c + 2 < R.c_hi;
-    if (more) fetch(c + 2);
-    mfmas(st);
-    if (more) stage(st ^ 1);
+  if constexpr (ST == 1) {
+    // (t, k): sweep step and chunk of the slice; the pair behind (t, k) is (t, k + 2), or the slice's first of step t - 1
+    int t = st_steps - 1, k = k_lo;
+    fetch(t * A.chunks_per_step + k, k + 1 < k_hi, t);
+    stage(0);
     __syncthreads();
+    for (int st = 0;; st ^= 1) {
+      int tn = t, kn = k + 2;
+      if (kn >= k_hi) { kn = k_lo; tn = t - 1; }
+      const bool more = tn >= A.st_cut;
+      if (more) fetch(tn * A.chunks_per_step + kn, kn + 1 < k_hi, tn);
+      mfmas(st);
+      if (more) stage(st ^ 1);
+      __syncthreads();
+      if (!more) break;
+      t = tn; k = kn;
+    }
+  } else {
+    fetch(R.c_lo, R.c_lo + 1 < R.c_hi, 0);
+    stage(0);
+    __syncthreads();
+    int st = 0;
+    for (int c = R.c_lo; c < R.c_hi; c += 2, st ^= 1) {
+      const bool more = c + 2 < R.c_hi;
+      if (more) fetch(c + 2, c + 3 < R.c_hi, 0);
+      mfmas(st);
+      if (more) stage(st ^ 1);
+      __syncthreads();
+    }
   }
   // lane holds dW[o = 16 (wid + 8 i) + 4 g + r][k = 16 j + c16].  Through LDS and out in rows (round 6): written from the
   // accumulators a store instruction covered four 64-byte pieces of four different rows -- 160 KB per workgroup in 2 560
@@ -1307,3 +1477,5 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
 }
 __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A, int l) { pm_dw_layer_body<false>(A, l); }
 __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_rc_kernel(const DwArgs A, int l) { pm_dw_layer_body<true>(A, l); }
+__global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_st_kernel(const DwArgs A, int l) { pm_dw_layer_body<true, 1>(A, l); }
+__global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_rcb_kernel(const DwArgs A, int l) { pm_dw_layer_body<true, 2>(A, l); }

@@ -57,6 +57,8 @@ struct PlanSwitches {
   int replay;           // PMBRL_REPLAY (default 1)
   bool dw_pipe_off, dw_pipe_ranges;   // PMBRL_DW_PIPE=off | n0,n1,... (the positive ones in dw_pipe)
   std::vector<int> dw_pipe;
+  bool dw_stream_off, dw_stream_set;  // PMBRL_DW_STREAM=off | <steps streamed>[,<consumer workgroups>]
+  int dw_stream_steps, dw_stream_wgs; // (wgs 0: the plan's)
 };
 
 #define PM_PIPE_MAX 8
@@ -90,6 +92,14 @@ struct pmbrl_plan {
   int pipe_K, pipe_lo[PM_PIPE_MAX], pipe_rows, pipe_grid;
   hipStream_t pipe_stream;
   hipEvent_t pipe_ev[PM_PIPE_MAX];
+  // The second hidden layer's dW GEMM BESIDE the one-launch adjoint sweep (plan_dw_stream; DwArgs::st_on): st_wgs consumer
+  // workgroups on pipe_stream follow the sweep over the steps [st_cut, H) through the head gradients it publishes
+  // (off_pub: tagged granules, pub_gen their launch generation), the steps below the cut follow the sweep as before
+  int st_on, st_cut, st_wgs;
+  size_t off_pub, pub_bytes;
+  const void* pub_ws;         // the workspace whose granules hold no tag a later launch could take for its own (xch_prepare's rule)
+  mutable unsigned pub_gen;
+  int dw_streamed;            // the latest adjoint call took the streamed form (a note for the record, as dw_g1_rebuilt)
   int dw_wave_first[PM_DW_NW + 1];
   // workspace offsets (bytes)
   size_t off_actT[PM_MAXL], off_gT[PM_MAXL], off_Tp, off_Td, off_xt, off_rt, off_part, off_mmfac,
@@ -224,7 +234,8 @@ void pm_pack_all_launch(const PackArgs& PK, hipStream_t s);   // (pmbrl.hip)
 int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max = PM_DW_TN,
                     const bool* skip = nullptr);
 int pm_dw_set_attr(const pmbrl_plan* p);
-void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s);
+void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s, hipEvent_t after = nullptr);
+void pm_dw_stream_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s);   // the streamed form's consumers
 void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s);   // launch k of the pipelined form
 void pm_dw_blocks_launch(const DwArgs& W, hipStream_t s);
 // the kernels around the sweeps (pmbrl_tail.hip); pm_dw_reduce's arguments are the kernel's
@@ -260,8 +271,9 @@ void pm_reg_pack_launch(const pmbrl_plan* p, char* ws, const float* pol_params, 
 void pm_reg_unpack_abits(const pmbrl_plan* p, char* ws, hipStream_t s);
 #define PM_REG_DW_LAYER 1      // the policy layer whose delta the family's adjoint does not stash: the second hidden one (200 x 200)
 void pm_reg_dw_rebuild_args(const pmbrl_plan* p, char* ws, DwArgs& W);   // what pm_dw_layer_rc_kernel reads of the family's workspace
+// (pub / pub_tag: the adjoint sweep publishes the policy head's gradient at this workspace offset -- RegArgs::pub; 0: no)
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,
-                   hipStream_t s, bool fwd);
+                   hipStream_t s, bool fwd, unsigned pub = 0, unsigned pub_tag = 0);
 // the sweep kernels' instance tables, one per object (pmbrl_instances.h; pmbrl.hip holds the general family's in exact fp32)
 PmInstTable pm_fast_f32_instances();
 PmInstTable pm_fast_split1_instances();     // PMBRL_PREC_SPLIT

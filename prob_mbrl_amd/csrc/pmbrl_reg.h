@@ -113,6 +113,10 @@ struct RegArgs {
   long long* prof;
   RegMM mm;                     // moment matching of states inside the sweep (pmbrl_reg_mm.h)
   int wg0;                      // first workgroup of this launch (groups launched in batches: workgroup = blockIdx.x + wg0)
+  // adjoint, plain instance: the policy head's gradient PUBLISHED step by step for the streamed dW GEMM that follows the
+  // sweep on the idle CUs (pmbrl_dw_kernels.h, pm_dw_layer_st_kernel) -- data-tagged granules {tag, 32 bits} at this
+  // workspace offset, [H][nwg][2 U][16], the gT[2] block's rows; 0: not asked for.  pub_tag + t is step t's tag
+  unsigned pub, pub_tag;
 };
 // the moment-matching arguments where the launch put them, in the kernel-argument segment (NOT &A.mm: the address of a
 // by-value kernel argument makes the compiler copy the whole struct to scratch)
@@ -1503,6 +1507,23 @@ __global__ __launch_bounds__(PR_NTHR, 1) void pm_reg_bwd_kernel(const RegArgs A)
         if (j >= 0 && j < U) {
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pm_[s]), srd, (j * 16 + row) * 4, pr_uni(so_g2), 0);
           __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(pl_[s]), srd, ((U + j) * 16 + row) * 4, pr_uni(so_g2), 0);
+        }
+      }
+      // ... and, asked for, the same values as granules: one agent-scope store each, nothing waited for (the streamed dW
+      // GEMM polls their tags).  Wave 2's stores alone, on top of what the counts below rely on
+      if constexpr (MMD == 0 && !TREE) {
+        if (A.pub) {
+          typedef PM_GLOBAL_ unsigned long long gu64;
+          const unsigned long long tg = (unsigned long long)(A.pub_tag + (unsigned)t) << 32;
+          gu64* const pb = (gu64*)((PM_GLOBAL_ char*)A.ws + A.pub) + (size_t)(t * A.nwg + wg) * (size_t)(2 * U * 16);
+#pragma unroll
+          for (int s = 0; s < 2; ++s) {
+            const int j = 2 * g + s - D;
+            if (j >= 0 && j < U) {
+              __hip_atomic_store(pb + j * 16 + row, tg | __float_as_uint(pm_[s]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              __hip_atomic_store(pb + (U + j) * 16 + row, tg | __float_as_uint(pl_[s]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+          }
         }
       }
     } else if (wid == 3) {

@@ -193,10 +193,11 @@ void pm_reg_dw_rebuild_args(const pmbrl_plan* p, char* ws, DwArgs& W) {
 }
 
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,
-                   hipStream_t s, bool fwd) {
+                   hipStream_t s, bool fwd, unsigned pub, unsigned pub_tag) {
   ++p->reg_calls[fwd ? 0 : 1];
   RegArgs R;
   reg_args(p, ws, A, reinterpret_cast<const float*>(ws + p->off_reg_pack), pol_params, dyn_params, R);
+  if (!fwd && !p->reg_mm) { R.pub = pub; R.pub_tag = pub_tag; }      // (the plain adjoint instance alone publishes)
   if (p->sw.reg_debug)
     fprintf(stderr, "pm_reg_launch %s: off_mmfac %zu off_reg_pack %zu gT %zu %zu %zu actT %zu %zu %zu abits %zu %zu %zu %zu ws_bytes %zu\n", fwd ? "fwd" : "bwd",
             p->off_mmfac, p->off_reg_pack, p->off_gT[0], p->off_gT[1], p->off_gT[2], p->off_actT[0], p->off_actT[1], p->off_actT[2],

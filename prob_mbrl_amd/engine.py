@@ -739,6 +739,15 @@ class Engine:
                 out[key] = tuple(names)
         return out
 
+    def dw_stream(self):
+        """(steps streamed, consumer workgroups) if the plan runs the second hidden layer's dW GEMM beside its adjoint
+        sweep (pmbrl_plan_dw_stream; PMBRL_DW_STREAM), else None."""
+        if not hasattr(self.lib, 'pmbrl_plan_dw_stream'):
+            return None
+        out = (C.c_int32 * 2)()
+        _lib.check(self.lib.pmbrl_plan_dw_stream(self.plan, out), 'plan_dw_stream')
+        return None if out[0] < 0 else (int(out[0]), int(out[1]))
+
     def replay_count(self):
         """(forward calls, adjoint calls) that went out as one graph launch so far."""
         n = (C.c_int64 * 2)()
