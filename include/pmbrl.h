@@ -282,6 +282,11 @@ int pmbrl_plan_sweep_kernel(const pmbrl_plan* plan, int variant, int adjoint, co
  * sweep leaves idle (the streamed form)?  out[0]: steps of the horizon that are streamed (-1: the form is off), out[1]:
  * consumer workgroups.  Environment PMBRL_DW_STREAM=off | <steps>[,<workgroups>] (read when the plan is created). */
 int pmbrl_plan_dw_stream(const pmbrl_plan* plan, int32_t* out /* [2] */);
+/* 1: the streamed consumers also form the policy head's dW / db, else 0.  The plan's rule: every step is streamed and the
+ * form was not forced through PMBRL_DW_STREAM=<steps>.  PMBRL_DW_HEAD=on overrides the second condition (a forced
+ * PMBRL_DW_STREAM that streams every step then streams the head too; with a cut the head stays in the block kernel),
+ * PMBRL_DW_HEAD=off never streams the head. */
+int pmbrl_plan_dw_head(const pmbrl_plan* plan);
 
 /* {0,1} float mask [B, h] -> bit rows [B, ceil(h/16)] uint16 (little-endian bit
  * order).  Replaces the per-step fp32 mask multiply of models/modules.py:61,160

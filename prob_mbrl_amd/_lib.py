@@ -97,6 +97,7 @@ EXPORTS = [
     'pmbrl_last_error', 'pmbrl_version', 'pmbrl_build_id', 'pmbrl_plan_create',
     'pmbrl_graph_capture_begin', 'pmbrl_graph_capture_end', 'pmbrl_graph_launch', 'pmbrl_graph_num_nodes', 'pmbrl_graph_destroy',
     'pmbrl_plan_destroy', 'pmbrl_plan_workspace_bytes', 'pmbrl_plan_info', 'pmbrl_plan_sweep_kernel', 'pmbrl_plan_dw_stream',
+    'pmbrl_plan_dw_head',
     'pmbrl_pack_mask', 'pmbrl_draw_masks', 'pmbrl_rollout_fwd', 'pmbrl_rollout_bwd', 'pmbrl_rollout_bwd_adam',
     'pmbrl_plan_set_loss',
     'pmbrl_weighted_sum', 'pmbrl_weighted_sum_steps', 'pmbrl_clip_adam', 'pmbrl_clip_adam_guarded', 'pmbrl_debug_linear',
@@ -161,6 +162,9 @@ def load():
     if hasattr(lib, 'pmbrl_plan_dw_stream'):      # (PMBRL_LIB_PATH may name an older build: Engine.dw_stream() says "off")
         lib.pmbrl_plan_dw_stream.restype = C.c_int
         lib.pmbrl_plan_dw_stream.argtypes = [vp, C.POINTER(i32)]
+    if hasattr(lib, 'pmbrl_plan_dw_head'):        # (the same: Engine.dw_head() says "off")
+        lib.pmbrl_plan_dw_head.restype = C.c_int
+        lib.pmbrl_plan_dw_head.argtypes = [vp]
     lib.pmbrl_pack_mask.restype = C.c_int
     lib.pmbrl_pack_mask.argtypes = [vp, vp, i32, i32, i32, vp]
     lib.pmbrl_rollout_fwd.restype = C.c_int

@@ -412,6 +412,8 @@ static PlanSwitches read_switches() {
       if (*q == ',') ++q;
     }
   }
+  s.dw_head = -1;
+  if (const char* e = getenv("PMBRL_DW_HEAD")) s.dw_head = !strcmp(e, "on") ? 1 : (!strcmp(e, "off") ? 0 : -1);
   if (const char* e = getenv("PMBRL_DW_STREAM")) {
     s.dw_stream_off = !strcmp(e, "off");
     s.dw_stream_set = e[0] >= '0' && e[0] <= '9';
@@ -953,6 +955,7 @@ static int plan_dw(pmbrl_plan* p) {
   }
   if (int rc = pm_dw_set_attr(p)) return rc;
   p->n_dw_blocks = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first, p->dw_split ? PM_DW_TN_S : PM_DW_TN, wide);
+  for (int l = 0; l < PM_MAXL; ++l) p->dw_skip[l] = wide[l];
   p->dw_n_chunks = c.H * p->nwg * p->RT;
   int nsplit = std::min(256, p->dw_n_chunks);   // one 8-wave workgroup per CU
   p->dw_chunks_per_split = (p->dw_n_chunks + nsplit - 1) / nsplit;
@@ -1046,6 +1049,41 @@ static int plan_dw_pipe(pmbrl_plan* p, int cus) {
 // in submission order the form is merely not faster.
 //   PMBRL_DW_STREAM=off | <steps streamed>[,<consumer workgroups>] (the second: any plan that meets the first four
 //   conditions -- tests, tuning)
+// ... and the policy HEAD's dW / db with it.  The head's only adjoint-side input is the head gradient -- what the consumers
+// receive anyway -- and its other operand, actT of the head, is the forward sweep's: the consumers form the head's gradient
+// beside the sweep too (pm_dw_layer_body, PmDwHead) and half of the block kernel's bytes leave the critical path.  Where
+// every step is streamed (no launch behind the sweep shares the consumers' rows) and the form was not forced through
+// PMBRL_DW_STREAM=<steps>, which keeps its meaning: the head in the block kernel.  PMBRL_DW_HEAD=on | off forces it where
+// every step is streamed / never.  The block kernel of such a call walks a table without the head, built here.
+static int plan_dw_head(pmbrl_plan* p) {
+  const PlanSwitches& sw = p->sw;
+  const DwArgs& W = p->dw_args;
+  const int l = p->dw_layer13, h = l + 1;
+  p->st_head = 0;
+  if (!p->st_on || p->st_cut != 0 || sw.dw_head == 0 || (sw.dw_head < 0 && sw.dw_stream_set)) return 0;
+  // the head is the last layer, one tile of outputs, a block-kernel layer of the fp32 form; the columns W_l, b_l, W_h, b_h are
+  // one contiguous range of the flat vector (what the reduction reads of the consumers' rows only)
+  if (h != p->pol.nl - 1 || p->pol.nt[h + 1] != 1 || p->pol.dim[h + 1] > 16 || p->dw_skip[h] || p->dw_split) return 0;
+  if (W.b_off[l] != W.w_off[l] + W.dim[l + 1] * W.dim[l] || W.w_off[h] != W.b_off[l] + W.dim[l + 1] ||
+      W.b_off[h] != W.w_off[h] + W.dim[h + 1] * W.dim[h])
+    return 0;
+  bool skip[PM_MAXL];
+  for (int i = 0; i < PM_MAXL; ++i) skip[i] = p->dw_skip[i] || i == h;
+  std::vector<DwBlock> blocks;
+  p->n_dw_blocks_nh = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first_nh, PM_DW_TN, skip, PM_DW_NW);
+  // (pm_dw_kernel_nh, the deeper ring: every block at most 2 x 1 tiles; else the block kernel as it is, on this table)
+  p->dw_nh_ring = 1;
+  for (const DwBlock& b : blocks) p->dw_nh_ring = p->dw_nh_ring && b.n_ot <= 2 && b.n_it <= 1;
+  // (a table that cannot be had is no reason to fail the plan: the head stays in the block kernel)
+  if (hipMalloc(&p->dw_blocks_nh_d, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock)) != hipSuccess ||
+      (!blocks.empty() &&
+       hipMemcpy(p->dw_blocks_nh_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice) != hipSuccess)) {
+    (void)hipGetLastError();
+    return 0;
+  }
+  p->st_head = 1;
+  return 0;
+}
 static int plan_dw_stream(pmbrl_plan* p, int cus) {
   const pmbrl_config& c = p->cfg;
   const PlanSwitches& sw = p->sw;
@@ -1081,7 +1119,7 @@ static int plan_dw_stream(pmbrl_plan* p, int cus) {
   if (!p->pipe_stream) HIPCHK(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
   for (int k = 0; k < 2; ++k)
     if (!p->pipe_ev[k]) HIPCHK(hipEventCreateWithFlags(&p->pipe_ev[k], hipEventDisableTiming));
-  return 0;
+  return plan_dw_head(p);
 }
 
 // stage 7: the register-resident family, and the workspace carve-up
@@ -1332,7 +1370,7 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
     // (the host-side notes the recorded call left -- forward: which families' weights it packed, the form of its activity
     //  bits; adjoint: whether its sweep left the second hidden layer's delta to the dW GEMM)
     if (slot == 0) { p->old_pack_stale = R.aux & 1; p->abits_packed = (R.aux >> 1) & 1; }
-    else { p->dw_g1_rebuilt = (R.aux >> 2) & 1; p->dw_streamed = (R.aux >> 3) & 1; }
+    else { p->dw_g1_rebuilt = (R.aux >> 2) & 1; p->dw_streamed = (R.aux >> 3) & 1; p->dw_head = (R.aux >> 4) & 1; }
     return 0;
   }
   if (!same || R.seen == 0) {      // first sight of these arguments: as usual, remember them
@@ -1371,7 +1409,8 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
     return body(s);
   }
   R.exec = ex;
-  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1) | ((p->dw_g1_rebuilt & 1) << 2) | ((p->dw_streamed & 1) << 3);
+  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1) | ((p->dw_g1_rebuilt & 1) << 2) | ((p->dw_streamed & 1) << 3) |
+          ((p->dw_head & 1) << 4);
   HIPCHK(hipGraphLaunch(R.exec, s));
   ++R.launches;
   return 0;
@@ -1431,6 +1470,7 @@ extern "C" void pmbrl_plan_destroy(pmbrl_plan* p) {
   if (p->wflag_d) (void)hipFree(p->wflag_d);
   if (p->ang_d) (void)hipFree(p->ang_d);
   if (p->dw_blocks_d) (void)hipFree(p->dw_blocks_d);
+  if (p->dw_blocks_nh_d) (void)hipFree(p->dw_blocks_nh_d);
   if (p->dw_units_d) (void)hipFree(p->dw_units_d);
   if (p->tail_buf_d) (void)hipFree(p->tail_buf_d);
   if (p->pipe_stream) {
@@ -1462,6 +1502,8 @@ extern "C" int pmbrl_plan_dw_stream(const pmbrl_plan* p, int32_t* out) {
   out[1] = p->st_on ? p->st_wgs : 0;
   return 0;
 }
+
+extern "C" int pmbrl_plan_dw_head(const pmbrl_plan* p) { return p && p->st_on && p->st_head ? 1 : 0; }
 
 extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   if (!p || !info) return fail(-1, "null argument");
@@ -2094,6 +2136,22 @@ static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutA
     W.st_pub = reinterpret_cast<const unsigned long long*>(static_cast<char*>(C.workspace) + p->off_pub);
     W.st_tag = ((++p->pub_gen) << 12) + 1u;
     W.st_fail = C.status ? C.status + 1 : nullptr;
+    if (W.st_cut == 0) {
+      // every step streamed: the layer's columns (W then b, one contiguous range of the flat vector) hold chunks in the
+      // consumers' rows only -- what the consumers need not zero and the reduction need not read
+      const int l = p->dw_layer13;
+      if (W.b_off[l] == W.w_off[l] + W.dim[l + 1] * W.dim[l]) {
+        W.own_lo = W.w_off[l];
+        W.own_hi = W.b_off[l] + W.dim[l + 1];
+      }
+      if (p->st_head) {
+        // ... and the head's (plan_dw_head: contiguous behind the layer's); the block kernel's table is the one without it
+        W.st_head = 1;
+        W.own_hi = W.b_off[l + 1] + W.dim[l + 2];
+        W.blocks = p->dw_blocks_nh_d;
+        for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first_nh[w];
+      }
+    }
   }
   for (int l = 0; l < p->pol.nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
   W.part = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_part);
@@ -2242,6 +2300,7 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   const bool streamed = bwd_streamed(p, C, reg_bwd);
   p->dw_streamed = streamed ? 1 : 0;
   const DwArgs W = dw_call_args(p, C, A, streamed);
+  p->dw_head = W.st_head;
   {
     ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
     static const int whole[1] = {0};
@@ -2276,7 +2335,7 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
                           W.chunks_per_split, norm_fused ? 1 : 0, (const int*)C.status, expect,
                           opt ? reinterpret_cast<long long*>(opt->step_d) : (long long*)nullptr,
                           loss_fused ? C.rewards : (const float*)nullptr, C.grad_rewards, (long long)p->cfg.H * p->cfg.B,
-                          (long long)p->cfg.B);
+                          (long long)p->cfg.B, W.own_lo, W.own_hi, W.st_wgs);
   }
   // the loss asked for with the optimiser step, where the reduction does not form it on the way: a launch of its own
   if (opt && opt->loss_out_d && !loss_fused)
@@ -2328,6 +2387,8 @@ static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
   // ... and whether the layer's GEMM runs beside the sweep (bwd_streamed)
   const int streamed = bwd_streamed(p, C, reg_bwd) ? 1 : 0;
   K.val(streamed);
+  const int head = streamed && p->st_head ? 1 : 0;      // ... with the policy head's dW in the consumers (plan_dw_head)
+  K.val(head);
   return K;
 }
 

@@ -64,7 +64,18 @@ struct DwArgs {
   const unsigned long long* st_pub;
   unsigned st_tag;
   int* st_fail;                          // the adjoint sweep's failure word (status[1]): set when a wait for a granule gives up
+  // Every step streamed (st_cut == 0): the flat columns [own_lo, own_hi) hold chunks in the consumers' rows only.  The
+  // reduction adds rows [0, st_wgs) alone in the float4 columns that lie wholly inside (pm_dw_reduce), and the consumers
+  // write zeros beyond their rows only at the range's unaligned edges.  Empty: every row of every column is written and read
+  int own_lo, own_hi;
+  // ... and the policy head with it (st_head; the layer behind the streamed one, at most 16 outputs): its only adjoint-side
+  // input is the head gradient the consumers hold anyway, so they form its dW = g^T actT and db = sum g too, with fp32 MFMAs
+  // on register operands, and write them into their own partial rows; the block kernel then walks a table without the head
+  // (pm_dw_kernel_nh) and [own_lo, own_hi) runs through the head's bias
+  int st_head;
 };
+// LDS of the streamed consumer behind the stages: the policy head's table and accumulators (pmbrl_dw_kernels.h, PM_DWH_TAB)
+#define PM_DWH_LDS_BYTES ((2 * 16 * 16 + PM_DW_NW * 64 * 12) * 4)
 
 // tile sizes of the kernels of whole layers, which the plan's choice of them reads (pmbrl_dw_kernels.h)
 #define PM_DWP_TM 256

@@ -13,11 +13,13 @@
 // blocks, dealt to the four SIMDs (waves w and w+4 share SIMD w) by decreasing size so that
 // every SIMD issues the same number of MFMAs.  Returns the number of blocks; `blocks` comes back
 // sorted by wave, wave w owning [wave_first[w], wave_first[w+1]).
+// (ot_parts_min: a layer's output tiles in at least this many parts where it has as many -- the table without the policy
+//  head, pm_dw_kernel_nh, has one layer left and wants a block on every wave)
 int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max,
-                           const bool* skip) {
+                           const bool* skip, int ot_parts_min) {
   blocks.clear();
-  auto split = [](int n, int maxsz, std::vector<std::pair<int, int>>& out) {
-    const int parts = (n + maxsz - 1) / maxsz;
+  auto split = [](int n, int maxsz, std::vector<std::pair<int, int>>& out, int parts_min = 1) {
+    const int parts = std::max((n + maxsz - 1) / maxsz, std::min(n, parts_min));
     int lo = 0;
     for (int i = 0; i < parts; ++i) {
       const int sz = n / parts + (i < n % parts ? 1 : 0);
@@ -28,7 +30,7 @@ int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wa
   for (int l = 0; l < nl; ++l) {
     if (skip && skip[l]) continue;      // a wide layer: pm_dw_wide_kernel
     std::vector<std::pair<int, int>> os, is;
-    split(nt[l + 1], PM_DW_TM, os);
+    split(nt[l + 1], PM_DW_TM, os, ot_parts_min);
     split(nt[l], tn_max, is);
     for (auto& o : os)
       for (auto& i : is) {
@@ -82,7 +84,7 @@ int pm_dw_set_attr(const pmbrl_plan* p) {
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rc_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_st_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
+                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES + PM_DWH_LDS_BYTES));
     HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rcb_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
   }
@@ -125,7 +127,13 @@ static DwArgs dw_range_args(const pmbrl_plan* p, const DwArgs& W, int k) {
 //  `after`, the event behind them, is waited for in front of it; the other kernels neither read nor write those columns)
 void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s, hipEvent_t after) {
   const dim3 rows(W.nsplit), units((W.nsplit + 7) / 8 * 8 * p->n_dw_units);
-  if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
+  // (W.st_head: the consumers formed the head; the call's table is the one without it -- dw_call_args -- and where every
+  //  block of that is at most 2 x 1 tiles, the kernel with the deeper ring walks it)
+  assert(!W.st_head || !W.pipe);      // (pm_dw_kernel_nh has no branch for a row of zeros: only a piped range asks for one)
+  if (W.st_head && p->n_dw_blocks_nh == 0) {}
+  else if (W.st_head && p->dw_nh_ring) hipLaunchKernelGGL(pm_dw_kernel_nh, rows, dim3(PM_DW_NT), 0, s, W);
+  else if (W.st_head) hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W);
+  else if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
   else if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, rows, dim3(PM_DW_NT), 0, s, W);
   else hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W);
   if (p->dw_pre_mask)
@@ -158,7 +166,8 @@ void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t
 // the streamed form's consumers (W.st_on): one workgroup per CU the adjoint sweep leaves idle, next to it
 void pm_dw_stream_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
   assert(W.st_on && W.rc_abits && W.RT == 1 && p->dw_layer13 == PM_REG_DW_LAYER);
-  hipLaunchKernelGGL(pm_dw_layer_st_kernel, dim3(W.st_wgs), dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
+  hipLaunchKernelGGL(pm_dw_layer_st_kernel, dim3(W.st_wgs), dim3(PM_DW_NT), PM_DWL_LDS_BYTES + PM_DWH_LDS_BYTES, s, W,
+                     p->dw_layer13);
 }
 // the block kernel alone, one partial row per workgroup: the BNN step's dW / db (its stashes have the same layout)
 void pm_dw_blocks_launch(const DwArgs& W, hipStream_t s) {

@@ -253,6 +253,111 @@ __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_kernel(const DwArgs A) {
   }
 }
 
+// The block kernel of a call whose head was formed beside the sweep (DwArgs::st_head): what is left for it is the first layer,
+// thirteen [16 outputs] x [one input tile] tiles at the 200-wide shapes, half the bytes.  Two waves' worth of loads in flight
+// per SIMD would not follow them (bytes in flight per CU / latency), so the host deals the output tiles over ALL EIGHT waves,
+// in blocks of at most two (build_dw_blocks' ot_parts_min), and a block keeps a ring of RING chunks in flight instead of two.
+// Per accumulator the same MFMAs on the same operands in the same order as pm_dw_block: the same bits.  Same load / wait
+// discipline (tools/check_inflight.py): the wait before chunk c leaves the RING - 1 younger chunks' loads outstanding.
+template <int NI, int RING>
+__device__ __forceinline__ void pm_dw_block_ring(const DwArgs& A, const DwBlock& blk, int c_lo, int c_hi, float* part, int lane,
+                                                 bool add) {
+  const int g = lane >> 4, c16 = lane & 15;
+  const int l = blk.layer;
+  const int Fo16 = A.nt[l + 1] * 16, Fi16 = A.nt[l] * 16;
+  const float* gbase = A.gT[l];
+  const float* abase = A.actT[l];
+  const size_t gblk = (size_t)Fo16 * A.Rw, ablk = (size_t)Fi16 * A.Rw;
+  unsigned goff[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    const int ot = blk.ot0 + (i < blk.n_ot ? i : blk.n_ot - 1);
+    goff[i] = (unsigned)(((ot * 16 + c16) * A.Rw + 4 * g) * 4);
+  }
+  const unsigned aoff = (unsigned)(((blk.it0 * 16 + c16) * A.Rw + 4 * g) * 4);
+  f32x4 acc[NI];
+  float bsum[NI];
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    bsum[i] = 0.f;
+    acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  const bool do_bias = blk.it0 == 0;
+  f32x4 ga[RING][NI], aa[RING];
+  auto load = [&](auto buf, int c) {
+    const int cc = c < c_hi ? c : c_hi - 1;     // past the end: harmless re-load of the last chunk
+    const int b = cc / A.RT, rt = cc - b * A.RT;
+    const float* gp = gbase + (size_t)b * gblk + rt * 16;
+    const float* ap = abase + (size_t)b * ablk + rt * 16;
+#pragma unroll
+    for (int i = 0; i < NI; ++i) pm_dw_ld(ga[decltype(buf)::value][i], goff[i], gp);
+    pm_dw_ld(aa[decltype(buf)::value], aoff, ap);
+  };
+  pr_for_dw<RING - 1>([&](auto d) { load(d, c_lo + decltype(d)::value); });
+  for (int c = c_lo; c < c_hi; c += RING) {
+    pr_for_dw<RING>([&](auto d) {
+      constexpr int D = decltype(d)::value;
+      load(std::integral_constant<int, (D + RING - 1) % RING>{}, c + D + RING - 1);
+      // everything but the (RING - 1) (NI + 1) loads issued last has landed: chunk c + D
+      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((RING - 1) * (NI + 1)));
+#pragma unroll
+      for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(ga[D][i]));
+      asm volatile("" : "+v"(aa[D]));
+      if (c + D < c_hi) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk)
+#pragma unroll
+          for (int i = 0; i < NI; ++i) acc[i] = mfma4(ga[D][i][kk], aa[D][kk], acc[i]);
+        if (do_bias) {
+#pragma unroll
+          for (int i = 0; i < NI; ++i) bsum[i] += (ga[D][i][0] + ga[D][i][1]) + (ga[D][i][2] + ga[D][i][3]);
+        }
+      }
+    });
+  }
+  asm volatile("s_waitcnt vmcnt(0)");   // drain the look-ahead loads before the registers are reused
+#pragma unroll
+  for (int d = 0; d < RING; ++d) {
+#pragma unroll
+    for (int i = 0; i < NI; ++i) asm volatile("" : "+v"(ga[d][i]));
+    asm volatile("" : "+v"(aa[d]));
+  }
+  const int O = A.dim[l + 1], K = A.dim[l];
+#pragma unroll
+  for (int i = 0; i < NI; ++i)
+    if (i < blk.n_ot) {
+      const int k = blk.it0 * 16 + c16;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int o = (blk.ot0 + i) * 16 + 4 * g + r;
+        if (o < O && k < K) pm_dw_put(part + A.w_off[l] + (size_t)o * K + k, acc[i][r], add);
+      }
+      if (do_bias) {
+        float s = bsum[i];
+        s += __shfl_xor(s, 16);
+        s += __shfl_xor(s, 32);
+        const int o = (blk.ot0 + i) * 16 + c16;
+        if (g == 0 && o < O) pm_dw_put(part + A.b_off[l] + o, s, add);
+      }
+    }
+}
+#define PM_DW_RING 4
+// every block of its table is at most 2 x 1 tiles (the host checks: pm_dw_launch)
+// (no branch for R.zero: pm_dw_range sets it for the pipelined form only, and the head is never streamed under that one)
+__global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_kernel_nh(const DwArgs A) {
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int row = blockIdx.x;
+  DwRange R;
+  if (!pm_dw_range(A, row, R)) return;
+  float* part = A.part + (size_t)row * A.part_stride;
+  for (int bi = A.wave_first[wid]; bi < A.wave_first[wid + 1]; ++bi) {
+    const DwBlock blk = A.blocks[bi];
+    if (blk.n_ot <= 1) pm_dw_block_ring<1, PM_DW_RING>(A, blk, R.c_lo, R.c_hi, part, lane, R.add);
+    else pm_dw_block_ring<2, PM_DW_RING>(A, blk, R.c_lo, R.c_hi, part, lane, R.add);
+  }
+}
+
 
 // ---------------------------------------------------------------------------
 // The same GEMM on split operands: every stashed fp32 value becomes two bf16 pieces in registers
@@ -1148,10 +1253,18 @@ struct PmDwRcSt : PmDwRc {
   unsigned want;                       // the tag of their step
   int gblk;
   bool gsecond, dead;
+  int ab_wv[2];                        // the sweep wave that holds the activity words of this wave's tiles
+  unsigned lane_;
 
-  __device__ __forceinline__ void init_st(const DwArgs& A) {
+  __device__ __forceinline__ void init_st(const DwArgs& A, int wid, int lane) {
     gblk = 2 * A.rc_U * 16;
     dead = false;
+    lane_ = (unsigned)lane;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int tr = (i == 0 || wid + 8 < PM_DWL_NT) ? wid + 8 * i : wid;
+      ab_wv[i] = tr == PR_XT ? pr_xwave(0) : (tr & (PR_NW - 1));
+    }
   }
   // (every lane asks, without a branch: a lane group without an action asks for action 0's granules, a step without a
   //  second chunk for the first one's again -- both inside the buffer, both ignored)
@@ -1162,7 +1275,7 @@ struct PmDwRcSt : PmDwRc {
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         gr[h][s][0] = __hip_atomic_load(q + hoff_m[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        gr[h][s][1] = __hip_atomic_load(q + hoff_l[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        gr[h][s][1] = __hip_atomic_load(q + (gblk >> 1) + hoff_m[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (= hoff_l[s]: U rows on)
       }
     }
   }
@@ -1175,8 +1288,9 @@ struct PmDwRcSt : PmDwRc {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const unsigned* ap = A.rc_abits + (size_t)(c + h) * (PR_NW * 64);
+      // (ab_off[i] = the sweep wave of tile i x 64 + lane: the wave part is this wave's own, a scalar -- one lane offset)
 #pragma unroll
-      for (int i = 0; i < 2; ++i) abw[h][i] = (h == 0 || second) ? ap[ab_off[i]] : 0u;
+      for (int i = 0; i < 2; ++i) abw[h][i] = (h == 0 || second) ? ap[ab_wv[i] * 64 + (int)lane_] : 0u;
     }
   }
   // before stage(): the granules have arrived -> the head gradient
@@ -1217,6 +1331,20 @@ struct PmDwRcSt : PmDwRc {
       }
   }
 };
+// The policy head beside the streamed layer (DwArgs::st_head).  The head is layer l + 1, one tile of outputs; its input stash
+// actT[l + 1] has the chunk layout of the layer's own (blocks [feature][16 rows]).  Wave w forms the output tiles [16 outputs]
+// x [features 16 w .. + 15] and (waves 0 .. 4) 16 (w + 8) of the head's dW with the block kernel's instruction, the fp32 MFMA
+// over four rows, both operands from registers: lane (c16, g) supplies rows 4 g .. + 3 of output c16 (the head gradient, out
+// of the table of the pair's granules) and of feature c16 of the tile (one 16-byte load a tile and chunk).
+// Two waves a SIMD leave 256 registers a lane and the layer's kernel holds 252 while its MFMAs run, so the head keeps NOTHING
+// in registers across a step: its accumulators (lane: dW[o = 4 g + r][feature 16 tile + c16]; db[o = c16] over rows 4 g .. + 3)
+// rest in LDS behind the stages, each wave's own, and its stash loads are not part of the step-ahead prefetch -- they go out
+// in stage(), once the layer's quads of the pair are in LDS and their registers free, and land while the wave waits for the
+// sweep's granules.  LDS behind the stages: the table [chunk][output][row] (every wave writes the same values into it between
+// the same two barriers), then per wave a record of twelve floats a lane.
+#define PM_DWH_TAB (2 * 16 * 16)
+#define PM_DWH_WAVE (64 * 12)      // floats a wave: [lane] x {tile 0's four, tile 1's four, db, -, -, -}
+static_assert(PM_DWH_LDS_BYTES == (PM_DWH_TAB + PM_DW_NW * PM_DWH_WAVE) * 4, "the head's LDS");
 // ST (pm_dw_layer_st_kernel): the streamed form's consumer, one of DwArgs::st_wgs workgroups next to the adjoint sweep.  It
 // walks the streamed steps in DESCENDING order, as the sweep produces them, and takes at each its fixed slice of the step's
 // chunks -- workgroup w of nc: chunks [w n / nc, (w + 1) n / nc) of the step's n, in pairs from the slice's first chunk
@@ -1224,6 +1352,11 @@ struct PmDwRcSt : PmDwRc {
 // write-out; its partial row is its own (never added to: it defines the row, zeros if its slices are empty).
 // (ST = 2, pm_dw_layer_rcb_kernel: the launch of the streamed form BEHIND the sweep -- the rebuilding kernel over the steps below
 //  the cut, pm_dw_range_st; an instance of its own, so that pm_dw_layer_rc_kernel stays the code it was)
+// (The streamed form runs on 16-row chunks only -- pm_dw_stream_launch -- and its instance knows: the paths of the wider chunks
+//  and what they keep in registers leave it.  Written as macros: the other instances then read the record at every use, as
+//  they did, and compile to the code they were -- a local or a lambda in their place moved their register allocation.)
+#define PM_DWL_RT (ST == 1 ? 1 : A.RT)
+#define PM_DWL_RW (ST == 1 ? 16 : A.Rw)
 template <bool RC, int ST = 0>
 __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
   static_assert(RC || ST == 0, "the streamed form rebuilds its operand");
@@ -1244,12 +1377,20 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
     R.c_lo = R.c_hi = 0;
     if (A.st_cut == 0) {
       // every step is streamed and no launch follows behind the sweep: the rows the reduction reads beyond the consumers'
-      // hold no chunk -- zeros, written here, while the sweep is still in its prologue
+      // hold no chunk -- zeros, written here, while the sweep is still in its prologue.  (The reduction does not read those
+      // rows in the float4 columns wholly inside [own_lo, own_hi), the consumers' columns: only the at most three elements
+      // at either unaligned edge of the range get their zeros)
       const int O_ = A.dim[l + 1], K_ = A.dim[l];
+      const int a_lo = (A.own_lo + 3) & ~3, a_hi = A.own_hi & ~3;
       for (int r = S.nc + row; r < S.rows; r += S.nc) {
         float* pz = A.part + (size_t)r * A.part_stride;
-        for (int e = tid; e < O_ * K_; e += PM_DW_NT) pz[A.w_off[l] + e] = 0.f;
-        for (int e = tid; e < O_; e += PM_DW_NT) pz[A.b_off[l] + e] = 0.f;
+        if (a_lo < a_hi) {
+          if (tid < a_lo - A.own_lo) pz[A.own_lo + tid] = 0.f;
+          if (tid < A.own_hi - a_hi) pz[a_hi + tid] = 0.f;
+        } else {
+          for (int e = tid; e < O_ * K_; e += PM_DW_NT) pz[A.w_off[l] + e] = 0.f;
+          for (int e = tid; e < O_; e += PM_DW_NT) pz[A.b_off[l] + e] = 0.f;
+        }
       }
     }
   } else if constexpr (ST == 2) {
@@ -1264,17 +1405,34 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
   if (R.zero) {
     for (int e = tid; e < O * K; e += PM_DW_NT) part[A.w_off[l] + e] = 0.f;
     for (int e = tid; e < O; e += PM_DW_NT) part[A.b_off[l] + e] = 0.f;
+    if constexpr (ST == 1) {
+      if (A.st_head) {      // (the head's columns of this consumer's row too)
+        const int O2 = A.dim[l + 2];
+        for (int e = tid; e < O2 * O; e += PM_DW_NT) part[A.w_off[l + 1] + e] = 0.f;
+        for (int e = tid; e < O2; e += PM_DW_NT) part[A.b_off[l + 1] + e] = 0.f;
+      }
+    }
     return;
   }
   const float* gbase = A.gT[l];
   const float* abase = A.actT[l];
-  const size_t gblk = (size_t)Fo16 * A.Rw, ablk = (size_t)Fi16 * A.Rw;
+  const size_t gblk = (size_t)Fo16 * PM_DWL_RW, ablk = (size_t)Fi16 * PM_DWL_RW;
   f32x4 rb[PM_DWL_Q];
+  float* const hd_tab = reinterpret_cast<float*>(dww_lds) + PM_DWL_LDS_BYTES / 4;      // (ST, st_head: see PM_DWH_TAB)
+  const unsigned hd_lo = (unsigned)(c16 * 16 + 4 * g);      // rows 4 g .. + 3 of row / feature / output c16 of a [16][16] block
+  float* const hd_acc = hd_tab + PM_DWH_TAB + wid * PM_DWH_WAVE;
+  if constexpr (ST == 1) {
+    if (A.st_head) {      // rows of outputs the head does not have stay zero in the table; the accumulators start at zero
+      for (int e = tid; e < PM_DWH_TAB; e += PM_DW_NT) hd_tab[e] = 0.f;
+      for (int e = lane; e < PM_DWH_WAVE; e += 64) hd_acc[e] = 0.f;
+      __syncthreads();
+    }
+  }
   // the delta operand: fetched (the classic form's raw quads, their offsets, the bias sums) or rebuilt -- one of the two
   // states, the other an empty struct
   std::conditional_t<RC, PmDwNone, PmDwFetched> cl;
   std::conditional_t<RC, std::conditional_t<ST == 1, PmDwRcSt, PmDwRc>, PmDwNone> rc;
-  if constexpr (ST == 1) rc.init_st(A);
+  if constexpr (ST == 1) rc.init_st(A, wid, lane);
   if constexpr (RC) rc.init(A, l, wid, lane);
   else {
 #pragma unroll
@@ -1284,9 +1442,9 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
     const int f = idx >> 3, kq = idx & 7;
     const float* p;
     bool live = f < F16;
-    if (A.RT >= 2) {
-      const int b = c / A.RT, rt = c - b * A.RT;
-      p = base + (size_t)b * blk + (size_t)f * A.Rw + rt * 16 + kq * 4;
+    if (PM_DWL_RT >= 2) {
+      const int b = c / PM_DWL_RT, rt = c - b * PM_DWL_RT;
+      p = base + (size_t)b * blk + (size_t)f * PM_DWL_RW + rt * 16 + kq * 4;
     } else {
       p = base + (size_t)(c + (kq >> 2)) * blk + (size_t)f * 16 + (kq & 3) * 4;
       live = live && (kq < 4 || second);
@@ -1297,26 +1455,38 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
   // constant -- loads with a scalar base and one 32-bit lane offset, no branch per load (a feature row past the layer's
   // is clamped to the last one: it is never staged).  fetch1 above is what remains for the odd step; it was ~25
   // instructions and a branch per load, eight loads a thread and step (as in pm_dw_wide_kernel).
-  const bool pow2 = (A.RT & (A.RT - 1)) == 0;
-  const int rt_sh = A.RT >= 4 ? 2 : (A.RT >= 2 ? 1 : 0);
+  const bool pow2 = (PM_DWL_RT & (PM_DWL_RT - 1)) == 0;
+  const int rt_sh = PM_DWL_RT >= 4 ? 2 : (PM_DWL_RT >= 2 ? 1 : 0);
   unsigned offB[PM_DWL_Q];
 #pragma unroll
   for (int j = 0; j < PM_DWL_Q; ++j) {
     const int idx = tid + PM_DW_NT * j, f = idx >> 3, kq = idx & 7;
     const int fa = min(f, Fo16 - 1), fb = min(f, Fi16 - 1);
-    if (A.RT >= 2) {
-      if constexpr (!RC) cl.offA[j] = (unsigned)(fa * A.Rw + kq * 4);
-      offB[j] = (unsigned)(fb * A.Rw + kq * 4);
+    if (PM_DWL_RT >= 2) {
+      if constexpr (!RC) cl.offA[j] = (unsigned)(fa * PM_DWL_RW + kq * 4);
+      offB[j] = (unsigned)(fb * PM_DWL_RW + kq * 4);
     } else {
       if constexpr (!RC) cl.offA[j] = (unsigned)((kq >> 2) * (int)gblk + fa * 16 + (kq & 3) * 4);
       offB[j] = (unsigned)((kq >> 2) * (int)ablk + fb * 16 + (kq & 3) * 4);
     }
   }
   auto fetch = [&](int c, bool second, int t) {      // (t: the sweep step of the pair, the streamed form's)
-    if constexpr (ST == 1) rc.fetch_st(A, c, second, t);
-    else if constexpr (RC) rc.fetch(A, l, c, second);
+    if constexpr (ST == 1) {
+      rc.fetch_st(A, c, second, t);
+      // (16-row chunks: the step's loads with a scalar base also where the pair has one chunk -- the quads of the absent one
+      //  are asked for in the first chunk's block and dropped; fetch1 and what it keeps in registers leave this instance)
+      const float* pa = abase + (size_t)c * ablk;
+      const bool drop = !second && (tid & 4) != 0;
+      const unsigned back = drop ? (unsigned)ablk : 0u;
+#pragma unroll
+      for (int j = 0; j < PM_DWL_Q; ++j) {
+        rb[j] = *reinterpret_cast<const f32x4*>(pa + (offB[j] - back));
+        if (drop) rb[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      return;
+    } else if constexpr (RC) rc.fetch(A, l, c, second);
     if (second && pow2) {
-      const int b = A.RT >= 2 ? c >> rt_sh : c, rt = A.RT >= 2 ? (c & (A.RT - 1)) : 0;
+      const int b = PM_DWL_RT >= 2 ? c >> rt_sh : c, rt = PM_DWL_RT >= 2 ? (c & (PM_DWL_RT - 1)) : 0;
       const float* pg = gbase + (size_t)b * gblk + rt * 16;
       const float* pa = abase + (size_t)b * ablk + rt * 16;
       if constexpr (!RC) {
@@ -1334,6 +1504,63 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
       fetch1(rb[j], abase, ablk, Fi16, idx, c, second);
     }
   };
+  // (ST, st_head) the head's share of the pair (c, c + 1) being staged.  head_load(): its tiles of the pair's two stash
+  // blocks (a chunk the pair does not have: zeros).  head_mfma(), behind settle(): the wave lays the pair's head gradient --
+  // every wave holds all of it, lane (row, g) the actions 2 g + s - D -- into the table and reads back its A operand; chunk
+  // by chunk, four rows an MFMA, the block kernel's order inside a chunk.
+  f32x4 ha[2][2];      // [chunk][tile]
+  auto head_load = [&](int c, bool second) {
+    if constexpr (ST == 1) {
+      const size_t hblk = (size_t)Fo16 * 16;      // (RT = 1: 16 rows a block)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const float* ph = A.actT[l + 1] + (size_t)(c + ((h == 1 && second) ? 1 : 0)) * hblk;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const int tr = min(wid + 8 * i, A.nt[l + 1] - 1);      // (wave-uniform: a scalar base and one lane offset, hd_lo)
+          ha[h][i] = *reinterpret_cast<const f32x4*>(ph + tr * 256 + hd_lo);
+          if (h == 1 && !second) ha[h][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+    }
+  };
+  auto head_mfma = [&]() {
+    if constexpr (ST == 1) {
+      // (two lane addresses and constant offsets: action 2 g + s - D's mean row and, U rows on, its log-std row)
+      float* const tm = hd_tab + ((2 * g - A.rc_D) * 16 + c16);
+      float* const tl = tm + A.rc_U * 16;
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+          if (rc.hok[s]) {
+            tm[h * 256 + s * 16] = rc.hgm[h][s];
+            tl[h * 256 + s * 16] = rc.hgl[h][s];
+          }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      f32x4 hg[2], hacc[2];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) hg[h] = *reinterpret_cast<const f32x4*>(hd_tab + h * 256 + hd_lo);
+#pragma unroll
+      for (int i = 0; i < 2; ++i) hacc[i] = *reinterpret_cast<const f32x4*>(hd_acc + lane * 12 + 4 * i);
+      float hb = hd_acc[lane * 12 + 8];
+      const bool two2 = wid + 8 < A.nt[l + 1];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+          hacc[0] = mfma4(hg[h][kk], ha[h][0][kk], hacc[0]);
+          if (two2) hacc[1] = mfma4(hg[h][kk], ha[h][1][kk], hacc[1]);
+        }
+        hb += (hg[h][0] + hg[h][1]) + (hg[h][2] + hg[h][3]);
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i) *reinterpret_cast<f32x4*>(hd_acc + lane * 12 + 4 * i) = hacc[i];
+      hd_acc[lane * 12 + 8] = hb;
+    }
+  };
   auto put = [&](unsigned short* plane, int f, int kq, const f32x4& v) {
     const unsigned h0 = pm_pk_bf16(v[0], v[1]), h1 = pm_pk_bf16(v[2], v[3]);
     const unsigned l0 = pm_pk_bf16(v[0] - pm_bf_lo(h0), v[1] - pm_bf_hi(h0));
@@ -1342,7 +1569,7 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
     *reinterpret_cast<uint2*>(q) = uint2{h0, h1};
     *reinterpret_cast<uint2*>(q + PM_DWL_F * PM_DWW_LDK) = uint2{l0, l1};
   };
-  auto stage = [&](int st) {
+  auto stage = [&](int st, int c = 0, bool second = false) {      // (c, second: the pair, the streamed form's)
     unsigned short* sa = dww_lds + st * PM_DWL_STAGE;
     unsigned short* sb = sa + 2 * PM_DWL_F * PM_DWW_LDK;
 #pragma unroll
@@ -1354,7 +1581,15 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
         if constexpr (!RC) cl.bs[j] += (cl.ra[j][0] + cl.ra[j][1]) + (cl.ra[j][2] + cl.ra[j][3]);
       }
     }
-    if constexpr (ST == 1) rc.settle(A, lane);
+    if constexpr (ST == 1) {
+      // (the scheduling barriers: the head's loads stay behind the puts, in the registers the layer's quads have just
+      //  left, and its MFMAs and their operands in front of rc.stage()'s -- interleaved, the two do not fit the registers)
+      __builtin_amdgcn_sched_barrier(0);
+      if (A.st_head) head_load(c, second);
+      rc.settle(A, lane);
+      if (A.st_head) head_mfma();
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (RC) rc.stage(sa, A.rc_inv_keep, lane);
   };
   f32x4 acc[2][PM_DWL_NT];
@@ -1392,7 +1627,7 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
     // (t, k): sweep step and chunk of the slice; the pair behind (t, k) is (t, k + 2), or the slice's first of step t - 1
     int t = st_steps - 1, k = k_lo;
     fetch(t * A.chunks_per_step + k, k + 1 < k_hi, t);
-    stage(0);
+    stage(0, t * A.chunks_per_step + k, k + 1 < k_hi);
     __syncthreads();
     for (int st = 0;; st ^= 1) {
       int tn = t, kn = k + 2;
@@ -1400,7 +1635,7 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
       const bool more = tn >= A.st_cut;
       if (more) fetch(tn * A.chunks_per_step + kn, kn + 1 < k_hi, tn);
       mfmas(st);
-      if (more) stage(st ^ 1);
+      if (more) stage(st ^ 1, tn * A.chunks_per_step + kn, kn + 1 < k_hi);
       __syncthreads();
       if (!more) break;
       t = tn; k = kn;
@@ -1460,6 +1695,27 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
       __syncthreads();
     }
   }
+  if constexpr (ST == 1) {
+    // the head's tiles and (wave 0) its bias sums into this consumer's own row, as the block kernel writes a block.  (The
+    // layer's write-out above went through the stages' LDS only: the head's records behind them are intact.)
+    if (A.st_head) {
+      const int O2 = A.dim[l + 2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(hd_acc + lane * 12 + 4 * i);
+        const int k = (wid + 8 * i) * 16 + c16;
+        if (i == 0 || wid + 8 < A.nt[l + 1]) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r)
+            if (4 * g + r < O2 && k < O) part[A.w_off[l + 1] + (size_t)(4 * g + r) * O + k] = v[r];
+        }
+      }
+      float b = hd_acc[lane * 12 + 8];
+      b += __shfl_xor(b, 16);
+      b += __shfl_xor(b, 32);
+      if (wid == 0 && g == 0 && c16 < O2) part[A.b_off[l + 1] + c16] = b;
+    }
+  }
   if constexpr (RC) {
     rc.bias_out(part + A.b_off[l], O, lane, R.add);
   } else {
@@ -1475,6 +1731,8 @@ __device__ __forceinline__ void pm_dw_layer_body(const DwArgs& A, int l) {
     }
   }
 }
+#undef PM_DWL_RT
+#undef PM_DWL_RW
 __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_kernel(const DwArgs A, int l) { pm_dw_layer_body<false>(A, l); }
 __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_rc_kernel(const DwArgs A, int l) { pm_dw_layer_body<true>(A, l); }
 __global__ __launch_bounds__(PM_DW_NT, 2) void pm_dw_layer_st_kernel(const DwArgs A, int l) { pm_dw_layer_body<true, 1>(A, l); }

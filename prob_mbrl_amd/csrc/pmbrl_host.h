@@ -57,6 +57,7 @@ struct PlanSwitches {
   int replay;           // PMBRL_REPLAY (default 1)
   bool dw_pipe_off, dw_pipe_ranges;   // PMBRL_DW_PIPE=off | n0,n1,... (the positive ones in dw_pipe)
   std::vector<int> dw_pipe;
+  int dw_head;                        // PMBRL_DW_HEAD=on | off: the policy head's dW in the streamed consumers (-1: the plan's rule)
   bool dw_stream_off, dw_stream_set;  // PMBRL_DW_STREAM=off | <steps streamed>[,<consumer workgroups>]
   int dw_stream_steps, dw_stream_wgs; // (wgs 0: the plan's)
 };
@@ -100,6 +101,12 @@ struct pmbrl_plan {
   const void* pub_ws;         // the workspace whose granules hold no tag a later launch could take for its own (xch_prepare's rule)
   mutable unsigned pub_gen;
   int dw_streamed;            // the latest adjoint call took the streamed form (a note for the record, as dw_g1_rebuilt)
+  // ... with the policy head's dW / db formed by the consumers too (plan_dw_stream: every step streamed and the form not
+  // forced, or PMBRL_DW_HEAD); the block kernel of such a call walks the table without the head
+  int st_head, dw_head;       // the plan's form; the latest adjoint call took it (a note, as dw_streamed)
+  bool dw_skip[PM_MAXL];      // layers that are not the block kernels' (plan_dw)
+  DwBlock* dw_blocks_nh_d;
+  int n_dw_blocks_nh, dw_nh_ring, dw_wave_first_nh[PM_DW_NW + 1];
   int dw_wave_first[PM_DW_NW + 1];
   // workspace offsets (bytes)
   size_t off_actT[PM_MAXL], off_gT[PM_MAXL], off_Tp, off_Td, off_xt, off_rt, off_part, off_mmfac,
@@ -232,7 +239,7 @@ void pm_pack_all_launch(const PackArgs& PK, hipStream_t s);   // (pmbrl.hip)
 
 // the dW GEMMs (pmbrl_dw.hip)
 int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max = PM_DW_TN,
-                    const bool* skip = nullptr);
+                    const bool* skip = nullptr, int ot_parts_min = 1);
 int pm_dw_set_attr(const pmbrl_plan* p);
 void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s, hipEvent_t after = nullptr);
 void pm_dw_stream_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s);   // the streamed form's consumers
@@ -243,7 +250,8 @@ void pm_dw_blocks_launch(const DwArgs& W, hipStream_t s);
 void pm_dw_reduce_launch(hipStream_t s, const float* part, int nsplit, int n, int stride, float* grad,
                          const int* nvalid = nullptr, int chunks_per_step = 0, int chunks_per_split = 1, int norm_on = 0,
                          const int* status = nullptr, int expect = 0, long long* step = nullptr, const float* loss_r = nullptr,
-                         const float* loss_w = nullptr, long long loss_n = 0, long long loss_per_step = 0);
+                         const float* loss_w = nullptr, long long loss_n = 0, long long loss_per_step = 0, int col_lo = 0,
+                         int col_hi = 0, int rows_in_range = 0);
 void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
                          long long n_per_step);
 int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, int64_t n,

@@ -186,7 +186,8 @@ __global__ __launch_bounds__(512) void pm_dw_reduce(const float* __restrict__ pa
                                                     long long* __restrict__ step = nullptr,
                                                     const float* __restrict__ loss_r = nullptr,
                                                     const float* __restrict__ loss_w = nullptr, long long loss_n = 0,
-                                                    long long loss_per_step = 0) {
+                                                    long long loss_per_step = 0, int col_lo = 0, int col_hi = 0,
+                                                    int rows_in_range = 0) {
   __shared__ f32x4 sm[8][64];
   __shared__ double sl_[8];
   // loss_r: the fused iteration's loss on the way -- this workgroup's slice of sum_i r_i w_i over the valid steps (requested
@@ -210,7 +211,12 @@ __global__ __launch_bounds__(512) void pm_dw_reduce(const float* __restrict__ pa
   const int col = threadIdx.x & 63, sl = threadIdx.x >> 6;
   const int c4 = blockIdx.x * 64 + col;            // float4 column
   const int per = (nsplit + 7) / 8;
-  const int k_lo = sl * per, k_hi = min(nsplit, k_lo + per);
+  int k_hi = min(nsplit, sl * per + per);
+  const int k_lo = sl * per;
+  // [col_lo, col_hi): columns whose rows beyond the first rows_in_range hold no chunk (the streamed dW form's, DwArgs::own_lo).
+  // A float4 column wholly inside adds those rows only -- the slices are the full range's, so every partial sum is the one
+  // it was without additions of +0 to a sum that began as +0: the same bits, and the rows beyond are never read
+  if (c4 * 4 >= col_lo && c4 * 4 + 4 <= col_hi) k_hi = min(k_hi, rows_in_range);
   f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
   if (c4 * 4 < n) {
     const float* p = part + (size_t)c4 * 4;
@@ -484,9 +490,11 @@ __global__ __launch_bounds__(64) void pm_tail_finish_kernel(const float* __restr
 // the launches of the kernels above that the rollout adjoint call and the BNN step queue (pmbrl_host.h)
 void pm_dw_reduce_launch(hipStream_t s, const float* part, int nsplit, int n, int stride, float* grad, const int* nvalid,
                          int chunks_per_step, int chunks_per_split, int norm_on, const int* status, int expect, long long* step,
-                         const float* loss_r, const float* loss_w, long long loss_n, long long loss_per_step) {
+                         const float* loss_r, const float* loss_w, long long loss_n, long long loss_per_step, int col_lo,
+                         int col_hi, int rows_in_range) {
   hipLaunchKernelGGL(pm_dw_reduce, dim3((n + 255) / 256), dim3(512), 0, s, part, nsplit, n, stride, grad, nvalid,
-                     chunks_per_step, chunks_per_split, norm_on, status, expect, step, loss_r, loss_w, loss_n, loss_per_step);
+                     chunks_per_step, chunks_per_split, norm_on, status, expect, step, loss_r, loss_w, loss_n, loss_per_step,
+                     col_lo, col_hi, rows_in_range);
 }
 void pm_tail_hvec_launch(hipStream_t s, float* hvec, int world, int rank, const int* status, int H) {
   hipLaunchKernelGGL(pm_tail_hvec_kernel, dim3(1), dim3(64), 0, s, hvec, world, rank, status, H);

@@ -748,6 +748,12 @@ class Engine:
         _lib.check(self.lib.pmbrl_plan_dw_stream(self.plan, out), 'plan_dw_stream')
         return None if out[0] < 0 else (int(out[0]), int(out[1]))
 
+    def dw_head(self):
+        """True if the streamed consumers also form the policy head's dW / db (pmbrl_plan_dw_head; PMBRL_DW_HEAD)."""
+        if not hasattr(self.lib, 'pmbrl_plan_dw_head'):
+            return False
+        return bool(self.lib.pmbrl_plan_dw_head(self.plan))
+
     def replay_count(self):
         """(forward calls, adjoint calls) that went out as one graph launch so far."""
         n = (C.c_int64 * 2)()
