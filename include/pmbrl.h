@@ -612,6 +612,38 @@ int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* call, void* workspa
                          const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
                          float* grad_x_d /* [B][n_in] */);
 
+/* Backward of pmbrl_mlp_forward with respect to its input rows AND its parameters, one launch (plus a small
+ * reduction): grad_x as pmbrl_mlp_grad_input gives it, and
+ *   grad_params = (d sample / d theta)^T g_sample + (d mean / d theta)^T g_mean + (d log_std / d theta)^T g_log_std
+ * in the layout of params_flat (W0 [out][in], b0, W1, b1, ...).  What a loss on a stand-alone Policy / Regressor /
+ * critic call needs (behaviour cloning, a custom dynamics or critic loss) and what a per-step rollout hook
+ * (utils/rollout.py:93-163, on_pol_eval) differentiates through.  The masks are constants (eval-mode dropout).
+ *  - Same ten inputs as the forward; any of the three upstream gradients may be NULL, all three NULL is -1.
+ *  - Either output may be NULL and its work is skipped; outputs are OVERWRITTEN, not accumulated into.
+ *  - No float atomics: two calls with the same inputs give the same bits.  At most PMBRL_MLP_BWD_MAX_BLOCKS workgroups
+ *    run; each walks its 16-row tiles in order and sums its share of the gradient in a slab [n_params] of its own in
+ *    the workspace, and a second launch adds the slabs in slab order.  The workspace therefore stops growing at
+ *    B = 16 * PMBRL_MLP_BWD_MAX_BLOCKS rows.  A network so large that this many slabs would exceed
+ *    PMBRL_MLP_BWD_SLAB_BYTES gets fewer workgroups (PMBRL_MLP_BWD_SLAB_BYTES / (4 n_params), at least one).
+ *  - The kernel keeps every Linear's input -- and with Tanh / SiLU every hidden layer's derivatives -- in LDS:
+ *    (n_layers + 2 [+ n_layers - 1]) * 16 * (widest layer rounded up to 16, + 8) floats + 24 KB.  Beyond 160 KB the
+ *    workspace query gives 0 and the call -3, both with a message (pmbrl_mlp_grad_input, which needs less, is a
+ *    separate call and unchanged).
+ * The workspace is pmbrl_mlp_backward_workspace_bytes (>= pmbrl_mlp_workspace_bytes; 0 + pmbrl_last_error on a bad
+ * call); it may be shared with the forward of the same call. */
+#define PMBRL_MLP_BWD_MAX_BLOCKS 256
+#define PMBRL_MLP_BWD_SLAB_BYTES (64u << 20)
+size_t pmbrl_mlp_backward_workspace_bytes(const pmbrl_mlp_call* call);
+int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* call, void* workspace_d,
+                       const float* x_d, const float* params_flat_d,
+                       const uint16_t* const* mask_bits_d, const float* z_d,
+                       const float* in_shift_d, const float* in_iscale_d,
+                       const float* out_scale_d, const float* out_shift_d,
+                       const float* sq_scale_d, const float* sq_bias_d,
+                       const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                       float* grad_x_d /* [B][n_in] or NULL */,
+                       float* grad_params_d /* flat, the layout of params_flat, or NULL */);
+
 /* ---- BNN maximum-likelihood training of the dynamics model ---------------- */
 /* Loss and gradient of one minibatch: the iteration body of the reference's
  * utils.train_regressor (utils/train_regressor.py:113-131) with the model in train() mode --

@@ -24,6 +24,7 @@ REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
 DROP_BY_TEMPERATURE, DROP_BERNOULLI = 0, 1      # pmbrl_bnn_config.drop_kind
+MLP_BWD_MAX_BLOCKS = 256                        # PMBRL_MLP_BWD_MAX_BLOCKS: workgroups (gradient slabs) of pmbrl_mlp_backward
 # pmbrl_plan_info indices (PMBRL_INFO_* of include/pmbrl.h)
 (INFO_ROWS_PER_WG, INFO_N_WG, INFO_ROW_TILES, INFO_LDS_BYTES, INFO_N_POL_PARAMS, INFO_N_DYN_PARAMS, INFO_DW_SPLITS,
  INFO_MM_MODE, INFO_LD, INFO_DW_BLOCKS, INFO_FAST, INFO_STAGES, INFO_MM_GRID, INFO_PRECISION, INFO_DW_PIPE, INFO_MM_PARTS,
@@ -103,6 +104,7 @@ EXPORTS = [
     'pmbrl_weighted_sum', 'pmbrl_weighted_sum_steps', 'pmbrl_clip_adam', 'pmbrl_clip_adam_guarded', 'pmbrl_debug_linear',
     'pmbrl_plan_set_timing', 'pmbrl_plan_read_timing', 'pmbrl_plan_set_prof', 'pmbrl_plan_set_replay', 'pmbrl_plan_replay_count',
     'pmbrl_mlp_workspace_bytes', 'pmbrl_mlp_forward', 'pmbrl_mlp_grad_input',
+    'pmbrl_mlp_backward_workspace_bytes', 'pmbrl_mlp_backward',
     'pmbrl_bnn_plan_create', 'pmbrl_bnn_plan_destroy', 'pmbrl_bnn_plan_workspace_bytes',
     'pmbrl_bnn_plan_n_params', 'pmbrl_bnn_plan_set_unit_keep', 'pmbrl_bnn_loss_grad', 'pmbrl_bnn_loss_grad_ex', 'pmbrl_bnn_train_steps',
     'pmbrl_comm_unique_id', 'pmbrl_comm_init', 'pmbrl_allreduce_sum', 'pmbrl_comm_count', 'pmbrl_comm_destroy',
@@ -188,6 +190,10 @@ def load():
     lib.pmbrl_mlp_forward.argtypes = [vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 10
     lib.pmbrl_mlp_grad_input.restype = C.c_int
     lib.pmbrl_mlp_grad_input.argtypes = [vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 11
+    lib.pmbrl_mlp_backward_workspace_bytes.restype = C.c_size_t
+    lib.pmbrl_mlp_backward_workspace_bytes.argtypes = [C.POINTER(MlpCall)]
+    lib.pmbrl_mlp_backward.restype = C.c_int
+    lib.pmbrl_mlp_backward.argtypes = [vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 12
     lib.pmbrl_bnn_plan_create.restype = C.c_int
     lib.pmbrl_bnn_plan_create.argtypes = [C.POINTER(BnnConfig), C.c_int, C.POINTER(vp)]
     lib.pmbrl_bnn_plan_destroy.restype = None

@@ -179,6 +179,55 @@ struct EpiMlpBwdAct {
   }
 };
 
+// the 16 input rows of a tile, normalised, zero beyond the valid rows and the true width
+__device__ __forceinline__ void pm_mlp_load_rows(const MlpArgs& A, float* H, int row0, int nvalid, int tid) {
+  const int K0 = A.dim[0], LD = A.LD;
+  for (int i = tid; i < 16 * A.nt[0] * 16; i += PM_NT) {
+    const int r = i / (A.nt[0] * 16), k = i - r * (A.nt[0] * 16);
+    float v = 0.f;
+    if (r < nvalid && k < K0) {
+      v = A.x[(size_t)(row0 + r) * K0 + k];
+      if (A.in_shift) v = (v - A.in_shift[k]) * A.in_iscale[k];
+    }
+    H[r * LD + k] = v;
+  }
+}
+
+// gradient wrt the raw head outputs [mu | log_std] (`raw`, from the recomputed forward) into `g`: exact zeros in the
+// rows past the valid ones and the columns past 2 n_out
+__device__ __forceinline__ void pm_mlp_head_grad(const MlpBwdArgs& B, const float* raw, float* g, int row0, int nvalid,
+                                                 int tid) {
+  const MlpArgs& A = B.f;
+  const int LD = A.LD;
+  const int n = A.n_out, W16 = A.nt[A.nl] * 16;
+  for (int i = tid; i < 16 * W16; i += PM_NT) {
+    const int r = i / W16, j = i - r * W16;
+    float gv = 0.f;
+    if (r < nvalid && j < 2 * n) {
+      const int d = j < n ? j : j - n;
+      const size_t o = (size_t)(row0 + r) * n + d;
+      const float mu0 = raw[r * LD + d], ls0 = raw[r * LD + n + d];
+      float ls = -softplusf(-ls0 + A.mls) + A.mls;
+      float mu = mu0, osc = 1.f;
+      if (A.out_scale) {
+        osc = A.out_scale[d];
+        ls += logf(osc);
+        mu = mu0 * osc + A.out_shift[d];
+      }
+      const float zz = A.z ? A.z[o] : 0.f;
+      const float e = expf(ls);
+      float gs = B.g_sample ? B.g_sample[o] : 0.f;
+      if (A.sq_scale && B.g_sample) {
+        const float th = tanhf(mu + zz * e);
+        gs *= A.sq_scale[d] * (1.f - th * th);
+      }
+      if (j < n) gv = (gs + (B.g_mean ? B.g_mean[o] : 0.f)) * osc;
+      else gv = (gs * zz * e + (B.g_log_std ? B.g_log_std[o] : 0.f)) * sigmoidf(A.mls - ls0);
+    }
+    g[r * LD + j] = gv;
+  }
+}
+
 __host__ __device__ inline size_t pm_mlp_bwd_lds_floats(int nl, int LD, int act = 0) {
   // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: the first hidden layer's derivatives
   return ((size_t)nl + 2 + (act ? 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
@@ -202,15 +251,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   // derivatives of hidden layer l (the output of Linear l): D0 for l = 0, else the dead input buffer of Linear l - 1
   auto dbuf = [&](int l) { return l == 0 ? D0 : H + (size_t)(l - 1) * R * LD; };
   const int K0 = A.dim[0];
-  for (int i = tid; i < R * A.nt[0] * 16; i += PM_NT) {
-    const int r = i / (A.nt[0] * 16), k = i - r * (A.nt[0] * 16);
-    float v = 0.f;
-    if (r < nvalid && k < K0) {
-      v = A.x[(size_t)(row0 + r) * K0 + k];
-      if (A.in_shift) v = (v - A.in_shift[k]) * A.in_iscale[k];
-    }
-    H[r * LD + k] = v;
-  }
+  pm_mlp_load_rows(A, H, row0, nvalid, tid);
   __syncthreads();
   for (int l = 0; l < nl - 1; ++l) {
     if (smooth) {
@@ -225,36 +266,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   }
   gemm_narrow<1>(A.wf[nl - 1], A.nt[nl], A.nt[nl - 1], A.bias[nl - 1], H + (size_t)(nl - 1) * R * LD, G1, LD, part,
                  wid, lane, tid);
-  // gradient wrt the raw head outputs [mu | log_std]
-  {
-    const int n = A.n_out, W16 = A.nt[nl] * 16;
-    for (int i = tid; i < R * W16; i += PM_NT) {
-      const int r = i / W16, j = i - r * W16;
-      float gv = 0.f;
-      if (r < nvalid && j < 2 * n) {
-        const int d = j < n ? j : j - n;
-        const size_t o = (size_t)(row0 + r) * n + d;
-        const float mu0 = G1[r * LD + d], ls0 = G1[r * LD + n + d];
-        float ls = -softplusf(-ls0 + A.mls) + A.mls;
-        float mu = mu0, osc = 1.f;
-        if (A.out_scale) {
-          osc = A.out_scale[d];
-          ls += logf(osc);
-          mu = mu0 * osc + A.out_shift[d];
-        }
-        const float zz = A.z ? A.z[o] : 0.f;
-        const float e = expf(ls);
-        float gs = B.g_sample ? B.g_sample[o] : 0.f;
-        if (A.sq_scale && B.g_sample) {
-          const float th = tanhf(mu + zz * e);
-          gs *= A.sq_scale[d] * (1.f - th * th);
-        }
-        if (j < n) gv = (gs + (B.g_mean ? B.g_mean[o] : 0.f)) * osc;
-        else gv = (gs * zz * e + (B.g_log_std ? B.g_log_std[o] : 0.f)) * sigmoidf(A.mls - ls0);
-      }
-      G0[r * LD + j] = gv;
-    }
-  }
+  pm_mlp_head_grad(B, G1, G0, row0, nvalid, tid);
   __syncthreads();
   float* Gin = G0;
   float* Gout = G1;
@@ -281,4 +293,144 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
       B.grad_x[(size_t)(row0 + r) * K0 + k] = v;
     }
   }
+}
+
+// ---------------------------------------------------------------------------
+// gradient with respect to the PARAMETERS as well (pmbrl_mlp_backward): pm_mlp_bwdx_kernel's recomputed forward and dX
+// chain, and at every Linear l -- while G_l (gradient at its output) and H_l (its input) both sit in LDS --
+//   dW_l += G_l^T H_l   (v_mfma_f32_16x16x4_f32 with the tile's 16 ROWS as K: four issues per 16 x 16 tile of dW_l)
+//   db_l += sum_r G_l[r]
+// The weight gradient reads every H_l, so the derivatives of a Tanh / SiLU layer cannot live in a dead H buffer as they
+// do above: they get buffers of their own (pm_mlp_bwdp_lds_floats).  The grid is capped (PMBRL_MLP_BWD_MAX_BLOCKS): a
+// workgroup strides over its tiles and adds into its own slab [n_params] of the workspace -- the same lane adds to the
+// same address in program order, the first tile stores instead of adding -- and pm_mlp_bwd_reduce_kernel sums the slabs
+// in slab order.  No atomics anywhere: the result is the same bits call after call.
+// ---------------------------------------------------------------------------
+struct MlpBwdPArgs {
+  MlpBwdArgs b;                    // grad_x may be null here
+  float* slab;                     // [gridDim.x][n_params] or null (no parameter gradient wanted)
+  size_t n_params;
+  size_t w_off[PM_MAXL], b_off[PM_MAXL];   // offsets of W_l [out][in] and b_l in the flat parameter order
+};
+
+__host__ __device__ inline size_t pm_mlp_bwdp_lds_floats(int nl, int LD, int act) {
+  // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: one derivative buffer per hidden layer
+  return ((size_t)nl + 2 + (act ? nl - 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
+}
+
+// slab[W_l] (+)= G^T H and slab[b_l] (+)= column sums of G; G, H: [16][LD] in LDS, rows >= nvalid read as exact zeros
+__device__ __forceinline__ void pm_mlp_accum_dw(const float* G, const float* H, int ld, int n_out, int n_in, float* dW,
+                                                float* db, bool first, int nvalid, int wid, int lane, int tid) {
+  const int c = lane & 15, g = lane >> 4;
+  const int n_ot = (n_out + 15) >> 4, n_it = (n_in + 15) >> 4;
+  for (int t = wid; t < n_ot * n_it; t += PM_NW) {
+    const int ot = t / n_it, it = t - ot * n_it;
+    const int o0 = ot * 16 + 4 * g, i = it * 16 + c;
+    f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!first && i < n_in) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (o0 + r < n_out) acc[r] = dW[(size_t)(o0 + r) * n_in + i];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int row = 4 * j + g;                       // K index g of issue j
+      const bool v = row < nvalid;
+      const float a = v ? G[row * ld + ot * 16 + c] : 0.f;
+      const float b = v ? H[row * ld + it * 16 + c] : 0.f;
+      acc = mfma4(a, b, acc);                          // D[i = out feature 4 g + r][j = in feature c]
+    }
+    if (i < n_in) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (o0 + r < n_out) dW[(size_t)(o0 + r) * n_in + i] = acc[r];
+    }
+  }
+  for (int o = tid; o < n_out; o += PM_NT) {
+    float s = first ? 0.f : db[o];
+    for (int r = 0; r < nvalid; ++r) s += G[r * ld + o];
+    db[o] = s;
+  }
+}
+
+__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const MlpBwdPArgs P) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int R = 16;
+  const MlpBwdArgs& B = P.b;
+  const MlpArgs& A = B.f;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int LD = A.LD, nl = A.nl;
+  float* H = smem;                                   // [nl][16][LD]
+  float* G0 = H + (size_t)nl * R * LD;
+  float* G1 = G0 + (size_t)R * LD;
+  float* part = G1 + (size_t)R * LD;
+  const bool smooth = A.act != PMBRL_ACT_RELU;
+  float* D = part + (size_t)PM_NW * PM_KS_NT * 256;  // (smooth only) [nl - 1][16][LD]: act' of hidden layer l
+  float* slab = P.slab ? P.slab + (size_t)blockIdx.x * P.n_params : nullptr;
+  const int K0 = A.dim[0];
+  const int n_tiles = (A.B + R - 1) / R;
+  for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int row0 = tile * R;
+    const int nvalid = min(R, A.B - row0);
+    const bool first = tile == (int)blockIdx.x;
+    pm_mlp_load_rows(A, H, row0, nvalid, tid);
+    __syncthreads();
+    for (int l = 0; l < nl - 1; ++l) {
+      if (smooth) {
+        EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, D + (size_t)l * R * LD, LD, row0,
+                    nvalid, A.nt[l + 1], lane, A.act, A.dim[l + 1]};
+        gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+      } else {
+        EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, LD, row0, nvalid, A.nt[l + 1], lane};
+        gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+      }
+      __syncthreads();
+    }
+    gemm_narrow<1>(A.wf[nl - 1], A.nt[nl], A.nt[nl - 1], A.bias[nl - 1], H + (size_t)(nl - 1) * R * LD, G1, LD, part,
+                   wid, lane, tid);
+    pm_mlp_head_grad(B, G1, G0, row0, nvalid, tid);
+    __syncthreads();
+    float* Gin = G0;
+    float* Gout = G1;
+    for (int l = nl - 1; l >= 0; --l) {
+      // Gin = G_l, the gradient at Linear l's output
+      if (slab)
+        pm_mlp_accum_dw(Gin, H + (size_t)l * R * LD, LD, A.dim[l + 1], A.dim[l], slab + P.w_off[l], slab + P.b_off[l], first,
+                        nvalid, wid, lane, tid);
+      if (l == 0) break;
+      if (smooth) {
+        EpiMlpBwdAct e{D + (size_t)(l - 1) * R * LD, Gout, LD, lane};
+        gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+      } else {
+        EpiMlpBwd e{H + (size_t)l * R * LD, 1.f / A.keep[l - 1], Gout, LD, lane};
+        gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+      }
+      __syncthreads();
+      float* t = Gin; Gin = Gout; Gout = t;
+    }
+    if (B.grad_x) {
+      // first layer: d / d x_in, then the input normalisation
+      EpiPlain e{nullptr, Gout, LD, lane};
+      gemm_tiles<1>(B.wb[0], A.nt[0], A.nt[1], Gin, LD, wid, lane, e);
+      __syncthreads();
+      for (int i = tid; i < nvalid * K0; i += PM_NT) {
+        const int r = i / K0, k = i - r * K0;
+        float v = Gout[r * LD + k];
+        if (A.in_iscale) v *= A.in_iscale[k];
+        B.grad_x[(size_t)(row0 + r) * K0 + k] = v;
+      }
+    }
+    __syncthreads();                                 // the next tile overwrites H and the gradient buffers
+  }
+}
+
+// grad_params[i] = sum over the slabs, in slab order
+__global__ void pm_mlp_bwd_reduce_kernel(const float* __restrict__ slab, int n_slab, size_t n_params,
+                                         float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_params) return;
+  float s = 0.f;
+  for (int b = 0; b < n_slab; ++b) s += slab[(size_t)b * n_params + i];
+  out[i] = s;
 }

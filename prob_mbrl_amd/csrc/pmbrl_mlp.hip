@@ -1,4 +1,4 @@
-// Stand-alone network evaluation (pmbrl_mlp.h): forward and input gradient of one MLP.
+// Stand-alone network evaluation (pmbrl_mlp.h): forward, input gradient and full backward of one MLP.
 #include <hip/hip_runtime.h>
 #include <string.h>
 
@@ -16,7 +16,7 @@
 struct MlpLayout {
   int nl, LD;
   int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
-  size_t wf[PM_MAXL], wb[PM_MAXL], bias[PM_MAXL], w_off[PM_MAXL], b_off[PM_MAXL], bytes, lds, lds_bwd;
+  size_t wf[PM_MAXL], wb[PM_MAXL], bias[PM_MAXL], w_off[PM_MAXL], b_off[PM_MAXL], bytes, lds, lds_bwd, lds_bwdp, n_params;
 };
 static int mlp_layout(const pmbrl_mlp_call* c, MlpLayout& L) {
   if (!c) return fail(-1, "null argument");
@@ -42,11 +42,13 @@ static int mlp_layout(const pmbrl_mlp_call* c, MlpLayout& L) {
     if (l < L.nl - 1 && !(m.keep[l] > 0.f)) return fail(-2, "mlp: keep must be > 0");
   }
   L.bytes = off;
+  L.n_params = po;
   L.LD = maxnt * 16 + 8;
   L.lds = (2 * (size_t)16 * L.LD + (size_t)PM_NW * PM_KS_NT * 256) * sizeof(float);
   if (c->act != PMBRL_ACT_RELU && c->act != PMBRL_ACT_TANH && c->act != PMBRL_ACT_SILU)
     return fail(-2, "mlp: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
   L.lds_bwd = pm_mlp_bwd_lds_floats(L.nl, L.LD, c->act) * sizeof(float);
+  L.lds_bwdp = pm_mlp_bwdp_lds_floats(L.nl, L.LD, c->act) * sizeof(float);
   if (L.lds > 160 * 1024) return fail(-3, "mlp: network too wide for LDS");
   return 0;
 }
@@ -156,3 +158,93 @@ extern "C" int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* c, void*
   return 0;
 }
 
+
+// ---------------------------------------------------------------------------
+// backward with respect to the input rows AND the parameters (pm_mlp_bwdp_kernel)
+// ---------------------------------------------------------------------------
+// the layout of a backward call: the forward's, refused where the kernel's own LDS need (every Linear's input, and with
+// Tanh / SiLU every hidden layer's derivatives, stay resident) exceeds the 160 KB of a CU
+static int mlp_backward_layout(const pmbrl_mlp_call* c, MlpLayout& L) {
+  int rc = mlp_layout(c, L);
+  if (rc) return rc;
+  if (L.lds_bwdp > 160 * 1024)
+    return fail(-3, "mlp: network too wide / deep for the backward kernel's LDS budget (160 KB)");
+  return 0;
+}
+// workgroups of the backward kernel = gradient slabs in the workspace
+static int mlp_backward_blocks(const pmbrl_mlp_call* c, const MlpLayout& L) {
+  const size_t slab = L.n_params * sizeof(float);
+  const size_t fit = std::max<size_t>(1, PMBRL_MLP_BWD_SLAB_BYTES / slab);
+  const size_t cap = std::min<size_t>(PMBRL_MLP_BWD_MAX_BLOCKS, fit);
+  return (int)std::min<size_t>(cap, ((size_t)c->B + 15) / 16);
+}
+static size_t mlp_slab_offset(const MlpLayout& L) { return (L.bytes + 255) & ~(size_t)255; }
+
+extern "C" size_t pmbrl_mlp_backward_workspace_bytes(const pmbrl_mlp_call* c) {
+  MlpLayout L;
+  if (mlp_backward_layout(c, L)) return 0;
+  return mlp_slab_offset(L) + (size_t)mlp_backward_blocks(c, L) * L.n_params * sizeof(float);
+}
+
+extern "C" int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
+                                  const float* x_d, const float* params_flat_d,
+                                  const uint16_t* const* mask_bits_d, const float* z_d,
+                                  const float* in_shift_d, const float* in_iscale_d,
+                                  const float* out_scale_d, const float* out_shift_d,
+                                  const float* sq_scale_d, const float* sq_bias_d,
+                                  const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                                  float* grad_x_d, float* grad_params_d) {
+  MlpLayout L;
+  int rc = mlp_backward_layout(c, L);
+  if (rc) return rc;
+  if (!workspace_d || !x_d || !params_flat_d) return fail(-1, "null argument");
+  if (!g_sample_d && !g_mean_d && !g_log_std_d) return fail(-1, "mlp backward: no upstream gradient given");
+  if ((in_shift_d == nullptr) != (in_iscale_d == nullptr) || (out_scale_d == nullptr) != (out_shift_d == nullptr) ||
+      (sq_scale_d == nullptr) != (sq_bias_d == nullptr))
+    return fail(-1, "mlp: shift/scale pointers come in pairs");
+  if (!grad_x_d && !grad_params_d) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace_d);
+  PackArgs PK;
+  PK.wflag = nullptr;
+  PK.gen = 0;
+  PK.n = 0;
+  PK.status = nullptr;
+  MlpBwdPArgs P;
+  memset(&P, 0, sizeof(P));
+  MlpArgs& A = P.b.f;
+  A.B = c->B; A.nl = L.nl; A.LD = L.LD; A.n_out = L.dim[L.nl] / 2;
+  for (int i = 0; i <= L.nl; ++i) { A.dim[i] = L.dim[i]; A.nt[i] = L.nt[i]; }
+  for (int l = 0; l < L.nl; ++l) {
+    float* wf = reinterpret_cast<float*>(ws + L.wf[l]);
+    float* wb = reinterpret_cast<float*>(ws + L.wb[l]);
+    float* bs = reinterpret_cast<float*>(ws + L.bias[l]);
+    PK.job[PK.n++] = PackJob{params_flat_d + L.w_off[l], wf, L.dim[l + 1], L.dim[l], 0, 1, 0, 0, 0};
+    PK.job[PK.n++] = PackJob{params_flat_d + L.w_off[l], wb, L.dim[l + 1], L.dim[l], 1, 1, 0, 0, 0};
+    PK.job[PK.n++] = PackJob{params_flat_d + L.b_off[l], bs, L.dim[l + 1], L.dim[l], 0, 1, 1, 0, 0};
+    A.wf[l] = wf; P.b.wb[l] = wb; A.bias[l] = bs;
+    A.mask[l] = (l < L.nl - 1 && mask_bits_d) ? mask_bits_d[l] : nullptr;
+    A.keep[l] = l < L.nl - 1 ? c->net.keep[l] : 1.f;
+    P.w_off[l] = L.w_off[l];
+    P.b_off[l] = L.b_off[l];
+  }
+  A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
+  A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
+  A.mls = c->max_log_std;
+  A.act = c->act;
+  P.b.g_sample = g_sample_d; P.b.g_mean = g_mean_d; P.b.g_log_std = g_log_std_d; P.b.grad_x = grad_x_d;
+  const int n_blocks = mlp_backward_blocks(c, L);
+  P.n_params = L.n_params;
+  P.slab = grad_params_d ? reinterpret_cast<float*>(ws + mlp_slab_offset(L)) : nullptr;
+  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdp_kernel),
+                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bwdp));
+  pm_pack_all_launch(PK, s);
+  hipLaunchKernelGGL(pm_mlp_bwdp_kernel, dim3(n_blocks), dim3(PM_NT), L.lds_bwdp, s, P);
+  HIPCHK(hipGetLastError());
+  if (grad_params_d) {
+    hipLaunchKernelGGL(pm_mlp_bwd_reduce_kernel, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, s, P.slab,
+                       n_blocks, L.n_params, grad_params_d);
+    HIPCHK(hipGetLastError());
+  }
+  return 0;
+}

@@ -166,6 +166,26 @@ class _MlpCall:
         return gx
 
 
+    def backward(self, g_sample=None, g_mean=None, g_log_std=None, want_x=True, want_params=True, out=None):
+        """(grad_x [B, n_in], grad_params flat in the order of params_flat) of pmbrl_mlp_backward; an output that is
+        not wanted is None and is not computed.  out = (grad_x, grad_params): write into these tensors."""
+        nbytes = self.lib.pmbrl_mlp_backward_workspace_bytes(C.byref(self.call))
+        if nbytes == 0:
+            msg = self.lib.pmbrl_last_error()
+            raise ValueError('pmbrl_mlp_backward_workspace_bytes: %s' % (msg.decode() if msg else 'bad shape'))
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.x.device)
+        gx, gp = out if out is not None else (None, None)
+        gx = (torch.empty_like(self.x) if gx is None else gx) if want_x else None
+        gp = (torch.empty_like(self.pf) if gp is None else gp) if want_params else None
+        for t, like in ((gx, self.x), (gp, self.pf)):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == like.shape)
+        p = self._p
+        gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_sample, g_mean, g_log_std)]
+        _lib.check(self.lib.pmbrl_mlp_backward(_stream(), C.byref(self.call), p(ws), *self._common(),
+                                               p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp)), 'pmbrl_mlp_backward')
+        return gx, gp
+
+
 class _MlpFunction(torch.autograd.Function):
     """Differentiable with respect to the input rows only (the network is a constant here)."""
 
@@ -182,19 +202,53 @@ class _MlpFunction(torch.autograd.Function):
         return gx, None, None
 
 
+class _MlpParamFunction(torch.autograd.Function):
+    """Differentiable with respect to the input rows and the parameter tensors W0, b0, W1, b1, ... (the pieces of the
+    call's params_flat), first order: one pmbrl_mlp_backward per backward pass."""
+
+    @staticmethod
+    def forward(ctx, call, want, x, *params):
+        ctx.call, ctx.want = call, want
+        ctx.shapes = [p.shape for p in params]
+        ctx.set_materialize_grads(False)
+        out = call.forward(want)
+        return tuple(out[k] for k in want)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        g = dict(zip(ctx.want, grads))
+        need_x, need_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3:]
+        gx, gp = ctx.call.backward(g.get('sample'), g.get('mean'), g.get('log_std'), want_x=need_x,
+                                   want_params=any(need_p))
+        out, off = [], 0
+        for shape, need in zip(ctx.shapes, need_p):
+            n = shape.numel()
+            out.append(gp[off:off + n].view(shape) if need else None)
+            off += n
+        return (None, None, gx) + tuple(out)
+
+
 def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=None, in_iscale=None,
                 out_scale=None, out_shift=None, sq_scale=None, sq_bias=None, max_log_std=math.log(5.0),
-                want=('sample',), act=0):
+                want=('sample',), act=0, params=None):
     """Stand-alone evaluation of one Bayesian MLP with a diagonal-Gaussian head on the rows of x
     (pmbrl_mlp_forward; models/core.py:169-187, 221-248).  dims = [n_in, h..., 2*n_out];
     mask_bits: per hidden layer an int16 bit-row tensor (pack_mask) or None.
     act: the hidden layers' activation (activations.RELU / TANH / SILU).
     Returns a dict with the requested outputs among 'sample', 'mean', 'log_std' ([B, n_out]).
-    If x requires grad the outputs are differentiable with respect to x (pmbrl_mlp_grad_input)."""
+    If x requires grad the outputs are differentiable with respect to x (pmbrl_mlp_grad_input).
+    params: the tensors [W0, b0, W1, b1, ...] whose values params_flat holds; where one of them requires grad the
+    outputs are connected to them (and to x where it requires grad) through pmbrl_mlp_backward."""
     want = tuple(want)
     xc = x.contiguous()
     call = _MlpCall(xc.detach(), params_flat, dims, keep, mask_bits, z, in_shift, in_iscale, out_scale,
                     out_shift, sq_scale, sq_bias, max_log_std, act=act)
+    if params is not None and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+        assert [tuple(p.shape) for p in params] == [s for i in range(len(dims) - 1)
+                                                    for s in ((dims[i + 1], dims[i]), (dims[i + 1],))]
+        outs = _MlpParamFunction.apply(call, want, xc, *params)
+        return dict(zip(want, outs))
     if x.requires_grad and torch.is_grad_enabled():
         outs = _MlpFunction.apply(xc, call, want)
         return dict(zip(want, outs))

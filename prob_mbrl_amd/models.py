@@ -8,9 +8,11 @@ reference's names (`model.fc0.weight`, `model.drop0.noise`, `mx`, `Sy`, `scale`
 (Linear -> ReLU -> dropout ... -> density sample -> squash / reward) is NOT done
 here: `prob_mbrl_amd.rollout.rollout` hands the tensors to the fused HIP kernels.
 """
+import contextlib
 import copy
 import inspect
 import math
+import threading
 from collections import OrderedDict
 from collections.abc import Iterable
 from functools import partial
@@ -18,6 +20,32 @@ from functools import partial
 import numpy as np
 import torch
 from torch import nn
+
+
+# ---------------------------------------------------------------------------
+# stand-alone calls that are differentiable in the network's parameters
+# ---------------------------------------------------------------------------
+_param_grad_state = threading.local()
+
+
+def param_grad_enabled():
+    """True inside `param_grad()` on this thread."""
+    return getattr(_param_grad_state, 'on', False)
+
+
+@contextlib.contextmanager
+def param_grad(enabled=True):
+    """Inside this context a stand-alone Policy / Regressor / DynamicsModel / critic call returns outputs connected
+    to the Linear parameters of the network (and to x where it requires grad), as the reference's torch modules
+    always are: `loss.backward()` fills `fc*.weight.grad` / `.bias.grad` (pmbrl_mlp_backward, first order; the dropout
+    masks are constants).  The forward is the same kernel with the same values.  Outside the context -- the default
+    -- the network is a constant of such a call.  Thread-local; nests, and restores the previous state on exit."""
+    prev = param_grad_enabled()
+    _param_grad_state.on = bool(enabled)
+    try:
+        yield
+    finally:
+        _param_grad_state.on = prev
 
 
 class StochasticModule(nn.Module):
@@ -310,9 +338,12 @@ class GaussianMixtureDensity(StochasticModule):
             self.z_pi.data = -(-u.log()).log()
         return self.z_pi
 
-    def from_head(self, x, my=None, Sy=None, return_samples=False, resample_noise=True, sampling_temperature=0.1):
+    def from_head(self, x, my=None, Sy=None, return_samples=False, resample_noise=True, sampling_temperature=0.1,
+                  draws=None):
         """models/densities.py:173-233 on the raw head rows x [B, (2 D + 1) n + 1]: (mean, log_std, logit_pi) with
-        mean / log_std [B, D, n], or samples [B, D]."""
+        mean / log_std [B, D, n], or samples [B, D].  draws = (z [B, D], z_grad [B, D], u [B]): this call's Gaussian
+        noise, the noise its derivative is taken with and the uniforms of an inverse-CDF component draw, as a device
+        rollout is handed them (a stepwise rollout replays the same draws; see exact_noise_grad)."""
         D, n = int(self.output_dims), self.n_components
         nD = D * n
         mean, log_std, extras = x[:, :nD], x[:, nD:2 * nD], x[:, 2 * nD:]
@@ -327,8 +358,16 @@ class GaussianMixtureDensity(StochasticModule):
             return mean, log_std, logit_pi
         z1 = self.frozen_gumbel(x.shape[0], resample_noise)
         k_soft = ((torch.log_softmax(logit_pi, -1) + z1) / sampling_temperature).softmax(-1)
-        k_idx = torch.distributions.Categorical(k_soft).sample().view(-1, 1)
-        k = torch.zeros_like(k_soft).scatter(1, k_idx, 1)[:, None, :]
+        if draws is not None:
+            k_idx = (draws[2].reshape(-1, 1) >= k_soft.detach().cumsum(-1)[:, :-1]).sum(-1, keepdim=True)
+        else:
+            k_idx = torch.distributions.Categorical(k_soft).sample().view(-1, 1)
+        k = torch.zeros_like(k_soft).scatter(1, k_idx, 1)
+        # the hard choice, differentiated through the softmax (:223-225); its value stays exactly one-hot
+        k = (k + (k_soft - k_soft.detach()))[:, None, :]
+        if draws is not None:
+            e = (log_std * k).sum(-1).exp()
+            return (mean * k).sum(-1) + draws[1] * e + ((draws[0] - draws[1]) * e).detach()
         self.z_normal.data = torch.randn(x.shape[0], D, device=x.device, dtype=x.dtype)   # (:228-231: every call)
         return (mean * k).sum(-1) + self.z_normal * (log_std * k).sum(-1).exp()
 
@@ -388,7 +427,7 @@ class BSequential(nn.Sequential):
 
     def device_forward(self, x, density, resample=True, seed=None, return_samples=False,
                        resample_noise=True, in_shift=None, in_iscale=None, out_scale=None,
-                       out_shift=None, squash=None, **kwargs):
+                       out_shift=None, squash=None, gmm_draws=None, **kwargs):
         """Evaluate the network + Gaussian head on the rows of x with pmbrl_mlp_forward
         (models/modules.py:215-232 + models/densities.py:87-121).  Returns samples [B, n_out]
         (squashed if `squash=(scale, bias)`) or (mean, log_std)."""
@@ -406,8 +445,18 @@ class BSequential(nn.Sequential):
         # dropout, exactly as the rollout sees the network (rollout.Bundle.scale_unit_rows; models/modules.py:55-61)
         from .rollout import Bundle
         unit = Bundle._unit_rows(drops, dims, x.device)
+        # param_grad(): the tensors the kernel's flat parameters are made of, as autograd sees them
+        params = None
+        if param_grad_enabled() and torch.is_grad_enabled():
+            params = [t for lin in linears for t in (lin.weight, lin.bias)]
         if unit:
             flat = Bundle.scale_unit_rows(flat.detach(), unit)
+            if params is not None:      # (the gradient of a scaled row is scaled back by autograd)
+                for l, dr in enumerate(drops):
+                    inv = dr.unit_inv_keep() if dr is not None else None
+                    if inv is not None:
+                        inv = inv.to(x.device)
+                        params[2 * l], params[2 * l + 1] = params[2 * l] * inv[:, None], params[2 * l + 1] * inv
         mixture = isinstance(density, GaussianMixtureDensity)
         plain = density is None or mixture
         if plain:
@@ -420,6 +469,9 @@ class BSequential(nn.Sequential):
             flat = torch.cat([flat[:flat.numel() - n_last], flat[-n_last:-O], flat.new_zeros(O * K),
                               flat[-O:], flat.new_zeros(O)])
             dims = dims[:-1] + [2 * O]
+            if params is not None:      # (the zero rows are constants: their gradient is sliced away by autograd)
+                params[-2:] = [torch.cat([params[-2], params[-2].new_zeros(O, K)]),
+                               torch.cat([params[-1], params[-1].new_zeros(O)])]
         keep, bits = [], []
         for lin, dr in zip(linears[:-1], drops):
             if dr is None:
@@ -432,12 +484,12 @@ class BSequential(nn.Sequential):
         if mixture:
             # the network on the device (raw head rows), the few head formulas of the mixture with torch ops on
             # those rows (stand-alone evaluation is not the hot path; rollouts and training are fused kernels)
-            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act)['mean']
+            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act, params=params)['mean']
             return density.from_head(o, out_shift, out_scale, return_samples=return_samples,
-                                     resample_noise=resample_noise)
+                                     resample_noise=resample_noise, draws=gmm_draws)
         if plain:
             return E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, out_scale,
-                                 out_shift, want=('mean',), act=act)['mean']
+                                 out_shift, want=('mean',), act=act, params=params)['mean']
         z = None
         if return_samples:
             z = density.frozen_noise(B, resample_noise, seed).to(device=x.device, dtype=torch.float32)
@@ -445,7 +497,7 @@ class BSequential(nn.Sequential):
                             squash[0] if (squash and return_samples) else None,
                             squash[1] if (squash and return_samples) else None,
                             max_log_std=float(density.max_log_std),
-                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act)
+                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act, params=params)
         if return_samples:
             return out['sample']
         return out['mean'], out['log_std']

@@ -377,6 +377,118 @@ def get_z_rnd(z, i, shape, device=None):
     return torch.randn(*shape, device=device)
 
 
+# ---------------------------------------------------------------------------
+# the stepwise rollout: a Python hook between the policy and the dynamics half of every step
+# ---------------------------------------------------------------------------
+def _cholesky64(S):
+    """Lower Cholesky factor of the (batched) d x d float64 matrices S, column by column in tensor ops: d is a state
+    width, and every op is differentiable.  A non-positive or non-finite pivot is a RuntimeError, as a failed
+    factorisation is in the reference."""
+    d = S.shape[-1]
+    idx = torch.arange(d, device=S.device)
+    cols, pivots = [], []
+    for j in range(d):
+        v = S[..., :, j]
+        for c in cols:
+            v = v - c * c[..., j:j + 1]
+        pivots.append(v[..., j])
+        cols.append(torch.where(idx >= j, v / v[..., j:j + 1].sqrt(), torch.zeros_like(v)))
+    if not bool((torch.stack(pivots) > 0).all()):
+        raise RuntimeError('moment matching: non-positive Cholesky pivot')
+    return torch.stack(cols, -1)
+
+
+def _mm_resample64(samples, z, infer_ns):
+    """utils/rollout.py:6-29 in float64, as the kernels do it (the fp32 form is 2e-5 .. 5e-3 off in the gradient):
+    mean, covariance + 1e-12 I, Cholesky, and the inferred noise variables too; the result is cast back."""
+    x = samples.double()
+    M, d = x.shape[-2], x.shape[-1]
+    m = x.mean(-2, keepdim=True)
+    deltas = x - m
+    S = deltas.transpose(-1, -2).matmul(deltas) / (M - 1) + 1e-12 * torch.eye(d, dtype=x.dtype, device=x.device)
+    L = _cholesky64(S)
+    with torch.no_grad():
+        if infer_ns:
+            # L zt = deltas^T by forward substitution
+            rows, b = [], deltas.transpose(-1, -2)
+            for i in range(d):
+                r = b[..., i, :]
+                for k in range(i):
+                    r = r - L[..., i, k:k + 1] * rows[k]
+                rows.append(r / L[..., i, i:i + 1])
+            zz = torch.stack(rows, -1)
+        else:
+            zz = z.double()
+            zz = (zz - zz.mean(-2, keepdim=True)) / zz.std(-2, keepdim=True)
+    return (m + zz.matmul(L.transpose(-1, -2))).to(samples.dtype)
+
+
+def _rollout_stepwise(states, dynamics, policy, steps, resample_model, resample_policy, resample_state_noise,
+                      resample_action_noise, mm_states, mm_rewards, infer_ns, z_mm, z_rr, mm_groups,
+                      breaking_condition, on_step, on_pol_eval):
+    """The reference's loop (utils/rollout.py:93-163) over the modules' own stand-alone forwards, differentiable in the
+    parameters (models.param_grad: pmbrl_mlp_forward / pmbrl_mlp_backward per network and step), with
+    `states, actions = on_pol_eval(i, states, actions)` between the two halves of a step.  The acting path, not a
+    throughput path: some tens of launches per step where the fused rollout has one per horizon."""
+    if not isinstance(policy, M.Policy) or not isinstance(dynamics, M.DynamicsModel):
+        raise TypeError('rollout() needs prob_mbrl_amd.models.Policy / DynamicsModel')
+    dev = policy.scale.device
+    states = states.to(device=dev, dtype=torch.float32)
+    B = states.shape[0]
+    ddens = dynamics.output_density
+    draws = None
+    if isinstance(ddens, M.GaussianMixtureDensity):
+        # the per-step draws of the mixture head, made up front as a device rollout makes them (Bundle)
+        forced = getattr(ddens, '_forced_draws', None)
+        if forced is not None:
+            draws = tuple(f.to(device=dev, dtype=torch.float32) for f in forced)
+        else:
+            draws = (torch.randn(steps, B, int(ddens.output_dims), device=dev), torch.rand(steps, B, device=dev))
+        ddens.z_normal.data = draws[0][-1]
+    trajectory, next_states = [], states
+    with M.param_grad():
+        for i in range(steps):
+            try:
+                z1 = get_z_rnd(z_mm, i, states.shape, dev) if mm_states else None
+                z2 = get_z_rnd(z_rr, i, (B, 1), dev) if mm_rewards else None
+                actions = policy(states, resample=resample_policy, return_samples=True,
+                                 resample_noise=resample_action_noise)
+                states, actions = on_pol_eval(i, states, actions)
+                kw = {}
+                if draws is not None:
+                    zt = draws[0][i]
+                    kw['gmm_draws'] = (zt, zt if getattr(ddens, 'exact_noise_grad', False) else draws[0][-1], draws[1][i])
+                next_states, rewards = dynamics((states, actions), return_samples=True, separate_outputs=True,
+                                                deltas=False, resample=resample_model,
+                                                resample_noise=resample_state_noise, **kw)
+                if mm_states:
+                    D = next_states.shape[-1]
+                    if mm_groups is not None:
+                        next_states = _mm_resample64(next_states.view(mm_groups, -1, D), z1.view(mm_groups, -1, D),
+                                                     infer_ns).view(-1, D)
+                    else:
+                        next_states = _mm_resample64(next_states, z1, infer_ns)
+                if mm_rewards:
+                    if mm_groups is not None:
+                        rewards = _mm_resample64(rewards.view(mm_groups, -1, 1), z2.view(mm_groups, -1, 1),
+                                                 infer_ns).view(-1, 1)
+                    else:
+                        rewards = _mm_resample64(rewards, z2, infer_ns)
+                trajectory.append((states, actions, rewards))
+                states = next_states
+                if callable(breaking_condition) and breaking_condition(trajectory):
+                    break
+                if callable(on_step):
+                    on_step(trajectory)
+            except RuntimeError:
+                if len(trajectory) > 5:
+                    break
+                raise
+    trajectory = [list(x) for x in zip(*trajectory)]
+    trajectory[0].append(next_states)
+    return trajectory
+
+
 def rollout(states, dynamics, policy, steps, resample_model=False, resample_policy=False,
             resample_state_noise=True, resample_action_noise=True, mm_states=False,
             mm_rewards=False, infer_noise_variables=False, z_mm=None, z_rr=None, mm_groups=None,
@@ -384,9 +496,21 @@ def rollout(states, dynamics, policy, steps, resample_model=False, resample_poli
     """Trajectory distribution (s_0, a_0, r_0, s_1, ...) of `policy` on `dynamics` from the
     given particles: returns [states (steps+1 x [B,D]), actions (steps x [B,U]),
     rewards (steps x [B,1])], connected to policy.parameters() (and to `states`) for autograd.
-    Same arguments as the reference (utils/rollout.py:62-79)."""
+    Same arguments as the reference (utils/rollout.py:62-79).  on_pol_eval: `states, actions = hook(i, states,
+    actions)` between the policy and the dynamics half of every step; such a rollout runs step by step
+    (_rollout_stepwise) instead of as one fused call."""
     if callable(on_pol_eval):
-        raise NotImplementedError('on_pol_eval needs a per-step Python hook; not offered')
+        sharded = [k for k in ('B_global', 'mm_span', 'agree_group') if kwargs.get(k) is not None]
+        if sharded:
+            raise NotImplementedError('on_pol_eval together with rows sharded over ranks (%s) is not offered: the '
+                                      'stepwise rollout is single-process' % ', '.join(sharded))
+        if kwargs.get('action_grad_norms_out') is not None:
+            raise NotImplementedError('on_pol_eval together with prioritized replay (the per-step action gradient '
+                                      'norms are an output of the fused adjoint sweep) is not offered')
+        return _rollout_stepwise(states, dynamics, policy, int(steps), resample_model, resample_policy,
+                                 resample_state_noise, resample_action_noise, mm_states, mm_rewards,
+                                 bool(infer_noise_variables), z_mm, z_rr, mm_groups, breaking_condition, on_step,
+                                 on_pol_eval)
     B = states.shape[0]
     B_global, row_offset = kwargs.pop('B_global', None), kwargs.pop('row_offset', 0)
     agn_out = kwargs.pop('action_grad_norms_out', None)

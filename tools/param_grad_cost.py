@@ -1,0 +1,96 @@
+#!/usr/bin/env python
+"""What the parameter gradient of a stand-alone network call and a hooked rollout cost on the device.
+
+  mlp      pmbrl_mlp_backward (input + parameter gradient) against pmbrl_mlp_grad_input (input gradient only) at
+           2 500 rows of a [4, 200, 200, 2] network, all three upstream gradients
+  rollout  rollout(..., on_pol_eval=identity) + loss.backward() at the C2 shape (2 500 rows, H = 40, 2 x 200 networks,
+           cart-pole widths, no moment matching): the stepwise path, beside the fused rollout + backward of the same
+           modules through the same autograd surface
+
+Blocks timed from a device synchronise to a device synchronise; prints median, min and max milliseconds per call as one
+JSON line.
+
+    python tools/param_grad_cost.py [--blocks 20] [--iters 10] [--warmup 3]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import prob_mbrl_amd as pm  # noqa: E402
+from prob_mbrl_amd import engine as E  # noqa: E402
+
+
+def timed(f, blocks, iters, warmup):
+    for _ in range(warmup):
+        f()
+    out = []
+    for _ in range(blocks):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(iters):
+            f()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) * 1e3 / iters)
+    t = np.asarray(out)
+    return dict(ms_median=float(np.median(t)), ms_min=float(t.min()), ms_max=float(t.max()))
+
+
+def mlp_case(dev, B=2500, dims=(4, 200, 200, 2)):
+    g = torch.Generator().manual_seed(0)
+    nl, n_out = len(dims) - 1, dims[-1] // 2
+    flat = torch.cat([t.reshape(-1) for i in range(nl) for t in
+                      (torch.randn(dims[i + 1], dims[i], generator=g) / np.sqrt(dims[i]), 0.1 * torch.randn(dims[i + 1], generator=g))])
+    bits = [E.pack_mask((torch.rand(B, dims[i + 1], generator=g) < 0.9).float().to(dev)) for i in range(nl - 1)]
+    call = E._MlpCall(torch.randn(B, dims[0], generator=g).to(dev), flat.to(dev), list(dims), [0.9] * (nl - 1), bits,
+                      torch.randn(B, n_out, generator=g).to(dev), None, None, None, None, torch.ones(n_out), torch.zeros(n_out),
+                      E.LOG_MAX_STD)
+    ups = [torch.randn(B, n_out, generator=g).to(dev) for _ in range(3)]
+    return (lambda: call.backward(*ups)), (lambda: call.grad_input(*ups))
+
+
+def rollout_case(dev, B=2500, H=40, D=4, U=1, hidden=(200, 200)):
+    torch.manual_seed(0)
+    dyn = pm.models.DynamicsModel(
+        pm.models.mlp(D + U, 2 * D, list(hidden), dropout_layers=[pm.models.CDropout(0.1 * np.ones(h)) for h in hidden]),
+        reward_func=pm.rewards.CartpoleReward(pole_length=torch.tensor(0.5)),
+        output_density=pm.models.DiagGaussianDensity(D)).float()
+    from functools import partial
+    pol = pm.models.Policy(pm.models.mlp(D, 2 * U, list(hidden), dropout_layers=[pm.models.BDropout(0.1) for _ in hidden],
+                                         output_nonlin=partial(pm.models.DiagGaussianDensity, U)), 10.0).float()
+    dyn.Sy.data = torch.full((1, D), 0.05)       # small steps: the trajectory stays bounded over the horizon
+    dyn, pol = dyn.to(dev).eval(), pol.to(dev)
+    x0 = 0.1 * torch.randn(B, D, device=dev)
+
+    def run(**kw):
+        pol.zero_grad()
+        _, _, rewards = pm.utils.rollout(x0, dyn, pol, H, resample_state_noise=False, resample_action_noise=False, **kw)
+        assert len(rewards) == H
+        (-torch.stack(rewards).mean()).backward()
+    return (lambda: run(on_pol_eval=lambda i, s, a: (s, a))), run
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--blocks', type=int, default=20)
+    ap.add_argument('--iters', type=int, default=10)
+    ap.add_argument('--warmup', type=int, default=3)
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit('needs a HIP device')
+    dev = torch.device('cuda:0')
+    bwd, gin = mlp_case(dev)
+    hooked, fused = rollout_case(dev)
+    out = dict(blocks=a.blocks,
+               mlp_backward=timed(bwd, a.blocks, a.iters, a.warmup), mlp_grad_input=timed(gin, a.blocks, a.iters, a.warmup),
+               rollout_hooked=timed(hooked, a.blocks, 1, 1), rollout_fused_autograd=timed(fused, a.blocks, a.iters, a.warmup))
+    print(json.dumps(out))
+
+
+if __name__ == '__main__':
+    main()
