@@ -25,6 +25,7 @@ PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
 DROP_BY_TEMPERATURE, DROP_BERNOULLI = 0, 1      # pmbrl_bnn_config.drop_kind
 MLP_BWD_MAX_BLOCKS = 256                        # PMBRL_MLP_BWD_MAX_BLOCKS: workgroups (gradient slabs) of pmbrl_mlp_backward
+MLP_BWD_SLAB_BYTES = 64 << 20                   # PMBRL_MLP_BWD_SLAB_BYTES: ... fewer where that many slabs would exceed this
 # pmbrl_plan_info indices (PMBRL_INFO_* of include/pmbrl.h)
 (INFO_ROWS_PER_WG, INFO_N_WG, INFO_ROW_TILES, INFO_LDS_BYTES, INFO_N_POL_PARAMS, INFO_N_DYN_PARAMS, INFO_DW_SPLITS,
  INFO_MM_MODE, INFO_LD, INFO_DW_BLOCKS, INFO_FAST, INFO_STAGES, INFO_MM_GRID, INFO_PRECISION, INFO_DW_PIPE, INFO_MM_PARTS,

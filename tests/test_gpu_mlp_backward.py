@@ -6,9 +6,11 @@ parameter tensor on its own.
 
 ReLU's derivative jumps at 0, and a kept unit whose pre-activation is closer to 0 than fp32 resolves may take either
 side there (common.kink_margin): the seeds of the ReLU cases are chosen so that the fp64 run's smallest kept
-|pre-activation| exceeds 1e-4 (test_relu_cases_stay_clear_of_the_kink, no device needed).  The many-row case has
-1.6 million hidden units, too many for any seed to keep them all that far from 0, and runs Tanh: what it is there for
--- the tile stride of a workgroup and the slab reduction -- does not depend on the activation."""
+|pre-activation| exceeds 1e-4 (test_relu_cases_stay_clear_of_the_kink, no device needed).  The many-row cases have
+1.6 and 1.9 million hidden units, too many for any seed to keep them all that far from 0, and run Tanh: what they are
+there for -- the tile stride of a workgroup and the slab reduction -- does not depend on the activation.
+
+pmbrl_mlp_forward on the same cases: the three outputs against the same fp64 evaluation (test_forward_matches_fp64)."""
 import functools
 import math
 
@@ -24,12 +26,23 @@ ACT = {RELU: torch.relu, TANH: torch.tanh, SILU: torch.nn.functional.silu}
 ALL = ('sample', 'mean', 'log_std')
 
 
-def _max_blocks():
+BLOCK_CAP, SLAB_CAP, PLAIN = 'block_cap', 'slab_cap', 'plain'
+
+
+def _rows(B, dims):
+    """B of a case: a number, or five rows past the last tile that still gets a workgroup (gradient slab) of its own."""
     from prob_mbrl_amd import _lib
-    return _lib.MLP_BWD_MAX_BLOCKS
+    if B == BLOCK_CAP:
+        return 16 * _lib.MLP_BWD_MAX_BLOCKS + 5
+    if B == SLAB_CAP:      # a network whose MAX_BLOCKS slabs would exceed the slab limit gets as many as fit
+        n_params = sum(dims[i + 1] * dims[i] + dims[i + 1] for i in range(len(dims) - 1))
+        blocks = _lib.MLP_BWD_SLAB_BYTES // (4 * n_params)
+        assert 1 < blocks < _lib.MLP_BWD_MAX_BLOCKS
+        return 16 * blocks + 5
+    return B
 
 
-# name: (seed, B, dims, act)
+# name: (seed, B, dims, act[, PLAIN: no masks, no input / output scaling, no squashing, no noise -- every optional pointer null])
 CASES = {
     'ragged_relu': (7, 45, [6, 40, 56, 6], RELU),
     'ragged_tanh': (7, 45, [6, 40, 56, 6], TANH),
@@ -39,15 +52,22 @@ CASES = {
     'one_hidden': (13, 21, [4, 24, 2], RELU),
     'three_hidden_relu': (14, 37, [7, 32, 48, 16, 4], RELU),
     'three_hidden_tanh': (14, 37, [7, 32, 48, 16, 4], TANH),
-    'many_rows': (15, None, [5, 200, 200, 2], TANH),      # B = 16 * PMBRL_MLP_BWD_MAX_BLOCKS + 5
+    'many_rows': (15, BLOCK_CAP, [5, 200, 200, 2], TANH),      # B = 16 * PMBRL_MLP_BWD_MAX_BLOCKS + 5
+    # the GEMM branches the fit kernels share (tests/fit_envelope_cases.py), in these calls' instances
+    'kb8': (16, 45, [6, 128, 120, 6], TANH),             # gemm_tiles_group_full: 8 k-tiles forward (128) and backward (120)
+    'w272': (17, 21, [6, 272, 272, 4], RELU),            # 17 output tiles: a wave's second tile group
+    'head64': (18, 45, [6, 40, 56, 64], SILU),           # gemm_narrow's tile-split head
+    'in20': (20, 45, [20, 40, 56, 6], RELU),             # two input tiles
+    'plain': (20, 45, [6, 40, 56, 6], RELU, PLAIN),      # the ragged shape, every unit kept
+    'slab_cap': (21, SLAB_CAP, [8, 264, 264, 4], TANH),  # about 3 650 rows on 228 workgroups: the block cap from the slab limit
 }
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(name):
     """The fp32 inputs of a case (CPU tensors), drawn once."""
-    seed, B, dims, act = CASES[name]
-    B = 16 * _max_blocks() + 5 if B is None else B
+    seed, B, dims, act = CASES[name][:4]
+    B = _rows(B, dims)
     g = torch.Generator().manual_seed(seed)
     nl, n_out = len(dims) - 1, dims[-1] // 2
     c = dict(B=B, dims=dims, act=act, nl=nl, n_out=n_out)
@@ -61,32 +81,42 @@ def inputs(name):
     c['osc'], c['osh'] = 0.5 + torch.rand(n_out, generator=g), torch.randn(n_out, generator=g)
     c['sqs'], c['sqb'] = 1.0 + torch.rand(n_out, generator=g), 0.1 * torch.randn(n_out, generator=g)
     c['up'] = dict(zip(ALL, (torch.randn(B, n_out, generator=g) for _ in range(3))))
+    if PLAIN in CASES[name][4:]:
+        c['masks'], c['keep'] = [None] * (nl - 1), [1.0] * (nl - 1)
+        c.update(dict.fromkeys(('z', 'shift', 'iscale', 'osc', 'osh', 'sqs', 'sqb')))
     return c
 
 
 @functools.lru_cache(maxsize=None)
 def reference(name, up=ALL, use_z=True, dtype=torch.float64):
-    """(grad_x, [grad W0, grad b0, ...], smallest kept |pre-activation|) by torch autograd in `dtype` on the CPU."""
+    """(grad_x, [grad W0, grad b0, ...], smallest kept |pre-activation|, the three outputs) by torch autograd in `dtype`
+    on the CPU.  An input that is None is a null pointer of the call: that step of the formula is left out."""
     c = inputs(name)
     d = lambda t: t.to(dtype)  # noqa: E731
     x = d(c['x']).requires_grad_(True)
     params = [d(t).requires_grad_(True) for pair in zip(c['Ws'], c['bs']) for t in pair]
-    h = (x - d(c['shift'])) * d(c['iscale'])
+    h = (x - d(c['shift'])) * d(c['iscale']) if c['shift'] is not None else x
     margin = math.inf
     for i in range(c['nl'] - 1):
         v = h @ params[2 * i].t() + params[2 * i + 1]
-        margin = min(margin, float(v.detach().abs()[c['masks'][i] > 0].min()))
-        h = ACT[c['act']](v) * d(c['masks'][i]) / c['keep'][i]
+        h = ACT[c['act']](v)
+        if c['masks'][i] is not None:
+            margin = min(margin, float(v.detach().abs()[c['masks'][i] > 0].min()))
+            h = h * d(c['masks'][i]) / c['keep'][i]
+        else:
+            margin = min(margin, float(v.detach().abs().min()))
     o = h @ params[-2].t() + params[-1]
     n = c['n_out']
     mu, ls = o[:, :n], o[:, n:]
-    ls = -torch.nn.functional.softplus(-ls + MLS) + MLS + d(c['osc']).log()
-    mu = mu * d(c['osc']) + d(c['osh'])
-    s = mu + d(c['z']) * ls.exp() if use_z else mu
-    smp = d(c['sqs']) * torch.tanh(s) + d(c['sqb'])
+    ls = -torch.nn.functional.softplus(-ls + MLS) + MLS
+    if c['osc'] is not None:
+        ls = ls + d(c['osc']).log()
+        mu = mu * d(c['osc']) + d(c['osh'])
+    s = mu + d(c['z']) * ls.exp() if use_z and c['z'] is not None else mu
+    smp = d(c['sqs']) * torch.tanh(s) + d(c['sqb']) if c['sqs'] is not None else s
     outs = dict(sample=smp, mean=mu, log_std=ls)
     sum((outs[k] * d(c['up'][k])).sum() for k in up).backward()
-    return x.grad, [p.grad for p in params], margin
+    return x.grad, [p.grad for p in params], margin, {k: v.detach() for k, v in outs.items()}
 
 
 def device_call(name, use_z=True):
@@ -94,8 +124,9 @@ def device_call(name, use_z=True):
     c = inputs(name)
     dev = torch.device('cuda:0')
     flat = torch.cat([t.reshape(-1) for pair in zip(c['Ws'], c['bs']) for t in pair]).to(dev)
-    bits = [E.pack_mask(m.to(dev)) for m in c['masks']]
-    return E._MlpCall(c['x'].to(dev), flat, c['dims'], c['keep'], bits, c['z'].to(dev) if use_z else None, c['shift'],
+    bits = [E.pack_mask(m.to(dev)) if m is not None else None for m in c['masks']]
+    z = c['z'].to(dev) if use_z and c['z'] is not None else None
+    return E._MlpCall(c['x'].to(dev), flat, c['dims'], c['keep'], bits, z, c['shift'],
                       c['iscale'], c['osc'], c['osh'], c['sqs'], c['sqb'], MLS, act=c['act'])
 
 
@@ -115,7 +146,7 @@ def split(name, flat):
 
 
 def check(name, gx, gp, ref, what=''):
-    rx, rp, _ = ref
+    rx, rp = ref[:2]
     errs = []
     if gx is not None:
         errs += grad_bars.errors([gx.cpu().numpy()], [rx.numpy()], ['grad_x'])
@@ -125,8 +156,8 @@ def check(name, gx, gp, ref, what=''):
 
 
 def test_relu_cases_stay_clear_of_the_kink():
-    for name, (_, _, _, act) in CASES.items():
-        if act == RELU:
+    for name, case in CASES.items():
+        if case[3] == RELU:
             assert reference(name)[2] > 1e-4, name
 
 
@@ -139,6 +170,20 @@ def test_backward_matches_fp64_autograd(name):
     call = device_call(name)
     gx, gp = call.backward(*upstream(name, ALL))
     check(name, gx, gp, reference(name))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', list(CASES))
+def test_forward_matches_fp64(name):
+    """pm_mlp_fwd_kernel (a kernel of its own, not the backward's recomputed forward) on the same cases: all three outputs
+    at the bar of tests/test_gpu_kernels.py::test_mlp_forward_matches_torch."""
+    out = device_call(name).forward(ALL)
+    want = reference(name)[3]
+    for k in ALL:
+        got, ref = out[k].cpu().numpy().astype(np.float64), want[k].numpy()
+        worst = float((np.abs(got - ref) / (2e-6 + 2e-5 * np.abs(ref))).max())
+        print('%s %s: max |got - want| / (2e-6 + 2e-5 |want|) = %.3f' % (name, k, worst))
+        assert np.allclose(got, ref, rtol=2e-5, atol=2e-6), (name, k)
 
 
 @pytest.mark.gpu
@@ -176,7 +221,7 @@ def test_no_upstream_gradient_is_refused():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize('name', ['ragged_tanh', 'many_rows'])
+@pytest.mark.parametrize('name', ['ragged_tanh', 'many_rows', 'slab_cap'])
 def test_two_calls_give_the_same_bits(name):
     call = device_call(name)
     ups = upstream(name, ALL)
