@@ -890,244 +890,9 @@ static int plan_angles(pmbrl_plan* p) {
   return 0;
 }
 
-// stage 5: the policy's dW GEMM -- wave blocks of the block kernels, tile units of the wide layers, chunks
-static int plan_dw(pmbrl_plan* p) {
+// stage 6: the workspace carve-up
+static int plan_workspace(pmbrl_plan* p) {
   const pmbrl_config& c = p->cfg;
-  std::vector<DwBlock> blocks;
-  // split-operand form of the dW GEMM (pmbrl_dw_kernels.h, pm_dw_kernel_s): where the fp32 form is bound by the matrix
-  // core -- 32- / 64-row workgroups and the general family's wide networks; the 16-row sweeps' dW is HBM-bound
-  p->dw_split = p->prec != 0 && (p->RT >= 2 || !p->fast);
-  // wide layers of the split form go to the LDS-staged tile kernel (pmbrl_dw_kernels.h, pm_dw_wide_kernel)
-  bool wide[PM_MAXL] = {false};
-  std::vector<DwUnit> units;
-  // (layers of at least 128 x 128 on the split-precision plans: also the 200 x 200 layer of the cart-pole shapes,
-  //  whose block-kernel GEMM re-read its stash 1.5 x -- C2 0.116 -> 0.102 ms, C4 0.50 -> 0.38 ms; the exact-fp32
-  //  plans keep the fp32 block kernel for every layer)
-  p->dw_layer13 = -1;
-  if (p->prec != 0 && !p->sw.dw_no_wide)
-    for (int l = 0; l < p->pol.nl; ++l)
-      if (p->pol.nt[l + 1] * 16 >= 128 && p->pol.nt[l] * 16 >= 128) {
-        wide[l] = true;
-        if (p->dw_layer13 < 0 && p->pol.nt[l + 1] <= PM_DWL_NT && p->pol.nt[l] <= PM_DWL_NT) {
-          // a whole layer of up to 13 x 13 tiles per workgroup
-          p->dw_layer13 = l;
-          continue;
-        }
-        for (int m0 = 0; m0 < p->pol.nt[l + 1] * 16; m0 += PM_DWW_TM)
-          for (int n0 = 0; n0 < p->pol.nt[l] * 16; n0 += PM_DWW_TN) units.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
-      }
-  // Round 6: the wide sweeps (64-row workgroups, in-place 512-wide layers: pmbrl_wide.h) write the stashes of the 512 x 512
-  // layers PRE-SPLIT, in the layout pm_dw_wide_pre_kernel streams into LDS without touching a register (pmbrl_dw_kernels.h).
-  // Every wide layer 512 x 512 exactly (32 tiles: the stash block's tile count).  (Such a plan has dw_split: the
-  // pre-split kernels walk chunk pairs.)
-  if (!units.empty() && p->inplace == 2 && p->RT == 4) {
-    bool all = true;
-    for (const DwUnit& u : units) all = all && p->pol.nt[u.layer] == 32 && p->pol.nt[u.layer + 1] == 32 &&
-                                        p->pol.dim[u.layer] == 512 && p->pol.dim[u.layer + 1] == 512;
-    // ... and every OTHER layer narrow on one side, 512 wide on the other (first layer: <= 32 inputs; head: <= 32 outputs):
-    // pm_dw_narrow_pre_kernel -- so that EVERY 512-wide stash is pre-split and the sweeps carry one form of stash store
-    for (int l = 0; l < p->pol.nl && all; ++l) {
-      bool is = false;
-      for (const DwUnit& u : units) is = is || u.layer == l;
-      p->dw_narrow[l] = 0;
-      if (is) continue;
-      if (p->pol.nt[l + 1] == 32 && p->pol.dim[l + 1] == 512 && p->pol.nt[l] <= 2) p->dw_narrow[l] = 1;
-      else if (p->pol.nt[l] == 32 && p->pol.dim[l] == 512 && p->pol.nt[l + 1] <= 2) p->dw_narrow[l] = 2;
-      else all = false;
-    }
-    if (all) {
-      std::vector<DwUnit> pre;
-      for (int l = 0; l < p->pol.nl; ++l) {
-        if (p->dw_narrow[l]) { wide[l] = true; continue; }      // (not the block kernels': skipped by build_dw_blocks)
-        p->dw_pre_mask |= 1u << l;
-        for (int m0 = 0; m0 < 512; m0 += PM_DWP_TM)
-          for (int n0 = 0; n0 < 512; n0 += PM_DWP_TN) pre.push_back(DwUnit{(int16_t)l, (int16_t)m0, (int16_t)n0, 0});
-      }
-      units = pre;
-    } else {
-      for (int l = 0; l < PM_MAXL; ++l) p->dw_narrow[l] = 0;
-    }
-  }
-  p->n_dw_units = (int)units.size();
-  if (p->n_dw_units) {
-    HIPCHK(hipMalloc(&p->dw_units_d, units.size() * sizeof(DwUnit)));
-    HIPCHK(hipMemcpy(p->dw_units_d, units.data(), units.size() * sizeof(DwUnit), hipMemcpyHostToDevice));
-  }
-  if (int rc = pm_dw_set_attr(p)) return rc;
-  p->n_dw_blocks = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first, p->dw_split ? PM_DW_TN_S : PM_DW_TN, wide);
-  for (int l = 0; l < PM_MAXL; ++l) p->dw_skip[l] = wide[l];
-  p->dw_n_chunks = c.H * p->nwg * p->RT;
-  int nsplit = std::min(256, p->dw_n_chunks);   // one 8-wave workgroup per CU
-  p->dw_chunks_per_split = (p->dw_n_chunks + nsplit - 1) / nsplit;
-  if (p->dw_split) p->dw_chunks_per_split = (p->dw_chunks_per_split + 1) & ~1;   // whole chunk pairs
-  p->dw_nsplit = (p->dw_n_chunks + p->dw_chunks_per_split - 1) / p->dw_chunks_per_split;
-  HIPCHK(hipMalloc(&p->dw_blocks_d, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock)));
-  if (!blocks.empty())
-    HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
-  // what the GEMM's argument record holds of the plan: a call copies it and adds its workspace pointers (dw_call_args)
-  DwArgs& W = p->dw_args;
-  memset(&W, 0, sizeof(W));
-  W.nl = p->pol.nl;
-  W.nsplit = p->dw_nsplit;
-  W.n_chunks = p->dw_n_chunks;
-  W.chunks_per_split = p->dw_chunks_per_split;
-  W.RT = p->RT;
-  W.Rw = 16 * p->RT;
-  W.n_params = (int)p->pol.n_params;
-  W.part_stride = (W.n_params + 3) / 4 * 4;
-  for (int i = 0; i <= p->pol.nl; ++i) { W.dim[i] = p->pol.dim[i]; W.nt[i] = p->pol.nt[i]; }
-  for (int l = 0; l < p->pol.nl; ++l) { W.w_off[l] = (int)p->pol.w_off[l]; W.b_off[l] = (int)p->pol.b_off[l]; }
-  W.blocks = p->dw_blocks_d;
-  for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first[w];
-  W.chunks_per_step = p->nwg * p->RT;
-  W.split_prec = p->dw_split;
-  return 0;
-}
-
-// stage 6: dW GEMM behind the adjoint sweep.  The sweep is latency-bound and holds nwg CUs completely (its
-// workgroups take a CU's whole register file); with fewer workgroups than CUs the rest of the chip idles
-// for its duration, and the dW GEMM -- 12-17 % of an iteration -- used to start when the sweep had
-// finished.  It needs only the deltas of the steps already swept: the sweep becomes pipe_K launches
-// over descending step ranges (the state gradient is carried through HBM, as in the per-step launch
-// modes) and the GEMM of range k runs next to the sweep of range k+1, on a second stream, in a grid that
-// fits the idle CUs (workgroups go round-robin to the 8 XCDs, so per XCD: CUs/8 - ceil(nwg/8) are free)
-// with workgroups that cannot share a CU with the sweep's.  Only the last, short range is exposed.
-// Correctness never depends on the overlap: every dependency is a stream event.
-static int plan_dw_pipe(pmbrl_plan* p, int cus) {
-  const pmbrl_config& c = p->cfg;
-  const PlanSwitches& sw = p->sw;
-  p->pipe_K = 1;
-  const bool no_pipe_pre = p->dw_pre_mask != 0;      // (the pre-split GEMMs run once, behind the whole sweep)
-  const int n_free = cus >= 64 && cus % 8 == 0 ? 8 * (cus / 8 - (p->nwg + 7) / 8) : 0;
-  const bool single = sweep_form(p) == SweepForm::Whole && p->mm_parts <= 1;   // (no second kernel next to flag barriers)
-  // Worth it where a range of the sweep is long against a launch boundary (tail of the last step, launch
-  // gap, the next launch's prologue: 15 us at 16 rows per workgroup, 40 us at 64) -- measured: the double
-  // cart-pole shape (64-row workgroups, 30 us per step) gains 7 % of an iteration, the cart-pole shapes
-  // (6 / 13 us per step) lose 1-5 %.  Proxy for the step time: rows per workgroup x weights of both nets.
-  const bool long_steps = (long long)p->RT * (long long)(p->pol.n_params + p->dyn.n_params) >= 256 * 1024 && c.H >= 16;
-  if (!single || no_pipe_pre || n_free < cus / 8 || c.H < 2 || sw.dw_pipe_off || !(long_steps || sw.dw_pipe_ranges))
-    return 0;
-  std::vector<int> cnt;
-  if (sw.dw_pipe_ranges) {     // PMBRL_DW_PIPE=n0,n1,...: steps per range, highest steps first (tests, tuning)
-    cnt = sw.dw_pipe;
-    int sum = 0;
-    for (int v : cnt) sum += v;
-    if (sum != c.H || (int)cnt.size() > PM_PIPE_MAX) cnt.clear();
-  }
-  if (cnt.empty() && long_steps) {
-    // 40 / 30 / 20 / 10 % of the horizon: the exposed tail is the GEMM of the last tenth
-    const int a3 = std::max(2, c.H / 10), a2 = a3 + std::max(2, c.H / 5), a1 = a2 + std::max(2, (3 * c.H) / 10);
-    cnt = {c.H - a1, a1 - a2, a2 - a3, a3};
-  }
-  // lower step bound of every range (the last one ends at step 0; ranges emptied by the adjustment are dropped)
-  int K = 0, lo = c.H;
-  for (size_t k = 0; k < cnt.size() && lo > 0; ++k) {
-    lo = k + 1 == cnt.size() ? 0 : std::max(0, lo - cnt[k]);
-    // split-operand GEMM: a K = 32 chunk pair must not straddle two launches
-    if (p->dw_split && ((p->nwg * p->RT) & 1) && (lo & 1)) lo -= 1;
-    if (K > 0 && lo >= p->pipe_lo[K - 1]) continue;
-    p->pipe_lo[K++] = lo;
-  }
-  if (K >= 2 && p->pipe_lo[K - 1] == 0) {
-    p->pipe_K = K;
-    p->pipe_grid = n_free;                     // workgroups (= partial rows) of a GEMM launch next to the sweep
-    p->pipe_rows = std::max(n_free, cus);      // ... of the last launch, which has the chip to itself
-    HIPCHK(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
-    for (int k = 0; k < p->pipe_K; ++k) HIPCHK(hipEventCreateWithFlags(&p->pipe_ev[k], hipEventDisableTiming));
-  }
-  return 0;
-}
-
-// The second hidden layer's dW GEMM BESIDE the adjoint sweep (the streamed form).  Cutting the sweep into ranges (above)
-// costs ~15 us a cut at the cart-pole shapes, more than it hides.  Behind a register-resident adjoint sweep the layer's
-// kernel REBUILDS its delta operand from the forward sweep's stashes and the policy head's gradient -- 2 U floats a row,
-// the only input the adjoint sweep produces.  So the sweep stays ONE launch and publishes that gradient step by step
-// (tagged granules, RegArgs::pub); st_wgs consumer workgroups (pm_dw_layer_st_kernel), one per CU the sweep leaves idle,
-// launched on the second stream next to it, follow it down the steps [st_cut, H); the steps below the cut go to the
-// layer's kernel behind the sweep, over the whole chip, which adds to the consumers' partial rows.  The sweep waits for
-// nothing; the consumers wait (bounded) for sweep workgroups only and are fewer than the CUs the sweep leaves: serialised
-// in submission order the form is merely not faster.
-//   PMBRL_DW_STREAM=off | <steps streamed>[,<consumer workgroups>] (the second: any plan that meets the first four
-//   conditions -- tests, tuning)
-// ... and the policy HEAD's dW / db with it.  The head's only adjoint-side input is the head gradient -- what the consumers
-// receive anyway -- and its other operand, actT of the head, is the forward sweep's: the consumers form the head's gradient
-// beside the sweep too (pm_dw_layer_body, PmDwHead) and half of the block kernel's bytes leave the critical path.  Where
-// every step is streamed (no launch behind the sweep shares the consumers' rows) and the form was not forced through
-// PMBRL_DW_STREAM=<steps>, which keeps its meaning: the head in the block kernel.  PMBRL_DW_HEAD=on | off forces it where
-// every step is streamed / never.  The block kernel of such a call walks a table without the head, built here.
-static int plan_dw_head(pmbrl_plan* p) {
-  const PlanSwitches& sw = p->sw;
-  const DwArgs& W = p->dw_args;
-  const int l = p->dw_layer13, h = l + 1;
-  p->st_head = 0;
-  if (!p->st_on || p->st_cut != 0 || sw.dw_head == 0 || (sw.dw_head < 0 && sw.dw_stream_set)) return 0;
-  // the head is the last layer, one tile of outputs, a block-kernel layer of the fp32 form; the columns W_l, b_l, W_h, b_h are
-  // one contiguous range of the flat vector (what the reduction reads of the consumers' rows only)
-  if (h != p->pol.nl - 1 || p->pol.nt[h + 1] != 1 || p->pol.dim[h + 1] > 16 || p->dw_skip[h] || p->dw_split) return 0;
-  if (W.b_off[l] != W.w_off[l] + W.dim[l + 1] * W.dim[l] || W.w_off[h] != W.b_off[l] + W.dim[l + 1] ||
-      W.b_off[h] != W.w_off[h] + W.dim[h + 1] * W.dim[h])
-    return 0;
-  bool skip[PM_MAXL];
-  for (int i = 0; i < PM_MAXL; ++i) skip[i] = p->dw_skip[i] || i == h;
-  std::vector<DwBlock> blocks;
-  p->n_dw_blocks_nh = build_dw_blocks(p->pol.nl, p->pol.nt, blocks, p->dw_wave_first_nh, PM_DW_TN, skip, PM_DW_NW);
-  // (pm_dw_kernel_nh, the deeper ring: every block at most 2 x 1 tiles; else the block kernel as it is, on this table)
-  p->dw_nh_ring = 1;
-  for (const DwBlock& b : blocks) p->dw_nh_ring = p->dw_nh_ring && b.n_ot <= 2 && b.n_it <= 1;
-  // (a table that cannot be had is no reason to fail the plan: the head stays in the block kernel)
-  if (hipMalloc(&p->dw_blocks_nh_d, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock)) != hipSuccess ||
-      (!blocks.empty() &&
-       hipMemcpy(p->dw_blocks_nh_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice) != hipSuccess)) {
-    (void)hipGetLastError();
-    return 0;
-  }
-  p->st_head = 1;
-  return 0;
-}
-static int plan_dw_stream(pmbrl_plan* p, int cus) {
-  const pmbrl_config& c = p->cfg;
-  const PlanSwitches& sw = p->sw;
-  p->st_on = 0;
-  const int n_free = cus >= 64 && cus % 8 == 0 ? 8 * (cus / 8 - (p->nwg + 7) / 8) : 0;
-  // the plain register-resident instance serves the adjoint in one launch, and its dW GEMM rebuilds the delta
-  const bool fam = p->reg && !p->reg_mm && sw.reg_bwd && p->dw_layer13 == PM_REG_DW_LAYER && p->RT == 1;
-  const bool single = sweep_form(p) == SweepForm::Whole && p->mm_parts <= 1 && p->pipe_K <= 1;
-  if (!fam || !single || n_free < 1 || n_free < cus / 8 || sw.dw_stream_off || c.H >= 4095) return 0;
-  // Large enough to hide something: every consumer gets at least a chunk of every sweep step (fewer, and it runs single
-  // chunks on half-empty K = 32 MFMAs or idles), and the layer's GEMM over the whole chip -- ~3.5 us per chunk pair and
-  // workgroup -- is worth more than what the form adds behind the sweep (the consumers' write-out and a launch, ~12 us):
-  // H nwg / (2 cus) pairs x 3.5 us >= 2 x 12 us
-  const bool large = p->nwg >= n_free && (long long)c.H * p->nwg >= 14ll * cus;
-  if (!large && !sw.dw_stream_set) return 0;
-  // The cut.  A consumer's share of a sweep step is ceil(nwg / n_free) chunks, taken in pairs.  With at most one pair a
-  // step -- nwg <= 2 n_free -- the consumers wait for the sweep at every step (2 us of work against a 4 us step at the
-  // cart-pole shape) and finish a write-out behind it, hidden behind the block kernel: EVERY step is streamed and no
-  // launch of the layer's kernel follows.  (Measured, DESIGN_LOG.md "dW beside the sweep": 40 of 40 steps 410 us an
-  // iteration, 38: 426, 35: 428, 30: 432, 20: 442, off: 430 -- a launch behind the sweep costs ~25 us before its first
-  // chunk; 64 consumers with two pairs a step fall behind: 494 us.)  More than a pair: the consumers do the share they can
-  // keep up with, the highest steps, and the launch behind the sweep takes the rest
-  int steps = p->nwg <= 2 * n_free ? c.H : (int)((long long)c.H * 2 * n_free / p->nwg);
-  int wgs = n_free;
-  if (sw.dw_stream_set) {
-    steps = sw.dw_stream_steps;
-    if (sw.dw_stream_wgs > 0) wgs = std::min(wgs, sw.dw_stream_wgs);
-  }
-  steps = std::max(0, std::min(c.H, steps));
-  p->st_on = 1;
-  p->st_cut = c.H - steps;
-  p->st_wgs = wgs;
-  if (!p->pipe_stream) HIPCHK(hipStreamCreateWithFlags(&p->pipe_stream, hipStreamNonBlocking));
-  for (int k = 0; k < 2; ++k)
-    if (!p->pipe_ev[k]) HIPCHK(hipEventCreateWithFlags(&p->pipe_ev[k], hipEventDisableTiming));
-  return plan_dw_head(p);
-}
-
-// stage 7: the register-resident family, and the workspace carve-up
-static int plan_workspace(pmbrl_plan* p, int cus) {
-  const pmbrl_config& c = p->cfg;
-  p->reg = pm_reg_plan_ok(p) ? 1 : 0;
-  p->reg_mm = pm_reg_mm_width(p);
-  if (int rc = plan_dw_stream(p, cus)) return rc;
   size_t off = 0;
   auto take = [&](size_t bytes) {
     const size_t o = off;
@@ -1185,17 +950,15 @@ static int plan_workspace(pmbrl_plan* p, int cus) {
   p->off_reg_pack = take(p->reg ? pm_reg_pack_bytes() : 0);
   for (int n = 0; n < 2; ++n)
     for (int l = 0; l < 2; ++l) p->off_reg_ab[n][l] = take(p->reg ? (size_t)c.H * p->nwg * 1024 : 0);
-  p->off_part = take((size_t)std::max(p->dw_nsplit, p->pipe_K > 1 ? p->pipe_rows : 0) *
-                     ((p->pol.n_params + 3) / 4 * 4) * sizeof(float));
-  // the policy head's gradient as the adjoint sweep publishes it for the streamed dW GEMM: [H][nwg][2 U][16] granules
-  p->pub_bytes = p->st_on ? (size_t)c.H * p->nwg * 2 * c.U * 16 * sizeof(unsigned long long) : 0;
-  p->off_pub = take(p->pub_bytes);
+  // the dW GEMM's partial rows, and the policy head's gradient as the adjoint sweep publishes it for the streamed form
+  p->dw.off_part = take((size_t)p->dw.part_rows * p->dw.args.part_stride * sizeof(float));
+  p->dw.off_pub = take(p->dw.pub_bytes);
   p->ws_bytes = off;
-  if (p->ws_bytes >= ((size_t)1 << 32)) p->reg = p->reg_mm = p->st_on = 0;      // (the family addresses its stashes with 32-bit workspace offsets)
+  if (p->ws_bytes >= ((size_t)1 << 32)) p->reg = p->reg_mm = p->dw.st_on = 0;      // (the family addresses its stashes with 32-bit workspace offsets)
   return 0;
 }
 
-// stage 8: the plan's sweep kernels, kernel attributes, and the residency the barrier form relies on
+// stage 7: the plan's sweep kernels, kernel attributes, and the residency the barrier form relies on
 static PmInstTable sweep_table(const pmbrl_plan* p) {
   if (p->fast)
     return p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_instances() : p->prec ? pm_fast_split1_instances() : pm_fast_f32_instances();
@@ -1223,7 +986,7 @@ static int resolve_sweeps(pmbrl_plan* p) {
   if (!p->fast) {
     // the table of the networks that are not ReLU is keyed by piece planes, the split one by the in-place form (3: the
     // wide layers with pre-split stashes), the exact-fp32 one by row tiles alone
-    const int wide_form = (p->inplace == 2 && p->dw_pre_mask) ? 3 : p->inplace;
+    const int wide_form = (p->inplace == 2 && p->dw.pre_mask) ? 3 : p->inplace;
     const PmInstKey k = pm_general_key(p->RT, p->act ? (p->prec ? 2 : 0) : p->prec ? wide_form : 0);
     return take(0, k) ? 0 : fail(-3, "no general-family instance for " + pm_inst_name(k));
   }
@@ -1313,9 +1076,12 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
   if (int rc = plan_layout(p.get(), cus)) return rc;
   if (int rc = plan_reward(p.get())) return rc;
   if (int rc = plan_angles(p.get())) return rc;
-  if (int rc = plan_dw(p.get())) return rc;
-  if (int rc = plan_dw_pipe(p.get(), cus)) return rc;
-  if (int rc = plan_workspace(p.get(), cus)) return rc;
+  // stage 5: whether the register-resident family serves the plan (its predicates read the layout alone -- nothing of the
+  // dW plan, which asks for them), then the policy's dW GEMM (pm_dw_plan_create, pmbrl_dw.hip; the rules: pmbrl_dw_plan.h)
+  p->reg = pm_reg_plan_ok(p.get()) ? 1 : 0;
+  p->reg_mm = pm_reg_mm_width(p.get());
+  if (int rc = pm_dw_plan_create(p.get(), cus)) return rc;
+  if (int rc = plan_workspace(p.get())) return rc;
   if (int rc = plan_attrs(p.get(), cus)) return rc;
   *out = p.release();
   return 0;
@@ -1367,10 +1133,8 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
   if (R.exec && same) {
     HIPCHK(hipGraphLaunch(R.exec, s));
     ++R.launches;
-    // (the host-side notes the recorded call left -- forward: which families' weights it packed, the form of its activity
-    //  bits; adjoint: whether its sweep left the second hidden layer's delta to the dW GEMM)
+    // (the host-side notes the recorded forward call left: which families' weights it packed, the form of its activity bits)
     if (slot == 0) { p->old_pack_stale = R.aux & 1; p->abits_packed = (R.aux >> 1) & 1; }
-    else { p->dw_g1_rebuilt = (R.aux >> 2) & 1; p->dw_streamed = (R.aux >> 3) & 1; p->dw_head = (R.aux >> 4) & 1; }
     return 0;
   }
   if (!same || R.seen == 0) {      // first sight of these arguments: as usual, remember them
@@ -1409,8 +1173,7 @@ static int replay_call(pmbrl_plan* p, int slot, const ReplayKey& K, hipStream_t 
     return body(s);
   }
   R.exec = ex;
-  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1) | ((p->dw_g1_rebuilt & 1) << 2) | ((p->dw_streamed & 1) << 3) |
-          ((p->dw_head & 1) << 4);
+  R.aux = (p->old_pack_stale & 1) | ((p->abits_packed & 1) << 1);
   HIPCHK(hipGraphLaunch(R.exec, s));
   ++R.launches;
   return 0;
@@ -1469,15 +1232,8 @@ extern "C" void pmbrl_plan_destroy(pmbrl_plan* p) {
   if (p->rew_d) (void)hipFree(p->rew_d);
   if (p->wflag_d) (void)hipFree(p->wflag_d);
   if (p->ang_d) (void)hipFree(p->ang_d);
-  if (p->dw_blocks_d) (void)hipFree(p->dw_blocks_d);
-  if (p->dw_blocks_nh_d) (void)hipFree(p->dw_blocks_nh_d);
-  if (p->dw_units_d) (void)hipFree(p->dw_units_d);
+  pm_dw_plan_destroy(p);
   if (p->tail_buf_d) (void)hipFree(p->tail_buf_d);
-  if (p->pipe_stream) {
-    (void)hipStreamDestroy(p->pipe_stream);
-    for (int k = 0; k < PM_PIPE_MAX; ++k)
-      if (p->pipe_ev[k]) (void)hipEventDestroy(p->pipe_ev[k]);
-  }
   delete p;
 }
 
@@ -1498,12 +1254,12 @@ extern "C" size_t pmbrl_plan_workspace_bytes(const pmbrl_plan* p) { return p ? p
 
 extern "C" int pmbrl_plan_dw_stream(const pmbrl_plan* p, int32_t* out) {
   if (!p || !out) return fail(-1, "null argument");
-  out[0] = p->st_on ? p->cfg.H - p->st_cut : -1;
-  out[1] = p->st_on ? p->st_wgs : 0;
+  out[0] = p->dw.st_on ? p->cfg.H - p->dw.st_cut : -1;
+  out[1] = p->dw.st_on ? p->dw.st_wgs : 0;
   return 0;
 }
 
-extern "C" int pmbrl_plan_dw_head(const pmbrl_plan* p) { return p && p->st_on && p->st_head ? 1 : 0; }
+extern "C" int pmbrl_plan_dw_head(const pmbrl_plan* p) { return p && p->dw.st_on && p->dw.st_head ? 1 : 0; }
 
 extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   if (!p || !info) return fail(-1, "null argument");
@@ -1514,15 +1270,15 @@ extern "C" int pmbrl_plan_info(const pmbrl_plan* p, int32_t* info) {
   info[PMBRL_INFO_LDS_BYTES] = (int32_t)p->lds_bytes;
   info[PMBRL_INFO_N_POL_PARAMS] = (int32_t)p->pol.n_params;
   info[PMBRL_INFO_N_DYN_PARAMS] = (int32_t)p->dyn.n_params;
-  info[PMBRL_INFO_DW_SPLITS] = p->dw_nsplit;
+  info[PMBRL_INFO_DW_SPLITS] = p->dw.args.nsplit;
   info[PMBRL_INFO_MM_MODE] = p->mm_mode;
   info[PMBRL_INFO_LD] = p->LD;
-  info[PMBRL_INFO_DW_BLOCKS] = p->n_dw_blocks;
+  info[PMBRL_INFO_DW_BLOCKS] = p->dw.n_blocks();
   info[PMBRL_INFO_FAST] = p->fast;
   info[PMBRL_INFO_STAGES] = p->CA * 16 + p->CB;
   info[PMBRL_INFO_MM_GRID] = p->mm_grid;
   info[PMBRL_INFO_PRECISION] = p->prec;
-  info[PMBRL_INFO_DW_PIPE] = p->pipe_K;
+  info[PMBRL_INFO_DW_PIPE] = p->dw.pipe_K;
   info[PMBRL_INFO_MM_PARTS] = p->mm_parts;
   info[PMBRL_INFO_REG] = p->reg;
   info[PMBRL_INFO_REPLAY] = replay_wanted(p) ? 1 : 0;
@@ -2124,44 +1880,6 @@ static int bwd_reward_adjoint(pmbrl_plan* p, const BwdCall& C, RolloutArgs& A, f
   return 0;
 }
 
-// the dW GEMM's arguments: the plan's part (plan_dw) + this call's stashes, partial rows and status word
-static DwArgs dw_call_args(const pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A, bool streamed) {
-  DwArgs W = p->dw_args;
-  if (streamed) {
-    // the streamed form of the layer's GEMM: the granules the sweep of THIS call publishes, under its launch generation
-    // (generation + step + 1, never 0: xch_prepare's rule)
-    W.st_on = 1;
-    W.st_cut = p->st_cut;
-    W.st_wgs = p->st_wgs;
-    W.st_pub = reinterpret_cast<const unsigned long long*>(static_cast<char*>(C.workspace) + p->off_pub);
-    W.st_tag = ((++p->pub_gen) << 12) + 1u;
-    W.st_fail = C.status ? C.status + 1 : nullptr;
-    if (W.st_cut == 0) {
-      // every step streamed: the layer's columns (W then b, one contiguous range of the flat vector) hold chunks in the
-      // consumers' rows only -- what the consumers need not zero and the reduction need not read
-      const int l = p->dw_layer13;
-      if (W.b_off[l] == W.w_off[l] + W.dim[l + 1] * W.dim[l]) {
-        W.own_lo = W.w_off[l];
-        W.own_hi = W.b_off[l] + W.dim[l + 1];
-      }
-      if (p->st_head) {
-        // ... and the head's (plan_dw_head: contiguous behind the layer's); the block kernel's table is the one without it
-        W.st_head = 1;
-        W.own_hi = W.b_off[l + 1] + W.dim[l + 2];
-        W.blocks = p->dw_blocks_nh_d;
-        for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first_nh[w];
-      }
-    }
-  }
-  for (int l = 0; l < p->pol.nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
-  W.part = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_part);
-  W.nvalid = C.status;
-  if (p->dw_g1_rebuilt) {      // (gT[1] does not exist: the layer kernel rebuilds it)
-    pm_reg_dw_rebuild_args(p, static_cast<char*>(C.workspace), W);
-    W.rc_inv_keep = A.pol.inv_keep[1];
-  }
-  return W;
-}
 // stage 4, the groups spanning workgroups (mm_mode 3): dL/dx travels between the steps through two carry buffers.
 // SweepForm::Barrier: one launch, the workgroups meet at a device-wide barrier per step
 static int bwd_sweep_barrier(pmbrl_plan* p, const BwdCall& C, RolloutArgs A) {
@@ -2201,11 +1919,11 @@ static int bwd_sweep_whole(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, const
     // the granules' tags: zeroed once per workspace; a RECORDED launch carries the fill -- its replays repeat its generation
     // and would meet their own tags of the replay before
     const bool rec = pm_stream_recording(s);
-    if (p->pub_ws != C.workspace || rec) {
-      HIPCHK(hipMemsetAsync(ws + p->off_pub, 0, p->pub_bytes, s));
-      p->pub_ws = rec ? nullptr : C.workspace;
+    if (p->dw.pub_ws != C.workspace || rec) {
+      HIPCHK(hipMemsetAsync(ws + p->dw.off_pub, 0, p->dw.pub_bytes, s));
+      p->dw.pub_ws = rec ? nullptr : C.workspace;
     }
-    HIPCHK(hipEventRecord(p->pipe_ev[0], s));
+    HIPCHK(hipEventRecord(p->dw.pipe_ev[0], s));
   }
   if (p->mm_parts > 1) {
     // groups split over workgroups: their own flags, and two buffers for the rows of dL/dx they exchange
@@ -2217,17 +1935,17 @@ static int bwd_sweep_whole(pmbrl_plan* p, const BwdCall& C, RolloutArgs A, const
     A.t0 = lo[k];
     A.t1 = k ? lo[k - 1] : p->cfg.H;
     A.gx_from_carry = k > 0;
-    if (reg_bwd) pm_reg_launch(p, ws, A, C.in->pol_params_d, C.in->dyn_params_d, s, false, W.st_on ? (unsigned)p->off_pub : 0u, W.st_tag);
+    if (reg_bwd) pm_reg_launch(p, ws, A, C.in->pol_params_d, C.in->dyn_params_d, s, false, W.st_on ? (unsigned)p->dw.off_pub : 0u, W.st_tag);
     else launch_bwd_rt(p, A, s);
     if (W.st_on) {
-      HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[0], 0));
-      pm_dw_stream_launch(p, W, p->pipe_stream);
-      HIPCHK(hipEventRecord(p->pipe_ev[1], p->pipe_stream));
+      HIPCHK(hipStreamWaitEvent(p->dw.pipe_stream, p->dw.pipe_ev[0], 0));
+      pm_dw_stream_launch(p, W, p->dw.pipe_stream);
+      HIPCHK(hipEventRecord(p->dw.pipe_ev[1], p->dw.pipe_stream));
     }
     if (k + 1 < K) {
-      HIPCHK(hipEventRecord(p->pipe_ev[k], s));
-      HIPCHK(hipStreamWaitEvent(p->pipe_stream, p->pipe_ev[k], 0));
-      pm_dw_launch_range(p, W, k, p->pipe_stream);
+      HIPCHK(hipEventRecord(p->dw.pipe_ev[k], s));
+      HIPCHK(hipStreamWaitEvent(p->dw.pipe_stream, p->dw.pipe_ev[k], 0));
+      pm_dw_launch_range(p, W, k, p->dw.pipe_stream);
     }
   }
   return 0;
@@ -2261,20 +1979,20 @@ static int bwd_dw(pmbrl_plan* p, const BwdCall& C, const DwArgs& W, bool piped) 
   ScopedTimer tm(p, PMBRL_TIMER_DW, C.stream);
   if (!piped) {
     // (streamed: the layer's kernel takes the steps below the cut and adds to the consumers' rows -- behind them)
-    pm_dw_launch(p, W, C.stream, W.st_on ? p->pipe_ev[1] : nullptr);
+    pm_dw_launch(p, W, C.stream, W.st_on ? p->dw.pipe_ev[1] : nullptr);
     return 0;
   }
   // the rows of the last range are added to what the second stream left: join it first
-  HIPCHK(hipEventRecord(p->pipe_ev[p->pipe_K - 1], p->pipe_stream));
-  HIPCHK(hipStreamWaitEvent(C.stream, p->pipe_ev[p->pipe_K - 1], 0));
-  pm_dw_launch_range(p, W, p->pipe_K - 1, C.stream);
+  HIPCHK(hipEventRecord(p->dw.pipe_ev[p->dw.pipe_K - 1], p->dw.pipe_stream));
+  HIPCHK(hipStreamWaitEvent(C.stream, p->dw.pipe_ev[p->dw.pipe_K - 1], 0));
+  pm_dw_launch_range(p, W, p->dw.pipe_K - 1, C.stream);
   return 0;
 }
 
-// does this call's dW GEMM of the second hidden layer run beside its sweep (plan_dw_stream)?  The plan's form, on the family
+// does this call's dW GEMM of the second hidden layer run beside its sweep (pm_dw_plan_stream)?  The plan's form, on the family
 // that publishes; not with the cycle stamps, nor with the exchange inside (one form of the sharded tail)
 static bool bwd_streamed(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
-  return p->st_on && reg_bwd && sweep_form(p) == SweepForm::Whole && p->pipe_K <= 1 && !p->prof_bwd && !bwd_tail(p, C);
+  return p->dw.st_on && reg_bwd && sweep_form(p) == SweepForm::Whole && p->dw.pipe_K <= 1 && !p->prof_bwd && !bwd_tail(p, C);
 }
 // A0, reg_bwd: the call's sweep arguments (bwd_args) and the family they go to, assembled once by rollout_bwd_replay --
 // its replay key holds the family too
@@ -2285,8 +2003,7 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   // the register-resident adjoint (always over its own family's forward stashes: the forward call takes the family
   // whenever the adjoint call can) stashes no delta of the policy's second hidden layer -- every dW launch of THIS call,
   // pipelined ranges and the sharded tail's included, rebuilds it; the other family's adjoint on the same forward
-  // (optional outputs, PMBRL_REG_BWD=0) writes gT[1] and keeps the classic kernel
-  p->dw_g1_rebuilt = reg_bwd ? 1 : 0;
+  // (optional outputs, PMBRL_REG_BWD=0) writes gT[1] and keeps the classic kernel: pm_dw_call_args' `rebuilt`
   const pmbrl_adam* opt = C.opt;
   const bool tail = bwd_tail(p, C);
   float* const xb = p->tail_buf_d;
@@ -2296,11 +2013,9 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   float* grt = reinterpret_cast<float*>(static_cast<char*>(C.workspace) + p->off_grt);
   if (int rc = bwd_reward_adjoint(p, C, A, grt)) return rc;
   const SweepForm form = sweep_form(p);
-  const bool piped = form == SweepForm::Whole && p->pipe_K > 1 && !p->prof_bwd;
+  const bool piped = form == SweepForm::Whole && p->dw.pipe_K > 1 && !p->prof_bwd;
   const bool streamed = bwd_streamed(p, C, reg_bwd);
-  p->dw_streamed = streamed ? 1 : 0;
-  const DwArgs W = dw_call_args(p, C, A, streamed);
-  p->dw_head = W.st_head;
+  const DwArgs W = pm_dw_call_args(p, C.workspace, C.status, A, reg_bwd, streamed);
   {
     ScopedTimer tm(p, PMBRL_TIMER_BWD, s);
     static const int whole[1] = {0};
@@ -2308,7 +2023,7 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
     switch (form) {
       case SweepForm::Barrier: rc = bwd_sweep_barrier(p, C, A); break;
       case SweepForm::StepInSweep: rc = bwd_sweep_steps(p, C, A); break;
-      case SweepForm::Whole: rc = bwd_sweep_whole(p, C, A, W, reg_bwd, piped ? p->pipe_K : 1, piped ? p->pipe_lo : whole); break;
+      case SweepForm::Whole: rc = bwd_sweep_whole(p, C, A, W, reg_bwd, piped ? p->dw.pipe_K : 1, piped ? p->dw.pipe_lo : whole); break;
       case SweepForm::StepExternal: rc = bwd_sweep_external(p, C, A, grt); break;
     }
     if (rc) return rc;
@@ -2329,9 +2044,9 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   {
     ScopedTimer tm(p, PMBRL_TIMER_DW_REDUCE, s);
     if (piped)   // every partial row was written (pm_dw_range)
-      pm_dw_reduce_launch(s, W.part, p->pipe_rows, n, W.part_stride, red_out, (const int*)nullptr, 0, 1);
+      pm_dw_reduce_launch(s, W.part, p->dw.pipe_rows, n, W.part_stride, red_out, (const int*)nullptr, 0, 1);
     else
-      pm_dw_reduce_launch(s, W.part, p->dw_nsplit, n, W.part_stride, red_out, (const int*)C.status, W.chunks_per_step,
+      pm_dw_reduce_launch(s, W.part, p->dw.args.nsplit, n, W.part_stride, red_out, (const int*)C.status, W.chunks_per_step,
                           W.chunks_per_split, norm_fused ? 1 : 0, (const int*)C.status, expect,
                           opt ? reinterpret_cast<long long*>(opt->step_d) : (long long*)nullptr,
                           loss_fused ? C.rewards : (const float*)nullptr, C.grad_rewards, (long long)p->cfg.H * p->cfg.B,
@@ -2381,13 +2096,13 @@ static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
   // what the forward call left behind decides which conversions the adjoint call queues (weights repacked for the other
   // family, activity words unpacked): a recording is only good for the state it was recorded in
   K.val(p->old_pack_stale); K.val(p->abits_packed);
-  // ... and the family this call's sweep takes decides which form of the layer's dW kernel follows it (dw_g1_rebuilt)
+  // ... and the family this call's sweep takes decides which form of the layer's dW kernel follows it (pm_dw_call_args' `rebuilt`)
   const int g1_rebuilt = reg_bwd ? 1 : 0;
   K.val(g1_rebuilt);
   // ... and whether the layer's GEMM runs beside the sweep (bwd_streamed)
   const int streamed = bwd_streamed(p, C, reg_bwd) ? 1 : 0;
   K.val(streamed);
-  const int head = streamed && p->st_head ? 1 : 0;      // ... with the policy head's dW in the consumers (plan_dw_head)
+  const int head = streamed && p->dw.st_head ? 1 : 0;      // ... with the policy head's dW in the consumers (pm_dw_plan_head)
   K.val(head);
   return K;
 }

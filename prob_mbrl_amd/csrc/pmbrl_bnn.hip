@@ -33,7 +33,7 @@ struct pmbrl_bnn_plan {
   int w_off[PM_MAXL], b_off[PM_MAXL], lp_poff[PM_MAXL], lp_off[PM_MAXL], has_drop[PM_MAXL];
   size_t off_wf[PM_MAXL], off_wb[PM_MAXL], off_bias[PM_MAXL], off_actT[PM_MAXL], off_gT[PM_MAXL];
   size_t off_part_lp, off_part_loss, off_part, off_reg_part, ws_bytes, lds;
-  int part_stride, n_dw_blocks, dw_wave_first[PM_DW_NW + 1];
+  int part_stride, dw_wave_first[PM_DW_NW + 1];
   DwBlock* dw_blocks_d;
   // fixed-rate Bernoulli layers (has_drop[l] == 2): noise_off / noise_h count the dropout layers of EITHER kind (the
   // u / bvar blocks), lp_off / sum_h the concrete ones (the logit gradients); keep_d[l]: the units' keep probabilities
@@ -41,7 +41,7 @@ struct pmbrl_bnn_plan {
   float* keep_d[PM_MAXL];
   float* keep_all_d;
   BnnKernels kern;
-  // What the kernels' argument records hold of the plan alone (bnn_plan_records; as pmbrl_plan::dw_args).  A call starts
+  // What the kernels' argument records hold of the plan alone (bnn_plan_records; as DwPlan::args).  A call starts
   // from a COPY -- the two calls alternate on one plan -- and adds its workspace and parameter pointers (bnn_bind) and
   // what is the call's own; everything else in them stays zero.
   BnnArgs args;
@@ -78,8 +78,7 @@ static void bnn_plan_records(pmbrl_bnn_plan* p) {
   // dW / db of every layer: the policy-gradient GEMM over the same stash layout (one 16-row chunk per split)
   W.nl = p->nl; W.nsplit = p->nwg; W.n_chunks = p->nwg; W.chunks_per_split = 1;
   W.RT = 1; W.Rw = 16; W.n_params = p->n_params; W.part_stride = p->part_stride;
-  W.blocks = p->dw_blocks_d;
-  for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = p->dw_wave_first[w];
+  pm_dw_bind_blocks(W, p->dw_blocks_d, p->dw_wave_first);
   for (int i = 0; i <= p->nl; ++i) {
     A.dim[i] = F.dim[i] = T.dim[i] = W.dim[i] = p->dim[i];
     A.nt[i] = T.nt[i] = W.nt[i] = p->nt[i];
@@ -206,9 +205,8 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->ws_bytes = off;
   HIPCHK(hipSetDevice(device));
   std::vector<DwBlock> blocks;
-  p->n_dw_blocks = build_dw_blocks(p->nl, p->nt, blocks, p->dw_wave_first);
-  HIPCHK(hipMalloc(&p->dw_blocks_d, blocks.size() * sizeof(DwBlock)));
-  HIPCHK(hipMemcpy(p->dw_blocks_d, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice));
+  build_dw_blocks(p->nl, p->nt, blocks, p->dw_wave_first);
+  HIPCHK(pm_dw_upload_blocks(blocks, &p->dw_blocks_d));
   if (p->any_bern) {
     // the Bernoulli layers' keep probabilities, one per unit (a scalar rate repeated; the padding of the last tile keeps 1)
     std::vector<float> keep;

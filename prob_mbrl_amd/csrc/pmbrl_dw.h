@@ -1,7 +1,12 @@
 // The records of the policy-gradient dW GEMM: what the plan (pmbrl_host.h) and the callers of its launchers hold.  The
-// kernels are in pmbrl_dw_kernels.h, compiled into pmbrl_dw.hip only.
+// kernels are in pmbrl_dw_kernels.h, compiled into pmbrl_dw.hip only.  Nothing here needs the device compiler: the host-only
+// planner (pmbrl_dw_plan.h) includes it.
 #pragma once
-#include "pmbrl_dev.h"
+#include <stdint.h>
+
+#include "pmbrl.h"
+
+#define PM_MAXL PMBRL_MAX_LAYERS      // (as pmbrl_dev.h)
 
 #define PM_DW_NW 8
 #define PM_DW_NT (PM_DW_NW * 64)
@@ -37,7 +42,7 @@ struct DwArgs {
   int wave_first[PM_DW_NW + 1];          // wave w owns blocks [wave_first[w], wave_first[w+1])
   float* part;                           // [nsplit][n_params]
   int split_prec;                        // 1: two bf16 pieces per operand on the bf16 matrix core (pm_dw_kernel_s)
-  // Pipelined form (pmbrl.hip: "dW behind the adjoint sweep"): the adjoint sweep runs as K launches over
+  // Pipelined form (pmbrl_dw_plan.h: "dW GEMM behind the adjoint sweep"): the adjoint sweep runs as K launches over
   // descending step ranges and launch k of this GEMM covers the chunks of range k only, [c_begin, c_end),
   // dealt to the same nsplit partial rows every time; the first launch that owns a valid step writes its
   // row (zeros if the row got no chunk), the later ones add to it -- still one fixed order of additions.
@@ -46,14 +51,14 @@ struct DwArgs {
   int c_begin, c_end;                    // chunk range of this launch (c_end = the previous launch's c_begin)
   int rows_before;                       // partial rows the earlier launches own (the last launch has more)
   // Rebuilding form of the whole-layer kernel (pm_dw_layer_rc_kernel: behind a register-resident adjoint sweep, which
-  // stashes no delta of the policy's second hidden layer; a call fills these, dw_call_args).  RT = 1: chunk c is the
+  // stashes no delta of the policy's second hidden layer; a call fills these, pm_dw_call_args).  RT = 1: chunk c is the
   // (step, workgroup) block c of every stash and of the activity words -- chunks_per_step is the sweep's nwg
   const unsigned* rc_abits;              // (nullptr: the classic form, the delta is fetched) the forward sweep's activity words of that layer: [chunk][sweep wave (4)][lane]
   const float* rc_head;                  // the adjoint pack's transposed head weights: [tile][2 blocks][lane][4]
   float rc_inv_keep;                     // 1 / keep of the layer's dropout
   int rc_D, rc_U;                        // state and action widths: which rows of a gT[l + 1] block a lane group holds
-  // Streamed form of the rebuilding kernel (pmbrl.hip: "the layer's dW GEMM beside the adjoint sweep").  The steps
-  // [st_cut, valid steps) go to st_wgs consumer workgroups (pm_dw_layer_st_kernel) that run NEXT TO the one-launch sweep, on
+  // Streamed form of the rebuilding kernel (pmbrl_dw_plan.h: "the second hidden layer's dW GEMM BESIDE the adjoint
+  // sweep").  The steps [st_cut, valid steps) go to st_wgs consumer workgroups (pm_dw_layer_st_kernel) that run NEXT TO the one-launch sweep, on
   // the CUs it leaves idle, and follow it step by step: of the three inputs only the head gradient comes from the adjoint
   // sweep, which publishes it as tagged granules (st_pub: [H][chunks per step][2 U][16] x {tag, 32 bits}, step t's tag
   // st_tag + t).  Consumer w owns partial row w; pm_dw_layer_rc_kernel then takes the steps below the cut, dealt to the
@@ -74,6 +79,7 @@ struct DwArgs {
   // (pm_dw_kernel_nh) and [own_lo, own_hi) runs through the head's bias
   int st_head;
 };
+static_assert(sizeof(DwArgs) == 472, "DwArgs is a kernel argument: its layout does not move");
 // LDS of the streamed consumer behind the stages: the policy head's table and accumulators (pmbrl_dw_kernels.h, PM_DWH_TAB)
 #define PM_DWH_LDS_BYTES ((2 * 16 * 16 + PM_DW_NW * 64 * 12) * 4)
 

@@ -1,5 +1,6 @@
-// The policy-gradient dW GEMM (pmbrl_dw_kernels.h): its kernels, the wave blocks they walk, their LDS attributes and
-// their launches.  Users: the rollout adjoint call (pmbrl.hip) and the BNN step (pmbrl_bnn.hip).
+// The policy-gradient dW GEMM (pmbrl_dw_kernels.h): its kernels, their LDS attributes, the rollout plan's dW record made
+// from the planner's decisions (pmbrl_dw_plan.h) and released, a call's argument record and the launches, which walk
+// the record.  Users: the rollout adjoint call (pmbrl.hip) and the BNN step (pmbrl_bnn.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,165 +10,182 @@
 #include "pmbrl_host.h"
 #include "pmbrl_dw_kernels.h"
 
-// dW wave blocks: balanced splits of every layer's output tile grid into <= 4 x 7 tile
-// blocks, dealt to the four SIMDs (waves w and w+4 share SIMD w) by decreasing size so that
-// every SIMD issues the same number of MFMAs.  Returns the number of blocks; `blocks` comes back
-// sorted by wave, wave w owning [wave_first[w], wave_first[w+1]).
-// (ot_parts_min: a layer's output tiles in at least this many parts where it has as many -- the table without the policy
-//  head, pm_dw_kernel_nh, has one layer left and wants a block on every wave)
-int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max,
-                           const bool* skip, int ot_parts_min) {
-  blocks.clear();
-  auto split = [](int n, int maxsz, std::vector<std::pair<int, int>>& out, int parts_min = 1) {
-    const int parts = std::max((n + maxsz - 1) / maxsz, std::min(n, parts_min));
-    int lo = 0;
-    for (int i = 0; i < parts; ++i) {
-      const int sz = n / parts + (i < n % parts ? 1 : 0);
-      out.push_back({lo, sz});
-      lo += sz;
-    }
-  };
-  for (int l = 0; l < nl; ++l) {
-    if (skip && skip[l]) continue;      // a wide layer: pm_dw_wide_kernel
-    std::vector<std::pair<int, int>> os, is;
-    split(nt[l + 1], PM_DW_TM, os, ot_parts_min);
-    split(nt[l], tn_max, is);
-    for (auto& o : os)
-      for (auto& i : is) {
-        DwBlock b;
-        b.layer = (int16_t)l;
-        b.ot0 = (int16_t)o.first;
-        b.n_ot = (int16_t)o.second;
-        b.it0 = (int16_t)i.first;
-        b.n_it = (int16_t)i.second;
-        b.pad = 0;
-        blocks.push_back(b);
-      }
-  }
-  const int n_blocks = (int)blocks.size();
-  // cost of a block = MFMAs per chunk in the shape class it runs in (see pm_dw_kernel)
-  auto cost = [tn_max](const DwBlock& b) {
-    const int ni = b.n_ot <= 1 ? 1 : (b.n_ot <= 3 ? 3 : 4);
-    const int nj = b.n_it <= 1 ? 1 : (b.n_it <= 4 ? 4 : (b.n_it <= 6 ? 6 : 7));
-    return ni * (tn_max <= 4 && nj > 1 ? 4 : nj);
-  };
-  std::stable_sort(blocks.begin(), blocks.end(),
-                   [&](const DwBlock& a, const DwBlock& b) { return cost(a) > cost(b); });
-  std::vector<DwBlock> per_wave[PM_DW_NW];
-  long wave_load[PM_DW_NW] = {0};
-  // waves w and w+4 of a workgroup share SIMD w (measured: pairing (2k, 2k+1) instead is 5% slower)
-  for (const DwBlock& b : blocks) {
-    int best_simd = 0;
-    for (int sm = 1; sm < 4; ++sm)
-      if (wave_load[sm] + wave_load[sm + 4] < wave_load[best_simd] + wave_load[best_simd + 4]) best_simd = sm;
-    const int w = wave_load[best_simd] <= wave_load[best_simd + 4] ? best_simd : best_simd + 4;
-    per_wave[w].push_back(b);
-    wave_load[w] += cost(b);
-  }
-  blocks.clear();
-  // the small blocks are latency-bound (a handful of MFMAs per chunk): the second wave of a SIMD runs
-  // its FIRST, while the SIMD's other wave keeps the MFMA pipe busy with its big block
-  for (int w = 0; w < PM_DW_NW; ++w) {
-    wave_first[w] = (int)blocks.size();
-    if (w >= 4) std::reverse(per_wave[w].begin(), per_wave[w].end());
-    for (const DwBlock& b : per_wave[w]) blocks.push_back(b);
-  }
-  wave_first[PM_DW_NW] = (int)blocks.size();
-  return n_blocks;
-}
-
-// dynamic LDS of the kernels plan_dw chose for this plan
-int pm_dw_set_attr(const pmbrl_plan* p) {
-  if (p->dw_layer13 >= 0) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rc_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_st_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES + PM_DWH_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_layer_rcb_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWL_LDS_BYTES));
-  }
-  if (p->dw_pre_mask) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-  }
-  if (p->n_dw_units) {
-    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWW_LDS_BYTES));
-    if (p->dw_pre_mask)
-      HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_dw_wide_pre_kernel),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, PM_DWP_LDS_BYTES));
-  }
+// dynamic LDS of the kernels the planner chose for this plan
+static int pm_dw_set_attr(const DwPlan& D) {
+  const bool layer = D.layer13 >= 0, pre = D.pre_mask != 0, units = D.unit_k != DwKernel::None;
+  const struct { bool on; const void* fn; int bytes; } K[] = {
+      {layer, reinterpret_cast<const void*>(&pm_dw_layer_kernel), PM_DWL_LDS_BYTES},
+      {layer, reinterpret_cast<const void*>(&pm_dw_layer_rc_kernel), PM_DWL_LDS_BYTES},
+      {layer, reinterpret_cast<const void*>(&pm_dw_layer_st_kernel), PM_DWL_LDS_BYTES + PM_DWH_LDS_BYTES},
+      {layer, reinterpret_cast<const void*>(&pm_dw_layer_rcb_kernel), PM_DWL_LDS_BYTES},
+      {pre, reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<1>), PM_DWP_LDS_BYTES},
+      {pre, reinterpret_cast<const void*>(&pm_dw_narrow_pre_kernel<2>), PM_DWP_LDS_BYTES},
+      {units, reinterpret_cast<const void*>(&pm_dw_wide_kernel), PM_DWW_LDS_BYTES},
+      {D.unit_k == DwKernel::WidePre, reinterpret_cast<const void*>(&pm_dw_wide_pre_kernel), PM_DWP_LDS_BYTES}};
+  for (const auto& k : K)
+    if (k.on) HIPCHK(hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.bytes));
   return 0;
 }
 
+// table -> device -> DwArgs::blocks / wave_first, for the rollout plan's two tables and the BNN step's
+hipError_t pm_dw_upload_blocks(const std::vector<DwBlock>& blocks, DwBlock** out) {
+  *out = nullptr;
+  hipError_t e = hipMalloc(out, std::max<size_t>(1, blocks.size()) * sizeof(DwBlock));
+  if (e == hipSuccess && !blocks.empty()) e = hipMemcpy(*out, blocks.data(), blocks.size() * sizeof(DwBlock), hipMemcpyHostToDevice);
+  if (e != hipSuccess && *out) { (void)hipFree(*out); *out = nullptr; }
+  return e;
+}
+void pm_dw_bind_blocks(DwArgs& W, const DwBlock* blocks_d, const int* wave_first) {
+  W.blocks = blocks_d;
+  for (int w = 0; w <= PM_DW_NW; ++w) W.wave_first[w] = wave_first[w];
+}
+
+// The plan's dW record: what the planner reads of the plan, its decisions, then what they need on the device -- the unit
+// list, the block tables, the kernels' attributes, the second stream and its events.  pm_dw_plan_destroy releases them
+// (pmbrl_plan_destroy; a plan that failed half-way too).
+int pm_dw_plan_create(pmbrl_plan* p, int cus) {
+  DwShape S{};
+  S.nl = p->pol.nl;
+  for (int i = 0; i <= S.nl; ++i) { S.nt[i] = p->pol.nt[i]; S.dim[i] = p->pol.dim[i]; }
+  for (int l = 0; l < S.nl; ++l) { S.w_off[l] = (int)p->pol.w_off[l]; S.b_off[l] = (int)p->pol.b_off[l]; }
+  S.n_params = (int)p->pol.n_params; S.dyn_n_params = (int)p->dyn.n_params;
+  S.prec = p->prec; S.RT = p->RT; S.fast = p->fast; S.inplace = p->inplace; S.nwg = p->nwg;
+  S.H = p->cfg.H; S.U = p->cfg.U; S.cus = cus;
+  S.whole = sweep_form(p) == SweepForm::Whole;
+  S.mm_parts = p->mm_parts; S.reg = p->reg; S.reg_mm = p->reg_mm; S.reg_bwd = p->sw.reg_bwd;
+  S.sw = p->sw;
+  DwPlan& D = p->dw;
+  pm_dw_plan(S, D);
+  if (!D.units.empty()) {
+    HIPCHK(hipMalloc(&D.units_d, D.units.size() * sizeof(DwUnit)));
+    HIPCHK(hipMemcpy(D.units_d, D.units.data(), D.units.size() * sizeof(DwUnit), hipMemcpyHostToDevice));
+  }
+  if (int rc = pm_dw_set_attr(D)) return rc;
+  DwBlock* blocks_d = nullptr;
+  HIPCHK(pm_dw_upload_blocks(D.blocks, &blocks_d));
+  D.args.blocks = blocks_d;
+  if (D.pipe_K > 1 || D.st_on) {
+    HIPCHK(hipStreamCreateWithFlags(&D.pipe_stream, hipStreamNonBlocking));
+    for (int k = 0; k < std::max(D.pipe_K, D.st_on ? 2 : 0); ++k)
+      HIPCHK(hipEventCreateWithFlags(&D.pipe_ev[k], hipEventDisableTiming));
+  }
+  // (a table that cannot be had is no reason to fail the plan: the head stays in the block kernel)
+  if (D.st_head && pm_dw_upload_blocks(D.blocks_nh, &D.blocks_nh_d) != hipSuccess) {
+    (void)hipGetLastError();
+    D.st_head = 0;
+    D.table_nh_k = DwKernel::None;
+  }
+  return 0;
+}
+void pm_dw_plan_destroy(pmbrl_plan* p) {
+  DwPlan& D = p->dw;
+  if (D.args.blocks) (void)hipFree(const_cast<DwBlock*>(D.args.blocks));
+  if (D.blocks_nh_d) (void)hipFree(D.blocks_nh_d);
+  if (D.units_d) (void)hipFree(D.units_d);
+  if (D.pipe_stream) (void)hipStreamDestroy(D.pipe_stream);
+  for (int k = 0; k < PM_PIPE_MAX; ++k)
+    if (D.pipe_ev[k]) (void)hipEventDestroy(D.pipe_ev[k]);
+}
+
+// the dW GEMM's arguments: the plan's part (DwPlan::args) + this call's stashes, partial rows and status word
+DwArgs pm_dw_call_args(const pmbrl_plan* p, void* workspace, int32_t* status, const RolloutArgs& A, bool rebuilt, bool streamed) {
+  const DwPlan& D = p->dw;
+  DwArgs W = D.args;
+  if (streamed) {
+    // the streamed form of the layer's GEMM: the granules the sweep of THIS call publishes, under its launch generation
+    // (generation + step + 1, never 0: xch_prepare's rule)
+    W.st_on = 1;
+    W.st_cut = D.st_cut;
+    W.st_wgs = D.st_wgs;
+    W.st_pub = reinterpret_cast<const unsigned long long*>(static_cast<char*>(workspace) + D.off_pub);
+    W.st_tag = ((++D.pub_gen) << 12) + 1u;
+    W.st_fail = status ? status + 1 : nullptr;
+    if (W.st_cut == 0) {
+      // every step streamed: the layer's columns (W then b, one contiguous range of the flat vector) hold chunks in the
+      // consumers' rows only -- what the consumers need not zero and the reduction need not read
+      const int l = D.layer13;
+      if (W.b_off[l] == W.w_off[l] + W.dim[l + 1] * W.dim[l]) {
+        W.own_lo = W.w_off[l];
+        W.own_hi = W.b_off[l] + W.dim[l + 1];
+      }
+      if (D.st_head) {
+        // ... and the head's (pm_dw_plan_head: contiguous behind the layer's); the block kernel's table is the one without it
+        W.st_head = 1;
+        W.own_hi = W.b_off[l + 1] + W.dim[l + 2];
+        pm_dw_bind_blocks(W, D.blocks_nh_d, D.wave_first_nh);
+      }
+    }
+  }
+  for (int l = 0; l < p->pol.nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
+  W.part = reinterpret_cast<float*>(static_cast<char*>(workspace) + D.off_part);
+  W.nvalid = status;
+  // (the rebuilding form is written for 16-row chunks and the policy's second hidden layer, which is all pm_reg_can_run
+  //  lets reach it; the streamed form is one of it)
+  assert(!rebuilt || (W.RT == 1 && D.layer13 == PM_REG_DW_LAYER));
+  assert(!streamed || rebuilt);
+  if (rebuilt) {      // (gT[1] does not exist: the layer kernel rebuilds it)
+    pm_reg_dw_rebuild_args(p, static_cast<char*>(workspace), W);
+    W.rc_inv_keep = A.pol.inv_keep[1];
+  }
+  return W;
+}
 // ... of launch k of the pipelined form: the chunks of step range k, dealt to the partial rows of a grid next to the sweep
 // (the last launch has the chip to itself)
-static DwArgs dw_range_args(const pmbrl_plan* p, const DwArgs& W, int k) {
+static DwArgs dw_range_args(const DwPlan& D, const DwArgs& W, int k, int H) {
   DwArgs Wk = W;
   const int cps = W.chunks_per_step;
   Wk.pipe = 1;
   Wk.pipe_k = k;
-  Wk.nsplit = k + 1 == p->pipe_K ? p->pipe_rows : p->pipe_grid;
-  Wk.rows_before = p->pipe_grid;
-  Wk.c_begin = p->pipe_lo[k] * cps;
-  Wk.c_end = (k ? p->pipe_lo[k - 1] : p->cfg.H) * cps;
+  Wk.nsplit = k + 1 == D.pipe_K ? D.pipe_rows : D.pipe_grid;
+  Wk.rows_before = D.pipe_grid;
+  Wk.c_begin = D.pipe_lo[k] * cps;
+  Wk.c_end = (k ? D.pipe_lo[k - 1] : H) * cps;
   Wk.chunks_per_split = (Wk.c_end - Wk.c_begin + Wk.nsplit - 1) / Wk.nsplit;
-  if (p->dw_split) Wk.chunks_per_split = (Wk.chunks_per_split + 1) & ~1;
+  if (W.split_prec) Wk.chunks_per_split = (Wk.chunks_per_split + 1) & ~1;
   return Wk;
 }
-// The dW GEMM over the chunks W describes, one partial row per workgroup: the only place that chooses its kernels.
-// (The pipelined ranges never meet a plan without block-kernel layers or with pre-split stashes: such a plan has
-//  dw_pre_mask -- the first layer's input is at most 40 wide, so only pm_dw_narrow_pre_kernel takes it from the block
-//  kernel -- and plan_dw_pipe leaves the pipeline off for it.)
+// The dW GEMM over the chunks W describes, one partial row per workgroup: a straight walk over the kernels the planner
+// resolved (DwPlan::table_k / table_nh_k, layer_k, unit_k, layer13).  Of the call it reads three facts, all in W: the
+// head in the consumers (st_head: the call's table is the one without it, pm_dw_call_args), streamed (st_on), the
+// delta rebuilt or fetched (rc_abits).
 // (W.st_on, the streamed form: the layer's kernel is the launch behind the consumers -- it adds to their partial rows, so
 //  `after`, the event behind them, is waited for in front of it; the other kernels neither read nor write those columns)
 void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s, hipEvent_t after) {
-  const dim3 rows(W.nsplit), units((W.nsplit + 7) / 8 * 8 * p->n_dw_units);
-  // (W.st_head: the consumers formed the head; the call's table is the one without it -- dw_call_args -- and where every
-  //  block of that is at most 2 x 1 tiles, the kernel with the deeper ring walks it)
-  assert(!W.st_head || !W.pipe);      // (pm_dw_kernel_nh has no branch for a row of zeros: only a piped range asks for one)
-  if (W.st_head && p->n_dw_blocks_nh == 0) {}
-  else if (W.st_head && p->dw_nh_ring) hipLaunchKernelGGL(pm_dw_kernel_nh, rows, dim3(PM_DW_NT), 0, s, W);
-  else if (W.st_head) hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W);
-  else if (p->n_dw_blocks == 0) {}      // (every layer has a GEMM kernel of its own: below)
-  else if (p->dw_split) hipLaunchKernelGGL(pm_dw_kernel_s, rows, dim3(PM_DW_NT), 0, s, W);
-  else hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W);
-  if (p->dw_pre_mask)
-    for (int l = 0; l < p->pol.nl; ++l) {
-      if (!p->dw_narrow[l]) continue;
-      const int g_wide = p->dw_narrow[l] == 1 ? 1 : 0, nt_n = g_wide ? p->pol.nt[l] : p->pol.nt[l + 1];
-      if (nt_n <= 1) hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<1>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
-      else hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<2>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
-    }
-  if (p->n_dw_units && p->dw_pre_mask)
-    hipLaunchKernelGGL(pm_dw_wide_pre_kernel, units, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
-  else if (p->n_dw_units)
-    hipLaunchKernelGGL(pm_dw_wide_kernel, units, dim3(PM_DW_NT), PM_DWW_LDS_BYTES, s, W, p->dw_units_d, p->n_dw_units);
-  // (W carries what rebuilds the delta operand -- dw_call_args, behind a register-resident adjoint sweep, which left no
-  //  stash of it: the rebuilding form.  It is written for 16-row chunks and the policy's second hidden layer, which is
-  //  all pm_reg_can_run lets reach it)
-  const bool rebuild = W.rc_abits != nullptr;
-  assert(!rebuild || (W.RT == 1 && p->dw_layer13 == PM_REG_DW_LAYER));
-  assert(!W.st_on || rebuild);
+  const DwPlan& D = p->dw;
+  const int n_units = (int)D.units.size();
+  const dim3 rows(W.nsplit), units((W.nsplit + 7) / 8 * 8 * n_units);
+  switch (W.st_head ? D.table_nh_k : D.table_k) {
+    case DwKernel::Block: hipLaunchKernelGGL(pm_dw_kernel, rows, dim3(PM_DW_NT), 0, s, W); break;
+    case DwKernel::BlockSplit: hipLaunchKernelGGL(pm_dw_kernel_s, rows, dim3(PM_DW_NT), 0, s, W); break;
+    case DwKernel::BlockRing: hipLaunchKernelGGL(pm_dw_kernel_nh, rows, dim3(PM_DW_NT), 0, s, W); break;
+    default: break;      // (every layer has a GEMM kernel of its own: below)
+  }
+  for (int l = 0; l < W.nl; ++l) {
+    const int g_wide = D.narrow[l] == 1 ? 1 : 0;
+    if (D.layer_k[l] == DwKernel::NarrowPre1)
+      hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<1>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
+    else if (D.layer_k[l] == DwKernel::NarrowPre2)
+      hipLaunchKernelGGL(pm_dw_narrow_pre_kernel<2>, rows, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, l, g_wide);
+  }
+  if (D.unit_k == DwKernel::WidePre)
+    hipLaunchKernelGGL(pm_dw_wide_pre_kernel, units, dim3(PM_DWP_NT), PM_DWP_LDS_BYTES, s, W, D.units_d, n_units);
+  else if (D.unit_k == DwKernel::Wide)
+    hipLaunchKernelGGL(pm_dw_wide_kernel, units, dim3(PM_DW_NT), PM_DWW_LDS_BYTES, s, W, D.units_d, n_units);
   if (after) (void)hipStreamWaitEvent(s, after, 0);
   if (W.st_on && W.st_cut == 0) return;      // (every step streamed: the consumers wrote every row the reduction reads)
-  if (p->dw_layer13 >= 0 && rebuild && W.st_on)
-    hipLaunchKernelGGL(pm_dw_layer_rcb_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
-  else if (p->dw_layer13 >= 0 && rebuild)
-    hipLaunchKernelGGL(pm_dw_layer_rc_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
-  else if (p->dw_layer13 >= 0)
-    hipLaunchKernelGGL(pm_dw_layer_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, p->dw_layer13);
+  if (D.layer13 < 0) return;
+  // (W carries what rebuilds the delta operand -- pm_dw_call_args, behind a register-resident adjoint sweep, which left no
+  //  stash of it: the rebuilding form)
+  if (W.st_on) hipLaunchKernelGGL(pm_dw_layer_rcb_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, D.layer13);
+  else if (W.rc_abits) hipLaunchKernelGGL(pm_dw_layer_rc_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, D.layer13);
+  else hipLaunchKernelGGL(pm_dw_layer_kernel, rows, dim3(PM_DW_NT), PM_DWL_LDS_BYTES, s, W, D.layer13);
 }
-void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s) { pm_dw_launch(p, dw_range_args(p, W, k), s); }
+void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s) { pm_dw_launch(p, dw_range_args(p->dw, W, k, p->cfg.H), s); }
 // the streamed form's consumers (W.st_on): one workgroup per CU the adjoint sweep leaves idle, next to it
 void pm_dw_stream_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s) {
-  assert(W.st_on && W.rc_abits && W.RT == 1 && p->dw_layer13 == PM_REG_DW_LAYER);
+  assert(W.st_on && W.rc_abits);
   hipLaunchKernelGGL(pm_dw_layer_st_kernel, dim3(W.st_wgs), dim3(PM_DW_NT), PM_DWL_LDS_BYTES + PM_DWH_LDS_BYTES, s, W,
-                     p->dw_layer13);
+                     p->dw.layer13);
 }
 // the block kernel alone, one partial row per workgroup: the BNN step's dW / db (its stashes have the same layout)
 void pm_dw_blocks_launch(const DwArgs& W, hipStream_t s) {

@@ -11,7 +11,8 @@
 //   pmbrl_fast_f32.hip       latency-optimised sweeps, exact fp32 MFMA: the same
 //   pmbrl_fast_split.hip     the same on split bf16 / fp16 operands; compiled once per precision (two objects)
 //   pmbrl_reg.hip            register-resident family: instances, resolution, packer and launch
-//   pmbrl_dw.hip             the policy-gradient dW GEMMs
+//   pmbrl_dw.hip             the policy-gradient dW GEMMs: kernels, the plan's dW record made and released
+//                            (pmbrl_dw_plan.h: the host-only planner), a call's argument record, the launches
 //   pmbrl_tail.hip           mask packing / drawing, weighted sum, dW reduction, gradient norm, clip + Adam, sharded tail
 //   pmbrl_bnn.hip            BNN training step
 //   pmbrl_mlp.hip            stand-alone network evaluation
@@ -26,6 +27,7 @@
 #include "pmbrl.h"
 #include "pmbrl_dev.h"
 #include "pmbrl_dw.h"
+#include "pmbrl_dw_plan.h"
 #include "pmbrl_instances.h"
 
 int pm_fail(int code, const std::string& msg);
@@ -49,20 +51,15 @@ struct NetPlan {
 };
 
 // The environment switches of a rollout plan (include/pmbrl.h lists them), read once when it is created
-struct PlanSwitches {
-  bool mm_perstep, mm_mode2, mm_no_batch, dw_no_wide, reg_debug;   // set at all: on
+// (the dW GEMM's: DwSwitches, pmbrl_dw_plan.h)
+struct PlanSwitches : DwSwitches {
+  bool mm_perstep, mm_mode2, mm_no_batch, reg_debug;   // set at all: on
   bool lds_tiles, mm_xch, mm_tree, reg, reg_mm, reg_tree, reg_bwd, fuse_loss, ztab_merge, wide;   // =0: off
   bool mm_parts_set;    // PMBRL_MM_PARTS=mm_parts
   int mm_parts;
   int replay;           // PMBRL_REPLAY (default 1)
-  bool dw_pipe_off, dw_pipe_ranges;   // PMBRL_DW_PIPE=off | n0,n1,... (the positive ones in dw_pipe)
-  std::vector<int> dw_pipe;
-  int dw_head;                        // PMBRL_DW_HEAD=on | off: the policy head's dW in the streamed consumers (-1: the plan's rule)
-  bool dw_stream_off, dw_stream_set;  // PMBRL_DW_STREAM=off | <steps streamed>[,<consumer workgroups>]
-  int dw_stream_steps, dw_stream_wgs; // (wgs 0: the plan's)
 };
 
-#define PM_PIPE_MAX 8
 struct pmbrl_plan {
   pmbrl_config cfg;
   PlanSwitches sw;
@@ -77,39 +74,10 @@ struct pmbrl_plan {
   int rew_k = PMBRL_MAX_TIP;   // tip residuals of the reward (which instance of the reward launch: pm_reward_kernel_for)
   int* wflag_d;        // weight-range flag of the fp16 packer (see RolloutArgs::wflag)
   int wgen;            // generation of the last forward call
-  int dw_split;        // dW GEMM on split bf16 operands (pm_dw_kernel_s)
   AngleDev* ang_d;
-  DwBlock* dw_blocks_d;
-  DwUnit* dw_units_d;   // 256 x 128 output tiles of the wide layers (pm_dw_wide_kernel); their blocks are not in dw_blocks_d
-  int n_dw_units;
-  int dw_narrow[PM_MAXL]; // 1: first-layer type (delta stash 512 wide), 2: head type (input stash 512 wide): pm_dw_narrow_pre_kernel
-  unsigned dw_pre_mask;   // layers whose dW GEMM reads pre-split stashes (pm_dw_wide_pre_kernel; the wide sweeps write them)
-  int dw_layer13;       // >= 0: this layer (at most 13 x 13 tiles) runs whole in one workgroup per row-step range (pm_dw_layer_kernel)
-  int n_dw_blocks, dw_nsplit, dw_chunks_per_split, dw_n_chunks;
-  DwArgs dw_args;       // what the dW GEMM's argument record holds of the plan (plan_dw); a call adds its workspace pointers and nvalid
-  // dW GEMM behind the adjoint sweep (pmbrl_rollout_bwd): the sweep as pipe_K launches over descending step
-  // ranges [pipe_lo[k], pipe_lo[k-1]); the GEMM of range k runs on pipe_stream, on the CUs the sweep leaves
-  // idle, while the sweep is in range k+1.  pipe_K <= 1: off.
-  int pipe_K, pipe_lo[PM_PIPE_MAX], pipe_rows, pipe_grid;
-  hipStream_t pipe_stream;
-  hipEvent_t pipe_ev[PM_PIPE_MAX];
-  // The second hidden layer's dW GEMM BESIDE the one-launch adjoint sweep (plan_dw_stream; DwArgs::st_on): st_wgs consumer
-  // workgroups on pipe_stream follow the sweep over the steps [st_cut, H) through the head gradients it publishes
-  // (off_pub: tagged granules, pub_gen their launch generation), the steps below the cut follow the sweep as before
-  int st_on, st_cut, st_wgs;
-  size_t off_pub, pub_bytes;
-  const void* pub_ws;         // the workspace whose granules hold no tag a later launch could take for its own (xch_prepare's rule)
-  mutable unsigned pub_gen;
-  int dw_streamed;            // the latest adjoint call took the streamed form (a note for the record, as dw_g1_rebuilt)
-  // ... with the policy head's dW / db formed by the consumers too (plan_dw_stream: every step streamed and the form not
-  // forced, or PMBRL_DW_HEAD); the block kernel of such a call walks the table without the head
-  int st_head, dw_head;       // the plan's form; the latest adjoint call took it (a note, as dw_streamed)
-  bool dw_skip[PM_MAXL];      // layers that are not the block kernels' (plan_dw)
-  DwBlock* dw_blocks_nh_d;
-  int n_dw_blocks_nh, dw_nh_ring, dw_wave_first_nh[PM_DW_NW + 1];
-  int dw_wave_first[PM_DW_NW + 1];
+  DwPlan dw;           // everything the plan decides about the policy's dW GEMM, and what it owns for it (pmbrl_dw_plan.h)
   // workspace offsets (bytes)
-  size_t off_actT[PM_MAXL], off_gT[PM_MAXL], off_Tp, off_Td, off_xt, off_rt, off_part, off_mmfac,
+  size_t off_actT[PM_MAXL], off_gT[PM_MAXL], off_Tp, off_Td, off_xt, off_rt, off_mmfac,
       off_gxc, off_gxc2, off_gsync, off_xch, xch_bytes, off_grt, off_Jx, off_Ja, off_gmm_c, off_gmm_k, ws_bytes;
   int wlds_off, lds_last_lanes;   // LDS-resident tiles (lds_tile_s): where they go (floats), lanes stored of the last K32 block
   const float* loss_w;   // pmbrl_plan_set_loss: dL/dr [H][B]; the forward call also leaves the loss in *loss_out
@@ -145,9 +113,6 @@ struct pmbrl_plan {
   size_t off_reg_ab[2][2];   // its activity words [net][hidden layer]: [step][workgroup][wave][lane] x 32 bits (pmbrl_reg.h)
   int abits_packed;      // the last forward call left the activity bits in that form only (pm_reg_unpack_abits: -> NetPlan::abits)
   int old_pack_stale;    // the last forward call packed the register-resident family's weights only
-  int dw_g1_rebuilt;     // the latest adjoint call's sweep ran on this family over its own forward stashes: gT[1] is NOT written,
-                         // that call's dW GEMM rebuilds the operand (dw_call_args hands it the inputs: DwArgs::rc_abits; a note for the record
-                         // a replayed call leaves behind, as abits_packed is -- the launches read DwArgs)
   // Replay (pmbrl_plan_set_replay): a call whose arguments equal the previous call's is recorded as a hipGraph the second
   // time it is seen and launched as one graph from then on.  Slot 0: pmbrl_rollout_fwd, slot 1: pmbrl_rollout_bwd(_adam).
   int replay;            // 0 off, 1 the one-launch-per-step forms, 2 every form
@@ -237,10 +202,15 @@ struct PackArgs {
 };
 void pm_pack_all_launch(const PackArgs& PK, hipStream_t s);   // (pmbrl.hip)
 
-// the dW GEMMs (pmbrl_dw.hip)
-int build_dw_blocks(int nl, const int* nt, std::vector<DwBlock>& blocks, int* wave_first, int tn_max = PM_DW_TN,
-                    const bool* skip = nullptr, int ot_parts_min = 1);
-int pm_dw_set_attr(const pmbrl_plan* p);
+// the dW GEMMs (pmbrl_dw.hip; the planner and build_dw_blocks: pmbrl_dw_plan.h)
+int pm_dw_plan_create(pmbrl_plan* p, int cus);   // plans (pm_dw_plan), uploads the tables, creates the second stream and the events
+void pm_dw_plan_destroy(pmbrl_plan* p);
+// a block table on the device (*out stays nullptr if it cannot be had) and in the argument record; also the BNN step's
+hipError_t pm_dw_upload_blocks(const std::vector<DwBlock>& blocks, DwBlock** out);
+void pm_dw_bind_blocks(DwArgs& W, const DwBlock* blocks_d, const int* wave_first);
+// a call's argument record: the plan's part + its stashes (A.actT / A.gT), partial rows and status word; rebuilt: the
+// call's sweep left no delta of the second hidden layer; streamed: the layer's GEMM runs beside the sweep
+DwArgs pm_dw_call_args(const pmbrl_plan* p, void* workspace, int32_t* status, const RolloutArgs& A, bool rebuilt, bool streamed);
 void pm_dw_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s, hipEvent_t after = nullptr);
 void pm_dw_stream_launch(const pmbrl_plan* p, const DwArgs& W, hipStream_t s);   // the streamed form's consumers
 void pm_dw_launch_range(const pmbrl_plan* p, const DwArgs& W, int k, hipStream_t s);   // launch k of the pipelined form
@@ -277,7 +247,6 @@ struct ZtabArgs;   // (pmbrl_mm.h: the noise table of split moment-matching grou
 void pm_reg_pack_launch(const pmbrl_plan* p, char* ws, const float* pol_params, const float* dyn_params, int* wflag, int gen,
                         hipStream_t s, int* status_reset, const ZtabArgs* ztab);
 void pm_reg_unpack_abits(const pmbrl_plan* p, char* ws, hipStream_t s);
-#define PM_REG_DW_LAYER 1      // the policy layer whose delta the family's adjoint does not stash: the second hidden one (200 x 200)
 void pm_reg_dw_rebuild_args(const pmbrl_plan* p, char* ws, DwArgs& W);   // what pm_dw_layer_rc_kernel reads of the family's workspace
 // (pub / pub_tag: the adjoint sweep publishes the policy head's gradient at this workspace offset -- RegArgs::pub; 0: no)
 void pm_reg_launch(const pmbrl_plan* p, char* ws, const RolloutArgs& A, const float* pol_params, const float* dyn_params,

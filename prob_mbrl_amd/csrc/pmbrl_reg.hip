@@ -138,7 +138,7 @@ bool pm_reg_can_run(const pmbrl_plan* p, const RolloutArgs& A, bool fwd) {
   if (!fwd && !p->sw.reg_bwd) return false;
   // (the adjoint sweep stashes no delta of the policy's second hidden layer: only behind the whole-layer dW kernel,
   //  which rebuilds it -- PMBRL_DW_NO_WIDE sends the adjoint to the other family)
-  if (!fwd && p->dw_layer13 != PM_REG_DW_LAYER) return false;
+  if (!fwd && p->dw.layer13 != PM_REG_DW_LAYER) return false;
   const bool ext = A.grad_states || A.grad_actions || A.agn || A.zpol_ss != 0 || A.zdyn_ss != 0 ||
                    (((A.flags & PMBRL_FLAG_MM_STATES) != 0) != (p->reg_mm != 0)) || A.t0 != 0 || A.t1 != A.H || A.gx_from_carry;
   if (p->reg_mm && p->mm_parts > 1 && !A.xch) return false;

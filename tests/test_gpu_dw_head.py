@@ -1,5 +1,5 @@
 """GPU (-m gpu): the policy HEAD's dW / db formed by the streamed consumers beside the one-launch adjoint sweep, and the
-reduction that reads the consumers' rows only (csrc/pmbrl.hip plan_dw_head, csrc/pmbrl_dw_kernels.h pm_dw_layer_body's head
+reduction that reads the consumers' rows only (csrc/pmbrl_dw_plan.h pm_dw_plan_head, csrc/pmbrl_dw_kernels.h pm_dw_layer_body's head
 phase and pm_dw_kernel_nh, csrc/pmbrl_tail.hip pm_dw_reduce's column range).  Every forced case runs with
 PMBRL_DW_STREAM=<H>[,<workgroups>] plus PMBRL_DW_HEAD=on and is compared with PMBRL_DW_STREAM=off on the same problem
 (tests/reg_envelope_cases.py; policy keep probability 0.9):

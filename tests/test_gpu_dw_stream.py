@@ -1,5 +1,5 @@
 """GPU (-m gpu): the dW GEMM of the policy's second hidden layer BESIDE the one-launch register-resident adjoint sweep
-(the streamed form: csrc/pmbrl.hip plan_dw_stream, csrc/pmbrl_dw_kernels.h pm_dw_layer_st_kernel, csrc/pmbrl_reg.h the
+(the streamed form: csrc/pmbrl_dw_plan.h pm_dw_plan_stream, csrc/pmbrl_dw_kernels.h pm_dw_layer_st_kernel, csrc/pmbrl_reg.h the
 publication of the policy head's gradient).  Every case is forced with PMBRL_DW_STREAM=<steps>[,<workgroups>] and compared
 with PMBRL_DW_STREAM=off on the same problem (tests/reg_envelope_cases.py; policy keep probability 0.9):
 
