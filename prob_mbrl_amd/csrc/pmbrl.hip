@@ -509,16 +509,19 @@ struct LayoutCalc {
   }
   // LDS of a workgroup: moment matching of mmd-wide states inside the sweep (0: none), groups split over `parts`
   // workgroups, in-place layers (general family)
+  // (latency-optimised family: its map, pmbrl_lds_map.h)
+  PmFastMap fast_map(int RT, int mmd, int parts = 1) const {
+    const pmbrl_config& c = p->cfg;
+    // in-kernel moment matching: one wave per whole group of the workgroup (a group split over `parts`
+    // workgroups: wave 0, and the whole group's rows in LDS)
+    const int mw = parts > 1 ? 1 : (mmd && p->M <= 16 * RT) ? std::min(PF_NW, std::max(1, 16 * RT / p->M)) : PF_NW;
+    return pm_fast_map(16 * RT, ld(RT), c.D, c.U, RT, p->pol.nt, p->pol.nl, p->dyn.nt, p->dyn.nl, mmd, prec(RT), mw,
+                       parts > 1 ? (parts > 8 ? 16 : p->M) : 0, parts > 1 ? c.H : 0);
+  }
   size_t lds(int RT, int mmd, int parts = 1, bool inplace = false) const {
     const pmbrl_config& c = p->cfg;
-    if (p->fast) {
-      // in-kernel moment matching: one wave per whole group of the workgroup (a group split over `parts`
-      // workgroups: wave 0, and the whole group's rows in LDS)
-      const int mw = parts > 1 ? 1 : (mmd && p->M <= 16 * RT) ? std::min(PF_NW, std::max(1, 16 * RT / p->M)) : PF_NW;
-      return pm_fast_lds_floats(16 * RT, ld(RT), c.D, c.U, RT, p->pol.nt, p->pol.nl, p->dyn.nt, p->dyn.nl, mmd, prec(RT),
-                                mw, parts > 1 ? (parts > 8 ? 16 : p->M) : 0, parts > 1 ? c.H : 0) * sizeof(float);
-    }
-    return pm_lds_floats(16 * RT, ld(RT), c.D, c.U, RT, mmd, inplace) * sizeof(float);
+    if (p->fast) return fast_map(RT, mmd, parts).total * sizeof(float);
+    return pm_lds_map(0, 16 * RT, ld(RT), c.D, c.U, RT, mmd, inplace).total * sizeof(float);
   }
 };
 
@@ -621,8 +624,7 @@ static int plan_groups(pmbrl_plan* p, LayoutCalc& L, int cus) {
   if (p->mm_mode == 2 && !p->span && !sw.mm_parts_set && shaped_mm1 && (c.flags & PMBRL_FLAG_MM_STATES) && sw.mm_tree) {
     const int parts = (p->M + 15) / 16;
     if (parts > 8 && (long long)p->G * parts <= max_wg && L.ld(1) == 240) {
-      const size_t tiles = (size_t)PF_NW * pm_lds_tile_floats(14, 2, 16 * ((16 * 13 - 32 * 6) / 8)) * sizeof(float);
-      if (L.lds(1, c.D, parts) + tiles + 16 <= PM_LDS_CAP) {
+      if (L.lds(1, c.D, parts) + pm_lds_tiles_bytes(13) + 16 <= PM_LDS_CAP) {      // (the tiles of 13 hidden tiles)
         p->mm_mode = 1;
         p->mm_parts = parts;
         p->RT = 1;
@@ -729,7 +731,8 @@ static int plan_layout(pmbrl_plan* p, int cus) {
       (size_t)2 * 16 * p->RT * L.ld(p->RT) * sizeof(float) >= (size_t)8 * 256 * sizeof(double))
     p->mm_mode = 3;
   p->LD = L.ld(p->RT);
-  p->lds_bytes = L.lds(p->RT, (p->mm_mode == 1 || p->mm_mode == 3) ? c.D : 0, p->mm_parts, p->inplace != 0);
+  int mmd = (p->mm_mode == 1 || p->mm_mode == 3) ? c.D : 0;      // moment matching inside the sweep: of states this wide
+  p->lds_bytes = L.lds(p->RT, mmd, p->mm_parts, p->inplace != 0);
   const StagePair sp = L.stages(p->RT);
   p->CA = sp.ca;
   p->CB = sp.cb;
@@ -754,7 +757,8 @@ static int plan_layout(pmbrl_plan* p, int cus) {
     p->cfg.mm_span_ranks = 1;
     p->cfg.mm_span_rank = 0;
     p->mm_mode = 2;
-    p->lds_bytes = L.lds(p->RT, 0);
+    mmd = 0;
+    p->lds_bytes = L.lds(p->RT, mmd);
   }
 
   // LDS-resident tiles of the sweeps' second streamed layer (pmbrl_fast.h, lds_tile_s): the shape-specialised 16-row
@@ -764,21 +768,13 @@ static int plan_layout(pmbrl_plan* p, int cus) {
   const int ht = hidden_tiles_3l(p);
   if (p->fast && p->RT == 1 && p->prec == PMBRL_PREC_SPLIT_F16 && p->CA + p->CB == 7 && (ht == 13 || ht == 14) &&
       !(c.flags & PMBRL_FLAG_NO_SHAPED) && sw.lds_tiles) {
-    const int last_lanes = 16 * ((16 * ht - 32 * 6) / 8);
-    size_t base = (p->lds_bytes + 15) / 16 * 16;
-    if (p->mm_parts > 1) {
-      // split groups: the instances that hold the tiles exchange sums and never touch the row blocks of the rows +
-      // flags form, the generic instances that use those never copy tiles: the two share the end of the LDS (a
-      // 100-row group in seven parts would not fit both)
-      const int mw = 1;
-      base = pm_fast_rows_area_off(16 * p->RT, p->LD, c.D, c.U, p->RT, p->pol.nt, p->pol.nl, p->dyn.nt, p->dyn.nl, c.D,
-                                   p->prec, mw, p->mm_parts > 8 ? 16 : p->M, c.H) * sizeof(float);
-      base = (base + 15) / 16 * 16;
-    }
-    const size_t tiles = (size_t)PF_NW * pm_lds_tile_floats(14, 2, last_lanes) * sizeof(float);
+    // behind everything else; split groups: the instances that hold the tiles exchange sums and never touch the row
+    // blocks of the rows + flags form, the generic instances that use those never copy tiles: the two share the end
+    // of the LDS (a 100-row group in seven parts would not fit both) -- the map's tile_base either way
+    const size_t base = L.fast_map(p->RT, mmd, p->mm_parts).m.tile_base * sizeof(float), tiles = pm_lds_tiles_bytes(ht);
     if (base + tiles <= PM_LDS_CAP) {
       p->wlds_off = (int)(base / sizeof(float));
-      p->lds_last_lanes = last_lanes;
+      p->lds_last_lanes = pm_lds_tile_last_lanes(ht);
       p->lds_bytes = std::max(p->lds_bytes, base + tiles);
     }
   }
@@ -1373,7 +1369,7 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
   A.xch = p->xch_bytes ? reinterpret_cast<unsigned long long*>(ws + p->off_xch) : nullptr;
   A.gx_carry_out = nullptr;
   if (p->fast) {
-    // weight streams (hidden->hidden layers) and LDS offsets: same walk as pm_fast_carve
+    // weight streams (hidden->hidden layers) and the per-layer LDS offsets
     const NetDev& P = A.pol;
     const NetDev& F = A.dyn;
     const int pm = p->CA + p->CB;
@@ -1402,13 +1398,11 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
     b.n = 0;
     for (int l = F.nl - 2; l >= 1; --l) add_stream(b, F.wb[l], F.nt[l], F.nt[l + 1], twb);
     for (int l = P.nl - 2; l >= 1; --l) add_stream(b, P.wb[l], P.nt[l], P.nt[l + 1], twb);
-    const size_t R = 16 * (size_t)p->RT;
-    size_t o = 2 * R * p->LD + 2 * R * c.D + R * c.U + R * 16 + 2 * R +
-               (pm_fast_hp_alias((int)R, p->LD, p->RT) ? 0 : (size_t)PF_NW * p->RT * 256);   // up to and incl. the hp region
-    for (int l = 0; l < P.nl; ++l) { A.fo.pbias[l] = (int)o; o += (size_t)P.nt[l + 1] * 16; }
-    for (int l = 0; l < F.nl; ++l) { A.fo.dbias[l] = (int)o; o += (size_t)F.nt[l + 1] * 16; }
-    for (int l = 0; l < P.nl - 1; ++l) { A.fo.pmask[l] = (int)o; o += (R * P.nt[l + 1] + 1) / 2; }
-    for (int l = 0; l < F.nl - 1; ++l) { A.fo.dmask[l] = (int)o; o += (R * F.nt[l + 1] + 1) / 2; }
+    const PmFastMap m = pm_fast_map(16 * p->RT, p->LD, c.D, c.U, p->RT, P.nt, P.nl, F.nt, F.nl, 0, p->prec);
+    for (int l = 0; l < P.nl; ++l) A.fo.pbias[l] = (int)m.pbias[l];
+    for (int l = 0; l < F.nl; ++l) A.fo.dbias[l] = (int)m.dbias[l];
+    for (int l = 0; l < P.nl - 1; ++l) A.fo.pmask[l] = (int)m.pmask[l];
+    for (int l = 0; l < F.nl - 1; ++l) A.fo.dmask[l] = (int)m.dmask[l];
   }
   if (in->pol_params_d && in->dyn_params_d) {
     A.pol_head_w = in->pol_params_d + p->pol.w_off[p->pol.nl - 1];

@@ -21,11 +21,9 @@
 #include <stdint.h>
 
 #include "pmbrl.h"
+#include "pmbrl_lds_map.h"      // PM_NW, PM_KS_NT and every other constant the LDS maps are made of
 
-#define PM_NW 8                 // waves per workgroup (two per SIMD)
 #define PM_NT (PM_NW * 64)      // threads per workgroup
-#define PM_MAXL PMBRL_MAX_LAYERS
-#define PM_KS_NT 3              // max out tiles handled by the K-split GEMM (< PM_NW)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -87,7 +85,7 @@ struct StreamDesc {
   // tw_off = offset (floats) of its LDS-resident weight k-blocks, n_kb_real = unpadded K blocks
   int ks[2 * PM_MAXL], tw_off[2 * PM_MAXL], n_kb_real[2 * PM_MAXL];
 };
-// LDS offsets (floats) of the per-layer regions of the fast kernels
+// LDS offsets (floats) of the per-layer regions of the fast kernels (from pm_fast_map, pmbrl_lds_map.h)
 struct FastOff {
   int pbias[PM_MAXL], dbias[PM_MAXL], pmask[PM_MAXL], dmask[PM_MAXL];
 };
@@ -173,6 +171,7 @@ struct RolloutArgs {
   FastOff fo;
   long long* prof;              // debug: cycle stamps [H][32] of workgroup 0 (nullptr = off)
 };
+static_assert(sizeof(RolloutArgs) == 2648, "RolloutArgs is a kernel argument: its layout does not move");
 
 #include "pmbrl_instances.h"   // PF_VAR_*: the kernel variants of the latency-optimised family (pmbrl_fast.h)
 
@@ -349,15 +348,8 @@ __device__ __forceinline__ void gemm_tiles(const float* __restrict__ wf, int n_o
 // partial tiles meet in LDS (`part`, [NW][PM_KS_NT][RT][64][4] floats) and are
 // summed in fixed wave order (deterministic) by gemm_ksplit_combine.
 // ---------------------------------------------------------------------------
-// Where the partial tiles live: a dedicated LDS region (`part`), or -- wide networks, where LDS is
-// what limits the workgroups per CU -- the columns >= 16 * PM_KS_NT of the OUTPUT buffer's rows,
-// which a narrow GEMM leaves untouched (`part` == nullptr, `alias` = that buffer; element e of the
-// region sits at row e / W, column 16 * PM_KS_NT + e % W with W = the free columns rounded down to 4).
-__host__ __device__ inline int pm_part_alias_w(int ld) { return (ld - 16 * PM_KS_NT) & ~3; }
-__host__ __device__ inline bool pm_part_alias_ok(int R, int ld, int RT) {
-  const int w = pm_part_alias_w(ld);
-  return w > 0 && (size_t)R * w >= (size_t)PM_NW * PM_KS_NT * RT * 256;
-}
+// Where the partial tiles live: a dedicated LDS region (`part`), or the free columns of the OUTPUT buffer's rows
+// (`part` == nullptr, `alias` = that buffer): pm_part_alias_ok / pm_part_alias_w, pmbrl_lds_map.h.
 __device__ __forceinline__ float* pm_part_at(float* part, float* alias, int ld, int e) {
   if (part) return part + e;
   const int w = pm_part_alias_w(ld);

@@ -37,39 +37,12 @@
 // The fast kernels run EIGHT waves per workgroup (two per SIMD): the two co-resident waves
 // of a SIMD share its MFMA pipe, so one wave's LDS / weight-load waits and epilogue overlap
 // the other's MFMAs.  Tile ot of a layer belongs to wave ot % 8.
-#define PF_NW 8
+// (PF_NW: pmbrl_lds_map.h)
 #define PF_NT (PF_NW * 64)
 #define PM_L0T 2           // max resident first-layer tiles per wave (<= 16 tiles per layer)
 #define PM_HJ 16           // max fused head / tail width
 
-// Tile balance: tile ot runs on wave ot mod 8, i.e. SIMD ot mod 4.  A layer with 4m+1 output
-// tiles (13 for a 200-wide layer) would put m+1 tiles on SIMD 0 and m on the others: the phase
-// then lasts as long as SIMD 0's extra tile (+25 % at m = 3).  Instead the LAST tile of such a
-// layer is K-split over all 8 waves (<= 2 k-blocks each, weights LDS-resident for the launch):
-// every wave adds its partial tile to LDS at the START of the phase and bumps a counter; the
-// last wave, which owns at most one regular tile, waits for the 8 partials after its tile,
-// sums them in fixed order and runs the tile's normal epilogue before the phase barrier.
-// (not with 64-row workgroups: LDS is the constraint there)
-// (split-bf16 precision: the tiles are short enough that the imbalance costs less than the K-split's
-// partial / gather round trip -- every tile is a regular tile there)
-__host__ __device__ constexpr bool pm_fast_ksplit(int n_ot, int RT, int prec = 0) {
-  return !prec && RT < 4 && n_ot >= 5 && (n_ot % 4) == 1;
-}
-// LDS floats for the K-split tail weights of one sweep direction (bwd: transposed layers)
-__host__ __device__ inline size_t pm_fast_tail_floats(const int* pnt, int pnl, const int* dnt, int dnl,
-                                                      bool bwd, int RT, int prec = 0) {
-  size_t n = 0;
-  if (prec) return 0;
-  for (int l = 1; l <= pnl - 2; ++l) {
-    const int n_ot = bwd ? pnt[l] : pnt[l + 1], n_kb = bwd ? pnt[l + 1] : pnt[l];
-    if (pm_fast_ksplit(n_ot, RT)) n += (size_t)n_kb * 256;
-  }
-  for (int l = 1; l <= dnl - 2; ++l) {
-    const int n_ot = bwd ? dnt[l] : dnt[l + 1], n_kb = bwd ? dnt[l + 1] : dnt[l];
-    if (pm_fast_ksplit(n_ot, RT)) n += (size_t)n_kb * 256;
-  }
-  return n;
-}
+// (Tile balance -- the K-split of a layer's last output tile, pm_fast_ksplit / pm_fast_tail_floats: pmbrl_lds_map.h)
 
 __host__ __device__ inline bool pm_fast_net_ok(const int* dim, const int* nt, int nl) {
   if (nl < 2) return false;
@@ -592,10 +565,7 @@ __device__ __forceinline__ void lds_tile_s(const float* wl, int last_lanes, cons
     epi(ot, rt, pm_chains_sum<F16, NP>(acc[0][rt], acc[1][rt]), pre[rt]);
   }
 }
-// floats of one such tile in LDS
-__host__ __device__ inline size_t pm_lds_tile_floats(int n_loads, int np, int last_lanes) {
-  return (size_t)(n_loads - np) * 256 + (size_t)np * last_lanes * 4;
-}
+// (floats of one such tile in LDS, and where the tiles go: pm_lds_tile_floats / pm_lds_tile_at, pmbrl_lds_map.h)
 
 // Register-resident single-k-block layer (first layer forward / head adjoint backward).
 template <int RT>
@@ -932,6 +902,7 @@ struct EpiBwdL {
 // LDS map of the fast kernels
 // ---------------------------------------------------------------------------
 struct FastLds {
+  static constexpr bool kLayers = false;      // (the per-layer regions: offsets in the kernel arguments, FastOff)
   float *bufA, *bufB, *xa, *xb, *av, *gad, *rr, *gr;
   int hp_off;                    // head / tail partial tiles [PF_NW][RT][64][4]: offset from bufA, or -1 when
                                  // they live in whichever activation buffer is idle (pm_fast_hp_alias)
@@ -948,115 +919,11 @@ struct FastLds {
   double* mm;
 };
 
-// The partial head tiles are written while one activation buffer (the head's input) is being
-// read and the other is dead: when that buffer is large enough they live there and cost no LDS.
-__host__ __device__ inline bool pm_fast_hp_alias(int R, int LD, int RT) {
-  return RT >= 4 && (size_t)R * LD >= (size_t)PF_NW * RT * 256;   // only where LDS is the constraint (64-row workgroups)
-}
-
-#define PM_XIN_LD 24             // = 8 (mod 16): conflict-free ds_read_b128 of the MFMA B operand
-// LDS of the statistics exchange of split groups (behind wave 0's moment-matching scratch): the reference point (8),
-// the z standardisation [zm | zi] of every step of the launch, and two staging sets, alternating between steps, of
-// what wave 1 fetches a step ahead while wave 0 works -- the part's noise rows (forward sweep); scratch with the
-// factor, the part's pre-mm rows and noise rows (adjoint).  A multiple of 4 floats.
-__host__ __device__ inline size_t pm_fast_xch_floats(int R, int d, int steps) {
-  const size_t n = 8 + 2 * (size_t)steps * 2 * d + 2 * (2 * pm_mm_scratch_doubles(d) + 2 * (size_t)R * d);
-  return (n + 3) & ~(size_t)3;
-}
-__host__ __device__ inline size_t pm_fast_lds_floats(int R, int LD, int D, int U, int RT,
-                                                     const int* pnt, int pnl, const int* dnt,
-                                                     int dnl, int mm_d, int prec = 0, int mm_waves = PF_NW,
-                                                     int mm_group_rows = 0, int mm_steps = 0) {
-  // (mm_waves: waves that do in-kernel moment matching at once = whole groups per workgroup, at most PF_NW;
-  //  mm_group_rows: rows of a group split over workgroups -- four row blocks of the whole group behind L.mm)
-  size_t n = 2 * (size_t)R * LD + 2 * (size_t)R * D + (size_t)R * U + (size_t)R * 16 + 2 * (size_t)R;
-  if (!pm_fast_hp_alias(R, LD, RT)) n += (size_t)PF_NW * RT * 256;
-  for (int l = 0; l < pnl; ++l) n += (size_t)pnt[l + 1] * 16;
-  for (int l = 0; l < dnl; ++l) n += (size_t)dnt[l + 1] * 16;
-  for (int l = 0; l < pnl - 1; ++l) n += ((size_t)R * pnt[l + 1] + 1) / 2;
-  for (int l = 0; l < dnl - 1; ++l) n += ((size_t)R * dnt[l + 1] + 1) / 2;
-  n += (size_t)R * U + (size_t)R * D;                 // zp, zd
-  n += 2 * (size_t)(D + U) + 3 * (size_t)D + 2 * (size_t)U;
-  n = (n + 3) & ~(size_t)3;
-  n += (size_t)R * 16 + (size_t)R * (1 + 2 * D + 3 * U) + (size_t)R * D;   // jx, stg, zs
-  n = (n + 3) & ~(size_t)3;
-  if (prec) n += (size_t)R * PM_XIN_LD + 4;                                 // xin, ovf
-  {
-    const size_t tf = pm_fast_tail_floats(pnt, pnl, dnt, dnl, false, RT, prec), tb = pm_fast_tail_floats(pnt, pnl, dnt, dnl, true, RT, prec);
-    const size_t tw = tf > tb ? tf : tb;
-    if (tw) n += (size_t)PF_NW * RT * 256 + 4 + tw;   // tp, tcnt, tw
-  }
-  n += 2 * (size_t)mm_waves * pm_mm_scratch_doubles(mm_d);
-  // split groups: what the statistics exchange keeps (pm_fast_xch_floats), then -- LAST, so that the LDS-resident weight
-  // tiles of the instances that never exchange rows can take its place (pm_fast_rows_area_off) -- four row blocks of
-  // the whole group for the rows + flags form
-  if (mm_group_rows) n += pm_fast_xch_floats(R, mm_d, mm_steps) + 4 * (size_t)mm_group_rows * mm_d;
-  return n;
-}
-// where the row blocks of the rows + flags form start (floats from the LDS base)
-__host__ __device__ inline size_t pm_fast_rows_area_off(int R, int LD, int D, int U, int RT, const int* pnt, int pnl,
-                                                        const int* dnt, int dnl, int mm_d, int prec, int mm_waves,
-                                                        int mm_group_rows, int mm_steps) {
-  return pm_fast_lds_floats(R, LD, D, U, RT, pnt, pnl, dnt, dnl, mm_d, prec, mm_waves, mm_group_rows, mm_steps) -
-         4 * (size_t)mm_group_rows * mm_d;
-}
-
-// (pnt / dnt: 16-wide tile counts of layer inputs / outputs, nl + 1 entries each)
-__device__ __forceinline__ FastLds pm_fast_carve(float* base, int R, int LD, int D, int U, int RT,
-                                                 const int* pnt, int pnl, const int* dnt, int dnl, int prec = 0) {
-  FastLds m;
-  float* p = base;
-  m.bufA = p; p += (size_t)R * LD;
-  m.bufB = p; p += (size_t)R * LD;
-  m.xa = p; p += (size_t)R * D;
-  m.xb = p; p += (size_t)R * D;
-  m.av = p; p += (size_t)R * U;
-  m.gad = p; p += (size_t)R * 16;
-  m.rr = p; p += R;
-  m.gr = p; p += R;
-  m.hp_off = -1;
-  if (!pm_fast_hp_alias(R, LD, RT)) {
-    m.hp_off = (int)(p - base);
-    p += (size_t)PF_NW * RT * 256;
-  }
-  m.base = base;
-  for (int l = 0; l < pnl; ++l) p += (size_t)pnt[l + 1] * 16;
-  for (int l = 0; l < dnl; ++l) p += (size_t)dnt[l + 1] * 16;
-  for (int l = 0; l < pnl - 1; ++l) p += ((size_t)R * pnt[l + 1] + 1) / 2;
-  for (int l = 0; l < dnl - 1; ++l) p += ((size_t)R * dnt[l + 1] + 1) / 2;
-  m.zp = p; p += (size_t)R * U;
-  m.zd = p; p += (size_t)R * D;
-  m.mx = p; p += D + U;
-  m.iSx = p; p += D + U;
-  m.my = p; p += D;
-  m.Sy = p; p += D;
-  m.lSy = p; p += D;
-  m.psc = p; p += U;
-  m.pbi = p; p += U;
-  size_t n = ((size_t)(p - base) + 3) & ~(size_t)3;
-  p = base + n;
-  m.jx = p; p += (size_t)R * 16;
-  m.stg = p; p += (size_t)R * (1 + 2 * D + 3 * U);
-  m.zs = p; p += (size_t)R * D;
-  n = ((size_t)(p - base) + 3) & ~(size_t)3;
-  p = base + n;
-  m.xin = p;
-  m.ovf = reinterpret_cast<int*>(p + (size_t)R * PM_XIN_LD);
-  if (prec) p += (size_t)R * PM_XIN_LD + 4;
-  {
-    const size_t tf = pm_fast_tail_floats(pnt, pnl, dnt, dnl, false, RT, prec), tb = pm_fast_tail_floats(pnt, pnl, dnt, dnl, true, RT, prec);
-    const size_t tw = tf > tb ? tf : tb;
-    m.tp = p;
-    m.tcnt = reinterpret_cast<int*>(p + (size_t)PF_NW * RT * 256);
-    m.tw = p + (size_t)PF_NW * RT * 256 + 4;
-    if (tw) p += (size_t)PF_NW * RT * 256 + 4 + tw;
-  }
-  m.mm = reinterpret_cast<double*>(p);
-  return m;
-}
+// the walk over the list of regions that fills it: pm_fast_walk, pmbrl_lds_map.h (the host's record of the same walk,
+// PmFastMap, gives the launch's size and the per-layer offsets)
 __device__ __forceinline__ FastLds pm_fast_carve(float* base, int R, int LD, int D, int U, int RT,
                                                  const NetDev& P, const NetDev& F, int prec = 0) {
-  return pm_fast_carve(base, R, LD, D, U, RT, P.nt, P.nl, F.nt, F.nl, prec);
+  return pm_fast_walk<FastLds>(base, R, LD, D, U, RT, P.nt, P.nl, F.nt, F.nl, prec);
 }
 // shape-specialised kernels: the whole carve-up from compile-time constants (-> immediate
 // LDS offsets); layer widths 1 | NT ... NT | 1 tiles
@@ -1067,14 +934,18 @@ __device__ __forceinline__ FastLds pm_fast_carve_shaped(float* base, const NetDe
     int nt[PM_MAXL + 1];
 #pragma unroll
     for (int l = 0; l <= PM_MAXL; ++l) nt[l] = (l == 0 || l >= SH::NL) ? 1 : SH::NT;
-    return pm_fast_carve(base, R, LD, D, U, RT, nt, SH::NL, nt, SH::NL, PR);
+    return pm_fast_walk<FastLds>(base, R, LD, D, U, RT, nt, SH::NL, nt, SH::NL, PR);
   } else {
     return pm_fast_carve(base, R, LD, D, U, RT, P, F, PR);
   }
 }
+// the moment-matching areas of a sweep whose groups are whole (pair false) or split over workgroups: behind L.mm
+__device__ __forceinline__ PmMmAreasT<float*> pm_fast_mm_areas(const FastLds& L, int R, int D, bool pair, int M, int H) {
+  return pm_fast_mm_areas(L.base, reinterpret_cast<float*>(L.mm), R, D, 1, pair ? M : 0, H);
+}
 
 // per-layer LDS regions: offsets (in floats from the LDS base) live in the kernel
-// arguments (FastOff, filled on the host with the same walk as pm_fast_carve) so that a
+// arguments (FastOff, filled on the host from the same map as pm_fast_carve) so that a
 // runtime layer index becomes a scalar load, not a private-memory array access
 #define PBIAS(l) (L.base + A.fo.pbias[l])
 #define DBIAS(l) (L.base + A.fo.dbias[l])
@@ -1481,7 +1352,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_fwd_fast(const RolloutArg
   const float* wlds = nullptr;
   if constexpr (LDSK) {
     constexpr int NLD = (CA + CB) * NP;
-    float* dst = smem + A.wlds_off + (size_t)wid * pm_lds_tile_floats(NLD, NP, A.lds_last_lanes);
+    float* dst = pm_lds_tile_at(smem, A.wlds_off, wid, NLD, NP, A.lds_last_lanes);
     const float* src = A.lds_w + (size_t)wid * NLD * 256;
     for (int i = 0; i < NLD - NP; ++i)
       *reinterpret_cast<f32x4*>(dst + (size_t)i * 256 + lane * 4) = ldg4(src + (size_t)i * 256 + lane * 4);
@@ -1506,14 +1377,18 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_fwd_fast(const RolloutArg
   const int mmp_first = mm_pair ? (wg / A.mm_parts) * A.mm_parts : 0;
   const int mmp_g0 = mm_pair ? (wg / A.mm_parts) * A.M : 0;
   // LDS behind wave 0's scratch: the statistics exchange's (mmx), then the row blocks of the rows + flags form (mmg)
-  float* const mmx = reinterpret_cast<float*>(L.mm + pm_mm_scratch_doubles(D));
-  float* const mmg = mmx + (mm_pair ? pm_fast_xch_floats(R, D, A.H) : 0);
+  // (the map's: pm_fast_mm_areas, pmbrl_lds_map.h; only this variant has them)
+  const PmMmAreasT<float*> MA = VAR == PF_VAR_MM ? pm_fast_mm_areas(L, R, D, mm_pair, A.M, A.H) : PmMmAreasT<float*>{};
+  float* const mmx = MA.xch;
+  auto mmg = [&](int k) { return pm_mm_rows_block(MA, k); };      // row block k: [M][D]
   // (statistics exchange: the first reference point is the group's first row, which every part can read)
   if (mm_xch && tid < D) mmx[tid] = ((T0 == 0) ? A.x0 : A.states + (size_t)T0 * B * D)[(size_t)mmp_g0 * D + tid];
   // ... and the standardisation of the group's noise rows, mean and 1 / std per column, for every step of the launch
   // (the noise is an input: nothing of it waits for the recursion)
-  double* const mmzt = reinterpret_cast<double*>(mmx + 8);      // [T1 - T0][zm (D) | zi (D)]
+  double* const mmzt = reinterpret_cast<double*>(MA.xch_zt);      // [T1 - T0][zm (D) | zi (D)]
   // this part's noise rows, two sets [R][D] (step t in set t & 1): fetched a step ahead by wave 1 while wave 0 works
+  // (= MA.xch_sets, formed HERE on purpose: taken from the map, this one value moves the register allocation of the
+  //  forward kernels of every variant -- DESIGN_LOG.md, "One LDS map per sweep family")
   float* const mmzs = reinterpret_cast<float*>(mmzt + (size_t)A.H * 2 * D);
   if (mm_xch) {
     {
@@ -1620,7 +1495,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_fwd_fast(const RolloutArg
           const int z0 = pm_zrow0(t, A.row_off + mmp_g0, A.flags);
           for (int i = tid; i < A.M * D; i += PF_NT) {
             const int r = i / D, d = i - r * D;
-            mmg[A.M * D + i] = zb[(size_t)pm_zidx(z0, r, A.Bg) * D + d];
+            mmg(1)[i] = zb[(size_t)pm_zidx(z0, r, A.Bg) * D + d];
           }
         } else {
         const int z0 = pm_zrow0(t, A.row_off + row0, A.flags);
@@ -1845,7 +1720,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_fwd_fast(const RolloutArg
       if (!pm_group_sync(A.gsync, wg, mmp_first, A.mm_parts, (unsigned)(t - T0 + 1)) && tid == 0) atomicMin(A.status, t);
       PF_MARK(28);
       const float* xg = A.xt + ((size_t)t * B + mmp_g0) * D;
-      for (int i = tid; i < A.M * D; i += PF_NT) mmg[i] = pm_ldc<true>(xg + i);
+      for (int i = tid; i < A.M * D; i += PF_NT) mmg(0)[i] = pm_ldc<true>(xg + i);
       __syncthreads();
       PF_MARK(29);
       if (wid == 0) {
@@ -1853,14 +1728,14 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_fwd_fast(const RolloutArg
         double* fac = wg == mmp_first ? A.mmfac + ((size_t)t * A.mmfac_groups + mmp_g0 / A.M) * pm_mm_fac_doubles(D) : nullptr;
         // (the compile-time-width routines keep one row per lane: groups of up to 64 rows)
         if (SH::D >= 1 && SH::D <= 6 && A.M <= 64)
-          ok = pm_mm_fwd_w<(SH::D >= 1 && SH::D <= 6) ? SH::D : 1>(mmg, D, A.M, mmg + A.M * D, D, mmg + 2 * A.M * D, D, lane, fac);
+          ok = pm_mm_fwd_w<(SH::D >= 1 && SH::D <= 6) ? SH::D : 1>(mmg(0), D, A.M, mmg(1), D, mmg(2), D, lane, fac);
         else
-          ok = pm_mm_fwd(mmg, D, A.M, D, mmg + A.M * D, D, 0, 0, false, mmg + 2 * A.M * D, D, L.mm, lane, fac);
+          ok = pm_mm_fwd(mmg(0), D, A.M, D, mmg(1), D, 0, 0, false, mmg(2), D, L.mm, lane, fac);
         if (!ok && lane == 0) atomicMin(A.status, t);
       }
       __syncthreads();
       PF_MARK(30);
-      const float* res = mmg + 2 * A.M * D + (row0 - mmp_g0) * D;
+      const float* res = mmg(2) + (row0 - mmp_g0) * D;
       for (int i = tid; i < nvalid * D; i += PF_NT) {
         xa[i] = res[i];
         A.states[((size_t)(t + 1) * B + row0) * D + i] = res[i];
@@ -1871,7 +1746,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_fwd_fast(const RolloutArg
       for (int gi = wid; gi < gpw; gi += PF_NW) {
         const int lr0 = gi * A.M;
         if (lr0 >= nvalid) break;
-        double* scr = L.mm + (size_t)wid * pm_mm_scratch_doubles(D);
+        double* scr = pm_mm_scratch_of(L.mm, wid, D);
         bool ok;
         if constexpr (SH::D >= 1 && SH::D <= 6) {
           // compile-time width: Gram tile on the fp64 matrix core, d x d algebra in registers (pmbrl_mm_w.h)
@@ -2065,7 +1940,7 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_bwd_fast(const RolloutArg
   const float* wlds = nullptr;
   if constexpr (LDSK) {
     constexpr int NLD = (CA + CB) * NP;
-    float* dst = smem + A.wlds_off + (size_t)wid * pm_lds_tile_floats(NLD, NP, A.lds_last_lanes);
+    float* dst = pm_lds_tile_at(smem, A.wlds_off, wid, NLD, NP, A.lds_last_lanes);
     const float* src = A.lds_w + (size_t)wid * NLD * 256;
     for (int i = 0; i < NLD - NP; ++i)
       *reinterpret_cast<f32x4*>(dst + (size_t)i * 256 + lane * 4) = ldg4(src + (size_t)i * 256 + lane * 4);
@@ -2142,19 +2017,18 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_bwd_fast(const RolloutArg
   const bool mm_xch = mm_pair && XW && (A.xch != nullptr);
   const int mmp_first = mm_pair ? (wg / A.mm_parts) * A.mm_parts : 0;
   const int mmp_g0 = mm_pair ? (wg / A.mm_parts) * A.M : 0;
-  float* const mmx = reinterpret_cast<float*>(L.mm + pm_mm_scratch_doubles(D));      // (layout: see the forward sweep)
-  float* const mmg = mmx + (mm_pair ? pm_fast_xch_floats(R, D, A.H) : 0);
+  const PmMmAreasT<float*> MA = VAR == PF_VAR_MM ? pm_fast_mm_areas(L, R, D, mm_pair, A.M, A.H) : PmMmAreasT<float*>{};      // (layout: see the forward sweep)
+  float* const mmx = MA.xch;
+  auto mmg = [&](int k) { return pm_mm_rows_block(MA, k); };      // row block k: [M][D]
   // statistics exchange: two staging sets (step t in set t & 1) of [scratch with the forward sweep's factor | this
   // part's pre-mm rows [R][D] | its noise rows [R][D]], fetched a step ahead by wave 1 while wave 0 works
-  const size_t mmst_set = 2 * pm_mm_scratch_doubles(D) + 2 * (size_t)R * D;      // floats
-  float* const mmst = mmx + 8 + 2 * (size_t)A.H * 2 * D;
   auto mm_stage = [&](int ts, int i0, int istep) {
-    float* set = mmst + (size_t)(ts & 1) * mmst_set;
+    float* set = pm_mm_xch_set(MA, ts & 1);
     double* fdst = reinterpret_cast<double*>(set);
     const double* fac = A.mmfac + ((size_t)ts * A.mmfac_groups + mmp_g0 / A.M) * pm_mm_fac_doubles(D);
     for (int e = i0; e < (int)pm_mm_fac_doubles(D); e += istep) fdst[e] = fac[e];
-    float* xdst = set + 2 * pm_mm_scratch_doubles(D);
-    float* zdst = xdst + R * D;
+    float* xdst = set + MA.xch_set_rows;
+    float* zdst = xdst + MA.xch_zset;
     const float* xsrc = A.xt + ((size_t)ts * B + row0) * D;
     const float* zb = pm_zbase(A.zmm, D, ts, A.Bg, A.flags);
     const int z0 = pm_zrow0(ts, A.row_off + mmp_g0, A.flags);
@@ -2236,9 +2110,9 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_bwd_fast(const RolloutArg
       // for its own rows.  What comes from HBM (the factor, this part's pre-mm rows and noise rows) was staged during
       // the previous step's moment matching by wave 1, which has nothing else to do then.
       constexpr int DDc = (SH::D >= 1 && SH::D <= 6) ? SH::D : 1;
-      float* const set = mmst + (size_t)(t & 1) * mmst_set;
-      float* const xst = set + 2 * pm_mm_scratch_doubles(D);      // this part's pre-mm rows [nvalid][D]
-      float* const zst = xst + R * D;                             // its noise rows of step t
+      float* const set = pm_mm_xch_set(MA, t & 1);
+      float* const xst = set + MA.xch_set_rows;      // this part's pre-mm rows [nvalid][D]
+      float* const zst = xst + MA.xch_zset;          // its noise rows of step t
       __syncthreads();          // dL/dx_{t+1} of this part's rows (gx) is complete
       PF_MARK(28);
       if (wid == 1 && t > T0) mm_stage(t - 1, lane, 64);      // (idle otherwise) what step t - 1 will need from HBM
@@ -2303,27 +2177,27 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_bwd_fast(const RolloutArg
         const int z0 = pm_zrow0(t, A.row_off + mmp_g0, A.flags);
         for (int i = tid; i < A.M * D; i += PF_NT) {
           const int r = i / D, d = i - r * D;
-          mmg[i] = xsrc[i];
-          mmg[A.M * D + i] = zb[(size_t)pm_zidx(z0, r, A.Bg) * D + d];
+          mmg(0)[i] = xsrc[i];
+          mmg(1)[i] = zb[(size_t)pm_zidx(z0, r, A.Bg) * D + d];
         }
         const double* fac = A.mmfac + ((size_t)t * A.mmfac_groups + mmp_g0 / A.M) * pm_mm_fac_doubles(D);
         if (SH::D >= 1 && SH::D <= 6 && A.M <= 64 && wid == 0)
           for (int e = lane; e < (int)pm_mm_fac_doubles(D); e += 64) L.mm[e] = fac[e];
       }
       if (!pm_group_sync(A.gsync, wg, mmp_first, A.mm_parts, (unsigned)(T1 - t)) && tid == 0 && A.status) atomicMax(A.status, 1);
-      for (int i = tid; i < A.M * D; i += PF_NT) mmg[2 * A.M * D + i] = pm_ldc<true>(carry + (size_t)mmp_g0 * D + i);
+      for (int i = tid; i < A.M * D; i += PF_NT) mmg(2)[i] = pm_ldc<true>(carry + (size_t)mmp_g0 * D + i);
       __syncthreads();
       if (wid == 0) {
         if (SH::D >= 1 && SH::D <= 6 && A.M <= 64)
-          pm_mm_bwd_l<(SH::D >= 1 && SH::D <= 6) ? SH::D : 1>(mmg, D, A.M, mmg + A.M * D, D, mmg + 2 * A.M * D, D,
-                                                                mmg + 3 * A.M * D, D, L.mm, lane, nullptr, true);
+          pm_mm_bwd_l<(SH::D >= 1 && SH::D <= 6) ? SH::D : 1>(mmg(0), D, A.M, mmg(1), D, mmg(2), D,
+                                                                mmg(3), D, L.mm, lane, nullptr, true);
         else
-          pm_mm_bwd(mmg, D, A.M, D, mmg + A.M * D, D, 0, 0, false, mmg + 2 * A.M * D, D, mmg + 3 * A.M * D, D, L.mm, lane,
+          pm_mm_bwd(mmg(0), D, A.M, D, mmg(1), D, 0, 0, false, mmg(2), D, mmg(3), D, L.mm, lane,
                     A.mmfac + ((size_t)t * A.mmfac_groups + mmp_g0 / A.M) * pm_mm_fac_doubles(D));
       }
       __syncthreads();
       for (int i = tid; i < R * D; i += PF_NT)
-        gxt[i] = i < nvalid * D ? mmg[3 * A.M * D + (row0 - mmp_g0) * D + i] : 0.f;
+        gxt[i] = i < nvalid * D ? mmg(3)[(row0 - mmp_g0) * D + i] : 0.f;
     } else if (mm_in) {
       // adjoint of the in-kernel moment matching of states (needs the pre-mm rows)
       // (scratch rows: the idle activation buffer, or -- split precision, where a stray fp32 row would
@@ -2367,14 +2241,14 @@ __global__ __launch_bounds__(PF_NT, 2) void pm_rollout_bwd_fast(const RolloutArg
       constexpr bool MML = SH::D >= 1 && SH::D <= 6;
       if (MML && wid < gpw && wid * A.M < nvalid) {
         const double* fac = A.mmfac + ((size_t)t * A.mmfac_groups + (row0 + wid * A.M) / A.M) * pm_mm_fac_doubles(D);
-        double* scr = L.mm + (size_t)wid * pm_mm_scratch_doubles(D);
+        double* scr = pm_mm_scratch_of(L.mm, wid, D);
         for (int e = lane; e < (int)pm_mm_fac_doubles(D); e += 64) scr[e] = fac[e];
       }
       __syncthreads();
       for (int gi = wid; gi < gpw; gi += PF_NW) {
         const int lr0 = gi * A.M;
         if (lr0 >= nvalid) break;
-        double* scr = L.mm + (size_t)wid * pm_mm_scratch_doubles(D);
+        double* scr = pm_mm_scratch_of(L.mm, wid, D);
         if constexpr (MML) {
           pm_mm_bwd_l<SH::D ? SH::D : 1>(xrows + lr0 * xrows_ld, xrows_ld, A.M, L.zs + lr0 * D, D, gx + lr0 * D, D,
                                          gxt + lr0 * D, D, scr, lane,

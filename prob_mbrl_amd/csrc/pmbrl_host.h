@@ -18,6 +18,9 @@
 //   pmbrl_mlp.hip            stand-alone network evaluation
 //   pmbrl_comm.hip           RCCL through dlopen, the plan's transports (host code only)
 //   pmbrl_p2p.hip            peer-to-peer transport
+// Host-only headers, each checked by a program of the host compiler alone: pmbrl_dw_plan.h (the dW GEMM's planner) and
+// pmbrl_lds_map.h (the LDS maps of the general and the latency-optimised sweeps: one walk per family gives the launch's
+// size, the kernels' pointers and the per-layer offsets in their arguments)
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -14,11 +14,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <type_traits>
+#include "pmbrl_lds_map.h"      // pm_mm_scratch_doubles, pm_mm_scratch_of
 typedef double pm_f64x4 __attribute__((ext_vector_type(4)));
-
-__host__ __device__ inline size_t pm_mm_scratch_doubles(int d) {
-  return d > 0 ? (size_t)3 * d * d + 5 * d : 0;
-}
 
 // leading part of the scratch that the forward pass hands to the adjoint: mean, zmean, zistd,
 // (mbar), invd, L  -- see pm_mm_carve
@@ -963,7 +960,7 @@ __device__ __forceinline__ bool pm_mm_fwd_rows(const float* s, int s_ld, int M, 
   double ref = 0.0;
   const pm_f64x4 G = pm_mm_sum_parts(pm_mm_gram_rows<DD, COH>(s, s_ld, z, z_ld, zrow0, Bg, r_lo, r_hi, lane, &ref),
                                      part, nw, wid, lane);
-  const MMScratch q = pm_mm_carve(scr + (size_t)wid * pm_mm_scratch_doubles(DD), DD);
+  const MMScratch q = pm_mm_carve(pm_mm_scratch_of(scr, wid, DD), DD);
   const bool ok = pm_mm_factor_from_gram_ref<DD>(G, M, ref, q, lane);
   for (int e = e0; e < o_hi * DD; e += 64) {
     const int r = e / DD, j = e - r * DD;
@@ -1051,7 +1048,7 @@ __device__ __forceinline__ void pm_mm_bwd_rows(const float* s, int s_ld, int M, 
   double ref = 0.0;
   pm_mm_gram_h_rows<DD, COH>(s, s_ld, z, z_ld, zrow0, Bg, g, g_ld, r_lo, r_hi, lane, G0, H, &ref);
   const pm_f64x4 G = pm_mm_sum_parts(G0, part, nw, wid, lane);
-  const MMScratch q = pm_mm_carve(scr + (size_t)wid * pm_mm_scratch_doubles(DD), DD);
+  const MMScratch q = pm_mm_carve(pm_mm_scratch_of(scr, wid, DD), DD);
   (void)pm_mm_factor_from_gram_ref<DD>(G, M, ref, q, lane);
   const double inv_m = 1.0 / (double)M, inv_m1 = 1.0 / (double)(M - 1);
   {

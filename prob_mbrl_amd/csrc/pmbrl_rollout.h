@@ -319,7 +319,7 @@ __device__ inline void reward_row_bwd(const RewardDev* __restrict__ rw, const fl
 }
 
 // ---------------------------------------------------------------------------
-// LDS carve-up (floats).  Must match pmbrl_lds_floats() on the host.
+// LDS carve-up: the pointers of the map (pm_lds_map, pmbrl_lds_map.h), which also gives the host the launch's size.
 // ---------------------------------------------------------------------------
 // moment-matching noise addressing: cyclic PEGASUS buffer or fresh rows per step
 __device__ __forceinline__ const float* pm_zbase(const float* z, int ld, int t, int Bg, int flags) {
@@ -334,37 +334,14 @@ struct LdsMap {
   double* mm;
 };
 // ip: in-place layers (gemm_layer_inplace_s) -- ONE activation buffer, narrow GEMM outputs at column PM_IP_NOFF of it
-#define PM_IP_NOFF 64
-__host__ __device__ inline size_t pm_lds_floats(int R, int LD, int D, int U, int RT, int mm_d, bool ip = false) {
-  size_t n = (ip ? 1 : 2) * (size_t)R * LD;          // bufA, bufB
-  n += 2 * (size_t)R * D;                 // xa, xb
-  n += (size_t)R * U;                     // av
-  n += (size_t)R * 16;                    // gad (action gradient, U <= 16)
-  n += 2 * (size_t)R;                     // rr, gr
-  if (!ip && !pm_part_alias_ok(R, LD, RT)) n += (size_t)PM_NW * PM_KS_NT * RT * 256;  // K-split partials (else: in the output buffer)
-  if (ip) n += 64;                        // nibble -> multipliers (pmbrl_wide.h)
-  n = (n + 3) & ~(size_t)3;
-  n += 2 * (size_t)PM_NW * pm_mm_scratch_doubles(mm_d);  // per-wave fp64 scratch
-  return n;
-}
 __device__ inline LdsMap pm_lds_carve(float* base, int R, int LD, int D, int U, int RT, bool ip = false) {
+  const PmLdsMapT<float*> o = pm_lds_map(base, R, LD, D, U, RT, 0, ip);
   LdsMap m;
-  m.bufA = base;
-  m.bufB = ip ? m.bufA : m.bufA + (size_t)R * LD;
-  m.xa = m.bufB + (size_t)R * LD;
-  m.xb = m.xa + (size_t)R * D;
-  m.av = m.xb + (size_t)R * D;
-  m.gad = m.av + (size_t)R * U;
-  m.rr = m.gad + (size_t)R * 16;
-  m.gr = m.rr + R;
-  m.part = m.gr + R;
-  size_t n = (size_t)(m.part - base);
-  m.tbl = m.part;
-  if (ip) n += 64;
-  if (ip || pm_part_alias_ok(R, LD, RT)) m.part = nullptr;
-  else n += (size_t)PM_NW * PM_KS_NT * RT * 256;
-  n = (n + 3) & ~(size_t)3;
-  m.mm = reinterpret_cast<double*>(base + n);
+  m.bufA = o.bufA; m.bufB = o.bufB; m.xa = o.xa; m.xb = o.xb;
+  m.av = o.av; m.gad = o.gad; m.rr = o.rr; m.gr = o.gr;
+  m.part = o.has_part ? o.part : nullptr;
+  m.tbl = o.tbl;
+  m.mm = reinterpret_cast<double*>(o.mm);
   return m;
 }
 
@@ -767,7 +744,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       for (int gi = wid; gi < gpw; gi += PM_NW) {
         const int lr0 = gi * A.M;
         if (lr0 >= nvalid) break;
-        double* scr = L.mm + (size_t)wid * pm_mm_scratch_doubles(D);
+        double* scr = pm_mm_scratch_of(L.mm, wid, D);
         if (A.flags & PMBRL_FLAG_MM_STATES) {
           const bool ok = pm_mm_fwd(xb + lr0 * D, D, A.M, D, pm_zbase(A.zmm, D, t, A.Bg, A.flags), D,
                                     pm_zrow0(t, A.row_off + row0 + lr0, A.flags),
@@ -916,7 +893,7 @@ __global__ __launch_bounds__(PM_NT, PR ? 1 : 2) void pm_rollout_bwd(const Rollou
       for (int gi = wid; gi < gpw; gi += PM_NW) {
         const int lr0 = gi * A.M;
         if (lr0 >= nvalid) break;
-        double* scr = L.mm + (size_t)wid * pm_mm_scratch_doubles(D);
+        double* scr = pm_mm_scratch_of(L.mm, wid, D);
         if (mms)
           pm_mm_bwd(Y + lr0 * LD, LD, A.M, D, pm_zbase(A.zmm, D, t, A.Bg, A.flags), D,
                     pm_zrow0(t, A.row_off + row0 + lr0, A.flags), A.Bg,
