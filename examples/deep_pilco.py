@@ -41,6 +41,11 @@ def parse(argv=None):
     ap.add_argument('--nonlin', type=str, default='relu', choices=['relu', 'tanh', 'silu'],
                     help='activation of the hidden layers of the dynamics model and the policy')
     ap.add_argument('--dyn_lr', type=float, default=1e-4)
+    ap.add_argument('--dyn_opt', type=str, default='adam', choices=['adam', 'adamw'],
+                    help='optimiser of the dynamics model: torch.optim.Adam (weight decay as an L2 term) or AdamW (decoupled)')
+    ap.add_argument('--dyn_weight_decay', type=float, default=0.0, help='on the weights; biases and dropout logits are not decayed')
+    ap.add_argument('--dyn_logit_lr', type=float, default=None,
+                    help='a learning rate of their own for the concrete-dropout logits (a parameter group over logit_p)')
     ap.add_argument('--dyn_opt_iters', type=int, default=2000)
     ap.add_argument('--dyn_batch_size', type=int, default=100)
     ap.add_argument('--dyn_drop_rate', type=float, default=0.1)
@@ -51,6 +56,8 @@ def parse(argv=None):
                     help='> 1: GaussianMixtureDensity dynamics head (examples/deep_pilco_mm.py:117-121)')
     ap.add_argument('--dyn_shape', type=lambda s: [int(v) for v in s.split(',')], default=[200, 200])
     ap.add_argument('--pol_lr', type=float, default=1e-3)
+    ap.add_argument('--pol_opt', type=str, default='adam', choices=['adam', 'adamw'], help='optimiser of the policy')
+    ap.add_argument('--pol_weight_decay', type=float, default=0.0, help='on the weights; biases are not decayed')
     ap.add_argument('--pol_clip', type=float, default=1.0)
     ap.add_argument('--pol_drop_rate', type=float, default=0.1)
     ap.add_argument('--pol_opt_iters', type=int, default=1000)
@@ -62,6 +69,26 @@ def parse(argv=None):
     ap.add_argument('--resampling_period', type=int, default=499)
     ap.add_argument('--device', type=str, default='cuda:0')
     return ap.parse_args(argv)
+
+
+def make_optimizer(net, kind, lr, weight_decay=0.0, logit_lr=None):
+    """torch.optim.Adam / AdamW over net.parameters().  With a weight decay or a learning rate for the dropout logits:
+    parameter groups -- weights (decayed), biases, and the logit_p tensors at logit_lr -- which the device-side optimiser
+    steps serve like the plain optimiser (prob_mbrl_amd/optim.py)."""
+    cls = torch.optim.AdamW if kind == 'adamw' else torch.optim.Adam
+    if weight_decay == 0.0 and logit_lr is None:
+        return cls(net.parameters(), lr, weight_decay=0.0) if kind == 'adamw' else cls(net.parameters(), lr)
+    named = [(n, p) for n, p in net.named_parameters() if p.requires_grad]
+    logits = [p for n, p in named if n.endswith('logit_p')] if logit_lr is not None else []
+    rest = [p for n, p in named if not any(p is q for q in logits)]
+    groups = [dict(params=[p for p in rest if p.dim() > 1], weight_decay=weight_decay),
+              dict(params=[p for p in rest if p.dim() <= 1], weight_decay=0.0)]
+    if logits:
+        groups.append(dict(params=logits, weight_decay=0.0, lr=logit_lr))
+    frozen = [p for p in net.parameters() if not p.requires_grad]
+    if frozen:
+        groups[1]['params'] += frozen
+    return cls([g for g in groups if g['params']], lr)
 
 
 def main(argv=None):
@@ -113,8 +140,8 @@ def main(argv=None):
     exp = utils.ExperienceDataset()
     if args.load_from is not None:
         utils.load_checkpoint(args.load_from, dyn, pol, exp)
-    opt1 = torch.optim.Adam(dyn.parameters(), args.dyn_lr)
-    opt2 = torch.optim.Adam(pol.parameters(), args.pol_lr)
+    opt1 = make_optimizer(dyn, args.dyn_opt, args.dyn_lr, args.dyn_weight_decay, args.dyn_logit_lr)
+    opt2 = make_optimizer(pol, args.pol_opt, args.pol_lr, args.pol_weight_decay)
     dyn, pol = dyn.to(dev), pol.to(dev)
 
     env.seed(args.seed)

@@ -444,6 +444,47 @@ int pmbrl_rollout_bwd_adam(pmbrl_plan* plan, void* stream, void* workspace_d, co
                            float* grad_pol_flat_d, float* grad_x0_d, float* action_grad_norms_d, int32_t* status_d,
                            const pmbrl_adam* opt);
 
+/* ---- optimiser rules: any torch.optim.Adam / AdamW configuration -----------------------------------------------------
+ * What the optimiser-step lines of the reference do when the caller hands them another Adam than the plain one
+ * (algorithms/mc_pilco.py:209-214, utils/train_regressor.py:113-131, examples/deep_pilco_no_mm_with_value.py:60: they
+ * accept any torch.optim optimiser): up to PMBRL_OPT_MAX_GROUPS parameter groups with their own lr / betas / eps /
+ * weight_decay, L2 or decoupled (AdamW) decay, amsgrad and maximize.  A segment is a contiguous run of the flat parameter
+ * vector that belongs to one group (the caller merges neighbouring tensors of the same group).  Per element, in torch's
+ * order (coef: the clip coefficient of the global norm of the RAW gradient over all groups):
+ *   g = coef g_raw (stored back, without the decay term);  MAXIMIZE: g = -g from here on (the stored one keeps its sign);
+ *   DECOUPLED: p *= (1 - lr wd), the factor formed in double and rounded once;  else wd != 0: g += wd p;
+ *   m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g;  AMSGRAD: vmax = max(vmax, v), used in place of v below;
+ *   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps).
+ * Bias corrections as pmbrl_clip_adam(_guarded) forms them; one step counter for all groups.  One launch covers all
+ * groups.  A rule with one group, no flags and weight_decay 0 gives the bits of the calls without a rule. */
+#define PMBRL_OPT_MAX_GROUPS   8
+#define PMBRL_OPT_MAX_SEGMENTS 32
+#define PMBRL_OPT_DECOUPLED 1
+#define PMBRL_OPT_AMSGRAD   2
+#define PMBRL_OPT_MAXIMIZE  4
+typedef struct pmbrl_opt_group { double lr, beta1, beta2, eps, weight_decay; int32_t flags; } pmbrl_opt_group;
+typedef struct pmbrl_opt_rule {
+  int32_t n_groups;   pmbrl_opt_group group[PMBRL_OPT_MAX_GROUPS];
+  int32_t n_segments; int64_t seg_end[PMBRL_OPT_MAX_SEGMENTS];   /* ascending, last == n */
+  int32_t seg_group[PMBRL_OPT_MAX_SEGMENTS];
+  float*  max_exp_avg_sq_d;   /* required iff any group has AMSGRAD; n floats */
+} pmbrl_opt_rule;
+/* Pure host code: 0, or -2 with a message for counts out of range, a seg_end that does not ascend or does not end at n, a
+ * group index out of range, lr < 0, a beta outside [0, 1), eps < 0, weight_decay < 0, unknown flag bits, AMSGRAD without
+ * max_exp_avg_sq_d.  Every call below goes through it. */
+int pmbrl_opt_rule_check(const pmbrl_opt_rule* rule, int64_t n);
+/* pmbrl_clip_adam / pmbrl_clip_adam_guarded with the hyper-parameters of `rule` */
+int pmbrl_clip_adam_rule(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, int64_t n,
+                         int64_t step, double max_norm, float* norm_out_d, const pmbrl_opt_rule* rule);
+int pmbrl_clip_adam_rule_guarded(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
+                                 int64_t n, int64_t* step_d, double max_norm, float* norm_out_d, const int32_t* status_d,
+                                 int32_t expect, const pmbrl_opt_rule* rule);
+/* The rule is copied into the plan; NULL detaches it.  While one is attached, pmbrl_rollout_bwd_adam (the sharded tail
+ * included) takes the hyper-parameters from it: lr / beta1 / beta2 / eps of pmbrl_adam are ignored, its pointers,
+ * max_norm, expect_steps and loss_out_d are kept.  The rule's contents, max_exp_avg_sq_d included, are part of what makes
+ * two backward calls "the same" for pmbrl_plan_set_replay. */
+int pmbrl_plan_set_optimizer(pmbrl_plan* plan, const pmbrl_opt_rule* rule);
+
 /* ---- gradient all-reduce over xGMI (RCCL) ---------------------------------- */
 /* The one collective of the sharded path: the sum of the flat policy gradient over the
  * ranks, in place, issued on the caller's stream right behind pmbrl_rollout_bwd -- no host round
@@ -733,6 +774,11 @@ int pmbrl_bnn_train_steps(pmbrl_bnn_plan* plan, void* stream, void* workspace_d,
                           float* exp_avg_sq_d, int64_t* step_d, double lr, double beta1, double beta2, double eps,
                           uint64_t seed, uint64_t first_step, const float* u_d, const float* bvar_d,
                           float* loss_out_d, float* loss_hist_d);
+/* An optimiser rule (pmbrl_opt_rule above) for pmbrl_bnn_train_steps: copied into the plan, NULL detaches it.  While one
+ * is attached the step of every iteration is the rule's (no clipping: coef = 1) and lr / beta1 / beta2 / eps of the call
+ * are ignored; the fragments the tail re-packs are the decayed, updated weights.  The flat layout is W0, b0, [logit_p0],
+ * W1, ...: every one of these tensors must lie in ONE segment (-2 otherwise). */
+int pmbrl_bnn_plan_set_optimizer(pmbrl_bnn_plan* plan, const pmbrl_opt_rule* rule);
 
 /* ---- test hooks (used by tests/ only) ---------------------------------- */
 /* y[R,O] = x[R,K] W[O,K]^T + b through the same MFMA tile routine the rollout

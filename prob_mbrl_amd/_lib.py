@@ -112,6 +112,8 @@ EXPORTS = [
     'pmbrl_plan_set_comm', 'pmbrl_plan_set_collective',
     'pmbrl_p2p_create', 'pmbrl_p2p_handle', 'pmbrl_p2p_open', 'pmbrl_p2p_allreduce_f32', 'pmbrl_p2p_allreduce_f64',
     'pmbrl_plan_set_p2p', 'pmbrl_p2p_error', 'pmbrl_p2p_destroy', 'pmbrl_plan_set_grad_comm',
+    'pmbrl_opt_rule_check', 'pmbrl_clip_adam_rule', 'pmbrl_clip_adam_rule_guarded', 'pmbrl_plan_set_optimizer',
+    'pmbrl_bnn_plan_set_optimizer',
 ]
 
 class Adam(C.Structure):
@@ -120,6 +122,23 @@ class Adam(C.Structure):
                 ('step_d', C.c_void_p), ('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double),
                 ('eps', C.c_double), ('max_norm', C.c_double), ('norm_out_d', C.c_void_p), ('expect_steps', C.c_int32),
                 ('loss_out_d', C.c_void_p)]
+
+
+OPT_MAX_GROUPS, OPT_MAX_SEGMENTS = 8, 32
+OPT_DECOUPLED, OPT_AMSGRAD, OPT_MAXIMIZE = 1, 2, 4
+
+
+class OptGroup(C.Structure):
+    """pmbrl_opt_group (include/pmbrl.h): one parameter group's hyper-parameters; flags: OPT_*."""
+    _fields_ = [('lr', C.c_double), ('beta1', C.c_double), ('beta2', C.c_double), ('eps', C.c_double),
+                ('weight_decay', C.c_double), ('flags', C.c_int32)]
+
+
+class OptRule(C.Structure):
+    """pmbrl_opt_rule: groups, the segments of the flat parameter vector they own, amsgrad's running maximum."""
+    _fields_ = [('n_groups', C.c_int32), ('group', OptGroup * OPT_MAX_GROUPS),
+                ('n_segments', C.c_int32), ('seg_end', C.c_int64 * OPT_MAX_SEGMENTS),
+                ('seg_group', C.c_int32 * OPT_MAX_SEGMENTS), ('max_exp_avg_sq_d', C.c_void_p)]
 
 
 _lib = None
@@ -260,6 +279,17 @@ def load():
     lib.pmbrl_plan_set_grad_comm.argtypes = [vp, vp, vp]
     lib.pmbrl_plan_set_collective.restype = C.c_int
     lib.pmbrl_plan_set_collective.argtypes = [vp, COLLECTIVE_FN, vp]
+    rule = C.POINTER(OptRule)
+    lib.pmbrl_opt_rule_check.restype = C.c_int
+    lib.pmbrl_opt_rule_check.argtypes = [rule, i64]
+    lib.pmbrl_clip_adam_rule.restype = C.c_int
+    lib.pmbrl_clip_adam_rule.argtypes = [vp, vp, vp, vp, vp, i64, i64, f64, vp, rule]
+    lib.pmbrl_clip_adam_rule_guarded.restype = C.c_int
+    lib.pmbrl_clip_adam_rule_guarded.argtypes = [vp, vp, vp, vp, vp, i64, vp, f64, vp, vp, i32, rule]
+    lib.pmbrl_plan_set_optimizer.restype = C.c_int
+    lib.pmbrl_plan_set_optimizer.argtypes = [vp, rule]
+    lib.pmbrl_bnn_plan_set_optimizer.restype = C.c_int
+    lib.pmbrl_bnn_plan_set_optimizer.argtypes = [vp, rule]
     _lib = lib
     return lib
 

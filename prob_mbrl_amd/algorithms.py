@@ -4,8 +4,8 @@ Two execution paths, same semantics:
  * fused (default): rollout forward -> loss -> adjoint sweep -> dW GEMM ->
    [gradient all-reduce] -> clip + Adam are C-ABI calls on flat buffers; no
    autograd graph, no torch.nn op, one host sync per iteration (status + loss).
-   Used when the optimiser is a plain torch.optim.Adam over the policy's Linear
-   parameters and no option needs autograd (CVaR, regulariser, value_func,
+   Used when the optimiser is a torch.optim.Adam or AdamW over the policy's Linear
+   parameters (any groups, weight decay, amsgrad, maximize: optim.py) and no option needs autograd (CVaR, regulariser, value_func,
    prioritized_replay).
  * autograd: `rollout()`'s single autograd node + torch's loss / clip / optimiser
    for everything else the reference signature allows.  value_func is evaluated by
@@ -20,6 +20,7 @@ import numpy as np
 import torch
 
 from . import engine as E
+from . import optim as OPT
 from . import rollout as RO
 from ._lib import PmbrlError
 from .utils import tile
@@ -40,26 +41,28 @@ def _discount_fn(discount, steps):
 
 
 def _adam_flat_state(opt, params, flat):
-    """If `opt` is a plain Adam over exactly `params`, return (m, v, step, group) with the
-    per-parameter state re-pointed at flat buffers (views), else None."""
-    if type(opt) is not torch.optim.Adam or len(opt.param_groups) != 1:
-        return None
-    g = opt.param_groups[0]
-    if g.get('weight_decay', 0) != 0 or g.get('amsgrad', False) or g.get('maximize', False):
-        return None
-    # frozen tensors (e.g. the reward module's constants inside DynamicsModel.parameters()) sit in
-    # the group but never receive a gradient: Adam skips them, so do we
-    gp = [p for p in g['params'] if p.requires_grad]
-    if len(gp) != len(params) or any(a is not b for a, b in zip(gp, params)):
+    """The one translator from a torch optimiser to the device-side steps.  If `opt` is a torch.optim.Adam or AdamW whose
+    1 to 8 groups hold exactly the trainable `params` (optim.layout), return the flat optimiser state: m, v, vmax
+    (amsgrad's running maximum, where a group asks for it), step, segments (the runs of the flat vector each group
+    owns), plain (the plain kernels' own rule: they serve it as before), group (the first group) -- the per-parameter
+    state of torch re-pointed at the flat buffers (views), existing state imported on first use.  Else None.
+    optim.rule_of(cache) is the rule of one step."""
+    segments = OPT.layout(opt, params)
+    if segments is None:
         return None
     cache = getattr(opt, '_pmbrl_flat', None)
-    if cache is not None and cache['flat_ptr'] == flat.data_ptr():
+    if cache is not None and cache['flat_ptr'] == flat.data_ptr() and cache['segments'] == segments:
         st = opt.state.get(params[0], {})
         if 'step' in st:   # torch may have stepped this optimiser in between
             cache['step'] = int(st['step'])
+        cache['plain'] = OPT.is_plain(opt)
+        if cache['vmax'] is None and any(g.get('amsgrad', False) for g in opt.param_groups):
+            cache['vmax'] = cache['v'].clone()       # (amsgrad switched on between two calls: torch starts it from zero)
+            cache['vmax'].zero_()
         return cache
     m = torch.zeros_like(flat)
     v = torch.zeros_like(flat)
+    vmax = torch.zeros_like(flat) if any(g.get('amsgrad', False) for g in opt.param_groups) else None
     step, off = 0, 0
     for p in params:
         n = p.numel()
@@ -67,16 +70,20 @@ def _adam_flat_state(opt, params, flat):
         if 'exp_avg' in st:
             m[off:off + n] = st['exp_avg'].reshape(-1)
             v[off:off + n] = st['exp_avg_sq'].reshape(-1)
-            step = int(st['step']) if not torch.is_tensor(st['step']) else int(st['step'].item())
+            if vmax is not None and 'max_exp_avg_sq' in st:
+                vmax[off:off + n] = st['max_exp_avg_sq'].reshape(-1)
+            step = max(step, int(st['step']) if not torch.is_tensor(st['step']) else int(st['step'].item()))
         off += n
-    cache = dict(m=m, v=v, step=step, group=g, flat_ptr=flat.data_ptr())
+    cache = dict(m=m, v=v, vmax=vmax, step=step, group=opt.param_groups[0], flat_ptr=flat.data_ptr(), opt=opt,
+                 params=list(params), segments=segments, plain=OPT.is_plain(opt))
     opt._pmbrl_flat = cache
     return cache
 
 
 def _sync_adam_state(opt, params, cache):
     """Expose the flat Adam state through opt.state (views) so state_dict()/later
-    opt.step() calls keep working."""
+    opt.step() calls keep working (max_exp_avg_sq for the parameters of an amsgrad group)."""
+    ams = {id(p) for g in opt.param_groups if g.get('amsgrad', False) for p in g['params']}
     off = 0
     for p in params:
         n = p.numel()
@@ -84,8 +91,9 @@ def _sync_adam_state(opt, params, cache):
         st['step'] = torch.tensor(float(cache['step']))
         st['exp_avg'] = cache['m'][off:off + n].view(p.shape)
         st['exp_avg_sq'] = cache['v'][off:off + n].view(p.shape)
+        if id(p) in ams and cache.get('vmax') is not None:
+            st['max_exp_avg_sq'] = cache['vmax'][off:off + n].view(p.shape)
         off += n
-
 
 
 @dataclass
@@ -200,8 +208,8 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
         run.cache['step'] = int(run.step_dev.item())
     _check_replicas_in_step(run)
     cache = getattr(opt, '_pmbrl_flat', None)
-    if cache is not None and type(opt) is torch.optim.Adam:
-        _sync_adam_state(opt, [p for p in opt.param_groups[0]['params'] if p.requires_grad], cache)
+    if cache is not None and type(opt) in (torch.optim.Adam, torch.optim.AdamW):
+        _sync_adam_state(opt, cache['params'], cache)
     policy.eval()
     dynamics.eval()
     policy_update_counter[policy] = run.n_opt_steps
@@ -366,7 +374,7 @@ def _iterate_pipelined(run, bundle, x0_, cache, tail, i):
     # rollout completed (pmbrl_rollout_bwd_adam)
     eng.backward(gw, adam=dict(params=bundle.pol_flat, exp_avg=cache['m'], exp_avg_sq=cache['v'], step=run.step_dev,
                                lr=grp['lr'], betas=grp['betas'], eps=grp['eps'], max_norm=run.clip_grad,
-                               expect=run.min_steps, loss_out=run.loss[k]))
+                               expect=run.min_steps, loss_out=run.loss[k], rule=OPT.rule_of(cache)))
     if tail is not None:
         # (the horizon the ranks agreed on and the summed failure flag exist only behind the backward call)
         run.snap[k].copy_(eng.status, non_blocking=True)
@@ -515,7 +523,7 @@ def _iterate_separate(run, bundle, x0_, cache, i):
     cache['step'] += 1
     grp = cache['group']
     E.clip_adam(bundle.pol_flat, g, cache['m'], cache['v'], cache['step'], grp['lr'],
-                grp['betas'], grp['eps'], max_norm=run.clip_grad)
+                grp['betas'], grp['eps'], max_norm=run.clip_grad, rule=OPT.rule_of(cache))
     return loss, states, actions, rewards
 
 

@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import engine as E
+from . import optim as OPT
 from .algorithms import _adam_flat_state, _sync_adam_state
 from .models import BDropout, CDropout
 from .train_regressor import bernoulli_keep_of, flat_module_parameters, stored_bernoulli_mask
@@ -83,7 +84,7 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     flat = flat_module_parameters(params, V)
     cache = _adam_flat_state(opt, params, flat)
     if cache is None:
-        raise NotImplementedError('the critic fit on the device needs a plain torch.optim.Adam over V.parameters()')
+        raise NotImplementedError('the critic fit on the device needs a %s over V.parameters()' % OPT.OFFERED)
     K = linears[-1].in_features
     n_last = K + 1
     padded = torch.cat([flat[:-n_last], flat[-n_last:-1], flat.new_zeros(K), flat[-1:], flat.new_zeros(1)])
@@ -140,7 +141,8 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     grad = torch.cat([gpad[:-(2 * K + 2)], gpad[-(2 * K + 2):-(K + 2)], gpad[-2:-1]]) * (Sy * Sy)
     cache['step'] += 1
     g = cache['group']
-    E.clip_adam(flat, grad, cache['m'], cache['v'], cache['step'], g['lr'], g['betas'], g['eps'], max_norm=None)
+    E.clip_adam(flat, grad, cache['m'], cache['v'], cache['step'], g['lr'], g['betas'], g['eps'], max_norm=None,
+                rule=OPT.rule_of(cache))
     _sync_adam_state(opt, params, cache)
     for dr in drops:
         if isinstance(dr, CDropout):

@@ -1781,6 +1781,15 @@ extern "C" int pmbrl_plan_set_loss(pmbrl_plan* p, const float* loss_weights_d, f
   return 0;
 }
 
+extern "C" int pmbrl_plan_set_optimizer(pmbrl_plan* p, const pmbrl_opt_rule* rule) {
+  if (!p) return fail(-1, "null plan");
+  if (!rule) { p->has_opt_rule = 0; return 0; }
+  if (int rc = pmbrl_opt_rule_check(rule, (int64_t)p->pol.n_params)) return rc;
+  p->opt_rule = *rule;
+  p->has_opt_rule = 1;
+  return 0;
+}
+
 // the in-place fp32 sum over the ranks through the plan's gradient transport (pmbrl_plan_set_grad_comm)
 static int tail_allreduce(pmbrl_plan* p, hipStream_t s, float* buf_d, int64_t n) {
   if (p->grad_p2p) return pmbrl_p2p_allreduce_f32(p->grad_p2p, s, buf_d, n);
@@ -2064,10 +2073,11 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   // around a device-wide barrier was measured at the C2 shape: 25.6 us against 13.7 + 4.7 + 7.1 us for the three launches
   // -- the barrier's L2 round trips cost what two launches do; not kept).  Behind the exchange the norm is done and the
   // loss is one summed partial; otherwise both are as the reduction left them
+  // (a rule attached to the plan -- pmbrl_plan_set_optimizer: its instance of the launch, the hyper-parameters from the rule)
   return clip_adam_guarded_impl(s, opt->params_d, C.grad_pol_flat, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d, opt->lr,
                                 opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, C.status, expect,
                                 tail || norm_fused, tail || loss_fused ? opt->loss_out_d : nullptr,
-                                tail ? (opt->loss_out_d ? 1 : 0) : n_loss_part);
+                                tail ? (opt->loss_out_d ? 1 : 0) : n_loss_part, p->has_opt_rule ? &p->opt_rule : nullptr);
 }
 
 // what makes two adjoint calls "the same" (pmbrl_plan_set_replay)
@@ -2083,6 +2093,17 @@ static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
     K.val(opt->params_d); K.val(opt->exp_avg_d); K.val(opt->exp_avg_sq_d); K.val(opt->step_d);
     K.val(opt->lr); K.val(opt->beta1); K.val(opt->beta2); K.val(opt->eps); K.val(opt->max_norm);
     K.val(opt->norm_out_d); K.val(opt->expect_steps);
+    // the attached rule, field by field like the struct above: a recording must never replay a stale learning rate
+    K.val(p->has_opt_rule);
+    if (p->has_opt_rule) {
+      const pmbrl_opt_rule& R = p->opt_rule;
+      K.val(R.n_groups); K.val(R.n_segments); K.val(R.max_exp_avg_sq_d);
+      for (int g = 0; g < R.n_groups; ++g) {
+        const pmbrl_opt_group& G = R.group[g];
+        K.val(G.lr); K.val(G.beta1); K.val(G.beta2); K.val(G.eps); K.val(G.weight_decay); K.val(G.flags);
+      }
+      for (int q = 0; q < R.n_segments; ++q) { K.val(R.seg_end[q]); K.val(R.seg_group[q]); }
+    }
   }
   if (bwd_tail(p, C)) {     // the transport, its buffer and the loss output: every pointer of a call with the exchange inside
     K.val(p->grad_comm); K.val(p->tail_buf_d); K.val(opt->loss_out_d);

@@ -15,6 +15,8 @@
 // policy-gradient dW GEMM (pmbrl_dw_kernels.h) consumes, so dW / db come from the same kernel.
 // pm_bnn_finish adds the regulariser, reduces the dropout-logit gradients and the loss.
 #pragma once
+#include <type_traits>
+
 #include "pmbrl_dev.h"
 
 struct BnnArgs {
@@ -544,8 +546,58 @@ struct BnnAdam {
   }
 };
 
-template <bool BERN = false>
-__global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
+// An optimiser rule (pmbrl_opt_rule, pmbrl_bnn_plan_set_optimizer) in the tail: an instance of its own, which takes this
+// record.  A workgroup updates three tensors -- the columns of W_L, the bias of Linear L and the dropout logits in front of
+// it -- and a tensor lies in one segment of the rule, so the host resolves a group per tensor: w / b / lp[l], the
+// hyper-parameters as the plain record holds them plus the decay, the sign and amsgrad.  vmax: the running maximum of the
+// second moment (no group has amsgrad: the second moment itself, read and never written -- no load under a condition).
+struct BnnOptRec {
+  float lr, b1, b2, eps;
+  float wd, decay, sgn;       // L2: g += wd p;  decoupled: p *= decay (1 - lr wd formed in double);  maximize: -1
+  int ams;
+  double ln_b1, ln_b2;
+};
+struct BnnTailRuleArgs : BnnTailArgs {
+  BnnOptRec w[PM_MAXL], b[PM_MAXL], lp[PM_MAXL];
+  float* vmax;
+};
+struct BnnAdamRule : BnnAdam {
+  float wd, decay, sgn;
+  int ams;
+  __device__ __forceinline__ BnnAdamRule() {}
+  __device__ __forceinline__ BnnAdamRule(const BnnOptRec& r, double st) {
+    b1 = r.b1; b2 = r.b2; omb1 = 1.f - r.b1; omb2 = 1.f - r.b2; eps = r.eps;
+    step_size = r.lr / -expm1f((float)(st * r.ln_b1));
+    bc2_sqrt = sqrtf(-expm1f((float)(st * r.ln_b2)));
+    inv_bc2 = 1.f / bc2_sqrt;
+    wd = r.wd; decay = r.decay; sgn = r.sgn; ams = r.ams;
+  }
+  // torch.optim.Adam / AdamW, any configuration, in torch's order; x: amsgrad's running maximum
+  __device__ __forceinline__ float operator()(float p, float g, float& m, float& v, float& x) const {
+    p *= decay;
+    g *= sgn;
+    if (wd != 0.f) g = fmaf(wd, p, g);
+    m = m * b1 + omb1 * g;
+    v = v * b2 + omb2 * g * g;
+    float dv = v;
+    if (ams) {
+      x = fmaxf(x, v);
+      dv = x;
+    }
+    return p - step_size * (m * pm_fast_rcp(sqrtf(dv) * inv_bc2 + eps));
+  }
+};
+__device__ __forceinline__ float pm_bnn_step(const BnnAdam& ad, float p, float g, float& m, float& v, float&) {
+  return ad(p, g, m, v);
+}
+__device__ __forceinline__ float pm_bnn_step(const BnnAdamRule& ad, float p, float g, float& m, float& v, float& x) {
+  return ad(p, g, m, v, x);
+}
+
+template <bool BERN = false, class ARGS = BnnTailArgs>
+__global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const ARGS A) {
+  constexpr bool RULE = !std::is_same<ARGS, BnnTailArgs>::value;
+  using AD = typename std::conditional<RULE, BnnAdamRule, BnnAdam>::type;
   __shared__ float s_s2[PM_BNT_NW][16];
   __shared__ double s_reg[PM_BNT_NT];
   __shared__ int s_last;
@@ -556,8 +608,13 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
   const int kt = (int)blockIdx.x - A.unit0[L];
   const int O = A.dim[L + 1], K = A.dim[L], n_ot = A.nt[L + 1], n_kb = A.nt[L];
   const int O16 = n_ot * 16, K16 = n_kb * 16;
-  BnnAdam ad;
-  {
+  AD ad, ad_b, ad_lp;      // (a rule: the groups of W_L, of its bias and of the logits in front of it)
+  if constexpr (RULE) {
+    const double st = (double)(A.step[0] + 1);
+    ad = BnnAdamRule(A.w[L], st);
+    ad_b = BnnAdamRule(A.b[L], st);
+    ad_lp = BnnAdamRule(A.lp[L >= 1 ? L - 1 : 0], st);
+  } else {
     // bias corrections 1 - beta^t from the device-side step count as -expm1(t ln beta), the exponent formed in double
     // (two double-precision pow calls were several hundred instructions at the head of every workgroup)
     const double st = (double)(A.step[0] + 1);
@@ -565,6 +622,7 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
     ad.step_size = A.lr / -expm1f((float)(st * A.ln_b1));
     ad.bc2_sqrt = sqrtf(-expm1f((float)(st * A.ln_b2)));
     ad.inv_bc2 = 1.f / ad.bc2_sqrt;
+    ad_b = ad_lp = ad;
   }
   // regulariser of the dropout layer in FRONT of Linear L (hidden layer q = L - 1): weight decay scaled by the units' keep
   // logits; none in front of the first layer
@@ -592,6 +650,7 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
   for (int ot0 = wid; ot0 < n_ot; ot0 += TB * PM_BNT_NW) {
     f32x4 a[TB][CB];
     float pw[TB][4], pm[TB][4], pv[TB][4], pb[TB], pbm[TB], pbv[TB];
+    float px[TB][4] = {}, pbx[TB] = {};
     int pidx[TB][4];
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb) {
@@ -606,11 +665,13 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
         pw[tb][r] = A.params[pidx[tb][r]];
         pm[tb][r] = A.m[pidx[tb][r]];
         pv[tb][r] = A.v[pidx[tb][r]];
+        if constexpr (RULE) px[tb][r] = A.vmax[pidx[tb][r]];
       }
       const int ob = A.b_off[L] + min(ot * 16 + c16, O - 1);
       pb[tb] = A.params[ob];
       pbm[tb] = A.m[ob];
       pbv[tb] = A.v[ob];
+      if constexpr (RULE) pbx[tb] = A.vmax[ob];
     }
 #pragma unroll
     for (int tb = 0; tb < TB; ++tb) {
@@ -647,14 +708,16 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
       for (int r = 0; r < 4; ++r) {
         const int o = ot * 16 + 4 * g + r;
         if (o < O && k < K) {
-          const int idx = pidx[tb][r];
+          // (a rule: the index formed again -- eight registers less across the GEMM, where its instance has none to spare)
+          const int idx = RULE ? A.w_off[L] + o * K + k : pidx[tb][r];
           const float w = pw[tb][r];
-          float mi = pm[tb][r], vi = pv[tb][r];
-          const float wn = ad(w, acc[r] + cw * w, mi, vi);
+          float mi = pm[tb][r], vi = pv[tb][r], xi = px[tb][r];
+          const float wn = pm_bnn_step(ad, w, acc[r] + cw * w, mi, vi, xi);
           s2 = fmaf(w, w, s2);
           A.params[idx] = wn;
           A.m[idx] = mi;
           A.v[idx] = vi;
+          if constexpr (RULE) { if (ad.ams) A.vmax[idx] = xi; }
           // forward fragments [ot][kb][lane (o % 16, (k % 16) / 4)][k % 4]; transposed ones [kt][ob][lane (k % 16, (o % 16) / 4)][o % 4]
           A.wf[L][(((size_t)ot * n_kb + kt) * 64 + ((4 * g + r) + 16 * (c16 >> 2))) * 4 + (c16 & 3)] = wn;
           A.wb[L][(((size_t)kt * n_ot + ot) * 64 + (c16 + 16 * g)) * 4 + r] = wn;
@@ -668,12 +731,13 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
         if (g == 0 && o < O) {
           const int idx = A.b_off[L] + o;
           const float bb = pb[tb];
-          float mi = pbm[tb], vi = pbv[tb];
-          const float bn = ad(bb, bsum + (drop ? 2.f * c * rs * bb : 0.f), mi, vi);
+          float mi = pbm[tb], vi = pbv[tb], xi = pbx[tb];
+          const float bn = pm_bnn_step(ad_b, bb, bsum + (drop ? 2.f * c * rs * bb : 0.f), mi, vi, xi);
           if (drop) reg += (double)(rs * bb * bb);
           A.params[idx] = bn;
           A.m[idx] = mi;
           A.v[idx] = vi;
+          if constexpr (RULE) { if (ad_b.ams) A.vmax[idx] = xi; }
           A.bias[L][o] = bn;
         }
       }
@@ -699,12 +763,14 @@ __global__ __launch_bounds__(PM_BNT_NT) void pm_bnn_tail(const BnnTailArgs A) {
     for (int w = 0; w < A.n_chunks; ++w) gdata += A.part_lp[(size_t)w * A.sum_h + A.lp_off[q] + k];
     const float lgp = logf(p_k), lg1 = logf(1.f - p_k);
     const int idx = A.lp_poff[q] + k;
-    float mi = A.m[idx], vi = A.v[idx];
-    const float ln = ad(A.params[idx], gdata + c * p_k * (1.f - p_k) * (rs * tot + dr * (lgp - lg1)), mi, vi);
+    float mi = A.m[idx], vi = A.v[idx], xi = 0.f;
+    if constexpr (RULE) xi = A.vmax[idx];
+    const float ln = pm_bnn_step(ad_lp, A.params[idx], gdata + c * p_k * (1.f - p_k) * (rs * tot + dr * (lgp - lg1)), mi, vi, xi);
     reg += (double)(rs * p_k * tot + dr * (p_k * lgp + (1.f - p_k) * lg1));
     A.params[idx] = ln;
     A.m[idx] = mi;
     A.v[idx] = vi;
+    if constexpr (RULE) { if (ad_lp.ams) A.vmax[idx] = xi; }
   }
   s_reg[tid] = reg;
   __syncthreads();

@@ -19,11 +19,14 @@ struct BnnKernels {
   void (*fwd_bwd)(const BnnArgs);
   void (*finish)(const BnnFinishArgs);
   void (*tail)(const BnnTailArgs);
+  void (*tail_rule)(const BnnTailRuleArgs);   // with an optimiser rule attached (pmbrl_bnn_plan_set_optimizer)
 };
 // ... chosen HERE and nowhere else: a plan without a Bernoulli layer launches the instances it always did
 static BnnKernels bnn_kernels(int act, int any_bern) {
-  if (any_bern) return {act ? pm_bnn_fwd_bwd<true, true> : pm_bnn_fwd_bwd<false, true>, pm_bnn_finish<true>, pm_bnn_tail<true>};
-  return {act ? pm_bnn_fwd_bwd<true> : pm_bnn_fwd_bwd<false>, pm_bnn_finish<false>, pm_bnn_tail<false>};
+  if (any_bern) return {act ? pm_bnn_fwd_bwd<true, true> : pm_bnn_fwd_bwd<false, true>, pm_bnn_finish<true>, pm_bnn_tail<true>,
+            pm_bnn_tail<true, BnnTailRuleArgs>};
+  return {act ? pm_bnn_fwd_bwd<true> : pm_bnn_fwd_bwd<false>, pm_bnn_finish<false>, pm_bnn_tail<false>,
+          pm_bnn_tail<false, BnnTailRuleArgs>};
 }
 
 struct pmbrl_bnn_plan {
@@ -50,6 +53,10 @@ struct pmbrl_bnn_plan {
   DwArgs dw;
   int n_finish;   // workgroups of pm_bnn_finish
   int units;      // workgroups of pm_bnn_tail (more than 512: pmbrl_bnn_train_steps refuses)
+  // optimiser rule (pmbrl_bnn_plan_set_optimizer): the groups of the layers' tensors, resolved when it was attached
+  int has_rule;
+  pmbrl_opt_rule rule;
+  int grp_w[PM_MAXL], grp_b[PM_MAXL], grp_lp[PM_MAXL];
 };
 
 static void bnn_plan_records(pmbrl_bnn_plan* p) {
@@ -250,6 +257,43 @@ extern "C" int pmbrl_bnn_plan_set_unit_keep(pmbrl_bnn_plan* p, int32_t layer, co
   HIPCHK(hipMemcpy(p->keep_d[layer], keep_h, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
   return 0;
 }
+// the group of the tensor [off, off + len) of the flat vector, -1 if it does not lie in one segment
+static int bnn_rule_group(const pmbrl_opt_rule& r, int64_t off, int64_t len) {
+  int64_t lo = 0;
+  for (int q = 0; q < r.n_segments; ++q) {
+    if (off >= lo && off < r.seg_end[q]) return off + len <= r.seg_end[q] ? r.seg_group[q] : -1;
+    lo = r.seg_end[q];
+  }
+  return -1;
+}
+extern "C" int pmbrl_bnn_plan_set_optimizer(pmbrl_bnn_plan* p, const pmbrl_opt_rule* rule) {
+  if (!p) return fail(-1, "null plan");
+  if (!rule) { p->has_rule = 0; return 0; }
+  if (int rc = pmbrl_opt_rule_check(rule, (int64_t)p->n_params)) return rc;
+  int gw[PM_MAXL] = {0}, gb[PM_MAXL] = {0}, glp[PM_MAXL] = {0};
+  for (int l = 0; l < p->nl; ++l) {
+    gw[l] = bnn_rule_group(*rule, p->w_off[l], (int64_t)p->dim[l + 1] * p->dim[l]);
+    gb[l] = bnn_rule_group(*rule, p->b_off[l], p->dim[l + 1]);
+    glp[l] = p->has_drop[l] == 1 ? bnn_rule_group(*rule, p->lp_poff[l], p->dim[l + 1]) : 0;
+    if (gw[l] < 0 || gb[l] < 0 || glp[l] < 0)
+      return fail(-2, "pmbrl_bnn_plan_set_optimizer: a weight, bias or logit tensor of the network lies in more than one segment");
+  }
+  p->rule = *rule;
+  for (int l = 0; l < p->nl; ++l) { p->grp_w[l] = gw[l]; p->grp_b[l] = gb[l]; p->grp_lp[l] = glp[l]; }
+  p->has_rule = 1;
+  return 0;
+}
+static BnnOptRec bnn_opt_rec(const pmbrl_opt_group& G) {
+  BnnOptRec r;
+  const bool dec = G.flags & PMBRL_OPT_DECOUPLED;
+  r.lr = (float)G.lr; r.b1 = (float)G.beta1; r.b2 = (float)G.beta2; r.eps = (float)G.eps;
+  r.wd = dec ? 0.f : (float)G.weight_decay;
+  r.decay = dec ? (float)(1.0 - G.lr * G.weight_decay) : 1.f;
+  r.sgn = (G.flags & PMBRL_OPT_MAXIMIZE) ? -1.f : 1.f;
+  r.ams = (G.flags & PMBRL_OPT_AMSGRAD) ? 1 : 0;
+  r.ln_b1 = log(G.beta1); r.ln_b2 = log(G.beta2);
+  return r;
+}
 extern "C" size_t pmbrl_bnn_plan_workspace_bytes(const pmbrl_bnn_plan* p) { return p ? p->ws_bytes : 0; }
 extern "C" int64_t pmbrl_bnn_plan_n_params(const pmbrl_bnn_plan* p) { return p ? p->n_params : 0; }
 
@@ -342,6 +386,19 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
   A.rng = u_d ? 0 : 1;
   A.prof = getenv("PMBRL_BNN_PROF") ? reinterpret_cast<long long*>(ws + p->off_reg_part) + 256 : nullptr;      // (debugging: stamps at floats 512.. of the scratch)
   A.rng_k0 = (unsigned)seed; A.rng_k1 = (unsigned)(seed >> 32);
+  // a rule attached to the plan: its instance of the tail, the hyper-parameters from the rule (lr .. eps above are ignored)
+  BnnTailRuleArgs TR;
+  if (p->has_rule) {
+    memset(&TR, 0, sizeof(TR));
+    bool ams = false;
+    for (int l = 0; l < p->nl; ++l) {
+      TR.w[l] = bnn_opt_rec(p->rule.group[p->grp_w[l]]);
+      TR.b[l] = bnn_opt_rec(p->rule.group[p->grp_b[l]]);
+      TR.lp[l] = bnn_opt_rec(p->rule.group[p->grp_lp[l]]);
+    }
+    for (int k = 0; k < p->rule.n_groups; ++k) ams = ams || (p->rule.group[k].flags & PMBRL_OPT_AMSGRAD);
+    TR.vmax = ams ? p->rule.max_exp_avg_sq_d : exp_avg_sq_d;
+  }
   HIPCHK(hipMemsetAsync(T.counter, 0, sizeof(unsigned), s));
   pm_pack_all_launch(PK, s);
   const size_t noise = (size_t)p->cfg.M * p->noise_h;
@@ -355,7 +412,12 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
       }
     T.loss_out = loss_hist_d ? loss_hist_d + (size_t)3 * i : loss_out_d;
     hipLaunchKernelGGL(p->kern.fwd_bwd, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
-    hipLaunchKernelGGL(p->kern.tail, dim3(p->units), dim3(PM_BNT_NT), 0, s, T);
+    if (p->has_rule) {
+      static_cast<BnnTailArgs&>(TR) = T;
+      hipLaunchKernelGGL(p->kern.tail_rule, dim3(p->units), dim3(PM_BNT_NT), 0, s, TR);
+    } else {
+      hipLaunchKernelGGL(p->kern.tail, dim3(p->units), dim3(PM_BNT_NT), 0, s, T);
+    }
   }
   if (loss_hist_d)
     HIPCHK(hipMemcpyAsync(loss_out_d, loss_hist_d + (size_t)3 * (n_steps - 1), 3 * sizeof(float), hipMemcpyDeviceToDevice, s));

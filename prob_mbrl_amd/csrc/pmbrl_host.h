@@ -128,6 +128,9 @@ struct pmbrl_plan {
   float* tail_buf_d;       // [n + 2 rounded up to 4 | tail_world]: gradient, loss partial, failure flag | horizon vector
   int* tail_err_d;         // the peer-to-peer object's error word (nullptr: RCCL)
   mutable int tail_calls;  // pmbrl_rollout_bwd_adam calls that ran with the exchange inside (pmbrl_plan_info)
+  // optimiser rule (pmbrl_plan_set_optimizer): while attached, the optimiser launch of pmbrl_rollout_bwd_adam is the rule's
+  int has_opt_rule;
+  pmbrl_opt_rule opt_rule;
   // optional per-kernel timing (hipEvents on the caller's stream)
   long long* prof_fwd;
   long long* prof_bwd;
@@ -230,7 +233,9 @@ void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long lon
 int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, int64_t n,
                            int64_t* step_d, double lr, double beta1, double beta2, double eps, double max_norm,
                            float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                           float* loss_out_d = nullptr, int n_loss_part = 0);
+                           float* loss_out_d = nullptr, int n_loss_part = 0, const pmbrl_opt_rule* rule = nullptr);
+// what pmbrl_opt_rule_check refuses, as text (nullptr: nothing); host code only
+const char* pm_opt_rule_refusal(const pmbrl_opt_rule* r, int64_t n);
 void pm_tail_hvec_launch(hipStream_t s, float* hvec, int world, int rank, const int* status, int H);
 void pm_tail_hmin_launch(hipStream_t s, const float* hvec, int world, int* status, int H);
 void pm_tail_pack_launch(hipStream_t s, float* xb, int n, int n_loss_part, int loss_here, const int* status, const int* err);

@@ -395,6 +395,256 @@ __global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p
   }
 }
 
+// ---------------------------------------------------------------------------
+// The same launch for an optimiser rule (pmbrl_opt_rule: parameter groups, L2 / decoupled weight decay, amsgrad, maximize).
+// pm_clip_adam_kernel above is the plain rule's and is left as it is; this one has its latency shape -- the first four
+// elements, vmax where the rule has one (VMAX: an instance of its own, no load under a condition) and the norm's partial
+// sums are requested before anything is decided; butterfly and loss sum are the plain kernel's.
+// The rule travels by value.  Segment boundaries and groups are read at CONSTANT offsets of the argument (scalar loads, no
+// copy of the table in scratch): an element compares its index against the boundaries in turn.  The groups'
+// hyper-parameters, the step-dependent ones included (lr / bc1, sqrt(bc2): one pair of expm1 per group, not per element),
+// live in the lanes: lane l of every wave holds group l & 7, an element fetches its group's with a lane shuffle --
+// neighbouring lanes may belong to different groups.
+// ---------------------------------------------------------------------------
+struct OptRuleDev {
+  int n_segments, n_groups;
+  int seg_group[PMBRL_OPT_MAX_SEGMENTS];
+  long long seg_end[PMBRL_OPT_MAX_SEGMENTS];
+  // per group (unused slots repeat group 0)
+  float b1[PMBRL_OPT_MAX_GROUPS], b2[PMBRL_OPT_MAX_GROUPS], omb1[PMBRL_OPT_MAX_GROUPS], omb2[PMBRL_OPT_MAX_GROUPS];
+  float eps[PMBRL_OPT_MAX_GROUPS];
+  float wd[PMBRL_OPT_MAX_GROUPS];         // L2: g += wd p (0: none, and for a decoupled group)
+  float decay[PMBRL_OPT_MAX_GROUPS];      // decoupled: p *= 1 - lr wd, formed in double, rounded once (1: none)
+  float sgn[PMBRL_OPT_MAX_GROUPS];        // maximize: -1
+  float step_size[PMBRL_OPT_MAX_GROUPS], bc2_sqrt[PMBRL_OPT_MAX_GROUPS];   // from the host's step count (not guarded)
+  int amsgrad[PMBRL_OPT_MAX_GROUPS];
+  double ln_b1[PMBRL_OPT_MAX_GROUPS], ln_b2[PMBRL_OPT_MAX_GROUPS], lr_d[PMBRL_OPT_MAX_GROUPS];
+  float* vmax;
+};
+// a[gl] as a chain of selects between SCALAR operands.  The values are pinned to scalar registers first: left alone, the
+// compiler folds the chain back into one load at a[gl] -- a per-lane load from the argument segment and a wait for it, one
+// more memory round trip at the head of every thread (seen in the ISA: global_load_dword ... s_waitcnt vmcnt(0))
+__device__ __forceinline__ int pm_scalar(int x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ float pm_scalar(float x) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x))); }
+__device__ __forceinline__ double pm_scalar(double x) {
+  const long long b = __double_as_longlong(x);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll));
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+template <class T>
+__device__ __forceinline__ T pm_pick_group(const T (&a)[PMBRL_OPT_MAX_GROUPS], int gl) {
+  T r = pm_scalar(a[0]);
+#pragma unroll
+  for (int k = 1; k < PMBRL_OPT_MAX_GROUPS; ++k) r = gl == k ? pm_scalar(a[k]) : r;
+  return r;
+}
+template <bool VMAX>
+__global__ __launch_bounds__(256) void pm_clip_adam_rule_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                                float* __restrict__ m, float* __restrict__ v,
+                                                                long long n, int n_part, float max_norm,
+                                                                float* __restrict__ norm_out,
+                                                                const long long* __restrict__ step, int guarded,
+                                                                float* __restrict__ loss_out, int n_loss_part,
+                                                                const OptRuleDev R) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  float gq[4], mq[4], vq[4], pq[4], xq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const long long j = min(i0 + u * stride, n - 1);
+    gq[u] = g[j];
+    mq[u] = m[j];
+    vq[u] = v[j];
+    pq[u] = p[j];
+    if constexpr (VMAX) xq[u] = R.vmax[j];
+  }
+  const int lane = threadIdx.x & 63;
+  double part[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const double x = g_norm_part[min(lane + 64 * u, PM_NORM_MAXB - 1)];
+    part[u] = lane + 64 * u < n_part ? x : 0.0;
+  }
+  if (loss_out && blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 128) {
+    double ls = 0.0;
+    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    if (lane == 0) loss_out[0] = (float)ls;
+  }
+  if (guarded && !g_adam_go) return;
+  // this lane's group record
+  const int gl = lane & (PMBRL_OPT_MAX_GROUPS - 1);
+  const float r_b1 = pm_pick_group(R.b1, gl), r_b2 = pm_pick_group(R.b2, gl);
+  const float r_omb1 = pm_pick_group(R.omb1, gl), r_omb2 = pm_pick_group(R.omb2, gl);
+  const float r_eps = pm_pick_group(R.eps, gl), r_wd = pm_pick_group(R.wd, gl), r_decay = pm_pick_group(R.decay, gl);
+  const float r_sgn = pm_pick_group(R.sgn, gl);
+  const int r_ams = pm_pick_group(R.amsgrad, gl);
+  float r_step = pm_pick_group(R.step_size, gl), r_bc2 = pm_pick_group(R.bc2_sqrt, gl);
+  if (step) {
+    // guarded form: the bias corrections of the device-side step counter, as pm_clip_adam_kernel forms them
+    const double st = (double)step[0];
+    const double bc1_d = -expm1(st * pm_pick_group(R.ln_b1, gl));
+    r_bc2 = (float)sqrt(-expm1(st * pm_pick_group(R.ln_b2, gl)));
+    r_step = (float)(pm_pick_group(R.lr_d, gl) / bc1_d);
+  }
+  double t = 0.0;
+  {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) t += part[u];
+    for (int b = lane + 256; b < n_part; b += 64) t += g_norm_part[b];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  }
+  const float norm = (float)sqrt(t);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
+  float coef = 1.f;
+  if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
+  for (long long i = i0;;) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = i + u * stride;
+      // the element's segment (every lane takes part in the shuffles: beyond n the last element's)
+      const long long jc = min(j, n - 1);
+      // (three walks by the number of segments, chosen by a scalar branch: none for one segment, 7 boundaries for up to 8
+      //  -- weights / biases groups of a three-layer network are 6 segments -- and all 31 beyond.  Measured at n = 550 416,
+      //  where the launch is no longer launch-bound: all 31 comparisons for every rule were 13 us of a 21.6 us launch with
+      //  one group; a walk that leaves at the rule's last boundary, one branch per boundary, took 50 us for 32 segments)
+      int grp = R.seg_group[0];
+      if (R.n_segments > 8) {
+#pragma unroll
+        for (int q = 1; q < PMBRL_OPT_MAX_SEGMENTS; ++q)
+          if (q < R.n_segments && jc >= R.seg_end[q - 1]) grp = R.seg_group[q];
+      } else if (R.n_segments > 1) {
+#pragma unroll
+        for (int q = 1; q < 8; ++q)
+          if (q < R.n_segments && jc >= R.seg_end[q - 1]) grp = R.seg_group[q];
+      }
+      // (one group: every lane holds its record -- the unused slots repeat group 0)
+      float b1 = r_b1, b2 = r_b2, omb1 = r_omb1, omb2 = r_omb2, eps = r_eps, wd = r_wd, decay = r_decay, sgn = r_sgn;
+      float step_size = r_step, bc2_sqrt = r_bc2;
+      int ams = r_ams;
+      if (R.n_groups > 1) {
+        b1 = __shfl(r_b1, grp); b2 = __shfl(r_b2, grp); omb1 = __shfl(r_omb1, grp); omb2 = __shfl(r_omb2, grp);
+        eps = __shfl(r_eps, grp); wd = __shfl(r_wd, grp); decay = __shfl(r_decay, grp); sgn = __shfl(r_sgn, grp);
+        step_size = __shfl(r_step, grp); bc2_sqrt = __shfl(r_bc2, grp);
+        ams = __shfl(r_ams, grp);
+      }
+      if (j < n) {
+        const float gi = gq[u] * coef;
+        const float pd = pq[u] * decay;
+        float gs = gi * sgn;
+        if (wd != 0.f) gs = fmaf(wd, pd, gs);
+        const float mi = mq[u] * b1 + omb1 * gs;
+        const float vi = vq[u] * b2 + omb2 * gs * gs;
+        float dv = vi;
+        if constexpr (VMAX) {
+          if (ams) {
+            dv = fmaxf(xq[u], vi);
+            R.vmax[j] = dv;
+          }
+        }
+        const float denom = sqrtf(dv) / bc2_sqrt + eps;
+        g[j] = gi;
+        m[j] = mi;
+        v[j] = vi;
+        p[j] = pd - step_size * (mi / denom);
+      }
+    }
+    i += 4 * stride;
+    // (a wave leaves the loop as a whole -- its first lane's index decides: the shuffles above read the group records from
+    //  lanes 0 .. 7, which must still be there when only some lanes have elements left)
+    if (i - lane >= n) break;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const long long j = min(i + u * stride, n - 1);
+      gq[u] = g[j];
+      mq[u] = m[j];
+      vq[u] = v[j];
+      pq[u] = p[j];
+      if constexpr (VMAX) xq[u] = R.vmax[j];
+    }
+  }
+}
+
+const char* pm_opt_rule_refusal(const pmbrl_opt_rule* r, int64_t n) {
+  if (!r) return "pmbrl_opt_rule: null rule";
+  if (n < 1) return "pmbrl_opt_rule: n < 1";
+  if (r->n_groups < 1 || r->n_groups > PMBRL_OPT_MAX_GROUPS) return "pmbrl_opt_rule: n_groups outside 1 .. PMBRL_OPT_MAX_GROUPS";
+  if (r->n_segments < 1 || r->n_segments > PMBRL_OPT_MAX_SEGMENTS)
+    return "pmbrl_opt_rule: n_segments outside 1 .. PMBRL_OPT_MAX_SEGMENTS";
+  bool ams = false;
+  for (int k = 0; k < r->n_groups; ++k) {
+    const pmbrl_opt_group& G = r->group[k];
+    if (!(G.lr >= 0.0) || !std::isfinite(G.lr)) return "pmbrl_opt_rule: lr < 0";
+    if (!(G.beta1 >= 0.0 && G.beta1 < 1.0) || !(G.beta2 >= 0.0 && G.beta2 < 1.0)) return "pmbrl_opt_rule: a beta outside [0, 1)";
+    if (!(G.eps >= 0.0) || !std::isfinite(G.eps)) return "pmbrl_opt_rule: eps < 0";
+    if (!(G.weight_decay >= 0.0) || !std::isfinite(G.weight_decay)) return "pmbrl_opt_rule: weight_decay < 0";
+    if (G.flags & ~(PMBRL_OPT_DECOUPLED | PMBRL_OPT_AMSGRAD | PMBRL_OPT_MAXIMIZE)) return "pmbrl_opt_rule: unknown flag bits";
+    ams = ams || (G.flags & PMBRL_OPT_AMSGRAD);
+  }
+  int64_t prev = 0;
+  for (int q = 0; q < r->n_segments; ++q) {
+    if (r->seg_end[q] <= prev) return "pmbrl_opt_rule: seg_end does not ascend";
+    prev = r->seg_end[q];
+    if (r->seg_group[q] < 0 || r->seg_group[q] >= r->n_groups) return "pmbrl_opt_rule: seg_group outside the groups";
+  }
+  if (prev != n) return "pmbrl_opt_rule: the last seg_end is not n";
+  if (ams && !r->max_exp_avg_sq_d) return "pmbrl_opt_rule: AMSGRAD without max_exp_avg_sq_d";
+  return nullptr;
+}
+extern "C" int pmbrl_opt_rule_check(const pmbrl_opt_rule* rule, int64_t n) {
+  const char* why = pm_opt_rule_refusal(rule, n);
+  return why ? fail(-2, why) : 0;
+}
+
+// the rule as the kernel takes it; step > 0: the host's step count (bias corrections as pmbrl_clip_adam forms them), 0: the
+// device-side counter's (formed in the kernel)
+static OptRuleDev opt_rule_dev(const pmbrl_opt_rule& r, long long step) {
+  OptRuleDev D;
+  D.n_segments = r.n_segments;
+  D.n_groups = r.n_groups;
+  for (int q = 0; q < PMBRL_OPT_MAX_SEGMENTS; ++q) {
+    const int qq = std::min(q, r.n_segments - 1);
+    D.seg_end[q] = r.seg_end[qq];
+    D.seg_group[q] = r.seg_group[qq];
+  }
+  for (int k = 0; k < PMBRL_OPT_MAX_GROUPS; ++k) {
+    const pmbrl_opt_group& G = r.group[k < r.n_groups ? k : 0];
+    const bool dec = G.flags & PMBRL_OPT_DECOUPLED;
+    D.b1[k] = (float)G.beta1; D.b2[k] = (float)G.beta2;
+    D.omb1[k] = (float)(1.0 - G.beta1); D.omb2[k] = (float)(1.0 - G.beta2);
+    D.eps[k] = (float)G.eps;
+    D.wd[k] = dec ? 0.f : (float)G.weight_decay;
+    D.decay[k] = dec ? (float)(1.0 - G.lr * G.weight_decay) : 1.f;
+    D.sgn[k] = (G.flags & PMBRL_OPT_MAXIMIZE) ? -1.f : 1.f;
+    D.amsgrad[k] = (G.flags & PMBRL_OPT_AMSGRAD) ? 1 : 0;
+    D.ln_b1[k] = log(G.beta1); D.ln_b2[k] = log(G.beta2); D.lr_d[k] = G.lr;
+    D.step_size[k] = D.bc2_sqrt[k] = 1.f;
+    if (step > 0) {
+      const float bc1 = (float)(1.0 - pow(G.beta1, (double)step));
+      D.step_size[k] = (float)(G.lr / (double)bc1);
+      D.bc2_sqrt[k] = (float)sqrt(1.0 - pow(G.beta2, (double)step));
+    }
+  }
+  bool ams = false;
+  for (int k = 0; k < r.n_groups; ++k) ams = ams || (r.group[k].flags & PMBRL_OPT_AMSGRAD);
+  D.vmax = ams ? r.max_exp_avg_sq_d : nullptr;    // (no group asks for it: the instance without the stream)
+  return D;
+}
+static void clip_adam_rule_launch(hipStream_t s, int nb, float* p, float* g, float* m, float* v, long long n, int n_part,
+                                  double max_norm, float* norm_out, const long long* step_d, int guarded, float* loss_out,
+                                  int n_loss_part, const pmbrl_opt_rule& rule, long long step) {
+  const OptRuleDev D = opt_rule_dev(rule, step);
+  if (D.vmax)
+    hipLaunchKernelGGL(pm_clip_adam_rule_kernel<true>, dim3(nb), dim3(256), 0, s, p, g, m, v, n, n_part, (float)max_norm,
+                       norm_out, step_d, guarded, loss_out, n_loss_part, D);
+  else
+    hipLaunchKernelGGL(pm_clip_adam_rule_kernel<false>, dim3(nb), dim3(256), 0, s, p, g, m, v, n, n_part, (float)max_norm,
+                       norm_out, step_d, guarded, loss_out, n_loss_part, D);
+}
+
 void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
                                 long long n_per_step) {
   const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 2047) / 2048));
@@ -406,12 +656,18 @@ void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long lon
 int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
                                   int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
                                   double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                                  float* loss_out_d, int n_loss_part) {
+                                  float* loss_out_d, int n_loss_part, const pmbrl_opt_rule* rule) {
   const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
   const int np = pm_norm_blocks(n);
   if (!norm_done)
     hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
                        (long long)n, (const int*)status_d, (int)expect, reinterpret_cast<long long*>(step_d), 1);
+  if (rule) {     // (checked when it was attached or by the entry point; n is the vector's it was checked against)
+    clip_adam_rule_launch((hipStream_t)stream, nb, params_d, grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, max_norm,
+                          norm_out_d, reinterpret_cast<const long long*>(step_d), 1, loss_out_d, n_loss_part, *rule, 0);
+    HIPCHK(hipGetLastError());
+    return 0;
+  }
   hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
                      grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, (float)lr, (float)beta1,
                      (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, 1.f, 1.f,
@@ -586,4 +842,31 @@ extern "C" int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* gra
     return fail(-1, "bad argument");
   return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, lr, beta1, beta2, eps, max_norm,
                                 norm_out_d, status_d, expect, false);
+}
+
+extern "C" int pmbrl_clip_adam_rule(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
+                                    int64_t n, int64_t step, double max_norm, float* norm_out_d, const pmbrl_opt_rule* rule) {
+  if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || n < 1 || step < 1) return fail(-1, "bad argument");
+  if (int rc = pmbrl_opt_rule_check(rule, n)) return rc;
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
+  const int np = pm_norm_blocks(n);
+  const bool need_norm = max_norm > 0.0 || norm_out_d != nullptr;
+  if (need_norm)
+    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
+                       (long long)n, (const int*)nullptr, 0, (long long*)nullptr, 0);
+  clip_adam_rule_launch((hipStream_t)stream, nb, params_d, grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, need_norm ? np : 0,
+                        max_norm, norm_out_d, (const long long*)nullptr, 0, (float*)nullptr, 0, *rule, (long long)step);
+  HIPCHK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int pmbrl_clip_adam_rule_guarded(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
+                                            float* exp_avg_sq_d, int64_t n, int64_t* step_d, double max_norm,
+                                            float* norm_out_d, const int32_t* status_d, int32_t expect,
+                                            const pmbrl_opt_rule* rule) {
+  if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || !step_d || !status_d || n < 1)
+    return fail(-1, "bad argument");
+  if (int rc = pmbrl_opt_rule_check(rule, n)) return rc;
+  return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, 0.0, 0.0, 0.0, 0.0, max_norm,
+                                norm_out_d, status_d, expect, false, nullptr, 0, rule);
 }

@@ -342,12 +342,21 @@ class BnnStep:
         return grad, self.loss
 
     def train_steps(self, Xn, Yn, idx_all, params, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8,
-                    seed=0, first_step=0, u=None, bvar=None, loss_hist=None):
+                    seed=0, first_step=0, u=None, bvar=None, loss_hist=None, rule=None):
         """Whole training iterations (loss, gradient, torch.optim.Adam's step: utils/train_regressor.py:113-131) in two
         launches each, all queued by this one call (pmbrl_bnn_train_steps).  idx_all int32 [n_steps, M]; params /
         exp_avg / exp_avg_sq flat fp32, updated in place; step: int64 device tensor [1] (Adam's step count, advanced on
         the device).  u, bvar: recorded dropout draws [n_steps, M * sum_h], or None: drawn in the kernel from `seed`
-        (counter first_step + i).  loss_hist: optional fp32 [n_steps, 3].  Returns loss[3] of the last iteration."""
+        (counter first_step + i).  loss_hist: optional fp32 [n_steps, 3].  rule: an optim.Rule attached to the plan for
+        this call (pmbrl_bnn_plan_set_optimizer: lr / betas / eps are then the rule's; a tensor of the network must lie in
+        one segment); none: the plain step.  Returns loss[3] of the last iteration."""
+        if rule is not None:
+            r = _rule_struct(rule, self.n_params)
+            _lib.check(self.lib.pmbrl_bnn_plan_set_optimizer(self.plan, C.byref(r)), 'pmbrl_bnn_plan_set_optimizer')
+            self._has_rule = True
+        elif getattr(self, '_has_rule', False):
+            _lib.check(self.lib.pmbrl_bnn_plan_set_optimizer(self.plan, None), 'pmbrl_bnn_plan_set_optimizer')
+            self._has_rule = False
         for t in (Xn, Yn, params, exp_avg, exp_avg_sq):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
         assert idx_all.is_cuda and idx_all.dtype == torch.int32 and idx_all.is_contiguous() and idx_all.numel() % self.M == 0
@@ -507,6 +516,7 @@ class Engine:
         self.grad_flat = torch.empty(self.n_pol_params, dtype=torch.float32, device=dev)
         self._traj = (self.states, self.actions, self.rewards)
         self._inputs = None
+        self._has_rule = False
         self._keep = None
         self.generation = 0    # bumped by every forward(); backward must match
 
@@ -740,6 +750,9 @@ class Engine:
                 t = adam[k]
                 assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == self.n_pol_params
             assert adam['step'].is_cuda and adam['step'].dtype == torch.int64
+            # rule: an optim.Rule attached to the plan for this call (pmbrl_plan_set_optimizer: the hyper-parameters are
+            # then the rule's); none: detached, the plain step
+            self.set_optimizer(adam.get('rule'))
             o = _lib.Adam(adam['params'].data_ptr(), adam['exp_avg'].data_ptr(), adam['exp_avg_sq'].data_ptr(),
                           adam['step'].data_ptr(), float(adam['lr']), float(adam['betas'][0]), float(adam['betas'][1]),
                           float(adam['eps']), float(adam.get('max_norm') or 0.0),
@@ -761,6 +774,18 @@ class Engine:
                                               _ptr(agn), _ptr(self.status)),
                    'pmbrl_rollout_bwd')
         return self.grad_flat, gx0, agn
+
+    def set_optimizer(self, rule):
+        """Attach an optim.Rule to the plan (pmbrl_plan_set_optimizer; the library copies it), or detach with None:
+        backward(adam=...) takes its hyper-parameters from the rule while one is attached."""
+        if rule is None:
+            if self._has_rule:
+                _lib.check(self.lib.pmbrl_plan_set_optimizer(self.plan, None), 'pmbrl_plan_set_optimizer')
+                self._has_rule = False
+            return
+        r = _rule_struct(rule, self.n_pol_params)
+        _lib.check(self.lib.pmbrl_plan_set_optimizer(self.plan, C.byref(r)), 'pmbrl_plan_set_optimizer')
+        self._has_rule = True
 
     def set_replay(self, on=1):
         """0: never replay repeated calls as hipGraphs; 1: the library's default (the one-launch-per-step forms); 2: every
@@ -838,13 +863,29 @@ class Engine:
         return out
 
 
-def clip_adam(params, grads, exp_avg, exp_avg_sq, step, lr, betas=(0.9, 0.999), eps=1e-8,
-              max_norm=None, norm_out=None):
-    """Fused clip_grad_norm_ + Adam.step on flat fp32 buffers (pmbrl_clip_adam)."""
+def _rule_struct(rule, n):
+    """The pmbrl_opt_rule of an optim.Rule for a flat vector of n elements (amsgrad's buffer checked here: the library
+    takes a pointer)."""
+    if rule.vmax is not None:
+        v = rule.vmax
+        assert v.is_cuda and v.dtype == torch.float32 and v.is_contiguous() and v.numel() == n
+    return rule.struct()
+
+
+def clip_adam(params, grads, exp_avg, exp_avg_sq, step, lr=None, betas=(0.9, 0.999), eps=1e-8,
+              max_norm=None, norm_out=None, rule=None):
+    """Fused clip_grad_norm_ + Adam.step on flat fp32 buffers (pmbrl_clip_adam).  rule: an optim.Rule -- parameter
+    groups, weight decay, amsgrad, maximize (pmbrl_clip_adam_rule); lr / betas / eps are then the rule's."""
     lib = _lib.load()
     for t in (params, grads, exp_avg, exp_avg_sq):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     n = params.numel()
+    if rule is not None:
+        r = _rule_struct(rule, n)
+        _lib.check(lib.pmbrl_clip_adam_rule(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n,
+                                            int(step), float(max_norm) if max_norm else 0.0, _ptr(norm_out), C.byref(r)),
+                   'pmbrl_clip_adam_rule')
+        return
     _lib.check(lib.pmbrl_clip_adam(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg),
                                    _ptr(exp_avg_sq), n, int(step), float(lr), float(betas[0]),
                                    float(betas[1]), float(eps),
@@ -897,14 +938,21 @@ class Graph:
 
 
 def clip_adam_guarded(params, grads, exp_avg, exp_avg_sq, step_dev, lr, status, expect, betas=(0.9, 0.999),
-                      eps=1e-8, max_norm=None, norm_out=None):
+                      eps=1e-8, max_norm=None, norm_out=None, rule=None):
     """clip + Adam taken on the device only if `status` (the rollout's status word) says all
     `expect` horizon steps completed; `step_dev` is the device-side int64 step counter
-    (pmbrl_clip_adam_guarded)."""
+    (pmbrl_clip_adam_guarded).  rule: an optim.Rule (pmbrl_clip_adam_rule_guarded); lr / betas / eps are then the rule's."""
     lib = _lib.load()
     for t in (params, grads, exp_avg, exp_avg_sq):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     assert step_dev.is_cuda and step_dev.dtype == torch.int64 and status.is_cuda and status.dtype == torch.int32
+    if rule is not None:
+        r = _rule_struct(rule, params.numel())
+        _lib.check(lib.pmbrl_clip_adam_rule_guarded(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq),
+                                                    params.numel(), _ptr(step_dev), float(max_norm) if max_norm else 0.0,
+                                                    _ptr(norm_out), _ptr(status), int(expect), C.byref(r)),
+                   'pmbrl_clip_adam_rule_guarded')
+        return
     _lib.check(lib.pmbrl_clip_adam_guarded(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg),
                                            _ptr(exp_avg_sq), params.numel(), _ptr(step_dev), float(lr),
                                            float(betas[0]), float(betas[1]), float(eps),

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import engine as E
+from . import optim as OPT
 from .algorithms import _adam_flat_state, _sync_adam_state
 from .models import BDropout, CDropout
 
@@ -106,7 +107,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
                     decoupled_reg=False, prioritized_sampling=False, priority_eps=1e-3, priority_alpha=0.6,
                     _replay=None, _warmup_iters=100):
     """Same call as the reference.  Offered on the device: the default Gaussian likelihood with a
-    plain torch.optim.Adam; decoupled_reg (the regulariser's gradient applied by a separate plain
+    torch.optim.Adam or AdamW (parameter groups, weight decay, amsgrad, maximize: optim.py); decoupled_reg (the regulariser's gradient applied by a separate plain
     SGD step, :133-147) and prioritized_sampling (minibatches from a per-model SumTree with
     importance weights, priorities from the rows' log-likelihoods, :88-131)."""
     from .models import GaussianMixtureDensity
@@ -165,8 +166,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
     flat = flat_module_parameters(params, model)
     cache = _adam_flat_state(optimizer, params, flat)
     if cache is None:
-        raise NotImplementedError('BNN training on the device needs a plain torch.optim.Adam over '
-                                  'model.parameters()')
+        raise NotImplementedError('BNN training on the device needs a %s over model.parameters()' % OPT.OFFERED)
     steps = {}
     grad = torch.empty_like(flat)
     # u / bvar: one [M, h_l] block per dropout layer of either kind, in layer order
@@ -253,8 +253,9 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
                                for a, (_, h) in zip(_replay['u'][done], drop_w)]).contiguous()
                 bv = torch.cat([1.0 - f32(a) for a in _replay['hard'][done]]).contiguous()      # hard = (bvar < probs)
             hist = torch.empty(len(take), 3, dtype=torch.float32, device=dev)
+            # (the groups' numbers are read per chunk: optim.rule_of; the plain rule goes the plain way)
             loss = st.train_steps(Xn, Yn, idx_all, flat, cache['m'], cache['v'], step_dev, g['lr'], g['betas'], g['eps'],
-                                  seed=seed, first_step=done, u=u, bvar=bv, loss_hist=hist)
+                                  seed=seed, first_step=done, u=u, bvar=bv, loss_hist=hist, rule=OPT.rule_of(cache))
             cache['step'] += len(take)
             last = loss
             if summary_writer is not None:
@@ -303,7 +304,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
         cache['step'] += 1
         g = cache['group']
         E.clip_adam(flat, grad, cache['m'], cache['v'], cache['step'], g['lr'], g['betas'], g['eps'],
-                    max_norm=None)
+                    max_norm=None, rule=OPT.rule_of(cache))
         if prioritized_sampling:
             # new priorities from the rows' log-likelihoods (utils/train_regressor.py:117-128)
             a = 2
@@ -317,7 +318,18 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
             if decoupled_reg and loss is not None:
                 loss = loss.clone()
             _, lreg = st.loss_grad(Xn, Yn, idx, flat, u_fixed, bvar, grad, terms=2)
-            flat.add_(grad, alpha=-float(g['lr']))
+            # (the reference builds it as torch.optim.SGD(optimizer.param_groups): every group's own lr, weight_decay as
+            #  SGD's L2 term and maximize)
+            lo = 0
+            for hi, k in cache['segments']:
+                gk = optimizer.param_groups[k]
+                d = grad[lo:hi]
+                if gk.get('maximize', False):
+                    d = -d
+                if gk.get('weight_decay', 0) != 0:
+                    d = d.add(flat[lo:hi], alpha=float(gk['weight_decay']))
+                flat[lo:hi].add_(d, alpha=-float(gk['lr']))
+                lo = hi
             loss[2] = lreg[2]
         last = loss
         if summary_writer is not None:
