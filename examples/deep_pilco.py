@@ -23,6 +23,15 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from prob_mbrl_amd import algorithms, envs, models, utils  # noqa: E402
 
 
+def nonlin_names(s):
+    """--nonlin: a name of prob_mbrl_amd.activations.NAMES, or a comma list of them with one name per hidden layer."""
+    from prob_mbrl_amd.activations import NAMES
+    for n in s.split(','):
+        if n.strip() not in NAMES:
+            raise argparse.ArgumentTypeError('%r is not one of %s' % (n, ', '.join(NAMES)))
+    return s
+
+
 def parse(argv=None):
     ap = argparse.ArgumentParser('Deep-PILCO (MI355X build)')
     ap.add_argument('-e', '--env', type=str, default='Cartpole')
@@ -38,8 +47,9 @@ def parse(argv=None):
     ap.add_argument('--no_mm', action='store_true', help='particles only (deep_pilco_no_mm.py)')
     ap.add_argument('--learn_reward', action='store_true',
                     help='a learned reward head: the dynamics model predicts the reward (examples/deep_pilco_mm.py:94-99)')
-    ap.add_argument('--nonlin', type=str, default='relu', choices=['relu', 'tanh', 'silu'],
-                    help='activation of the hidden layers of the dynamics model and the policy')
+    ap.add_argument('--nonlin', type=nonlin_names, default='relu',
+                    help='activation of the hidden layers of the dynamics model and the policy: relu | tanh | silu | sin | '
+                         'exp | sinlu | hhsinlu | none, or a comma list with one name per hidden layer (relu,sin)')
     ap.add_argument('--dyn_lr', type=float, default=1e-4)
     ap.add_argument('--dyn_opt', type=str, default='adam', choices=['adam', 'adamw'],
                     help='optimiser of the dynamics model: torch.optim.Adam (weight decay as an L2 term) or AdamW (decoupled)')
@@ -122,7 +132,7 @@ def main(argv=None):
     else:   # (learned reward: one more mean and log-std, examples/deep_pilco_mm.py:117)
         Dy = D + 1 if args.learn_reward else D
         density, dynE = models.DiagGaussianDensity(Dy), 2 * Dy
-    # --nonlin: one activation for the hidden layers of both networks (relu | tanh | silu)
+    # --nonlin: the hidden layers' activations of both networks, one name or one per layer
     from prob_mbrl_amd.activations import module_of
     nonlin = module_of(args.nonlin)
     dyn = models.DynamicsModel(

@@ -83,16 +83,37 @@ extern "C" {
  * SPLIT_F16; not offered with the mixture head (dyn_components > 1) or with groups spread over ranks (mm_span_rows). */
 #define PMBRL_REWARD_LEARNED 2
 
-/* Activation of a network's hidden layers (models/core.py:15-99, nonlin=): ONE for all hidden layers of a network,
- * chosen per network -- pmbrl_config::pol_act / dyn_act, pmbrl_mlp_call::act, pmbrl_bnn_config::act, each the LAST field
- * of its struct (pmbrl_mlp keeps its layout); 0 = ReLU, so a zero-initialised struct means what it did.  TANH = torch.nn.Tanh, SILU = torch.nn.SiLU = models/activations.py:4-6 (Swish, x sigmoid(x)).
- * A rollout plan with a network that is not ReLU runs on the general kernel family (pmbrl_plan_info: fast = 0,
+/* Activation of a network's hidden layers (models/core.py:15-99, nonlin=; models/activations.py), chosen per network and,
+ * within a network, per hidden layer -- pmbrl_config::pol_act / dyn_act, pmbrl_mlp_call::act, pmbrl_bnn_config::act, each
+ * the LAST field of its struct (pmbrl_mlp keeps its layout).  With a the pre-activation, j the unit's index and n the
+ * layer's width:
+ *   RELU     max(a, 0)                      TANH  torch.nn.Tanh          SILU  torch.nn.SiLU = Swish, a sigmoid(a)
+ *   SIN      sin a                          EXP   exp(-a^2 / 2)          SINLU a if a > 0, else sin a
+ *   HHSINLU  with s_j = -1 for even j, +1 for odd j: sin(s_j a) for j < ceil(n / 2), else max(s_j a, 0)
+ *   NONE     a (a hidden Linear with no activation behind it)
+ * sin / cos are the accurate library forms at any argument.  Two forms of the field:
+ *   - the plain form, a value 0 .. 2 (RELU, TANH, SILU): that code for every hidden layer, exactly the values the field
+ *     has always taken (0 = ReLU, so a zero-initialised struct means what it did); a plain 3 .. 7 is refused as every
+ *     plain value above 2 has always been -- callers that probed with such a value see what they saw;
+ *   - the per-layer form, the only one that carries SIN .. NONE (the same code in every layer for a uniform network):
+ *     PMBRL_ACT_PER_LAYER | code_0 | code_1 << 3 | ... | code_l << (3 l): hidden layer l has code_l (PMBRL_ACT_LAYER;
+ *     at most PMBRL_MAX_LAYERS - 1 = 7 hidden layers, 21 bits).  Bits of layers the network does not have must be 0.
+ * A rollout plan with a hidden layer that is not ReLU runs on the general kernel family (pmbrl_plan_info: fast = 0,
  * PMBRL_INFO_REG = 0, PMBRL_INFO_INPLACE = 0), F32 or SPLIT_F16; its forward sweep leaves act'(pre-activation) x mask /
- * keep per hidden unit and row-step for the adjoint (4 bytes each, in place of the 1-bit activity flags of ReLU).
- * Any other value: plan creation (pmbrl_plan_create, pmbrl_bnn_plan_create) and the stand-alone calls return -2. */
+ * keep per hidden unit and row-step for the adjoint (4 bytes each, in place of the 1-bit activity flags of ReLU); a
+ * plan whose layers are all ReLU, in either form, runs what it always ran.
+ * Any other value: plan creation (pmbrl_plan_create, pmbrl_bnn_plan_create) and the stand-alone calls return -2
+ * (pmbrl_act_check). */
 #define PMBRL_ACT_RELU 0
 #define PMBRL_ACT_TANH 1
 #define PMBRL_ACT_SILU 2
+#define PMBRL_ACT_SIN 3
+#define PMBRL_ACT_EXP 4
+#define PMBRL_ACT_SINLU 5
+#define PMBRL_ACT_HHSINLU 6
+#define PMBRL_ACT_NONE 7
+#define PMBRL_ACT_PER_LAYER (1 << 30)
+#define PMBRL_ACT_LAYER(code, l) ((code) << (3 * (l)))
 
 /* One MLP as built by models/core.py:15-99 (mlp): Linear -> activation -> dropout ...
  * -> Linear.  dims[0] = input width, dims[n_layers] = output width.
@@ -242,6 +263,11 @@ enum {
 };
 
 const char* pmbrl_last_error(void);
+/* Pure host code: is `act` a valid activation field (PMBRL_ACT_*, above) for a network with n_hidden hidden layers
+ * (0 .. PMBRL_MAX_LAYERS - 1)?  0, or -2 with a message: a plain value above 2; in the per-layer form a non-zero code
+ * of a layer the network does not have, or any bit other than PMBRL_ACT_PER_LAYER above the 21 code bits; a negative
+ * value; n_hidden out of range.  Every entry point that takes an activation goes through it. */
+int pmbrl_act_check(int32_t act, int32_t n_hidden);
 int pmbrl_version(void);
 /* 16 hex digits: hash of the kernel sources the library was built from.  Hardware-counter measurements under
  * profiles/ record it; bench.py reports such a measurement only if it was taken on the build it is running. */

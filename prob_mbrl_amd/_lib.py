@@ -113,7 +113,7 @@ EXPORTS = [
     'pmbrl_p2p_create', 'pmbrl_p2p_handle', 'pmbrl_p2p_open', 'pmbrl_p2p_allreduce_f32', 'pmbrl_p2p_allreduce_f64',
     'pmbrl_plan_set_p2p', 'pmbrl_p2p_error', 'pmbrl_p2p_destroy', 'pmbrl_plan_set_grad_comm',
     'pmbrl_opt_rule_check', 'pmbrl_clip_adam_rule', 'pmbrl_clip_adam_rule_guarded', 'pmbrl_plan_set_optimizer',
-    'pmbrl_bnn_plan_set_optimizer',
+    'pmbrl_bnn_plan_set_optimizer', 'pmbrl_act_check',
 ]
 
 class Adam(C.Structure):
@@ -280,6 +280,8 @@ def load():
     lib.pmbrl_plan_set_collective.restype = C.c_int
     lib.pmbrl_plan_set_collective.argtypes = [vp, COLLECTIVE_FN, vp]
     rule = C.POINTER(OptRule)
+    lib.pmbrl_act_check.restype = C.c_int
+    lib.pmbrl_act_check.argtypes = [C.c_int32, C.c_int32]
     lib.pmbrl_opt_rule_check.restype = C.c_int
     lib.pmbrl_opt_rule_check.argtypes = [rule, i64]
     lib.pmbrl_clip_adam_rule.restype = C.c_int

@@ -36,8 +36,8 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
         raise RuntimeError('the critic must live on a HIP device (no CPU fallback)')
     if V.output_density is not None:
         raise NotImplementedError('critic with an output density: not offered on the device path')
-    linears, drops, inner = V.model.layer_spec()
-    act = V.model.activation()      # the hidden layers' activation (activations.RELU / TANH / SILU)
+    linears, drops, inner, _ = V.model.layers_spec()
+    act = V.model.activation()      # the hidden layers' activations, packed (activations.pack)
     if inner is not None or linears[-1].out_features != 1:
         raise NotImplementedError('the device path fits a critic with one plain output')
     draws = list(_bernoulli) if _bernoulli is not None else None

@@ -336,6 +336,26 @@ __global__ __launch_bounds__(PM_MMW_NT) void pm_mmw_bwd_kernel(RolloutArgs A, in
 // ---------------------------------------------------------------------------
 static size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
+const char* pm_act_refusal(int32_t act, int n_hidden) {
+  if (n_hidden < 0 || n_hidden > PM_MAXL - 1) return "activation: n_hidden outside 0 .. PMBRL_MAX_LAYERS - 1";
+  if (act < 0) return "unknown activation (a negative value)";
+  if (!(act & PMBRL_ACT_PER_LAYER)) {
+    // (the plain form stays what it was, three values; whatever it refused before it still refuses)
+    if (act > PMBRL_ACT_SILU)
+      return "unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU for every hidden layer, or "
+             "PMBRL_ACT_PER_LAYER with one code PMBRL_ACT_RELU .. PMBRL_ACT_NONE per hidden layer, are offered)";
+    return nullptr;
+  }
+  const int32_t codes = act & ~PMBRL_ACT_PER_LAYER;
+  if (codes >> (3 * (PM_MAXL - 1))) return "activation: stray bits above the per-layer codes";
+  if (codes >> (3 * n_hidden)) return "activation: a code for a hidden layer the network does not have";
+  return nullptr;
+}
+extern "C" int pmbrl_act_check(int32_t act, int32_t n_hidden) {
+  const char* why = pm_act_refusal(act, n_hidden);
+  return why ? fail(-2, why) : 0;
+}
+
 static int net_plan(const pmbrl_mlp& m, int act, NetPlan& n, int in_expect, int out_expect,
                     const char* name) {
   if (m.n_layers < 1 || m.n_layers > PM_MAXL)
@@ -349,9 +369,8 @@ static int net_plan(const pmbrl_mlp& m, int act, NetPlan& n, int in_expect, int 
   }
   if (n.dim[0] != in_expect || n.dim[n.nl] != out_expect)
     return fail(-2, std::string(name) + ": input/output width does not match D/U");
-  if (act != PMBRL_ACT_RELU && act != PMBRL_ACT_TANH && act != PMBRL_ACT_SILU)
-    return fail(-2, std::string(name) + ": unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
-  n.act = act;
+  if (const char* why = pm_act_refusal(act, n.nl - 1)) return fail(-2, std::string(name) + ": " + why);
+  n.act = pm_act_layers(act, n.nl - 1);
   for (int l = 0; l < n.nl; ++l) {
     n.keep[l] = (l < n.nl - 1) ? m.keep[l] : 1.f;
     if (l < n.nl - 1 && !(n.keep[l] > 0.f)) return fail(-2, std::string(name) + ": keep must be > 0");
@@ -447,7 +466,7 @@ static int plan_nets(pmbrl_plan* p) {
   if (rc == 0)
     rc = net_plan(c.dyn, c.dyn_act, p->dyn, c.D + c.U + c.n_dyn_angle,
                   gmm ? (2 * c.D + 1) * c.dyn_components + 1 : 2 * (c.D + p->learned), "dynamics");
-  p->act = rc == 0 && (p->pol.act != PMBRL_ACT_RELU || p->dyn.act != PMBRL_ACT_RELU);
+  p->act = rc == 0 && (p->pol.act != 0 || p->dyn.act != 0);   // (some hidden layer of some network is not ReLU)
   return rc;
 }
 
@@ -1312,7 +1331,7 @@ static int fill_args(const pmbrl_plan* p, void* workspace, const pmbrl_inputs* i
   memset(&A, 0, sizeof(A));
   A.B = c.B; A.D = c.D; A.U = c.U; A.H = c.H;
   A.Bg = c.B_global; A.row_off = c.row_offset; A.flags = c.flags;
-  A.flags |= (p->pol.act << PM_ACT_POL_SHIFT) | (p->dyn.act << PM_ACT_DYN_SHIFT);   // (read by the ACT instances only)
+  A.pol_acts = p->pol.act; A.dyn_acts = p->dyn.act;   // (read by the ACT instances only)
   A.G = p->G; A.M = p->M; A.mm_mode = p->mm_mode;
   A.t0 = 0; A.t1 = c.H;
   A.rows_per_wg = p->rows_per_wg; A.nwg = p->nwg; A.Rw = 16 * p->RT; A.LD = p->LD; A.LDB = p->LDB;

@@ -46,7 +46,7 @@ struct BnnArgs {
   int rng;
   unsigned rng_k0, rng_k1, rng_step;
   long long* prof;                 // debugging: cycle stamps of workgroup 0 (nullptr: none)
-  int act;                         // PMBRL_ACT_* of the hidden layers (pm_bnn_fwd_bwd<true> when not ReLU)
+  int act;                         // PMBRL_ACT_* per hidden layer, pm_act_code (pm_bnn_fwd_bwd<true> when not 0 = all ReLU)
   // fixed-rate Bernoulli dropout behind hidden layer l (pm_bnn_fwd_bwd<., true>): the units' keep probabilities
   // [nt[l+1] * 16] (a scalar rate is stored once per unit), nullptr for a layer of another kind.  m = bvar < p_j.
   const float* keep[PM_MAXL];
@@ -60,7 +60,8 @@ __device__ __forceinline__ float pm_fast_rcp(float d) {
 
 // hidden layer forward: out = relu(acc + b) * hard ;  q = relu(.) * d mask / d logit_p
 // ACT: out = act(acc + b) * hard, q = act(.) * d mask / d logit_p, and d_out = act'(acc + b) * hard for the backward pass
-// (pm_act; act = PMBRL_ACT_TANH / PMBRL_ACT_SILU).  The ReLU instance is what it was.
+// (pm_act; act = this layer's PMBRL_ACT_* code).  The ReLU instance is what it was.  Padded units and rows past nvalid
+// are forced to 0 in out, q and d_out after the activation, whatever act(0) is (PMBRL_ACT_EXP: 1).
 // BERN (plans with a Bernoulli layer; keep != nullptr marks one): m = bvar < p_j, out = act(acc + b) * m / p_j -- divided as
 // BDropout.forward divides, per unit -- q = 0 (there is no logit), d_out = act'(acc + b) * m / p_j.
 template <bool ACT = false, bool BERN = false>
@@ -97,7 +98,7 @@ struct EpiBnnFwd {
     for (int r = 0; r < 4; ++r) {
       const int f = f0 + r;
       float v, dv = 0.f;
-      if constexpr (ACT) pm_act(act, acc[r] + b[r], v, dv);
+      if constexpr (ACT) pm_act(act, acc[r] + b[r], f, width, v, dv);
       else v = fmaxf(acc[r] + b[r], 0.f);
       float hv = v, qv = 0.f;
       if (logit_p && f < width && lrow < nvalid) {
@@ -219,7 +220,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   BNN_STAMP(1);
   // ---- forward
   for (int l = 0; l < nl - 1; ++l) {
-    EpiBnnFwd<ACT, BERN> e{A.act, ACT ? dbuf(l) : nullptr, A.bias[l], A.logit_p[l], BERN ? A.keep[l] : nullptr, A.u[l], A.bvar[l], A.inv_temp[l],
+    EpiBnnFwd<ACT, BERN> e{pm_act_code(A.act, l), ACT ? dbuf(l) : nullptr, A.bias[l], A.logit_p[l], BERN ? A.keep[l] : nullptr, A.u[l], A.bvar[l], A.inv_temp[l],
                 H + (size_t)(l + 1) * R * LD, Q + (size_t)l * R * LD,
                 A.actT[l + 1] + (size_t)wg * A.nt[l + 1] * 16 * 16, LD, row0, nvalid, A.dim[l + 1], lane,
                 A.rng, A.rng_k0, A.rng_k1, A.rng_step, (unsigned)l};

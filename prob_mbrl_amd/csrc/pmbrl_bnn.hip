@@ -32,6 +32,7 @@ static BnnKernels bnn_kernels(int act, int any_bern) {
 struct pmbrl_bnn_plan {
   pmbrl_bnn_config cfg;
   int device, nl, LD, nwg, sum_h, n_params;
+  int acts;       // PMBRL_ACT_* per hidden layer (pm_act_layers of cfg.act); 0: every layer is ReLU
   int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
   int w_off[PM_MAXL], b_off[PM_MAXL], lp_poff[PM_MAXL], lp_off[PM_MAXL], has_drop[PM_MAXL];
   size_t off_wf[PM_MAXL], off_wb[PM_MAXL], off_bias[PM_MAXL], off_actT[PM_MAXL], off_gT[PM_MAXL];
@@ -75,7 +76,7 @@ static void bnn_plan_records(pmbrl_bnn_plan* p) {
     A.n_out = ((p->dim[p->nl] - 1) / A.gmm_n - 1) / 2;
   }
   A.n_in = p->dim[0]; A.sum_h = p->sum_h;
-  A.act = c.act;
+  A.act = p->acts;
   A.mls = c.max_log_std;
   A.mse = c.loss_kind == 1;
   A.inv_M = F.inv_M = T.inv_M = 1.f / (float)c.M;
@@ -189,11 +190,12 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->n_params = po;
   p->LD = maxnt * 16 + 8;
   p->nwg = (cfg->M + 15) / 16;
-  if (cfg->act != PMBRL_ACT_RELU && cfg->act != PMBRL_ACT_TANH && cfg->act != PMBRL_ACT_SILU) {
+  if (const char* why = pm_act_refusal(cfg->act, p->nl - 1)) {
     delete p;
-    return fail(-2, "bnn: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
+    return fail(-2, std::string("bnn: ") + why);
   }
-  p->lds = pm_bnn_lds_floats(p->nl, p->LD, cfg->act) * sizeof(float);
+  p->acts = pm_act_layers(cfg->act, p->nl - 1);
+  p->lds = pm_bnn_lds_floats(p->nl, p->LD, p->acts) * sizeof(float);
   if (p->lds > 160 * 1024) { delete p; return fail(-3, "bnn: network too wide / deep for the fused training step's LDS budget"); }
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
@@ -229,7 +231,7 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
     for (int l = 0; l < p->nl - 1; ++l)
       if (p->has_drop[l] == 2) p->keep_d[l] = p->keep_all_d + koff[l];
   }
-  p->kern = bnn_kernels(cfg->act, p->any_bern);
+  p->kern = bnn_kernels(p->acts, p->any_bern);
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(p->kern.fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
                              (int)p->lds));
   bnn_plan_records(p);

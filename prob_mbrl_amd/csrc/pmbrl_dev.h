@@ -170,8 +170,12 @@ struct RolloutArgs {
   StreamDesc sd_fwd, sd_bwd;
   FastOff fo;
   long long* prof;              // debug: cycle stamps [H][32] of workgroup 0 (nullptr = off)
+  // the hidden layers' activations of the policy / the dynamics model, three bits a layer (pm_act_code); read by the ACT
+  // instances only, and last, so that no field another kernel reads has moved
+  int pol_acts, dyn_acts;
 };
-static_assert(sizeof(RolloutArgs) == 2648, "RolloutArgs is a kernel argument: its layout does not move");
+static_assert(offsetof(RolloutArgs, pol_acts) == 2648 && sizeof(RolloutArgs) == 2656,
+              "RolloutArgs is a kernel argument: its layout does not move (the 2648 bytes in front of pol_acts are what they were)");
 
 #include "pmbrl_instances.h"   // PF_VAR_*: the kernel variants of the latency-optimised family (pmbrl_fast.h)
 
@@ -498,12 +502,15 @@ __device__ __forceinline__ float sigmoidf(float x) { return 1.f / (1.f + expf(-x
 // testing a sign, so a further activation is one more branch here.  Saturation: tanhf is +-1 beyond |a| = 9, and
 // sigmoidf's IEEE division turns the overflowed exp(-a) = inf into 0, not a NaN (a reciprocal with a Newton step would):
 // |a| = 50 and beyond gives tanh = +-1, d = 0 and silu = a or -0, d = 1 or 0.
-// A rollout plan with a network that is not ReLU carries the two activations in bits of RolloutArgs::flags the public
-// PMBRL_FLAG_* do not use: no kernel of another family sees a new argument.
-#define PM_ACT_POL_SHIFT 20
-#define PM_ACT_DYN_SHIFT 22
-#define PM_ACT_MASK 3
-__device__ __forceinline__ void pm_act(int act, float a, float& h, float& d) {
+// j is the unit's index in its layer and n the layer's width: HHSINLU (models/activations.py:28-39) flips the sign of
+// every even unit, takes the sine in the first ceil(n / 2) units -- torch.chunk gives the first half the odd one -- and
+// ReLU in the rest.  sin / cos are the library's (full argument reduction: pre-activations of +-50 and beyond keep fp32
+// accuracy; the hardware's v_sin_f32 does not).  EXP is the one activation with act(0) != 0: every caller forces h = d = 0
+// in padded units, rows past the batch and masked units AFTER this call, none relies on act(0) = 0.
+// The codes are per hidden layer (pm_act_layers, pmbrl_host.h): layer l's in bits 3 l .. 3 l + 2; a rollout plan carries
+// them in RolloutArgs::pol_acts / dyn_acts, which only the ACT instances read.
+__device__ __forceinline__ int pm_act_code(int acts, int l) { return (acts >> (3 * l)) & 7; }
+__device__ __forceinline__ void pm_act(int act, float a, int j, int n, float& h, float& d) {
   if (act == PMBRL_ACT_TANH) {
     h = tanhf(a);
     d = 1.f - h * h;
@@ -511,6 +518,30 @@ __device__ __forceinline__ void pm_act(int act, float a, float& h, float& d) {
     const float s = sigmoidf(a);
     h = a * s;
     d = s * (1.f + a * (1.f - s));
+  } else if (act == PMBRL_ACT_SIN) {
+    h = sinf(a);
+    d = cosf(a);
+  } else if (act == PMBRL_ACT_EXP) {
+    h = expf(-0.5f * a * a);
+    d = -a * h;
+  } else if (act == PMBRL_ACT_SINLU) {
+    const bool pos = a > 0.f;
+    h = pos ? a : sinf(a);
+    d = pos ? 1.f : cosf(a);
+  } else if (act == PMBRL_ACT_HHSINLU) {
+    const float s = (j & 1) ? 1.f : -1.f;
+    const float sa = s * a;
+    if (2 * j < n + (n & 1)) {
+      h = sinf(sa);
+      d = s * cosf(sa);
+    } else {
+      const bool pos = sa > 0.f;
+      h = pos ? sa : 0.f;
+      d = pos ? s : 0.f;
+    }
+  } else if (act == PMBRL_ACT_NONE) {
+    h = a;
+    d = 1.f;
   } else {
     const bool pos = a > 0.f;
     h = pos ? a : 0.f;

@@ -1,4 +1,4 @@
-// General kernel family for plans with a network that is not ReLU (pmbrl_mlp activations PMBRL_ACT_TANH / PMBRL_ACT_SILU;
+// General kernel family for plans with a hidden layer that is not ReLU (PMBRL_ACT_TANH .. PMBRL_ACT_NONE, per layer;
 // pmbrl_rollout.h: the ACT instances of pm_rollout_fwd / pm_rollout_bwd, EpiActFwdT / EpiActBwdT): the instantiations of
 // PM_GENERAL_ACT_INSTANCES -- exact fp32 and split operands (two fp16 pieces forward, two bf16 pieces in the adjoint) --
 // and their table.  Two activation buffers always: the in-place and wide layers stay ReLU-only.

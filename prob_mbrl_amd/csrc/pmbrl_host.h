@@ -46,7 +46,7 @@ struct NetPlan {
   int nl;
   int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
   float keep[PM_MAXL];
-  int act;                                 // PMBRL_ACT_* of the hidden layers
+  int act;                                 // PMBRL_ACT_* per hidden layer (pm_act_layers); 0: every layer is ReLU
   size_t w_off[PM_MAXL], b_off[PM_MAXL];   // offsets (floats) in the flat parameter vector
   size_t n_params;
   // workspace offsets (bytes)
@@ -72,7 +72,7 @@ struct pmbrl_plan {
   size_t lds_bytes;
   NetPlan pol, dyn;
   RewardDev* rew_d;
-  int act;             // a network is not ReLU: the general family's ACT instances, per-unit act' stashes in place of the activity bits
+  int act;             // some hidden layer of some network is not ReLU: the general family's ACT instances, per-unit act' stashes in place of the activity bits
   int learned;         // PMBRL_REWARD_LEARNED: the dynamics head predicts the reward (general family only)
   int rew_k = PMBRL_MAX_TIP;   // tip residuals of the reward (which instance of the reward launch: pm_reward_kernel_for)
   int* wflag_d;        // weight-range flag of the fp16 packer (see RolloutArgs::wflag)
@@ -234,6 +234,16 @@ int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float*
                            int64_t* step_d, double lr, double beta1, double beta2, double eps, double max_norm,
                            float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
                            float* loss_out_d = nullptr, int n_loss_part = 0, const pmbrl_opt_rule* rule = nullptr);
+// what pmbrl_act_check refuses, as text (nullptr: nothing); host code only (pmbrl.hip)
+const char* pm_act_refusal(int32_t act, int n_hidden);
+// An activation field that passed pmbrl_act_check, in the one form the kernels read (pm_act_code, pmbrl_dev.h): the code
+// of hidden layer l in bits 3 l .. 3 l + 2, the plain form (0 .. 2) spread over the n_hidden layers; 0 = every layer is ReLU
+inline int pm_act_layers(int32_t act, int n_hidden) {
+  if (act & PMBRL_ACT_PER_LAYER) return act & ~PMBRL_ACT_PER_LAYER;
+  int v = 0;
+  for (int l = 0; l < n_hidden; ++l) v |= PMBRL_ACT_LAYER(act, l);
+  return v;
+}
 // what pmbrl_opt_rule_check refuses, as text (nullptr: nothing); host code only
 const char* pm_opt_rule_refusal(const pmbrl_opt_rule* r, int64_t n);
 void pm_tail_hvec_launch(hipStream_t s, float* hvec, int world, int rank, const int* status, int H);

@@ -17,11 +17,12 @@ struct MlpArgs {
   const float *x, *z, *in_shift, *in_iscale, *out_scale, *out_shift, *sq_scale, *sq_bias;
   float mls;
   float *sample, *mean, *log_std;
-  int act;                          // PMBRL_ACT_* of the hidden layers
+  int act;                          // PMBRL_ACT_* per hidden layer (pm_act_code); 0: every layer is ReLU
 };
 
-// The same with act = PMBRL_ACT_TANH / PMBRL_ACT_SILU (pm_act): h = act(v) * mask / keep, and -- d_out given, the input
-// gradient's recomputed forward -- act'(v) * mask / keep next to it.  Padded units (width .. nt * 16) stay 0 in both.
+// The same with this layer's activation (pm_act; act = its PMBRL_ACT_* code): h = act(v) * mask / keep, and -- d_out
+// given, the input gradient's recomputed forward -- act'(v) * mask / keep next to it.  Padded units (width .. nt * 16),
+// rows past nvalid and masked units are 0 in both, whatever act(0) is (PMBRL_ACT_EXP: 1).
 struct EpiMlpAct {
   const float* bias;
   const uint16_t* mask;
@@ -40,7 +41,7 @@ struct EpiMlpAct {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float hv, dv;
-      pm_act(act, acc[r] + b[r], hv, dv);
+      pm_act(act, acc[r] + b[r], f0 + r, width, hv, dv);
       const bool m = ((nib >> r) & 1u) && f0 + r < width;
       h[r] = m ? (keep == 1.f ? hv : hv / keep) : 0.f;
       d[r] = m ? (keep == 1.f ? dv : dv / keep) : 0.f;
@@ -102,7 +103,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_fwd_kernel(const MlpArgs A) {
   __syncthreads();
   for (int l = 0; l < A.nl - 1; ++l) {
     if (A.act != PMBRL_ACT_RELU) {
-      EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], Y, nullptr, LD, row0, nvalid, A.nt[l + 1], lane, A.act, A.dim[l + 1]};
+      EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], Y, nullptr, LD, row0, nvalid, A.nt[l + 1], lane, pm_act_code(A.act, l), A.dim[l + 1]};
       gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], X, LD, wid, lane, e);
     } else {
       EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], Y, LD, row0, nvalid, A.nt[l + 1], lane};
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   for (int l = 0; l < nl - 1; ++l) {
     if (smooth) {
       EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, dbuf(l), LD, row0, nvalid, A.nt[l + 1],
-                  lane, A.act, A.dim[l + 1]};
+                  lane, pm_act_code(A.act, l), A.dim[l + 1]};
       gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
     } else {
       EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, LD, row0, nvalid, A.nt[l + 1], lane};
@@ -379,7 +380,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const MlpBwdPArgs
     for (int l = 0; l < nl - 1; ++l) {
       if (smooth) {
         EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, D + (size_t)l * R * LD, LD, row0,
-                    nvalid, A.nt[l + 1], lane, A.act, A.dim[l + 1]};
+                    nvalid, A.nt[l + 1], lane, pm_act_code(A.act, l), A.dim[l + 1]};
         gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
       } else {
         EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, LD, row0, nvalid, A.nt[l + 1], lane};

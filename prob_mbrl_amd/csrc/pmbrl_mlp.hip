@@ -14,7 +14,7 @@
 // stand-alone network evaluation
 // ---------------------------------------------------------------------------
 struct MlpLayout {
-  int nl, LD;
+  int nl, LD, act;      // act: PMBRL_ACT_* per hidden layer (pm_act_layers)
   int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
   size_t wf[PM_MAXL], wb[PM_MAXL], bias[PM_MAXL], w_off[PM_MAXL], b_off[PM_MAXL], bytes, lds, lds_bwd, lds_bwdp, n_params;
 };
@@ -45,10 +45,10 @@ static int mlp_layout(const pmbrl_mlp_call* c, MlpLayout& L) {
   L.n_params = po;
   L.LD = maxnt * 16 + 8;
   L.lds = (2 * (size_t)16 * L.LD + (size_t)PM_NW * PM_KS_NT * 256) * sizeof(float);
-  if (c->act != PMBRL_ACT_RELU && c->act != PMBRL_ACT_TANH && c->act != PMBRL_ACT_SILU)
-    return fail(-2, "mlp: unknown activation (PMBRL_ACT_RELU, PMBRL_ACT_TANH, PMBRL_ACT_SILU are offered)");
-  L.lds_bwd = pm_mlp_bwd_lds_floats(L.nl, L.LD, c->act) * sizeof(float);
-  L.lds_bwdp = pm_mlp_bwdp_lds_floats(L.nl, L.LD, c->act) * sizeof(float);
+  if (const char* why = pm_act_refusal(c->act, L.nl - 1)) return fail(-2, std::string("mlp: ") + why);
+  L.act = pm_act_layers(c->act, L.nl - 1);
+  L.lds_bwd = pm_mlp_bwd_lds_floats(L.nl, L.LD, L.act) * sizeof(float);
+  L.lds_bwdp = pm_mlp_bwdp_lds_floats(L.nl, L.LD, L.act) * sizeof(float);
   if (L.lds > 160 * 1024) return fail(-3, "mlp: network too wide for LDS");
   return 0;
 }
@@ -96,7 +96,7 @@ extern "C" int pmbrl_mlp_forward(void* stream, const pmbrl_mlp_call* c, void* wo
   A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
   A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
   A.mls = c->max_log_std;
-  A.act = c->act;
+  A.act = L.act;
   A.sample = sample_d; A.mean = mean_d; A.log_std = log_std_d;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_fwd_kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
@@ -148,7 +148,7 @@ extern "C" int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* c, void*
   A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
   A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
   A.mls = c->max_log_std;
-  A.act = c->act;
+  A.act = L.act;
   Bw.g_sample = g_sample_d; Bw.g_mean = g_mean_d; Bw.g_log_std = g_log_std_d; Bw.grad_x = grad_x_d;
   HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdx_kernel),
                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bwd));
@@ -231,7 +231,7 @@ extern "C" int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* c, void* w
   A.x = x_d; A.z = z_d; A.in_shift = in_shift_d; A.in_iscale = in_iscale_d;
   A.out_scale = out_scale_d; A.out_shift = out_shift_d; A.sq_scale = sq_scale_d; A.sq_bias = sq_bias_d;
   A.mls = c->max_log_std;
-  A.act = c->act;
+  A.act = L.act;
   P.b.g_sample = g_sample_d; P.b.g_mean = g_mean_d; P.b.g_log_std = g_log_std_d; P.b.grad_x = grad_x_d;
   const int n_blocks = mlp_backward_blocks(c, L);
   P.n_params = L.n_params;

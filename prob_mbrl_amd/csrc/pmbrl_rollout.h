@@ -139,9 +139,12 @@ struct EpiHiddenBwdT {
 //   h = act(acc + b) * mask / keep,   dact = act'(acc + b) * mask / keep
 // dact ([B][nt * 16] floats of step t, in the workspace region the activity bits of a ReLU plan have) is all the adjoint
 // needs of the layer: g_pre = acc * dact.  tanh' could be had from the stashed h, SiLU's cannot (it is not monotone),
-// and the dynamics layers have no stash of h at all: one form for every activation, a ReLU network of a mixed plan
-// included (dact = mask / keep where the pre-activation is positive).  Padded units (width .. nt * 16) get h = 0 and
-// dact = 0 whatever act'(0) is.
+// and the dynamics layers have no stash of h at all: one form for every activation, a ReLU layer or network of a mixed
+// plan included (dact = mask / keep where the pre-activation is positive; PMBRL_ACT_NONE: dact = mask / keep).  `act` is
+// THIS layer's code (pm_act_code of RolloutArgs::pol_acts / dyn_acts).  Padded units (width .. nt * 16), rows past
+// nvalid (their mask word is read as 0) and masked units get h = 0 and dact = 0 whatever act(0) and act'(0) are --
+// PMBRL_ACT_EXP has act(0) = 1 -- so the LDS operand of the next layer, the stash the dW GEMM reads and dact hold zeros
+// there.
 template <int NP = 0, bool F16 = false, int R = 0>
 struct EpiActFwdT {
   const float* bias;
@@ -172,7 +175,7 @@ struct EpiActFwdT {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       float hv, dv;
-      pm_act(act, acc[r] + pr.b[r], hv, dv);
+      pm_act(act, acc[r] + pr.b[r], f0 + r, width, hv, dv);
       const bool m = ((nib >> r) & 1u) && f0 + r < width;
       // (the reference's division, x / p)
       h[r] = m ? (keep == 1.f ? hv : hv / keep) : 0.f;
@@ -438,7 +441,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       if constexpr (ACT) {
         EpiActFwdT<SP ? 2 : 0, SP, R> ea{P.bias[l], mk, reinterpret_cast<float*>(P.abits[l]) + (size_t)t * B * nt * 16,
                                         P.keep[l], Y, A.actT[l + 1] + blk * (size_t)nt * 16 * A.Rw, LD, A.Rw, row0, nvalid,
-                                        nt, lane, (A.flags >> PM_ACT_POL_SHIFT) & PM_ACT_MASK, P.dim[l + 1], p_ovf};
+                                        nt, lane, pm_act_code(A.pol_acts, l), P.dim[l + 1], p_ovf};
         if constexpr (SP) gemm_tiles_s<RT, true>(P.wf[l], nt, pm_kb32(P.nt[l]), X, LDB, wid, lane, ea);
         else gemm_tiles<RT>(P.wf[l], nt, P.nt[l], X, LD, wid, lane, ea);
       } else if constexpr (IP >= 2) {
@@ -562,7 +565,7 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_rollout_fwd(const RolloutArgs A) 
       if constexpr (ACT) {
         EpiActFwdT<SP ? 2 : 0, SP, R> ea{F.bias[l], mk, reinterpret_cast<float*>(F.abits[l]) + (size_t)t * B * nt * 16,
                                         F.keep[l], Y, nullptr, LD, A.Rw, row0, nvalid, nt, lane,
-                                        (A.flags >> PM_ACT_DYN_SHIFT) & PM_ACT_MASK, F.dim[l + 1], p_ovf};
+                                        pm_act_code(A.dyn_acts, l), F.dim[l + 1], p_ovf};
         if constexpr (SP) gemm_tiles_s<RT, true>(F.wf[l], nt, pm_kb32(F.nt[l]), X, LDB, wid, lane, ea);
         else gemm_tiles<RT>(F.wf[l], nt, F.nt[l], X, LD, wid, lane, ea);
       } else if constexpr (IP >= 2) {

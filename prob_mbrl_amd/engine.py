@@ -235,7 +235,7 @@ def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=Non
     """Stand-alone evaluation of one Bayesian MLP with a diagonal-Gaussian head on the rows of x
     (pmbrl_mlp_forward; models/core.py:169-187, 221-248).  dims = [n_in, h..., 2*n_out];
     mask_bits: per hidden layer an int16 bit-row tensor (pack_mask) or None.
-    act: the hidden layers' activation (activations.RELU / TANH / SILU).
+    act: the hidden layers' activations, packed (activations.pack).
     Returns a dict with the requested outputs among 'sample', 'mean', 'log_std' ([B, n_out]).
     If x requires grad the outputs are differentiable with respect to x (pmbrl_mlp_grad_input).
     params: the tensors [W0, b0, W1, b1, ...] whose values params_flat holds; where one of them requires grad the
@@ -272,7 +272,7 @@ class BnnStep:
         cfg.M, cfg.N = int(M), int(N)
         nl = len(dims) - 1
         cfg.net.n_layers = nl
-        cfg.act = int(act)      # the hidden layers' activation (activations.RELU / TANH / SILU)
+        cfg.act = int(act)      # the hidden layers' activations, packed (activations.pack)
         for i, d in enumerate(dims):
             cfg.net.dims[i] = int(d)
         for l in range(nl - 1):
@@ -450,7 +450,7 @@ class Engine:
                 mlp.dims[i] = int(d)
             for i in range(_lib.MAX_LAYERS):
                 mlp.keep[i] = float(keep[i]) if i < len(keep) else 1.0
-        # the hidden layers' activations (activations.RELU / TANH / SILU), one per network: anything but ReLU runs on the
+        # the hidden layers' activations, packed (activations.pack), one per network: anything but ReLU runs on the
         # general kernel family
         cfg.pol_act, cfg.dyn_act = int(pol_act), int(dyn_act)
         cfg.reward = make_reward_struct(reward_spec, D, U)

@@ -433,7 +433,9 @@ class BSequential(nn.Sequential):
         (squashed if `squash=(scale, bias)`) or (mean, log_std)."""
         from . import engine as E
         from .rollout import flat_parameters
-        linears, drops, inner, act = self._parse()
+        linears, drops, inner, acts = self._parse()
+        from . import activations as ACT
+        act = ACT.pack(acts)
         density = inner if inner is not None else density
         if not x.is_cuda:
             raise RuntimeError('the network lives on a HIP device: pass a device tensor (no CPU fallback)')
@@ -505,13 +507,32 @@ class BSequential(nn.Sequential):
     # --- structure the fused kernels understand ---------------------------
     def layer_spec(self):
         """Parse Linear -> activation -> [dropout] ... -> Linear [-> density] into
-        (linears, dropouts-per-hidden-layer, density).  The activation -- one for all hidden layers -- is
-        activation()."""
-        return self._parse()[:3]
+        (linears, dropouts-per-hidden-layer, density) for a network with ONE activation for all hidden layers, which
+        activation() names.  This pair is the interface callers written for one activation per network use; a network
+        whose hidden layers differ would be misread by them, so it is refused here as it always was: layers_spec()
+        describes it."""
+        from . import activations as ACT
+        linears, drops, density, acts = self._parse()
+        if len(set(acts)) > 1:
+            raise NotImplementedError('layer_spec() describes a network with one activation for all hidden layers; this '
+                                      'one mixes them: use layers_spec(), which gives one code per hidden layer '
+                                      '(hidden activations offered: %s)' % ACT.OFFERED)
+        return linears, drops, density
+
+    def layers_spec(self):
+        """(linears, dropouts-per-hidden-layer, density, PMBRL_ACT_* code per hidden layer) of
+        Linear -> [activation] -> [dropout] ... -> Linear [-> density]; what the device path itself reads."""
+        return self._parse()
+
+    def activations(self):
+        """PMBRL_ACT_* of every hidden layer (activations.RELU .. NONE); NONE: a hidden Linear with no activation."""
+        return list(self._parse()[3])
 
     def activation(self):
-        """PMBRL_ACT_* of the hidden layers (activations.RELU / TANH / SILU)."""
-        return self._parse()[3]
+        """The `act` value the C ABI takes for this network (activations.pack): the single code when all hidden layers
+        agree, the per-layer form otherwise."""
+        from . import activations as ACT
+        return ACT.pack(self._parse()[3])
 
     def _parse(self):
         from . import activations as ACT
@@ -522,10 +543,7 @@ class BSequential(nn.Sequential):
             if isinstance(m, nn.Linear):
                 if pending is not None:
                     drops.append(pending['drop'])
-                    if pending['act'] is None:
-                        raise NotImplementedError('every hidden layer needs an activation on the device path: %s are '
-                                                  'offered' % ACT.OFFERED)
-                    acts.append(pending['act'])
+                    acts.append(ACT.NONE if pending['act'] is None else pending['act'])
                 pending = dict(drop=None, act=None)
                 linears.append(m)
             elif pending is not None and pending['act'] is None and pending['drop'] is None and \
@@ -542,16 +560,13 @@ class BSequential(nn.Sequential):
                                           'offered: %s' % (name, type(m).__name__, ACT.OFFERED))
         if pending is not None and (pending['drop'] is not None or pending['act'] is not None):
             raise NotImplementedError('the output layer must be a plain Linear')
-        if len(set(acts)) > 1:
-            raise NotImplementedError('mixed activations inside one network are not offered on the device path: one of '
-                                      '%s for all hidden layers (policy and dynamics model choose independently)'
-                                      % ACT.OFFERED)
-        act = acts[0] if acts else ACT.RELU
-        if act != ACT.RELU and any(d is not None and d.unit_inv_keep() is not None for d in drops):
+        if len(acts) > ACT.MAX_HIDDEN:
+            raise NotImplementedError('at most %d hidden layers on the device path' % ACT.MAX_HIDDEN)
+        if any(a != ACT.RELU for a in acts) and any(d is not None and d.unit_inv_keep() is not None for d in drops):
             raise NotImplementedError('per-unit BDropout rates fold 1 / p_j into the layer in front, which is only valid '
-                                      'for ReLU (positively homogeneous); with Tanh / SiLU use a scalar rate (hidden '
-                                      'activations offered: %s)' % ACT.OFFERED)
-        return linears, drops, density, act
+                                      'for ReLU (positively homogeneous) on every hidden layer; with any other '
+                                      'activation use a scalar rate (hidden activations offered: %s)' % ACT.OFFERED)
+        return linears, drops, density, acts
 
 
 def mlp(input_dims, output_dims, hidden_dims=[200, 200], nonlin=nn.ReLU, output_nonlin=None,

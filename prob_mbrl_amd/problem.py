@@ -223,6 +223,18 @@ def loss_weights(d, B_global):
     return (sign * g[:, None] * np.ones((1, B_global)) / B_global).astype(np.float32)
 
 
+def _act_of(d, net):
+    from . import activations as ACT
+    if net + '_acts' in d:
+        return ACT.pack(int(c) for c in np.asarray(d[net + '_acts']))
+    if net + '_act' not in d:
+        return ACT.RELU
+    act = int(d[net + '_act'])
+    if act & ACT.PER_LAYER or act > ACT.NONE:      # already the ABI's value (or not a code: the library says so)
+        return act
+    return ACT.pack([act] * (int(d[net + '_n_layers']) - 1))      # one code for the network
+
+
 def engine_from_problem(d, device='cuda:0', rows_per_wg_hint=0, shard=None, B_global=None,
                         row_offset=None, force_generic=False, no_shaped=False, precision=None, mm_span=None,
                         reward_spec=None):
@@ -262,8 +274,9 @@ def engine_from_problem(d, device='cuda:0', rows_per_wg_hint=0, shard=None, B_gl
                    pol_angle_dims=[int(a) for a in np.asarray(d.get('pol_angle_dims', []))],
                    dyn_angle_dims=[int(a) for a in np.asarray(d.get('dyn_angle_dims', []))],
                    dyn_components=int(d['dyn_gmm_n']) if 'dyn_gmm_n' in d else 0, mm_span=mm_span,
-                   # the hidden layers' activations (activations.RELU / TANH / SILU), where the problem names them
-                   pol_act=int(d['pol_act']) if 'pol_act' in d else 0, dyn_act=int(d['dyn_act']) if 'dyn_act' in d else 0)
+                   # the hidden layers' activations, where the problem names them: one code per network (pol_act /
+                   # dyn_act) or one per hidden layer (pol_acts / dyn_acts), as the C ABI's `act` value
+                   pol_act=_act_of(d, 'pol'), dyn_act=_act_of(d, 'dyn'))
     T = lambda a: torch.tensor(np.asarray(a, dtype=np.float32), device=dev)  # noqa: E731
 
     def rows(m):

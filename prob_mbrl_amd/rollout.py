@@ -145,9 +145,9 @@ class Bundle:
         if not self.learned and not hasattr(dynamics.reward_func, 'spec'):
             raise NotImplementedError('DynamicsModel.reward_func must be a prob_mbrl_amd.rewards module, or None '
                                       'with a learned reward head')
-        plin, pdrop, pdens = policy.model.layer_spec()
-        dlin, ddrop, ddens_inner = dynamics.model.layer_spec()
-        # the hidden layers' activations (activations.RELU / TANH / SILU): each network has its own
+        plin, pdrop, pdens, _ = policy.model.layers_spec()
+        dlin, ddrop, ddens_inner, _ = dynamics.model.layers_spec()
+        # the hidden layers' activations, packed (activations.pack): each network has its own
         self.acts = (policy.model.activation(), dynamics.model.activation())
         ddens = dynamics.output_density
         self.gmm = isinstance(ddens, M.GaussianMixtureDensity)

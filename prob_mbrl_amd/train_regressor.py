@@ -127,8 +127,8 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
     Yn = ((model.Y - model.my) * model.iSy).to(torch.float32).contiguous()
     N = Xn.shape[0]
     print('train_regressor >', 'Dataset size [%d]' % int(N))
-    linears, drops, inner = model.model.layer_spec()
-    act = model.model.activation()      # the hidden layers' activation (activations.RELU / TANH / SILU)
+    linears, drops, inner, _ = model.model.layers_spec()
+    act = model.model.activation()      # the hidden layers' activations, packed (activations.pack)
     density = inner if inner is not None else model.output_density
     if density is None:
         raise NotImplementedError('a diagonal-Gaussian output density is required')

@@ -1,17 +1,19 @@
 #!/usr/bin/env python
-"""What Tanh / SiLU hidden layers cost on the device, at the C2 shape (2 500 rows, H = 40, 2 x 200 networks, cart-pole
+"""What hidden layers other than ReLU cost on the device, at the C2 shape (2 500 rows, H = 40, 2 x 200 networks, cart-pole
 widths): a full iteration -- forward sweep, rewards, adjoint sweep, dW GEMM, clip and Adam -- on the general kernel
 family with
 
   relu   ReLU networks forced onto the general family (PMBRL_FLAG_FORCE_GENERIC): activity bits for the adjoint
   tanh   both networks Tanh (the family's ACT instances: act' x mask / keep per hidden unit and row-step, 4 bytes)
   silu   both networks SiLU
+  sin | exp | sinlu | hhsinlu | none   likewise (prob_mbrl_amd.activations.NAMES)
 
-Blocks of --iters iterations, timed from a device synchronise to a device synchronise, the three cases interleaved
+--acts names the cases to run (default: all eight; relu is always among them).
+Blocks of --iters iterations, timed from a device synchronise to a device synchronise, the cases interleaved
 block by block; prints the median, min and max milliseconds per iteration of each and the extra stash bytes per
 row-step as one JSON line.
 
-    python tools/activation_cost.py [--blocks 25] [--iters 10] [--warmup 5]
+    python tools/activation_cost.py [--acts relu,sin,hhsinlu] [--blocks 25] [--iters 10] [--warmup 5]
 """
 import argparse
 import json
@@ -49,11 +51,13 @@ def main():
     ap.add_argument('--blocks', type=int, default=25)
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--acts', type=str, default=','.join(ACT.NAMES), help='comma list of %s' % ', '.join(ACT.NAMES))
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('needs a HIP device')
     d = PB.synthetic_problem('cartpole_nomm')
-    cases = {k: case(d, v) for k, v in ACT.NAMES.items()}
+    names = ['relu'] + [k for k in a.acts.split(',') if k != 'relu']
+    cases = {k: case(d, ACT.NAMES[k]) for k in names}
     times = {k: [] for k in cases}
     for _, f in cases.values():
         for _ in range(a.warmup):
