@@ -274,7 +274,8 @@ def loss_weights(P, B):
 
 
 def backward(P, st, gr_all=None):
-    """Returns (flat policy grad in torch parameter order, dL/dx0, G stash)."""
+    """Returns (flat policy grad in torch parameter order, dL/dx0, G stash); leaves dL/da_t [B, U] of every step in
+    st['grad_actions'] (the rows whose norms the device's per-step action-gradient output holds)."""
     B, D = P.x0.shape
     H, G = P.H, P.G
     M = B // G
@@ -285,6 +286,7 @@ def backward(P, st, gr_all=None):
     gb = [np.zeros_like(b) for b in P.pb]
     gx = np.zeros((B, D), dtype=P.dtype)
     Gst = []
+    st['grad_actions'] = [None] * H
     for t in reversed(range(H)):
         x, a = st['states'][t], st['actions'][t]
         xt, rt = st['xt'][t], st['rt'][t]
@@ -316,6 +318,7 @@ def backward(P, st, gr_all=None):
         gxa = expand_bwd(gh * P.iSx, np.concatenate([x, a], 1), P.dyn_adims)
         gx = gxt + gxa[:, :D]
         ga = ga + gxa[:, D:]
+        st['grad_actions'][t] = ga
         # policy head
         th = (a - P.pbias) / P.pscale
         gu = ga * P.pscale * (1.0 - th * th)
