@@ -125,12 +125,11 @@ def main(argv=None):
         reward_func, args.learn_reward = None, True
     else:
         reward_func = env.reward_func
-    if args.dyn_components > 1:     # mixture-of-Gaussians head: (2 D + 1) n + 1 outputs
-        if args.learn_reward:
-            raise SystemExit('--learn_reward is not offered with --dyn_components > 1')
-        density, dynE = models.GaussianMixtureDensity(D, args.dyn_components), (2 * D + 1) * args.dyn_components + 1
-    else:   # (learned reward: one more mean and log-std, examples/deep_pilco_mm.py:117)
-        Dy = D + 1 if args.learn_reward else D
+    # (learned reward: the density has one more dimension, examples/deep_pilco_mm.py:94-99,117-121)
+    Dy = D + 1 if args.learn_reward else D
+    if args.dyn_components > 1:     # mixture-of-Gaussians head: (2 Dy + 1) n + 1 outputs
+        density, dynE = models.GaussianMixtureDensity(Dy, args.dyn_components), (2 * Dy + 1) * args.dyn_components + 1
+    else:
         density, dynE = models.DiagGaussianDensity(Dy), 2 * Dy
     # --nonlin: the hidden layers' activations of both networks, one name or one per layer
     from prob_mbrl_amd.activations import module_of

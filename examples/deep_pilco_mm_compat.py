@@ -60,6 +60,9 @@ def main(argv=None):
     ap.add_argument('--pol_shape', type=utils.load_csv, default=[200, 200])
     ap.add_argument('--resampling_period', type=int, default=499)
     ap.add_argument('--reference_shaped_reward', action='store_true')
+    # examples/deep_pilco_mm.py:94-123: the dynamics model predicts the reward too / a mixture-of-Gaussians head
+    ap.add_argument('--learn_reward', action='store_true')
+    ap.add_argument('--dyn_components', type=int, default=1)
     args = ap.parse_args(argv)
 
     torch.manual_seed(args.seed)
@@ -74,13 +77,20 @@ def main(argv=None):
         reward_func = CartpoleReward(env.reward_func.pole_length, env.reward_func.Q, env.reward_func.R,
                                      env.reward_func.target)
 
-    # dynamics model: concrete dropout after every hidden layer, diagonal Gaussian over the next-state deltas
-    dyn_model = models.mlp(D + U, 2 * D, args.dyn_shape,
+    if args.learn_reward:
+        reward_func = None
+    # dynamics model: concrete dropout after every hidden layer, diagonal Gaussian (or a mixture of them) over the
+    # next-state deltas -- and the reward, when it is learned
+    Dy = D + 1 if args.learn_reward else D
+    if args.dyn_components > 1:
+        density, dynE = models.GaussianMixtureDensity(Dy, args.dyn_components), (2 * Dy + 1) * args.dyn_components + 1
+    else:
+        density, dynE = models.DiagGaussianDensity(Dy), 2 * Dy
+    dyn_model = models.mlp(D + U, dynE, args.dyn_shape,
                            dropout_layers=[models.modules.CDropout(args.dyn_drop_rate * np.ones(hid))
                                            if args.dyn_drop_rate > 0 else None for hid in args.dyn_shape],
                            nonlin=torch.nn.ReLU)
-    dyn = models.DynamicsModel(dyn_model, reward_func=reward_func,
-                               output_density=models.DiagGaussianDensity(D)).float()
+    dyn = models.DynamicsModel(dyn_model, reward_func=reward_func, output_density=density).float()
     # policy: Bernoulli dropout, Gaussian output squashed to the action range
     pol_model = models.mlp(D, 2 * U, args.pol_shape,
                            dropout_layers=[models.modules.BDropout(args.pol_drop_rate)
@@ -102,7 +112,7 @@ def main(argv=None):
         ret = utils.apply_controller(env, act, args.control_H)
         exp.append_episode(*ret, policy_params=[])
         exp.policy_parameters[-1] = copy.deepcopy(pol.state_dict())
-        X, Y = exp.get_dynmodel_dataset(deltas=True, return_costs=False)
+        X, Y = exp.get_dynmodel_dataset(deltas=True, return_costs=args.learn_reward)
         dyn.set_dataset(X.to(dyn.X.device, dyn.X.dtype), Y.to(dyn.X.device, dyn.X.dtype))
         utils.train_regressor(dyn, args.dyn_opt_iters, args.dyn_batch_size, True, opt1,
                               log_likelihood=dyn.output_density.log_prob)

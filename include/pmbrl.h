@@ -80,7 +80,14 @@ extern "C" {
  * (z_dyn_step_stride = B (D + 1) for a per-step draw), and r~ = my[D] + Sy[D] mean_r + z[D] exp(ls_r + log Sy[D]) with
  * ls_r clamped as the states' log-stds (models/core.py:265-303 with the D of the tuple path).  The other fields of
  * pmbrl_reward are ignored.  Runs on the general kernel family only (pmbrl_plan_info reports fast = 0), F32 or
- * SPLIT_F16; not offered with the mixture head (dyn_components > 1) or with groups spread over ranks (mm_span_rows). */
+ * SPLIT_F16; not offered with groups spread over ranks (mm_span_rows).
+ * With the mixture head (dyn_components = n > 1: examples/deep_pilco_mm.py:117-121 with --learn_reward) the density has
+ * Dh = D + 1 dimensions: dyn.dims[n_layers] = (2 Dh + 1) n + 1, the row [n Dh means | n Dh log-stds | n logits | 1
+ * log-temperature] with means and log-stds viewed as [Dh, n], component fastest -- the mixture layout with D -> Dh.  One
+ * component draw per row and step (z_pi_d, u_cat_d) serves all Dh dimensions; dimensions 0 .. D-1 of the sample are the
+ * state change, dimension D is r~.  my_d / Sy_d are Dh wide and z_dyn_d is the per-step draw [H, B, Dh]
+ * (z_dyn_step_stride = B Dh); the noise term's derivative is taken with the last step's rows, or each step's own under
+ * PMBRL_FLAG_GMM_EXACT_NOISE_GRAD, in all Dh dimensions. */
 #define PMBRL_REWARD_LEARNED 2
 
 /* Activation of a network's hidden layers (models/core.py:15-99, nonlin=; models/activations.py), chosen per network and,
@@ -176,7 +183,7 @@ typedef struct pmbrl_config {
    * n components, dyn.dims[n_layers] = (2D + 1) n + 1 = [n D means | n D log-stds | n logits | log-temperature],
    * means / log-stds indexed [d * n + c].  0 or 1: the DiagGaussianDensity head (dyn.dims[n_layers] = 2D).
    * Needs z_pi_d and u_cat_d, and z_dyn_d as a per-step draw (z_dyn_step_stride = B * D: the reference redraws
-   * the Gaussian noise of this head at every step). */
+   * the Gaussian noise of this head at every step).  With PMBRL_REWARD_LEARNED: D + 1 in place of D, see there. */
   int32_t dyn_components;
   /* Moment-matching groups whose rows are spread over several ranks (e.g. mm_groups=None of
    * examples/deep_pilco_mm.py:31 on a sharded run: ONE Gaussian over the particles of all GPUs, utils/rollout.py:20-29).
@@ -350,7 +357,7 @@ typedef struct pmbrl_inputs {
   const uint16_t* pol_mask_bits_d[PMBRL_MAX_LAYERS]; /* per hidden layer, from pmbrl_pack_mask */
   const uint16_t* dyn_mask_bits_d[PMBRL_MAX_LAYERS];
   const float* z_pol_d;       /* [B, U]  models/densities.py:78,111-119 */
-  const float* z_dyn_d;       /* [B, D] ([B, D + 1] with PMBRL_REWARD_LEARNED) */
+  const float* z_dyn_d;       /* [B, D] ([B, D + 1] with PMBRL_REWARD_LEARNED); mixture head: [H, B, D] ([H, B, D + 1]) */
   int64_t z_pol_step_stride;  /* elements between steps; 0 = the same frozen z at every step
                                  (resample_noise=False), B*U = a fresh [H,B,U] draw per step */
   int64_t z_dyn_step_stride;

@@ -455,17 +455,21 @@ static int plan_nets(pmbrl_plan* p) {
   if (c.reward.kind != PMBRL_REWARD_EXP && c.reward.kind != PMBRL_REWARD_NEG && c.reward.kind != PMBRL_REWARD_LEARNED)
     return fail(-2, "unknown reward kind");
   p->learned = c.reward.kind == PMBRL_REWARD_LEARNED;
-  if (p->learned && gmm)
-    return fail(-2, "learned reward head: not offered with the mixture head (dyn_components > 1)");
   if (p->learned && c.mm_span_rows > 0)
     return fail(-2, "learned reward head: not offered with moment-matching groups spread over ranks (mm_span_rows > 0)");
   if (p->learned && c.D + 1 > PMBRL_MAX_DIM) return fail(-2, "learned reward head: D + 1 exceeds PMBRL_MAX_DIM");
+  // (said here, not by net_plan: a head (2 D + 1) n + 1 wide -- the mixture of the states alone -- is the likely mistake)
+  if (p->learned && gmm && c.dyn.n_layers >= 1 && c.dyn.n_layers <= PM_MAXL &&
+      c.dyn.dims[c.dyn.n_layers] != (2 * (c.D + 1) + 1) * c.dyn_components + 1)
+    return fail(-2, "learned reward head with the mixture head: the density has D + 1 dimensions, a dynamics head "
+                    "(2 (D + 1) + 1) dyn_components + 1 wide");
   int rc = net_plan(c.pol, c.pol_act, p->pol, c.D + c.n_pol_angle, 2 * c.U, "policy");
   // (mixture head: n D means, n D log-stds, n logits, one log-temperature -- examples/deep_pilco_mm.py:117-121;
-  //  learned reward: one more mean and log-std for the reward, examples/deep_pilco_mm.py:94-99)
+  //  learned reward: one more mean and log-std for the reward, examples/deep_pilco_mm.py:94-99; both: a mixture
+  //  density of D + 1 dimensions)
   if (rc == 0)
     rc = net_plan(c.dyn, c.dyn_act, p->dyn, c.D + c.U + c.n_dyn_angle,
-                  gmm ? (2 * c.D + 1) * c.dyn_components + 1 : 2 * (c.D + p->learned), "dynamics");
+                  gmm ? (2 * (c.D + p->learned) + 1) * c.dyn_components + 1 : 2 * (c.D + p->learned), "dynamics");
   p->act = rc == 0 && (p->pol.act != 0 || p->dyn.act != 0);   // (some hidden layer of some network is not ReLU)
   return rc;
 }
@@ -685,6 +689,9 @@ static int plain_row_tiles(pmbrl_plan* p, const LayoutCalc& L, int cus) {
   // on request (rows_per_wg_hint >= 64): widths <= 512, every narrow width (2U, 2D, D + U) <= 64, no mixture head,
   // no angle features.
   const bool angles = c.n_pol_angle > 0 || c.n_dyn_angle > 0;
+  // (!p->learned, dyn_components <= 1: the sweeps rely on it -- pm_rollout_fwd / _bwd take the (D + 1)-wide strides of a
+  //  learned reward on the mixture head in kernels of their own, which exist for the two-buffer layers only; plan_workspace
+  //  refuses a plan that would break it)
   if (L.gsplit && !angles && c.dyn_components <= 1 && !p->learned && !p->act && L.maxnt <= 32 && 2 * c.D <= PM_IP_NOFF && 2 * c.U <= PM_IP_NOFF &&
       c.D + c.U <= PM_IP_NOFF && RT < 4) {
     // every hidden layer 512 wide: the in-place layers of pmbrl_wide.h (compile-time shape, lean epilogue) -- taken by
@@ -928,6 +935,8 @@ static int plan_workspace(pmbrl_plan* p) {
     }
   }
   const bool gmm = c.dyn_components > 1;
+  if (p->learned && gmm && p->inplace)   // (cannot happen while plain_row_tiles keeps both off the in-place layers)
+    return fail(-3, "learned reward head with the mixture head: the in-place sweeps do not serve it");
   const size_t Rw = 16 * p->RT;
   for (int l = 0; l < p->pol.nl; ++l) {
     p->off_actT[l] = take((size_t)c.H * p->nwg * p->pol.nt[l] * 16 * Rw * sizeof(float));
@@ -935,7 +944,8 @@ static int plan_workspace(pmbrl_plan* p) {
   }
   p->off_Tp = take((size_t)c.H * c.B * c.U * sizeof(float));
   p->off_Td = take((size_t)c.H * c.B * c.D * sizeof(float));
-  p->off_gmm_c = take(gmm ? (size_t)c.H * c.B * (c.dyn_components + 1) * c.D * sizeof(float) : 0);
+  // (a learned reward head gives the coefficient table a column for r~)
+  p->off_gmm_c = take(gmm ? (size_t)c.H * c.B * (c.dyn_components + 1) * (c.D + p->learned) * sizeof(float) : 0);
   p->off_gmm_k = take(gmm ? (size_t)c.H * c.B * sizeof(int) : 0);
   p->off_xt = take((size_t)c.H * c.B * c.D * sizeof(float));
   p->off_rt = take((size_t)c.H * c.B * sizeof(float));
@@ -977,6 +987,8 @@ static int plan_workspace(pmbrl_plan* p) {
 static PmInstTable sweep_table(const pmbrl_plan* p) {
   if (p->fast)
     return p->prec == PMBRL_PREC_SPLIT_F16 ? pm_fast_split2_instances() : p->prec ? pm_fast_split1_instances() : pm_fast_f32_instances();
+  // (a learned reward head on the mixture head has sweeps of its own: pm_rollout_fwd_gmmr / _bwd_gmmr)
+  if (p->learned && p->cfg.dyn_components > 1) return p->act ? pm_general_gmmr_act_instances() : pm_general_gmmr_instances();
   if (p->act) return pm_general_act_instances();
   return p->prec ? pm_general_split_instances() : PmInstTable{pm_general_f32_keys, general_f32_fns, pm_general_f32_n};
 }
@@ -1002,7 +1014,8 @@ static int resolve_sweeps(pmbrl_plan* p) {
     // the table of the networks that are not ReLU is keyed by piece planes, the split one by the in-place form (3: the
     // wide layers with pre-split stashes), the exact-fp32 one by row tiles alone
     const int wide_form = (p->inplace == 2 && p->dw.pre_mask) ? 3 : p->inplace;
-    const PmInstKey k = pm_general_key(p->RT, p->act ? (p->prec ? 2 : 0) : p->prec ? wide_form : 0);
+    const bool planes = p->act || (p->learned && c.dyn_components > 1);      // (tables keyed by piece planes)
+    const PmInstKey k = pm_general_key(p->RT, planes ? (p->prec ? 2 : 0) : p->prec ? wide_form : 0);
     return take(0, k) ? 0 : fail(-3, "no general-family instance for " + pm_inst_name(k));
   }
   // not on request (tests), and not for split groups without the statistics exchange (PMBRL_MM_XCH=0): only the generic

@@ -115,7 +115,8 @@ struct RolloutArgs {
   // GaussianMixtureDensity dynamics head (general family only): components (0: diagonal Gaussian head), frozen
   // Gumbel noise [B][n], uniforms [H][B], the Gaussian noise rows the derivative of the noise term uses (the last
   // step's: the reference's autograd; nullptr: each step's own), and the stashes the adjoint consumes:
-  // component drawn [H][B], coefficients of dL/d(logits, log-temperature) [H][B][n + 1][D]
+  // component drawn [H][B], coefficients of dL/d(logits, log-temperature) [H][B][n + 1][D] ([n + 1][D + 1] with a
+  // learned reward head: the density then has D + 1 dimensions, and so have the rows of zdyn / zdyn_grad)
   int gmm_n;
   const float *zpi, *ucat, *zdyn_grad;
   // general family: rewards, their Jacobians (Jx, Ja) and their moment matching are computed for all row-steps
@@ -140,6 +141,7 @@ struct RolloutArgs {
   // that the arguments of every other kernel keep their layout: the forward sweep samples r~ from head columns D and
   // 2D + 1 and writes it to `rewards` (the host points that at rt when the rewards are moment matched), and keeps
   // d r~/d ls_r [H][B] in Jx for the adjoint, which seeds those two columns with dL/dr~ instead of using Jx / Ja
+  // (mixture head: r~ is dimension D of the (D + 1)-dimensional sample, Jx keeps d r~/d ls_r of the drawn component)
   int* status;          // forward: number of valid steps (atomicMin); backward: failure flag of the sweep (or nullptr)
   const int* nvalid;    // backward: the forward's status word; the sweep covers steps t < min(t1, *nvalid) (nullptr: t1)
   // backward only

@@ -8,6 +8,8 @@
 //                            (it also resolves a plan's sweep kernels from the tables and launches them)
 //   pmbrl_general_split.hip  the general family on split operands: instances and table, nothing else
 //   pmbrl_general_act.hip    the general family for networks that are not ReLU: the same
+//   pmbrl_general_gmmr.hip   the general family's sweeps for a learned reward head on the mixture head: the same; compiled
+//                            once for ReLU networks and once for the others (two objects)
 //   pmbrl_fast_f32.hip       latency-optimised sweeps, exact fp32 MFMA: the same
 //   pmbrl_fast_split.hip     the same on split bf16 / fp16 operands; compiled once per precision (two objects)
 //   pmbrl_reg.hip            register-resident family: instances, resolution, packer and launch
@@ -275,3 +277,5 @@ PmInstTable pm_fast_split1_instances();     // PMBRL_PREC_SPLIT
 PmInstTable pm_fast_split2_instances();     // PMBRL_PREC_SPLIT_F16
 PmInstTable pm_general_split_instances();
 PmInstTable pm_general_act_instances();
+PmInstTable pm_general_gmmr_instances();       // learned reward on the mixture head: ReLU networks ...
+PmInstTable pm_general_gmmr_act_instances();   // ... and networks with a hidden layer that is not ReLU

@@ -303,7 +303,8 @@ class GaussianMixtureDensity(StochasticModule):
     sample picks ONE component -- straight-through one-hot over the tempered Gumbel-softmax of the logits -- and
     adds that component's Gaussian noise.  Offered as the dynamics model's `output_density` inside rollouts (the
     sampling phase of the general kernel family and its adjoint: csrc/pmbrl_rollout.h); `log_prob` is the mixture
-    log-likelihood (torch ops, for callers that evaluate it themselves).
+    log-likelihood (torch ops, for callers that evaluate it themselves).  With a learned reward (DynamicsModel(
+    reward_func=None)) output_dims is D + 1: one component draw serves the state change and the reward.
 
     Random draws, as the reference makes them: `z_pi` (Gumbel noise, [B, n]) is frozen until `resample()` / a
     shape change / resample_noise=True; the Gaussian noise is redrawn at EVERY step whatever resample_noise says
@@ -678,8 +679,9 @@ class Regressor(_Loadable):
 class DynamicsModel(Regressor):
     """models/core.py:251-303.  `reward_func` is one of prob_mbrl_amd.rewards.* (an analytic reward with a
     `.spec(D)`), or None for a learned reward: the model then has a head 2 (D + 1) wide with
-    output_density=DiagGaussianDensity(D + 1) and predicts the transition's reward in its last output column
-    (examples/deep_pilco_mm.py:94-99; trained on get_dynmodel_dataset(return_costs=True)).  The reference's own
+    output_density=DiagGaussianDensity(D + 1) -- or (2 (D + 1) + 1) n + 1 wide with GaussianMixtureDensity(D + 1, n) --
+    and predicts the transition's reward in the last dimension of its density's sample
+    (examples/deep_pilco_mm.py:94-99,117-121; trained on get_dynmodel_dataset(return_costs=True)).  The reference's own
     learned-reward branch takes D from the concatenated-input path only (an UnboundLocalError with tuple inputs,
     SURVEY.md 8c); here D is the width of prev_states for tuple inputs and outs.shape[-1] - 1 otherwise."""
 
@@ -710,11 +712,13 @@ class DynamicsModel(Regressor):
         if not kwargs.get('return_samples', False):
             return outs
         if self.reward_func is None:
-            # learned reward head: [state change | reward] from one density sample
+            # learned reward head: [state change | reward] from one density sample (diagonal Gaussian or mixture of
+            # D + 1 dimensions: the split is at D either way)
             D = prev_states.shape[-1] if as_tuple else outs.shape[-1] - 1
             if as_tuple and outs.shape[-1] != D + 1:
                 raise NotImplementedError('reward_func=None needs a learned reward head: widen the dynamics head to '
-                                          '2 (D + 1) outputs with DiagGaussianDensity(D + 1), or pass a reward module')
+                                          '2 (D + 1) outputs with DiagGaussianDensity(D + 1) -- (2 (D + 1) + 1) n + 1 with '
+                                          'GaussianMixtureDensity(D + 1, n) --, or pass a reward module')
             if not as_tuple:
                 prev_states, actions = inputs[..., :D], inputs[..., D:]
             dstates, rewards = outs[..., :D], outs[..., D:D + 1]

@@ -173,16 +173,17 @@ class Bundle:
         n_dyn_in = self.D + self.U + len(self.angle_dims[1])
         self.n_comp = ddens.n_components if self.gmm else 0
         if self.learned:
-            if self.gmm:
-                raise NotImplementedError('a learned reward head is not offered with GaussianMixtureDensity')
-            if self.dyn_dims[-1] != 2 * (self.D + 1) or int(ddens.output_dims) != self.D + 1:
+            # (a mixture density of D + 1 dimensions: (2 (D + 1) + 1) n + 1 outputs, examples/deep_pilco_mm.py:117-121)
+            n_head = (2 * (self.D + 1) + 1) * self.n_comp + 1 if self.gmm else 2 * (self.D + 1)
+            if self.dyn_dims[-1] != n_head or int(ddens.output_dims) != self.D + 1:
                 raise NotImplementedError(
-                    'reward_func=None needs a learned reward head: widen the dynamics head to 2 (D + 1) = %d outputs '
-                    'with output_density=DiagGaussianDensity(D + 1), or pass a prob_mbrl_amd.rewards module as '
-                    'reward_func' % (2 * (self.D + 1)))
+                    'reward_func=None needs a learned reward head: widen the dynamics head to %d outputs '
+                    'with an output_density of D + 1 dimensions (DiagGaussianDensity(D + 1): 2 (D + 1) outputs, '
+                    'GaussianMixtureDensity(D + 1, n): (2 (D + 1) + 1) n + 1), or pass a prob_mbrl_amd.rewards module as '
+                    'reward_func' % n_head)
         # the width of the head's samples: the states, and the reward after them when it is learned
         self.Dy = self.D + 1 if self.learned else self.D
-        n_dyn_out = (2 * self.D + 1) * self.n_comp + 1 if self.gmm else 2 * self.Dy
+        n_dyn_out = (2 * self.Dy + 1) * self.n_comp + 1 if self.gmm else 2 * self.Dy
         if self.dyn_dims[0] != n_dyn_in or self.dyn_dims[-1] != n_dyn_out:
             raise NotImplementedError('dynamics must map [x|u] (%d inputs with its angle_dims) to %d outputs'
                                       % (n_dyn_in, n_dyn_out))
@@ -242,7 +243,7 @@ class Bundle:
             if forced is not None:
                 self.z_dyn, self.u_cat = (f.to(device=dev, dtype=torch.float32).contiguous() for f in forced)
             else:
-                self.z_dyn = torch.randn(H, B, self.D, device=dev)
+                self.z_dyn = torch.randn(H, B, self.Dy, device=dev)
                 self.u_cat = torch.rand(H, B, device=dev)
             ddens.z_normal.data = self.z_dyn[-1]
         elif resample_state_noise:

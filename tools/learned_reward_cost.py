@@ -5,6 +5,9 @@ widths): a full iteration -- forward sweep, rewards, adjoint sweep, dW GEMM, cli
   learned   the learned reward head (PMBRL_REWARD_LEARNED; the general kernel family)
   generic   the analytic cart-pole reward on the same networks, forced onto the general family (PMBRL_FLAG_FORCE_GENERIC)
   default   the analytic reward with the plan the library chooses (the register-resident family)
+  mixture   the analytic reward on a two-component Gaussian-mixture dynamics head (the general family)
+  mixture_learned   the learned reward head on that mixture head: a density of D + 1 dimensions (left out, and said so,
+            by a library that refuses the combination)
 
 Blocks of --iters iterations, timed from a device synchronise to a device synchronise, the three cases interleaved
 block by block; prints the median, min and max milliseconds per iteration of each as one JSON line.
@@ -43,6 +46,27 @@ def learned_problem(d, seed=1):
     return d
 
 
+def mixture_problem(d, n=2, seed=2):
+    """d (analytic or learned_problem's) with a mixture head of n components over its density: every component starts
+    from the diagonal head's mean and log-std rows plus a small spread, [means | log-stds] component-fastest, then n
+    logits and the log-temperature; frozen Gumbel noise, and a uniform and Gaussian noise per row-step."""
+    d = dict(d)
+    B, H = d['x0'].shape[0], int(d['H'])
+    nl = int(d['dyn_n_layers'])
+    W, b = np.asarray(d['dyn_W%d' % (nl - 1)]), np.asarray(d['dyn_b%d' % (nl - 1)])
+    Dh = W.shape[0] // 2
+    rng = np.random.default_rng(seed)
+    rows = np.repeat(W, n, 0) + (0.02 * rng.standard_normal((2 * Dh * n, W.shape[1]))).astype(np.float32)
+    extra = (0.05 * rng.standard_normal((n + 1, W.shape[1]))).astype(np.float32)
+    d['dyn_W%d' % (nl - 1)] = np.concatenate([rows, extra], 0).astype(np.float32)
+    d['dyn_b%d' % (nl - 1)] = np.concatenate([np.repeat(b, n), np.zeros(n + 1)]).astype(np.float32)
+    d['dyn_gmm_n'] = n
+    d['dyn_zpi'] = -np.log(-np.log(rng.uniform(1e-6, 1.0, (B, n)))).astype(np.float32)
+    d['dyn_ucat'] = rng.uniform(0.0, 1.0, (H, B)).astype(np.float32)
+    d['dyn_z'] = rng.standard_normal((H, B, Dh)).astype(np.float32)
+    return d
+
+
 def case(d, learned=False, force_generic=False):
     eng, args, _ = PB.engine_from_problem(d, force_generic=force_generic,
                                           reward_spec=E.LEARNED_REWARD if learned else None)
@@ -69,7 +93,12 @@ def main():
         raise SystemExit('needs a HIP device')
     d = PB.synthetic_problem('cartpole_nomm')
     cases = {'learned': case(learned_problem(d), learned=True), 'generic': case(d, force_generic=True),
-             'default': case(d)}
+             'default': case(d), 'mixture': case(mixture_problem(d))}
+    refused = None
+    try:
+        cases['mixture_learned'] = case(mixture_problem(learned_problem(d)), learned=True)
+    except Exception as e:      # (a library from before the combination was offered)
+        refused = str(e)
     times = {k: [] for k in cases}
     for _, f in cases.values():
         for _ in range(a.warmup):
@@ -90,6 +119,8 @@ def main():
         out[k] = dict(ms_median=float(np.median(t)), ms_min=float(t.min()), ms_max=float(t.max()),
                       fast=eng.info['fast'], reg=eng.info['reg'], precision=eng.info['precision'],
                       valid_steps=eng.valid_steps())
+    if refused:
+        out['mixture_learned'] = dict(refused=refused)
     print(json.dumps(out))
 
 
