@@ -2106,10 +2106,16 @@ static int rollout_bwd(pmbrl_plan* p, const BwdCall& C, const RolloutArgs& A0, b
   // -- the barrier's L2 round trips cost what two launches do; not kept).  Behind the exchange the norm is done and the
   // loss is one summed partial; otherwise both are as the reduction left them
   // (a rule attached to the plan -- pmbrl_plan_set_optimizer: its instance of the launch, the hyper-parameters from the rule)
-  return clip_adam_guarded_impl(s, opt->params_d, C.grad_pol_flat, opt->exp_avg_d, opt->exp_avg_sq_d, n, opt->step_d, opt->lr,
-                                opt->beta1, opt->beta2, opt->eps, opt->max_norm, opt->norm_out_d, C.status, expect,
-                                tail || norm_fused, tail || loss_fused ? opt->loss_out_d : nullptr,
-                                tail ? (opt->loss_out_d ? 1 : 0) : n_loss_part, p->has_opt_rule ? &p->opt_rule : nullptr);
+  AdamStep S;
+  S.params = opt->params_d; S.grads = C.grad_pol_flat; S.exp_avg = opt->exp_avg_d; S.exp_avg_sq = opt->exp_avg_sq_d; S.n = n;
+  S.step_d = opt->step_d; S.status = C.status; S.expect = expect;
+  S.max_norm = opt->max_norm; S.norm_out = opt->norm_out_d;
+  S.norm_done = tail || norm_fused;
+  S.loss_out = tail || loss_fused ? opt->loss_out_d : nullptr;
+  S.n_loss_part = tail ? (opt->loss_out_d ? 1 : 0) : n_loss_part;
+  S.lr = opt->lr; S.beta1 = opt->beta1; S.beta2 = opt->beta2; S.eps = opt->eps;
+  S.rule = p->has_opt_rule ? &p->opt_rule : nullptr;   // (checked for this vector when it was attached)
+  return pm_adam_launch(s, S);
 }
 
 // what makes two adjoint calls "the same" (pmbrl_plan_set_replay)

@@ -287,13 +287,10 @@ extern "C" int pmbrl_bnn_plan_set_optimizer(pmbrl_bnn_plan* p, const pmbrl_opt_r
 }
 static BnnOptRec bnn_opt_rec(const pmbrl_opt_group& G) {
   BnnOptRec r;
-  const bool dec = G.flags & PMBRL_OPT_DECOUPLED;
+  const OptGroupConsts c = pm_opt_group_consts(G);
   r.lr = (float)G.lr; r.b1 = (float)G.beta1; r.b2 = (float)G.beta2; r.eps = (float)G.eps;
-  r.wd = dec ? 0.f : (float)G.weight_decay;
-  r.decay = dec ? (float)(1.0 - G.lr * G.weight_decay) : 1.f;
-  r.sgn = (G.flags & PMBRL_OPT_MAXIMIZE) ? -1.f : 1.f;
-  r.ams = (G.flags & PMBRL_OPT_AMSGRAD) ? 1 : 0;
-  r.ln_b1 = log(G.beta1); r.ln_b2 = log(G.beta2);
+  r.wd = c.wd; r.decay = c.decay; r.sgn = c.sgn; r.ams = c.ams;
+  r.ln_b1 = c.ln_b1; r.ln_b2 = c.ln_b2;
   return r;
 }
 extern "C" size_t pmbrl_bnn_plan_workspace_bytes(const pmbrl_bnn_plan* p) { return p ? p->ws_bytes : 0; }

@@ -26,6 +26,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -232,10 +233,40 @@ void pm_dw_reduce_launch(hipStream_t s, const float* part, int nsplit, int n, in
                          int col_hi = 0, int rows_in_range = 0);
 void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
                          long long n_per_step);
-int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, int64_t n,
-                           int64_t* step_d, double lr, double beta1, double beta2, double eps, double max_norm,
-                           float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                           float* loss_out_d = nullptr, int n_loss_part = 0, const pmbrl_opt_rule* rule = nullptr);
+// One clip_grad_norm_ + Adam step on flat vectors, as every caller states it (the four pmbrl_clip_adam* entry points, the
+// fused iteration of pmbrl_rollout_bwd_adam).  pm_adam_launch decides the launch shapes and whether the norm's launch is
+// needed, and queues it and the optimiser launch.
+struct AdamStep {
+  float *params, *grads, *exp_avg, *exp_avg_sq;
+  int64_t n;
+  int64_t step = 0;                // the host's step count (>= 1), or
+  int64_t* step_d = nullptr;       // the GUARDED form: the device-side counter, advanced if status says `expect` steps completed
+  const int32_t* status = nullptr;
+  int32_t expect = 0;
+  double max_norm = 0.0;           // <= 0: no clipping
+  float* norm_out = nullptr;
+  float* loss_out = nullptr;       // the fused iteration's loss: the sum of the first n_loss_part entries of g_loss_part
+  int n_loss_part = 0;
+  // the partial sums of squares and the go / no-go decision are already on the device (the fused iteration's gradient
+  // reduction formed them: pm_dw_reduce with norm_on, or pm_tail_finish_kernel behind the exchange)
+  bool norm_done = false;
+  double lr = 0.0, beta1 = 0.0, beta2 = 0.0, eps = 0.0;   // torch.optim.Adam's, or
+  const pmbrl_opt_rule* rule = nullptr;                   // a rule that pmbrl_opt_rule_check passed for n: the hyper-parameters are its
+};
+int pm_adam_launch(hipStream_t s, const AdamStep& A);
+// what the kernels take of a rule's group beside lr, the betas and eps
+struct OptGroupConsts {
+  float wd;             // L2: g += wd p (0: none, and for a decoupled group)
+  float decay;          // decoupled: p *= 1 - lr wd, formed in double, rounded once (1: none)
+  float sgn;            // maximize: -1
+  int ams;
+  double ln_b1, ln_b2;  // for the bias corrections of a device-side step counter
+};
+inline OptGroupConsts pm_opt_group_consts(const pmbrl_opt_group& G) {
+  const bool dec = G.flags & PMBRL_OPT_DECOUPLED;
+  return {dec ? 0.f : (float)G.weight_decay, dec ? (float)(1.0 - G.lr * G.weight_decay) : 1.f,
+          (G.flags & PMBRL_OPT_MAXIMIZE) ? -1.f : 1.f, (G.flags & PMBRL_OPT_AMSGRAD) ? 1 : 0, log(G.beta1), log(G.beta2)};
+}
 // what pmbrl_act_check refuses, as text (nullptr: nothing); host code only (pmbrl.hip)
 const char* pm_act_refusal(int32_t act, int n_hidden);
 // An activation field that passed pmbrl_act_check, in the one form the kernels read (pm_act_code, pmbrl_dev.h): the code

@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <string>
+#include <type_traits>
 
 #include "pmbrl_host.h"
 
@@ -276,6 +277,30 @@ __global__ __launch_bounds__(512) void pm_dw_reduce(const float* __restrict__ pa
 }
 
 static inline int pm_norm_blocks(long long n) { return (int)std::max<long long>(1, std::min<long long>(PM_NORM_MAXB, (n + 255) / 256)); }
+// this workgroup's (one wave's) entry of g_norm_part: one block of 256 elements of src per workgroup up to PM_NORM_MAXB of
+// them; a longer vector is walked in strides, the blocks' sums added in block order.  dst: the elements are also copied there
+// (COPY: pm_tail_finish_kernel's form)
+template <bool COPY>
+__device__ __forceinline__ void pm_norm_walk(const float* __restrict__ src, float* __restrict__ dst, long long n) {
+  double tot = 0.0;
+  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
+    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
+    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (i0 + 3 < n) {
+      t = *reinterpret_cast<const f32x4*>(src + i0);
+      if constexpr (COPY)
+        for (int r = 0; r < 4; ++r) dst[i0 + r] = t[r];
+    } else {
+      for (int r = 0; r < 4; ++r) {
+        t[r] = i0 + r < n ? src[i0 + r] : 0.f;
+        if constexpr (COPY)
+          if (i0 + r < n) dst[i0 + r] = t[r];
+      }
+    }
+    tot += pm_sq4_wave(t, i0, n);
+  }
+  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
+}
 // clip_grad_norm_ + Adam in two launches: (1) partial sums of g^2 over blocks of 256 elements (pm_sq4_wave above:
 // the same partial sums the fused iteration's gradient reduction forms on the way), (2) every block adds the partials in
 // the same order (identical norm everywhere) and updates its slice.
@@ -286,126 +311,82 @@ __global__ __launch_bounds__(64) void pm_gradnorm_kernel(const float* __restrict
                                                          const int* __restrict__ status, int expect,
                                                          long long* __restrict__ step, int guarded) {
   if (guarded && blockIdx.x == 0 && threadIdx.x == 0) pm_adam_decide(status, expect, step);
-  // (one block of 256 elements per workgroup up to PM_NORM_MAXB of them; a longer vector is walked in strides, the
-  //  blocks' sums added in block order)
-  double tot = 0.0;
-  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
-    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
-    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (i0 + 3 < n) t = *reinterpret_cast<const f32x4*>(g + i0);
-    else
-      for (int r = 0; r < 4; ++r) t[r] = i0 + r < n ? g[i0 + r] : 0.f;
-    tot += pm_sq4_wave(t, i0, n);
-  }
-  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
+  pm_norm_walk<false>(g, nullptr, n);
 }
 
-__global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p, float* __restrict__ g,
-                                                           float* __restrict__ m, float* __restrict__ v,
-                                                           long long n, int n_part, float lr, float b1,
-                                                           float b2, float omb1, float omb2, float eps,
-                                                           float bc1, float bc2_sqrt, float max_norm,
-                                                           float* __restrict__ norm_out,
-                                                           const long long* __restrict__ step, int guarded,
-                                                           double ln_b1, double ln_b2, double lr_d,
-                                                           float* __restrict__ loss_out, int n_loss_part) {
-  // The first four elements of this thread and the norm's partial sums are requested before anything is decided: as
-  // "go? -> step counter -> partial sums (a loop of dependent loads) -> elements (a loop of four)" this launch was ten
-  // memory round trips in a row around a few hundred instructions.
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  float gq[4], mq[4], vq[4], pq[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    // (beyond n: the last element's address, never used -- loads under a condition are waited for one by one)
-    const long long j = min(i0 + u * stride, n - 1);
-    gq[u] = g[j];
-    mq[u] = m[j];
-    vq[u] = v[j];
-    pq[u] = p[j];
-  }
-  const int lane = threadIdx.x & 63;
-  double part[4];
+// The norm's partial sums as the optimiser launch takes them: the first four of this lane are REQUESTED before anything is
+// decided (pm_norm_request) and added later (pm_norm_sum) -- block b on lane b mod 64 in block order, then a fixed
+// butterfly: the same bits in every wave of every block
+__device__ __forceinline__ void pm_norm_request(double (&part)[4], int lane, int n_part) {
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
     const double x = g_norm_part[min(lane + 64 * u, PM_NORM_MAXB - 1)];
     part[u] = lane + 64 * u < n_part ? x : 0.0;
   }
-  // the fused iteration's loss: the sums pm_dw_reduce's workgroups left, added in workgroup order by one wave (taken or
-  // not, the step's loss is reported)
-  if (loss_out && blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 128) {
-    double ls = 0.0;
-    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
-    if (lane == 0) loss_out[0] = (float)ls;
-  }
-  if (guarded && !g_adam_go) return;   // the rollout failed: leave parameters and moments alone
-  double step_size_d = lr_d / (double)bc1;
-  if (step) {
-    // guarded form: bias corrections 1 - beta^t of the device-side step counter as -expm1(t ln beta), the exponent formed
-    // and evaluated in double (torch forms them in Python floats; in fp32 the sixth digit of the step size differs and a
-    // five-iteration comparison of the moments notices), ln beta from the host -- two double-precision pow calls were a
-    // thousand instructions at the head of every thread, expm1 is a third of that
-    const double st = (double)step[0];
-    bc1 = (float)-expm1(st * ln_b1);
-    bc2_sqrt = (float)sqrt(-expm1(st * ln_b2));
-    step_size_d = lr_d / -expm1(st * ln_b1);      // (torch: lr / bias_correction1 in Python floats, rounded once)
-  }
-  // the partial sums of squares, block b on lane b mod 64 in block order, and a fixed butterfly: the same bits in every wave
-  // of every block
+}
+__device__ __forceinline__ double pm_norm_sum(const double (&part)[4], int lane, int n_part) {
   double t = 0.0;
-  {
 #pragma unroll
-    for (int u = 0; u < 4; ++u) t += part[u];                         // (absent: + 0)
-    for (int b = lane + 256; b < n_part; b += 64) t += g_norm_part[b];
+  for (int u = 0; u < 4; ++u) t += part[u];                         // (absent: + 0)
+  for (int b = lane + 256; b < n_part; b += 64) t += g_norm_part[b];
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-  }
-  const float norm = (float)sqrt(t);
-  if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
-  float coef = 1.f;
-  if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
-  const float step_size = (float)step_size_d;
-  for (long long i = i0;;) {
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
+  return t;
+}
+// the fused iteration's loss: the sums pm_dw_reduce's workgroups left, added in workgroup order by one wave
+__device__ __forceinline__ double pm_loss_sum(int lane, int n_loss_part) {
+  double ls = 0.0;
+  for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
 #pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = i + u * stride;
-      if (j < n) {
-        const float gi = gq[u] * coef;
-        const float mi = mq[u] * b1 + omb1 * gi;
-        const float vi = vq[u] * b2 + omb2 * gi * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        g[j] = gi;
-        m[j] = mi;
-        v[j] = vi;
-        p[j] = pq[u] - step_size * (mi / denom);
-      }
-    }
-    i += 4 * stride;
-    if (i >= n) break;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const long long j = min(i + u * stride, n - 1);
-      gq[u] = g[j];
-      mq[u] = m[j];
-      vq[u] = v[j];
-      pq[u] = p[j];
-    }
-  }
+  for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+  return ls;
 }
 
 // ---------------------------------------------------------------------------
-// The same launch for an optimiser rule (pmbrl_opt_rule: parameter groups, L2 / decoupled weight decay, amsgrad, maximize).
-// pm_clip_adam_kernel above is the plain rule's and is left as it is; this one has its latency shape -- the first four
-// elements, vmax where the rule has one (VMAX: an instance of its own, no load under a condition) and the norm's partial
-// sums are requested before anything is decided; butterfly and loss sum are the plain kernel's.
+// clip + Adam: ONE kernel body (pm_clip_adam_kernel below), instantiated for a policy that says where an element's
+// hyper-parameters come from.  AdamPlain: torch.optim.Adam with one set of them, scalars of the argument.  AdamTable: an
+// optimiser rule (pmbrl_opt_rule: parameter groups, L2 / decoupled weight decay, amsgrad, maximize), without and with
+// amsgrad's running maximum (VMAX: an instance of its own, no load under a condition).  A policy gives
+//   prepare(lane, step)  this lane's record, the step-dependent entries included (step: the device-side counter of the
+//                        guarded form, nullptr: the host's step count, already in the policy)
+//   at(L, j, n)          the record of element j; every lane of the wave calls it together
+//   done(i, lane, n)     whether a thread whose next element is i leaves the update loop
+// ---------------------------------------------------------------------------
+struct AdamLane {
+  float b1, b2, omb1, omb2, eps;
+  float wd, decay, sgn;          // OptGroupConsts (pmbrl_host.h)
+  float step_size, bc2_sqrt;
+  int ams;
+};
+struct AdamPlain {
+  static constexpr bool kVmax = false;
+  float b1, b2, omb1, omb2, eps;
+  float bc1, bc2_sqrt;           // from the host's step count (not guarded)
+  double ln_b1, ln_b2, lr_d;
+  // (wd, decay, sgn and ams are constants here: the instance carries nothing of a rule -- x * 1.f and the dead branches fold)
+  __device__ __forceinline__ AdamLane prepare(int, const long long* step) const {
+    double step_size_d = lr_d / (double)bc1;
+    float bc2 = bc2_sqrt;
+    if (step) {
+      // guarded form: bias corrections 1 - beta^t of the device-side step counter as -expm1(t ln beta), the exponent formed
+      // and evaluated in double (torch forms them in Python floats; in fp32 the sixth digit of the step size differs and a
+      // five-iteration comparison of the moments notices), ln beta from the host -- two double-precision pow calls were a
+      // thousand instructions at the head of every thread, expm1 is a third of that
+      const double st = (double)step[0];
+      bc2 = (float)sqrt(-expm1(st * ln_b2));
+      step_size_d = lr_d / -expm1(st * ln_b1);      // (torch: lr / bias_correction1 in Python floats, rounded once)
+    }
+    return AdamLane{b1, b2, omb1, omb2, eps, 0.f, 1.f, 1.f, (float)step_size_d, bc2, 0};
+  }
+  __device__ __forceinline__ AdamLane at(const AdamLane& L, long long, long long) const { return L; }
+  __device__ __forceinline__ bool done(long long i, int, long long n) const { return i >= n; }
+};
+
 // The rule travels by value.  Segment boundaries and groups are read at CONSTANT offsets of the argument (scalar loads, no
 // copy of the table in scratch): an element compares its index against the boundaries in turn.  The groups'
 // hyper-parameters, the step-dependent ones included (lr / bc1, sqrt(bc2): one pair of expm1 per group, not per element),
 // live in the lanes: lane l of every wave holds group l & 7, an element fetches its group's with a lane shuffle --
 // neighbouring lanes may belong to different groups.
-// ---------------------------------------------------------------------------
 struct OptRuleDev {
   int n_segments, n_groups;
   int seg_group[PMBRL_OPT_MAX_SEGMENTS];
@@ -413,9 +394,7 @@ struct OptRuleDev {
   // per group (unused slots repeat group 0)
   float b1[PMBRL_OPT_MAX_GROUPS], b2[PMBRL_OPT_MAX_GROUPS], omb1[PMBRL_OPT_MAX_GROUPS], omb2[PMBRL_OPT_MAX_GROUPS];
   float eps[PMBRL_OPT_MAX_GROUPS];
-  float wd[PMBRL_OPT_MAX_GROUPS];         // L2: g += wd p (0: none, and for a decoupled group)
-  float decay[PMBRL_OPT_MAX_GROUPS];      // decoupled: p *= 1 - lr wd, formed in double, rounded once (1: none)
-  float sgn[PMBRL_OPT_MAX_GROUPS];        // maximize: -1
+  float wd[PMBRL_OPT_MAX_GROUPS], decay[PMBRL_OPT_MAX_GROUPS], sgn[PMBRL_OPT_MAX_GROUPS];   // OptGroupConsts (pmbrl_host.h)
   float step_size[PMBRL_OPT_MAX_GROUPS], bc2_sqrt[PMBRL_OPT_MAX_GROUPS];   // from the host's step count (not guarded)
   int amsgrad[PMBRL_OPT_MAX_GROUPS];
   double ln_b1[PMBRL_OPT_MAX_GROUPS], ln_b2[PMBRL_OPT_MAX_GROUPS], lr_d[PMBRL_OPT_MAX_GROUPS];
@@ -440,64 +419,89 @@ __device__ __forceinline__ T pm_pick_group(const T (&a)[PMBRL_OPT_MAX_GROUPS], i
   return r;
 }
 template <bool VMAX>
-__global__ __launch_bounds__(256) void pm_clip_adam_rule_kernel(float* __restrict__ p, float* __restrict__ g,
-                                                                float* __restrict__ m, float* __restrict__ v,
-                                                                long long n, int n_part, float max_norm,
-                                                                float* __restrict__ norm_out,
-                                                                const long long* __restrict__ step, int guarded,
-                                                                float* __restrict__ loss_out, int n_loss_part,
-                                                                const OptRuleDev R) {
+struct AdamTable : OptRuleDev {
+  static constexpr bool kVmax = VMAX;
+  __device__ __forceinline__ AdamLane prepare(int lane, const long long* step) const {
+    const int gl = lane & (PMBRL_OPT_MAX_GROUPS - 1);
+    AdamLane L{pm_pick_group(b1, gl),   pm_pick_group(b2, gl),        pm_pick_group(omb1, gl),
+               pm_pick_group(omb2, gl), pm_pick_group(eps, gl),       pm_pick_group(wd, gl),
+               pm_pick_group(decay, gl), pm_pick_group(sgn, gl),      pm_pick_group(step_size, gl),
+               pm_pick_group(bc2_sqrt, gl), pm_pick_group(amsgrad, gl)};
+    if (step) {
+      // guarded form: the bias corrections of the device-side step counter, as AdamPlain forms them
+      const double st = (double)step[0];
+      const double bc1_d = -expm1(st * pm_pick_group(ln_b1, gl));
+      L.bc2_sqrt = (float)sqrt(-expm1(st * pm_pick_group(ln_b2, gl)));
+      L.step_size = (float)(pm_pick_group(lr_d, gl) / bc1_d);
+    }
+    return L;
+  }
+  __device__ __forceinline__ AdamLane at(const AdamLane& L, long long j, long long n) const {
+    // the element's segment (every lane takes part in the shuffles: beyond n the last element's)
+    const long long jc = min(j, n - 1);
+    // (three walks by the number of segments, chosen by a scalar branch: none for one segment, 7 boundaries for up to 8
+    //  -- weights / biases groups of a three-layer network are 6 segments -- and all 31 beyond.  Measured at n = 550 416,
+    //  where the launch is no longer launch-bound: all 31 comparisons for every rule were 13 us of a 21.6 us launch with
+    //  one group; a walk that leaves at the rule's last boundary, one branch per boundary, took 50 us for 32 segments)
+    int grp = seg_group[0];
+    if (n_segments > 8) {
+#pragma unroll
+      for (int q = 1; q < PMBRL_OPT_MAX_SEGMENTS; ++q)
+        if (q < n_segments && jc >= seg_end[q - 1]) grp = seg_group[q];
+    } else if (n_segments > 1) {
+#pragma unroll
+      for (int q = 1; q < 8; ++q)
+        if (q < n_segments && jc >= seg_end[q - 1]) grp = seg_group[q];
+    }
+    // (one group: every lane holds its record -- the unused slots repeat group 0)
+    if (n_groups <= 1) return L;
+    return AdamLane{__shfl(L.b1, grp),   __shfl(L.b2, grp),        __shfl(L.omb1, grp),
+                    __shfl(L.omb2, grp), __shfl(L.eps, grp),       __shfl(L.wd, grp),
+                    __shfl(L.decay, grp), __shfl(L.sgn, grp),      __shfl(L.step_size, grp),
+                    __shfl(L.bc2_sqrt, grp), __shfl(L.ams, grp)};
+  }
+  // (a wave leaves the loop as a whole -- its first lane's index decides: the shuffles above read the group records from
+  //  lanes 0 .. 7, which must still be there when only some lanes have elements left)
+  __device__ __forceinline__ bool done(long long i, int lane, long long n) const { return i - lane >= n; }
+};
+
+template <class RULE>
+__global__ __launch_bounds__(256) void pm_clip_adam_kernel(float* __restrict__ p, float* __restrict__ g,
+                                                           float* __restrict__ m, float* __restrict__ v,
+                                                           long long n, int n_part, float max_norm,
+                                                           float* __restrict__ norm_out,
+                                                           const long long* __restrict__ step, int guarded,
+                                                           float* __restrict__ loss_out, int n_loss_part,
+                                                           const RULE R) {
+  // The first four elements of this thread (amsgrad's running maximum where the rule has one) and the norm's partial sums
+  // are requested before anything is decided: as "go? -> step counter -> partial sums (a loop of dependent loads) ->
+  // elements (a loop of four)" this launch was ten memory round trips in a row around a few hundred instructions.
   const long long stride = (long long)gridDim.x * blockDim.x;
   const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   float gq[4], mq[4], vq[4], pq[4], xq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int u = 0; u < 4; ++u) {
+    // (beyond n: the last element's address, never used -- loads under a condition are waited for one by one)
     const long long j = min(i0 + u * stride, n - 1);
     gq[u] = g[j];
     mq[u] = m[j];
     vq[u] = v[j];
     pq[u] = p[j];
-    if constexpr (VMAX) xq[u] = R.vmax[j];
+    if constexpr (RULE::kVmax) xq[u] = R.vmax[j];
   }
   const int lane = threadIdx.x & 63;
   double part[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const double x = g_norm_part[min(lane + 64 * u, PM_NORM_MAXB - 1)];
-    part[u] = lane + 64 * u < n_part ? x : 0.0;
-  }
+  pm_norm_request(part, lane, n_part);
+  // (the go flag with them: read where it is tested, its round trip sat between the rule's scalar loads and the exit)
+  const int go = g_adam_go;
+  // (taken or not, the step's loss is reported)
   if (loss_out && blockIdx.x == 0 && threadIdx.x >= 64 && threadIdx.x < 128) {
-    double ls = 0.0;
-    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    const double ls = pm_loss_sum(lane, n_loss_part);
     if (lane == 0) loss_out[0] = (float)ls;
   }
-  if (guarded && !g_adam_go) return;
-  // this lane's group record
-  const int gl = lane & (PMBRL_OPT_MAX_GROUPS - 1);
-  const float r_b1 = pm_pick_group(R.b1, gl), r_b2 = pm_pick_group(R.b2, gl);
-  const float r_omb1 = pm_pick_group(R.omb1, gl), r_omb2 = pm_pick_group(R.omb2, gl);
-  const float r_eps = pm_pick_group(R.eps, gl), r_wd = pm_pick_group(R.wd, gl), r_decay = pm_pick_group(R.decay, gl);
-  const float r_sgn = pm_pick_group(R.sgn, gl);
-  const int r_ams = pm_pick_group(R.amsgrad, gl);
-  float r_step = pm_pick_group(R.step_size, gl), r_bc2 = pm_pick_group(R.bc2_sqrt, gl);
-  if (step) {
-    // guarded form: the bias corrections of the device-side step counter, as pm_clip_adam_kernel forms them
-    const double st = (double)step[0];
-    const double bc1_d = -expm1(st * pm_pick_group(R.ln_b1, gl));
-    r_bc2 = (float)sqrt(-expm1(st * pm_pick_group(R.ln_b2, gl)));
-    r_step = (float)(pm_pick_group(R.lr_d, gl) / bc1_d);
-  }
-  double t = 0.0;
-  {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) t += part[u];
-    for (int b = lane + 256; b < n_part; b += 64) t += g_norm_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o);
-  }
-  const float norm = (float)sqrt(t);
+  if (guarded && !go) return;   // the rollout failed: leave parameters and moments alone
+  const AdamLane L = R.prepare(lane, step);
+  const float norm = (float)sqrt(pm_norm_sum(part, lane, n_part));
   if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
   float coef = 1.f;
   if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.f);
@@ -505,57 +509,30 @@ __global__ __launch_bounds__(256) void pm_clip_adam_rule_kernel(float* __restric
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long long j = i + u * stride;
-      // the element's segment (every lane takes part in the shuffles: beyond n the last element's)
-      const long long jc = min(j, n - 1);
-      // (three walks by the number of segments, chosen by a scalar branch: none for one segment, 7 boundaries for up to 8
-      //  -- weights / biases groups of a three-layer network are 6 segments -- and all 31 beyond.  Measured at n = 550 416,
-      //  where the launch is no longer launch-bound: all 31 comparisons for every rule were 13 us of a 21.6 us launch with
-      //  one group; a walk that leaves at the rule's last boundary, one branch per boundary, took 50 us for 32 segments)
-      int grp = R.seg_group[0];
-      if (R.n_segments > 8) {
-#pragma unroll
-        for (int q = 1; q < PMBRL_OPT_MAX_SEGMENTS; ++q)
-          if (q < R.n_segments && jc >= R.seg_end[q - 1]) grp = R.seg_group[q];
-      } else if (R.n_segments > 1) {
-#pragma unroll
-        for (int q = 1; q < 8; ++q)
-          if (q < R.n_segments && jc >= R.seg_end[q - 1]) grp = R.seg_group[q];
-      }
-      // (one group: every lane holds its record -- the unused slots repeat group 0)
-      float b1 = r_b1, b2 = r_b2, omb1 = r_omb1, omb2 = r_omb2, eps = r_eps, wd = r_wd, decay = r_decay, sgn = r_sgn;
-      float step_size = r_step, bc2_sqrt = r_bc2;
-      int ams = r_ams;
-      if (R.n_groups > 1) {
-        b1 = __shfl(r_b1, grp); b2 = __shfl(r_b2, grp); omb1 = __shfl(r_omb1, grp); omb2 = __shfl(r_omb2, grp);
-        eps = __shfl(r_eps, grp); wd = __shfl(r_wd, grp); decay = __shfl(r_decay, grp); sgn = __shfl(r_sgn, grp);
-        step_size = __shfl(r_step, grp); bc2_sqrt = __shfl(r_bc2, grp);
-        ams = __shfl(r_ams, grp);
-      }
+      const AdamLane E = R.at(L, j, n);
       if (j < n) {
         const float gi = gq[u] * coef;
-        const float pd = pq[u] * decay;
-        float gs = gi * sgn;
-        if (wd != 0.f) gs = fmaf(wd, pd, gs);
-        const float mi = mq[u] * b1 + omb1 * gs;
-        const float vi = vq[u] * b2 + omb2 * gs * gs;
+        const float pd = pq[u] * E.decay;
+        float gs = gi * E.sgn;
+        if (E.wd != 0.f) gs = fmaf(E.wd, pd, gs);
+        const float mi = mq[u] * E.b1 + E.omb1 * gs;
+        const float vi = vq[u] * E.b2 + E.omb2 * gs * gs;
         float dv = vi;
-        if constexpr (VMAX) {
-          if (ams) {
+        if constexpr (RULE::kVmax) {
+          if (E.ams) {
             dv = fmaxf(xq[u], vi);
             R.vmax[j] = dv;
           }
         }
-        const float denom = sqrtf(dv) / bc2_sqrt + eps;
+        const float denom = sqrtf(dv) / E.bc2_sqrt + E.eps;
         g[j] = gi;
         m[j] = mi;
         v[j] = vi;
-        p[j] = pd - step_size * (mi / denom);
+        p[j] = pd - E.step_size * (mi / denom);
       }
     }
     i += 4 * stride;
-    // (a wave leaves the loop as a whole -- its first lane's index decides: the shuffles above read the group records from
-    //  lanes 0 .. 7, which must still be there when only some lanes have elements left)
-    if (i - lane >= n) break;
+    if (R.done(i, lane, n)) break;
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
       const long long j = min(i + u * stride, n - 1);
@@ -563,7 +540,7 @@ __global__ __launch_bounds__(256) void pm_clip_adam_rule_kernel(float* __restric
       mq[u] = m[j];
       vq[u] = v[j];
       pq[u] = p[j];
-      if constexpr (VMAX) xq[u] = R.vmax[j];
+      if constexpr (RULE::kVmax) xq[u] = R.vmax[j];
     }
   }
 }
@@ -612,15 +589,12 @@ static OptRuleDev opt_rule_dev(const pmbrl_opt_rule& r, long long step) {
   }
   for (int k = 0; k < PMBRL_OPT_MAX_GROUPS; ++k) {
     const pmbrl_opt_group& G = r.group[k < r.n_groups ? k : 0];
-    const bool dec = G.flags & PMBRL_OPT_DECOUPLED;
+    const OptGroupConsts c = pm_opt_group_consts(G);
     D.b1[k] = (float)G.beta1; D.b2[k] = (float)G.beta2;
     D.omb1[k] = (float)(1.0 - G.beta1); D.omb2[k] = (float)(1.0 - G.beta2);
     D.eps[k] = (float)G.eps;
-    D.wd[k] = dec ? 0.f : (float)G.weight_decay;
-    D.decay[k] = dec ? (float)(1.0 - G.lr * G.weight_decay) : 1.f;
-    D.sgn[k] = (G.flags & PMBRL_OPT_MAXIMIZE) ? -1.f : 1.f;
-    D.amsgrad[k] = (G.flags & PMBRL_OPT_AMSGRAD) ? 1 : 0;
-    D.ln_b1[k] = log(G.beta1); D.ln_b2[k] = log(G.beta2); D.lr_d[k] = G.lr;
+    D.wd[k] = c.wd; D.decay[k] = c.decay; D.sgn[k] = c.sgn; D.amsgrad[k] = c.ams;
+    D.ln_b1[k] = c.ln_b1; D.ln_b2[k] = c.ln_b2; D.lr_d[k] = G.lr;
     D.step_size[k] = D.bc2_sqrt[k] = 1.f;
     if (step > 0) {
       const float bc1 = (float)(1.0 - pow(G.beta1, (double)step));
@@ -633,17 +607,6 @@ static OptRuleDev opt_rule_dev(const pmbrl_opt_rule& r, long long step) {
   D.vmax = ams ? r.max_exp_avg_sq_d : nullptr;    // (no group asks for it: the instance without the stream)
   return D;
 }
-static void clip_adam_rule_launch(hipStream_t s, int nb, float* p, float* g, float* m, float* v, long long n, int n_part,
-                                  double max_norm, float* norm_out, const long long* step_d, int guarded, float* loss_out,
-                                  int n_loss_part, const pmbrl_opt_rule& rule, long long step) {
-  const OptRuleDev D = opt_rule_dev(rule, step);
-  if (D.vmax)
-    hipLaunchKernelGGL(pm_clip_adam_rule_kernel<true>, dim3(nb), dim3(256), 0, s, p, g, m, v, n, n_part, (float)max_norm,
-                       norm_out, step_d, guarded, loss_out, n_loss_part, D);
-  else
-    hipLaunchKernelGGL(pm_clip_adam_rule_kernel<false>, dim3(nb), dim3(256), 0, s, p, g, m, v, n, n_part, (float)max_norm,
-                       norm_out, step_d, guarded, loss_out, n_loss_part, D);
-}
 
 void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long long n, float* out, const int* nvalid,
                                 long long n_per_step) {
@@ -651,28 +614,41 @@ void launch_weighted_sum(hipStream_t s, const float* a, const float* w, long lon
   hipLaunchKernelGGL(pm_weighted_sum_kernel, dim3(nb), dim3(256), 0, s, a, w, n, out, nvalid, n_per_step);
 }
 
-// norm_done: the partial sums of squares and the go / no-go decision are already on the device (the fused iteration's
-// gradient reduction formed them: pm_dw_reduce, norm_on)
-int clip_adam_guarded_impl(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
-                                  int64_t n, int64_t* step_d, double lr, double beta1, double beta2, double eps,
-                                  double max_norm, float* norm_out_d, const int32_t* status_d, int32_t expect, bool norm_done,
-                                  float* loss_out_d, int n_loss_part, const pmbrl_opt_rule* rule) {
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
-  const int np = pm_norm_blocks(n);
-  if (!norm_done)
-    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
-                       (long long)n, (const int*)status_d, (int)expect, reinterpret_cast<long long*>(step_d), 1);
-  if (rule) {     // (checked when it was attached or by the entry point; n is the vector's it was checked against)
-    clip_adam_rule_launch((hipStream_t)stream, nb, params_d, grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, max_norm,
-                          norm_out_d, reinterpret_cast<const long long*>(step_d), 1, loss_out_d, n_loss_part, *rule, 0);
-    HIPCHK(hipGetLastError());
-    return 0;
+// The optimiser step of an AdamStep (pmbrl_host.h): the only place that launches pm_gradnorm_kernel for it and
+// pm_clip_adam_kernel.  The norm's launch: a guarded step always needs it (it takes the decision) unless the caller says
+// both are done; an unguarded one has nothing for it to do without clipping and without a norm to report.
+int pm_adam_launch(hipStream_t s, const AdamStep& A) {
+  const int guarded = A.step_d ? 1 : 0;
+  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (A.n + 1023) / 1024));
+  const int np = pm_norm_blocks(A.n);
+  const bool need_norm = guarded ? !A.norm_done : (A.max_norm > 0.0 || A.norm_out != nullptr);
+  long long* const step_d = reinterpret_cast<long long*>(A.step_d);
+  if (need_norm)
+    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, s, A.grads, (long long)A.n, (const int*)A.status,
+                       (int)A.expect, step_d, guarded);
+  const int n_part = guarded || need_norm ? np : 0;
+  auto launch = [&](const auto& R) {
+    hipLaunchKernelGGL(pm_clip_adam_kernel<std::decay_t<decltype(R)>>, dim3(nb), dim3(256), 0, s, A.params, A.grads, A.exp_avg,
+                       A.exp_avg_sq, (long long)A.n, n_part, (float)A.max_norm, A.norm_out, (const long long*)step_d, guarded,
+                       A.loss_out, A.n_loss_part, R);
+  };
+  if (A.rule) {
+    const OptRuleDev D = opt_rule_dev(*A.rule, guarded ? 0 : (long long)A.step);
+    if (D.vmax) launch(AdamTable<true>{D});
+    else launch(AdamTable<false>{D});
+  } else {
+    AdamPlain P;
+    P.b1 = (float)A.beta1; P.b2 = (float)A.beta2;
+    P.omb1 = (float)(1.0 - A.beta1); P.omb2 = (float)(1.0 - A.beta2);
+    P.eps = (float)A.eps;
+    P.bc1 = P.bc2_sqrt = 1.f;
+    if (!guarded) {
+      P.bc1 = (float)(1.0 - pow(A.beta1, (double)A.step));
+      P.bc2_sqrt = (float)sqrt(1.0 - pow(A.beta2, (double)A.step));
+    }
+    P.ln_b1 = log(A.beta1); P.ln_b2 = log(A.beta2); P.lr_d = A.lr;
+    launch(P);
   }
-  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
-                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, np, (float)lr, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps, 1.f, 1.f,
-                     (float)max_norm, norm_out_d, reinterpret_cast<const long long*>(step_d), 1, log(beta1), log(beta2), lr,
-                     loss_out_d, n_loss_part);
   HIPCHK(hipGetLastError());
   return 0;
 }
@@ -701,10 +677,7 @@ __global__ __launch_bounds__(64) void pm_tail_pack_kernel(float* __restrict__ xb
                                                           const int* __restrict__ status, const int* __restrict__ err) {
   const int lane = threadIdx.x;
   if (n_loss_part > 0) {
-    double ls = 0.0;
-    for (int b = lane; b < n_loss_part; b += 64) ls += g_loss_part[b];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) ls += __shfl_xor(ls, o);
+    const double ls = pm_loss_sum(lane, n_loss_part);
     if (lane == 0) xb[n] = (float)ls;
   } else if (!loss_here && lane == 0) {
     xb[n] = 0.f;
@@ -722,25 +695,10 @@ __global__ __launch_bounds__(64) void pm_tail_finish_kernel(const float* __restr
     // status word, the others learn it from the sticky error word in the next exchange.)
     const int bad = (xb[n + 1] != 0.f || (err && *err != 0)) ? 1 : 0;
     if (bad) status[1] = 1;
-    const int go = (status[0] >= expect && status[1] == 0) ? 1 : 0;
-    g_adam_go = go;
-    if (go && step) step[0] += 1;
+    pm_adam_decide(status, expect, step);
     g_loss_part[0] = (double)xb[n];
   }
-  double tot = 0.0;
-  for (long long eb = blockIdx.x; eb * 256 < n; eb += gridDim.x) {
-    const long long i0 = eb * 256 + 4 * (long long)threadIdx.x;
-    f32x4 t = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (i0 + 3 < n) {
-      t = *reinterpret_cast<const f32x4*>(xb + i0);
-      for (int r = 0; r < 4; ++r) g[i0 + r] = t[r];
-    } else {
-      for (int r = 0; r < 4; ++r)
-        if (i0 + r < n) { t[r] = xb[i0 + r]; g[i0 + r] = t[r]; }
-    }
-    tot += pm_sq4_wave(t, i0, n);
-  }
-  if (threadIdx.x == 0) g_norm_part[blockIdx.x] = tot;
+  pm_norm_walk<true>(xb, g, n);
 }
 
 // the launches of the kernels above that the rollout adjoint call and the BNN step queue (pmbrl_host.h)
@@ -811,27 +769,23 @@ extern "C" int pmbrl_weighted_sum_steps(void* stream, const float* a_d, const fl
   return 0;
 }
 
+// the four stand-alone optimiser calls: argument checks and an AdamStep
+static AdamStep adam_step_on(float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d, int64_t n, double max_norm,
+                             float* norm_out_d) {
+  AdamStep A;
+  A.params = params_d; A.grads = grads_d; A.exp_avg = exp_avg_d; A.exp_avg_sq = exp_avg_sq_d; A.n = n;
+  A.max_norm = max_norm; A.norm_out = norm_out_d;
+  return A;
+}
 extern "C" int pmbrl_clip_adam(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
                                float* exp_avg_sq_d, int64_t n, int64_t step, double lr, double beta1,
                                double beta2, double eps, double max_norm, float* norm_out_d) {
   if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || n < 1 || step < 1)
     return fail(-1, "bad argument");
-  const double bc1 = 1.0 - pow(beta1, (double)step);
-  const double bc2 = 1.0 - pow(beta2, (double)step);
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
-  const int np = pm_norm_blocks(n);
-  // without clipping and without a norm to report there is nothing for the norm kernel to do
-  const bool need_norm = max_norm > 0.0 || norm_out_d != nullptr;
-  if (need_norm)
-    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
-                       (long long)n, (const int*)nullptr, 0, (long long*)nullptr, 0);
-  hipLaunchKernelGGL(pm_clip_adam_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, params_d,
-                     grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, need_norm ? np : 0, (float)lr, (float)beta1,
-                     (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), (float)eps,
-                     (float)bc1, (float)sqrt(bc2), (float)max_norm, norm_out_d, (const long long*)nullptr, 0, 0.0, 0.0, lr,
-                     (float*)nullptr, 0);
-  HIPCHK(hipGetLastError());
-  return 0;
+  AdamStep A = adam_step_on(params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, max_norm, norm_out_d);
+  A.step = step;
+  A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps;
+  return pm_adam_launch((hipStream_t)stream, A);
 }
 
 extern "C" int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
@@ -840,24 +794,20 @@ extern "C" int pmbrl_clip_adam_guarded(void* stream, float* params_d, float* gra
                                        float* norm_out_d, const int32_t* status_d, int32_t expect) {
   if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || !step_d || !status_d || n < 1)
     return fail(-1, "bad argument");
-  return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, lr, beta1, beta2, eps, max_norm,
-                                norm_out_d, status_d, expect, false);
+  AdamStep A = adam_step_on(params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, max_norm, norm_out_d);
+  A.step_d = step_d; A.status = status_d; A.expect = expect;
+  A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps;
+  return pm_adam_launch((hipStream_t)stream, A);
 }
 
 extern "C" int pmbrl_clip_adam_rule(void* stream, float* params_d, float* grads_d, float* exp_avg_d, float* exp_avg_sq_d,
                                     int64_t n, int64_t step, double max_norm, float* norm_out_d, const pmbrl_opt_rule* rule) {
   if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || n < 1 || step < 1) return fail(-1, "bad argument");
   if (int rc = pmbrl_opt_rule_check(rule, n)) return rc;
-  const int nb = (int)std::max<long long>(1, std::min<long long>(PM_RED_MAXB, (n + 1023) / 1024));
-  const int np = pm_norm_blocks(n);
-  const bool need_norm = max_norm > 0.0 || norm_out_d != nullptr;
-  if (need_norm)
-    hipLaunchKernelGGL(pm_gradnorm_kernel, dim3(np), dim3(64), 0, (hipStream_t)stream, grads_d,
-                       (long long)n, (const int*)nullptr, 0, (long long*)nullptr, 0);
-  clip_adam_rule_launch((hipStream_t)stream, nb, params_d, grads_d, exp_avg_d, exp_avg_sq_d, (long long)n, need_norm ? np : 0,
-                        max_norm, norm_out_d, (const long long*)nullptr, 0, (float*)nullptr, 0, *rule, (long long)step);
-  HIPCHK(hipGetLastError());
-  return 0;
+  AdamStep A = adam_step_on(params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, max_norm, norm_out_d);
+  A.step = step;
+  A.rule = rule;
+  return pm_adam_launch((hipStream_t)stream, A);
 }
 
 extern "C" int pmbrl_clip_adam_rule_guarded(void* stream, float* params_d, float* grads_d, float* exp_avg_d,
@@ -867,6 +817,8 @@ extern "C" int pmbrl_clip_adam_rule_guarded(void* stream, float* params_d, float
   if (!params_d || !grads_d || !exp_avg_d || !exp_avg_sq_d || !step_d || !status_d || n < 1)
     return fail(-1, "bad argument");
   if (int rc = pmbrl_opt_rule_check(rule, n)) return rc;
-  return clip_adam_guarded_impl(stream, params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, step_d, 0.0, 0.0, 0.0, 0.0, max_norm,
-                                norm_out_d, status_d, expect, false, nullptr, 0, rule);
+  AdamStep A = adam_step_on(params_d, grads_d, exp_avg_d, exp_avg_sq_d, n, max_norm, norm_out_d);
+  A.step_d = step_d; A.status = status_d; A.expect = expect;
+  A.rule = rule;
+  return pm_adam_launch((hipStream_t)stream, A);
 }

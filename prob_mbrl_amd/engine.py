@@ -350,13 +350,7 @@ class BnnStep:
         (counter first_step + i).  loss_hist: optional fp32 [n_steps, 3].  rule: an optim.Rule attached to the plan for
         this call (pmbrl_bnn_plan_set_optimizer: lr / betas / eps are then the rule's; a tensor of the network must lie in
         one segment); none: the plain step.  Returns loss[3] of the last iteration."""
-        if rule is not None:
-            r = _rule_struct(rule, self.n_params)
-            _lib.check(self.lib.pmbrl_bnn_plan_set_optimizer(self.plan, C.byref(r)), 'pmbrl_bnn_plan_set_optimizer')
-            self._has_rule = True
-        elif getattr(self, '_has_rule', False):
-            _lib.check(self.lib.pmbrl_bnn_plan_set_optimizer(self.plan, None), 'pmbrl_bnn_plan_set_optimizer')
-            self._has_rule = False
+        _attach_rule(self, 'pmbrl_bnn_plan_set_optimizer', rule, self.n_params)
         for t in (Xn, Yn, params, exp_avg, exp_avg_sq):
             assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
         assert idx_all.is_cuda and idx_all.dtype == torch.int32 and idx_all.is_contiguous() and idx_all.numel() % self.M == 0
@@ -778,14 +772,7 @@ class Engine:
     def set_optimizer(self, rule):
         """Attach an optim.Rule to the plan (pmbrl_plan_set_optimizer; the library copies it), or detach with None:
         backward(adam=...) takes its hyper-parameters from the rule while one is attached."""
-        if rule is None:
-            if self._has_rule:
-                _lib.check(self.lib.pmbrl_plan_set_optimizer(self.plan, None), 'pmbrl_plan_set_optimizer')
-                self._has_rule = False
-            return
-        r = _rule_struct(rule, self.n_pol_params)
-        _lib.check(self.lib.pmbrl_plan_set_optimizer(self.plan, C.byref(r)), 'pmbrl_plan_set_optimizer')
-        self._has_rule = True
+        _attach_rule(self, 'pmbrl_plan_set_optimizer', rule, self.n_pol_params)
 
     def set_replay(self, on=1):
         """0: never replay repeated calls as hipGraphs; 1: the library's default (the one-launch-per-step forms); 2: every
@@ -872,25 +859,38 @@ def _rule_struct(rule, n):
     return rule.struct()
 
 
-def clip_adam(params, grads, exp_avg, exp_avg_sq, step, lr=None, betas=(0.9, 0.999), eps=1e-8,
-              max_norm=None, norm_out=None, rule=None):
-    """Fused clip_grad_norm_ + Adam.step on flat fp32 buffers (pmbrl_clip_adam).  rule: an optim.Rule -- parameter
-    groups, weight decay, amsgrad, maximize (pmbrl_clip_adam_rule); lr / betas / eps are then the rule's."""
+def _attach_rule(owner, setter, rule, n):
+    """Attach an optim.Rule to owner.plan through the library's `setter` (it copies the rule), or detach with None -- once:
+    a plan that holds none is not told again."""
+    if rule is None and not getattr(owner, '_has_rule', False):
+        return
+    r = _rule_struct(rule, n) if rule is not None else None
+    _lib.check(getattr(owner.lib, setter)(owner.plan, C.byref(r) if r is not None else None), setter)
+    owner._has_rule = rule is not None
+
+
+def _clip_adam(name, params, grads, exp_avg, exp_avg_sq, step, guard, lr, betas, eps, max_norm, norm_out, rule):
+    """The body of clip_adam and clip_adam_guarded: pmbrl_<name> with the plain hyper-parameters, or pmbrl_<name with
+    _rule> with an optim.Rule.  step: what the entry point takes as its step; guard: its trailing arguments."""
     lib = _lib.load()
     for t in (params, grads, exp_avg, exp_avg_sq):
         assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     n = params.numel()
+    head = (_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n, step)
+    tail = (float(max_norm) if max_norm else 0.0, _ptr(norm_out)) + guard
     if rule is not None:
+        name = name.replace('clip_adam', 'clip_adam_rule')
         r = _rule_struct(rule, n)
-        _lib.check(lib.pmbrl_clip_adam_rule(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq), n,
-                                            int(step), float(max_norm) if max_norm else 0.0, _ptr(norm_out), C.byref(r)),
-                   'pmbrl_clip_adam_rule')
+        _lib.check(getattr(lib, name)(*head, *tail, C.byref(r)), name)
         return
-    _lib.check(lib.pmbrl_clip_adam(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg),
-                                   _ptr(exp_avg_sq), n, int(step), float(lr), float(betas[0]),
-                                   float(betas[1]), float(eps),
-                                   float(max_norm) if max_norm else 0.0, _ptr(norm_out)),
-               'pmbrl_clip_adam')
+    _lib.check(getattr(lib, name)(*head, float(lr), float(betas[0]), float(betas[1]), float(eps), *tail), name)
+
+
+def clip_adam(params, grads, exp_avg, exp_avg_sq, step, lr=None, betas=(0.9, 0.999), eps=1e-8,
+              max_norm=None, norm_out=None, rule=None):
+    """Fused clip_grad_norm_ + Adam.step on flat fp32 buffers (pmbrl_clip_adam).  rule: an optim.Rule -- parameter
+    groups, weight decay, amsgrad, maximize (pmbrl_clip_adam_rule); lr / betas / eps are then the rule's."""
+    _clip_adam('pmbrl_clip_adam', params, grads, exp_avg, exp_avg_sq, int(step), (), lr, betas, eps, max_norm, norm_out, rule)
 
 
 class Graph:
@@ -942,22 +942,9 @@ def clip_adam_guarded(params, grads, exp_avg, exp_avg_sq, step_dev, lr, status, 
     """clip + Adam taken on the device only if `status` (the rollout's status word) says all
     `expect` horizon steps completed; `step_dev` is the device-side int64 step counter
     (pmbrl_clip_adam_guarded).  rule: an optim.Rule (pmbrl_clip_adam_rule_guarded); lr / betas / eps are then the rule's."""
-    lib = _lib.load()
-    for t in (params, grads, exp_avg, exp_avg_sq):
-        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
     assert step_dev.is_cuda and step_dev.dtype == torch.int64 and status.is_cuda and status.dtype == torch.int32
-    if rule is not None:
-        r = _rule_struct(rule, params.numel())
-        _lib.check(lib.pmbrl_clip_adam_rule_guarded(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg), _ptr(exp_avg_sq),
-                                                    params.numel(), _ptr(step_dev), float(max_norm) if max_norm else 0.0,
-                                                    _ptr(norm_out), _ptr(status), int(expect), C.byref(r)),
-                   'pmbrl_clip_adam_rule_guarded')
-        return
-    _lib.check(lib.pmbrl_clip_adam_guarded(_stream(), _ptr(params), _ptr(grads), _ptr(exp_avg),
-                                           _ptr(exp_avg_sq), params.numel(), _ptr(step_dev), float(lr),
-                                           float(betas[0]), float(betas[1]), float(eps),
-                                           float(max_norm) if max_norm else 0.0, _ptr(norm_out),
-                                           _ptr(status), int(expect)), 'pmbrl_clip_adam_guarded')
+    _clip_adam('pmbrl_clip_adam_guarded', params, grads, exp_avg, exp_avg_sq, _ptr(step_dev), (_ptr(status), int(expect)),
+               lr, betas, eps, max_norm, norm_out, rule)
 
 
 def debug_linear(x, W, b, transpose_w=False):
