@@ -70,6 +70,10 @@ def parse(argv=None):
     ap.add_argument('--pol_weight_decay', type=float, default=0.0, help='on the weights; biases are not decayed')
     ap.add_argument('--pol_clip', type=float, default=1.0)
     ap.add_argument('--pol_drop_rate', type=float, default=0.1)
+    ap.add_argument('--pol_dropout', type=str, default='bernoulli', choices=['concrete', 'bernoulli'],
+                    help='dropout of the policy: fixed-rate Bernoulli (BDropout at --pol_drop_rate) or concrete (CDropout, '
+                         'rates learned by the policy search from --pol_drop_rate; such a search runs at the stepwise '
+                         "rollout's cost and does not combine with --prioritized_replay)")
     ap.add_argument('--pol_opt_iters', type=int, default=1000)
     ap.add_argument('--pol_batch_size', type=int, default=100)
     ap.add_argument('--ps_iters', type=int, default=100)
@@ -143,8 +147,9 @@ def main(argv=None):
         reward_func=reward_func, output_density=density).float()
     pol = models.Policy(
         models.mlp(D, 2 * U, args.pol_shape,
-                   dropout_layers=[models.BDropout(args.pol_drop_rate) if args.pol_drop_rate > 0 else None
-                                   for h in args.pol_shape], nonlin=nonlin,
+                   dropout_layers=[None if args.pol_drop_rate <= 0 else
+                                   (models.BDropout(args.pol_drop_rate) if args.pol_dropout == 'bernoulli' else
+                                    models.CDropout(args.pol_drop_rate * np.ones(h))) for h in args.pol_shape], nonlin=nonlin,
                    output_nonlin=partial(models.DiagGaussianDensity, U)), maxU, minU).float()
     exp = utils.ExperienceDataset()
     if args.load_from is not None:

@@ -718,6 +718,37 @@ int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* call, void* workspace
                        float* grad_x_d /* [B][n_in] or NULL */,
                        float* grad_params_d /* flat, the layout of params_flat, or NULL */);
 
+/* pmbrl_mlp_backward for a network some of whose hidden layers are concrete dropout in TRAIN mode
+ * (models/modules.py:102-118,151-153): the mask of such a layer is a hard Bernoulli sample of
+ *   probs = sigmoid((logit_p[j] + log((u[r][j] + 1e-7) / (1 - (u[r][j] - 1e-7)))) / temp),   h = a * hard  (keep = 1),
+ * and the backward goes through probs, which is how a dropout rate is learned:
+ *   grad_logit[j] = sum_r gh[r][j] * a[r][j] * probs[r][j] * (1 - probs[r][j]) / temp
+ * with a the activation before the mask and gh the gradient at the layer's output before the mask, both at dropped
+ * units too.  mask_bits_d stay the caller's hard sample (it may be a replayed recording); u_d is the noise it was drawn
+ * from.  Layers with u_d[l] == NULL (Bernoulli dropout, no dropout) are as in pmbrl_mlp_backward, and grad_x / grad_params
+ * are the bits pmbrl_mlp_backward gives on the same inputs.  grad_logit_d: the concrete layers' [h_l], concatenated in
+ * layer order, OVERWRITTEN; formed like the weight gradient (slabs summed in slab order, no atomics: the same bits
+ * call after call).  probs (1 - probs) is formed as e / (1 + e)^2, e = exp(-|c / temp|): finite for any c / temp.
+ * LDS: one more 16-row buffer per concrete layer than pmbrl_mlp_backward; beyond 160 KB the workspace query gives 0 and
+ * the call -3, both with a message.  At least one layer must be concrete (else -2); keep of a concrete layer must be 1. */
+typedef struct {
+  const float* u_d[PMBRL_MAX_LAYERS];     /* [B][h_l] fp32 uniform noise, NULL: hidden layer l is not concrete */
+  const float* logit_d[PMBRL_MAX_LAYERS]; /* [h_l] */
+  float temp[PMBRL_MAX_LAYERS];           /* > 0 */
+} pmbrl_mlp_concrete;
+size_t pmbrl_mlp_backward_concrete_workspace_bytes(const pmbrl_mlp_call* call, const pmbrl_mlp_concrete* conc);
+int pmbrl_mlp_backward_concrete(void* stream, const pmbrl_mlp_call* call, void* workspace_d,
+                                const float* x_d, const float* params_flat_d,
+                                const uint16_t* const* mask_bits_d, const float* z_d,
+                                const float* in_shift_d, const float* in_iscale_d,
+                                const float* out_scale_d, const float* out_shift_d,
+                                const float* sq_scale_d, const float* sq_bias_d,
+                                const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                                float* grad_x_d /* [B][n_in] or NULL */,
+                                float* grad_params_d /* flat, the layout of params_flat, or NULL */,
+                                const pmbrl_mlp_concrete* conc,
+                                float* grad_logit_d /* the concrete layers' [h_l] in layer order */);
+
 /* ---- BNN maximum-likelihood training of the dynamics model ---------------- */
 /* Loss and gradient of one minibatch: the iteration body of the reference's
  * utils.train_regressor (utils/train_regressor.py:113-131) with the model in train() mode --

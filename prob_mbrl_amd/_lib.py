@@ -46,6 +46,11 @@ class MlpCall(C.Structure):
     _fields_ = [('B', C.c_int32), ('net', MLP), ('max_log_std', C.c_float), ('act', C.c_int32)]     # act: ACT_*
 
 
+class MlpConcrete(C.Structure):
+    """pmbrl_mlp_concrete (include/pmbrl.h): the train-mode concrete-dropout layers of pmbrl_mlp_backward_concrete."""
+    _fields_ = [('u_d', C.c_void_p * MAX_LAYERS), ('logit_d', C.c_void_p * MAX_LAYERS), ('temp', C.c_float * MAX_LAYERS)]
+
+
 class BnnConfig(C.Structure):
     _fields_ = [('M', C.c_int32), ('N', C.c_int32), ('net', MLP), ('max_log_std', C.c_float),
                 ('temperature', C.c_float * MAX_LAYERS), ('reg_scale', C.c_float * MAX_LAYERS),
@@ -106,6 +111,7 @@ EXPORTS = [
     'pmbrl_plan_set_timing', 'pmbrl_plan_read_timing', 'pmbrl_plan_set_prof', 'pmbrl_plan_set_replay', 'pmbrl_plan_replay_count',
     'pmbrl_mlp_workspace_bytes', 'pmbrl_mlp_forward', 'pmbrl_mlp_grad_input',
     'pmbrl_mlp_backward_workspace_bytes', 'pmbrl_mlp_backward',
+    'pmbrl_mlp_backward_concrete_workspace_bytes', 'pmbrl_mlp_backward_concrete',
     'pmbrl_bnn_plan_create', 'pmbrl_bnn_plan_destroy', 'pmbrl_bnn_plan_workspace_bytes',
     'pmbrl_bnn_plan_n_params', 'pmbrl_bnn_plan_set_unit_keep', 'pmbrl_bnn_loss_grad', 'pmbrl_bnn_loss_grad_ex', 'pmbrl_bnn_train_steps',
     'pmbrl_comm_unique_id', 'pmbrl_comm_init', 'pmbrl_allreduce_sum', 'pmbrl_comm_count', 'pmbrl_comm_destroy',
@@ -214,6 +220,11 @@ def load():
     lib.pmbrl_mlp_backward_workspace_bytes.argtypes = [C.POINTER(MlpCall)]
     lib.pmbrl_mlp_backward.restype = C.c_int
     lib.pmbrl_mlp_backward.argtypes = [vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 12
+    lib.pmbrl_mlp_backward_concrete_workspace_bytes.restype = C.c_size_t
+    lib.pmbrl_mlp_backward_concrete_workspace_bytes.argtypes = [C.POINTER(MlpCall), C.POINTER(MlpConcrete)]
+    lib.pmbrl_mlp_backward_concrete.restype = C.c_int
+    lib.pmbrl_mlp_backward_concrete.argtypes = ([vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 12 +
+                                                [C.POINTER(MlpConcrete), vp])
     lib.pmbrl_bnn_plan_create.restype = C.c_int
     lib.pmbrl_bnn_plan_create.argtypes = [C.POINTER(BnnConfig), C.c_int, C.POINTER(vp)]
     lib.pmbrl_bnn_plan_destroy.restype = None

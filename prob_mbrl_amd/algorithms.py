@@ -7,7 +7,8 @@ Two execution paths, same semantics:
    Used when the optimiser is a torch.optim.Adam or AdamW over the policy's Linear
    parameters (any groups, weight decay, amsgrad, maximize: optim.py) and no option needs autograd (CVaR, regulariser, value_func,
    prioritized_replay).
- * autograd: `rollout()`'s single autograd node + torch's loss / clip / optimiser
+ * autograd: `rollout()`'s single autograd node (the stepwise rollout for a train-mode concrete-dropout policy, whose
+   logit_p the optimiser then updates too) + torch's loss / clip / optimiser
    for everything else the reference signature allows.  value_func is evaluated by
    pmbrl_mlp_forward and differentiated by pmbrl_mlp_grad_input; the priorities of
    prioritized_replay come from pmbrl_rollout_bwd's action_grad_norms output.
@@ -177,8 +178,13 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
         if not (isinstance(init_state_noise, float) and init_state_noise == 0.0):
             x0_ = x0_ + torch.as_tensor(init_state_noise, device=run.dev) * torch.randn_like(x0_)
         try:
-            bundle = _make_bundle(run, x0_, run.precision)
-            path, cache, tail = _route(run, bundle)
+            if RO.concrete_train_policy(policy):
+                # learned policy dropout rates: the stepwise rollout, torch's clip and step over policy.parameters()
+                # (logit_p among them); the fused and pipelined paths never see such a policy
+                path = 'autograd'
+            else:
+                bundle = _make_bundle(run, x0_, run.precision)
+                path, cache, tail = _route(run, bundle)
             if path == 'autograd':
                 loss, states, actions, rewards = _autograd_iteration(run, x0_, i)
             elif path == 'pipelined':

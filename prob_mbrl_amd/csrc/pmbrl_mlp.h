@@ -314,10 +314,96 @@ struct MlpBwdPArgs {
   size_t w_off[PM_MAXL], b_off[PM_MAXL];   // offsets of W_l [out][in] and b_l in the flat parameter order
 };
 
-__host__ __device__ inline size_t pm_mlp_bwdp_lds_floats(int nl, int LD, int act) {
-  // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: one derivative buffer per hidden layer
-  return ((size_t)nl + 2 + (act ? nl - 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
+__host__ __device__ inline size_t pm_mlp_bwdp_lds_floats(int nl, int LD, int act, int n_conc = 0) {
+  // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: one derivative buffer per hidden layer; one Q buffer
+  // per train-mode concrete-dropout layer (pmbrl_mlp_backward_concrete)
+  return ((size_t)nl + 2 + (act ? nl - 1 : 0) + n_conc) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
 }
+
+// ---------------------------------------------------------------------------
+// train-mode concrete dropout (pmbrl_mlp_backward_concrete; models/modules.py:102-118,151-153): the mask of layer l is
+// a hard Bernoulli sample of probs = sigmoid(c / temp), c = logit_p[j] + log((u + 1e-7) / (1 - (u - 1e-7))), and the
+// backward goes through probs:  d logit_p[j] += sum_r gh[r][j] a[r][j] probs (1 - probs) / temp  with a the activation
+// BEFORE the mask and gh the gradient at the layer's output before the mask -- both at dropped units too.  The
+// recomputed forward leaves Q = a probs (1 - probs) / temp in a buffer of its own, the dX chain multiplies its
+// accumulator (gh) by it and sums the tile's 16 rows.
+// ---------------------------------------------------------------------------
+struct MlpConcArgs {
+  const float* u[PM_MAXL];         // [B][dim[l + 1]] uniform noise of hidden layer l, or null: not a concrete layer
+  const float* logit[PM_MAXL];     // [dim[l + 1]]
+  float temp[PM_MAXL];
+  int q_idx[PM_MAXL];              // which Q buffer
+  size_t g_off[PM_MAXL];           // offset of the layer's logits in the gradient
+  float* slab;                     // [gridDim.x][n_logit]
+  size_t n_logit;
+};
+
+// the base epilogue of the recomputed forward, and Q next to it: exact zeros in rows >= nvalid and columns >= width
+template <class Base>
+struct EpiMlpConcFwd {
+  Base base;
+  const float *bias, *u, *logit;
+  float temp;
+  float* q_out;
+  int ld, row0, nvalid, lane, act, width;
+  bool smooth;
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
+    base(ot, rt, acc);
+    const int g = lane >> 4;
+    const int lrow = rt * 16 + (lane & 15);
+    const int f0 = ot * 16 + 4 * g;
+    const f32x4 b = ldg4(bias + f0);
+    f32x4 q;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int j = f0 + r;
+      float qv = 0.f;
+      if (lrow < nvalid && j < width) {
+        const float v = acc[r] + b[r];
+        float a = v > 0.f ? v : 0.f, d;
+        if (smooth) pm_act(act, v, j, width, a, d);
+        const float uu = u[(size_t)(row0 + lrow) * width + j];
+        const float c = logit[j] + logf((uu + 1e-7f) / (1.f - (uu - 1e-7f)));
+        // probs (1 - probs) = e / (1 + e)^2 with e = exp(-|c / temp|): no overflow, an exact 0 once probs saturates
+        const float e = expf(-fabsf(c / temp));
+        qv = a * (e / ((1.f + e) * (1.f + e))) / temp;
+      }
+      q[r] = qv;
+    }
+    *reinterpret_cast<f32x4*>(q_out + lrow * ld + f0) = q;
+  }
+};
+
+// the base epilogue of the dX chain (acc = gh), and gl[j] (+)= sum over the tile's rows of gh Q: a lane holds one row
+// and four units, so the 16 rows meet by a butterfly over the lanes of a 16-lane group -- a fixed order -- and lane 0 of
+// the group owns the four addresses: the first tile stores, later tiles add in program order
+template <class Base>
+struct EpiMlpConcBwd {
+  Base base;
+  const float* q_in;
+  float* gl;
+  bool first;
+  int ld, lane, width;
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
+    base(ot, rt, acc);
+    const int g = lane >> 4, lrow = lane & 15;
+    const int f0 = ot * 16 + 4 * g;
+    const f32x4 q = *reinterpret_cast<const f32x4*>(q_in + lrow * ld + f0);
+    f32x4 s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) s[r] = acc[r] * q[r];
+#pragma unroll
+    for (int o = 1; o < 16; o <<= 1) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s[r] += __shfl_xor(s[r], o);
+    }
+    if (lrow == 0) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (f0 + r < width) gl[f0 + r] = first ? s[r] : gl[f0 + r] + s[r];
+    }
+  }
+};
 
 // slab[W_l] (+)= G^T H and slab[b_l] (+)= column sums of G; G, H: [16][LD] in LDS, rows >= nvalid read as exact zeros
 __device__ __forceinline__ void pm_mlp_accum_dw(const float* G, const float* H, int ld, int n_out, int n_in, float* dW,
@@ -354,9 +440,25 @@ __device__ __forceinline__ void pm_mlp_accum_dw(const float* G, const float* H, 
   }
 }
 
-__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const MlpBwdPArgs P) {
+struct MlpBwdCArgs {
+  MlpBwdPArgs p;
+  MlpConcArgs c;
+};
+template <bool CONC> struct MlpBwdPSel { typedef MlpBwdPArgs type; };
+template <> struct MlpBwdPSel<true> { typedef MlpBwdCArgs type; };
+__device__ __forceinline__ const MlpBwdPArgs& pm_bwdp_of(const MlpBwdPArgs& a) { return a; }
+__device__ __forceinline__ const MlpBwdPArgs& pm_bwdp_of(const MlpBwdCArgs& a) { return a.p; }
+__device__ __forceinline__ const MlpConcArgs* pm_conc_of(const MlpBwdPArgs&) { return nullptr; }
+__device__ __forceinline__ const MlpConcArgs* pm_conc_of(const MlpBwdCArgs& a) { return &a.c; }
+
+// CONC: some hidden layers are train-mode concrete dropout (MlpBwdCArgs); <false> is pmbrl_mlp_backward's kernel as it
+// always was
+template <bool CONC>
+__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename MlpBwdPSel<CONC>::type PP) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 16;
+  const MlpBwdPArgs& P = pm_bwdp_of(PP);
+  const MlpConcArgs* Cc = pm_conc_of(PP);
   const MlpBwdArgs& B = P.b;
   const MlpArgs& A = B.f;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -369,6 +471,12 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const MlpBwdPArgs
   const bool smooth = A.act != PMBRL_ACT_RELU;
   float* D = part + (size_t)PM_NW * PM_KS_NT * 256;  // (smooth only) [nl - 1][16][LD]: act' of hidden layer l
   float* slab = P.slab ? P.slab + (size_t)blockIdx.x * P.n_params : nullptr;
+  float* Q = nullptr;                                // (CONC) [concrete layers][16][LD]
+  float* lslab = nullptr;
+  if constexpr (CONC) {
+    Q = D + (smooth ? (size_t)(nl - 1) * R * LD : 0);
+    lslab = Cc->slab + (size_t)blockIdx.x * Cc->n_logit;
+  }
   const int K0 = A.dim[0];
   const int n_tiles = (A.B + R - 1) / R;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -378,13 +486,28 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const MlpBwdPArgs
     pm_mlp_load_rows(A, H, row0, nvalid, tid);
     __syncthreads();
     for (int l = 0; l < nl - 1; ++l) {
+      bool conc = false;
+      if constexpr (CONC) conc = Cc->u[l] != nullptr;
       if (smooth) {
         EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, D + (size_t)l * R * LD, LD, row0,
                     nvalid, A.nt[l + 1], lane, pm_act_code(A.act, l), A.dim[l + 1]};
-        gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+        if (conc) {
+          EpiMlpConcFwd<EpiMlpAct> ec{e, A.bias[l], Cc->u[l], Cc->logit[l], Cc->temp[l], Q + (size_t)Cc->q_idx[l] * R * LD,
+                                      LD, row0, nvalid, lane, pm_act_code(A.act, l), A.dim[l + 1], true};
+          gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, ec);
+        } else {
+          gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+        }
       } else {
         EpiMlpHidden e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, LD, row0, nvalid, A.nt[l + 1], lane};
-        gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+        if (conc) {
+          EpiMlpConcFwd<EpiMlpHidden> ec{e, A.bias[l], Cc->u[l], Cc->logit[l], Cc->temp[l],
+                                         Q + (size_t)Cc->q_idx[l] * R * LD, LD, row0, nvalid, lane, PMBRL_ACT_RELU,
+                                         A.dim[l + 1], false};
+          gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, ec);
+        } else {
+          gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+        }
       }
       __syncthreads();
     }
@@ -400,12 +523,26 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const MlpBwdPArgs
         pm_mlp_accum_dw(Gin, H + (size_t)l * R * LD, LD, A.dim[l + 1], A.dim[l], slab + P.w_off[l], slab + P.b_off[l], first,
                         nvalid, wid, lane, tid);
       if (l == 0) break;
+      bool conc = false;                               // is hidden layer l - 1, whose gh this GEMM forms, concrete?
+      if constexpr (CONC) conc = Cc->u[l - 1] != nullptr;
       if (smooth) {
         EpiMlpBwdAct e{D + (size_t)(l - 1) * R * LD, Gout, LD, lane};
-        gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+        if (conc) {
+          EpiMlpConcBwd<EpiMlpBwdAct> ec{e, Q + (size_t)Cc->q_idx[l - 1] * R * LD, lslab + Cc->g_off[l - 1], first, LD,
+                                         lane, A.dim[l]};
+          gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, ec);
+        } else {
+          gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+        }
       } else {
         EpiMlpBwd e{H + (size_t)l * R * LD, 1.f / A.keep[l - 1], Gout, LD, lane};
-        gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+        if (conc) {
+          EpiMlpConcBwd<EpiMlpBwd> ec{e, Q + (size_t)Cc->q_idx[l - 1] * R * LD, lslab + Cc->g_off[l - 1], first, LD, lane,
+                                      A.dim[l]};
+          gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, ec);
+        } else {
+          gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
+        }
       }
       __syncthreads();
       float* t = Gin; Gin = Gout; Gout = t;

@@ -186,23 +186,68 @@ extern "C" size_t pmbrl_mlp_backward_workspace_bytes(const pmbrl_mlp_call* c) {
   return mlp_slab_offset(L) + (size_t)mlp_backward_blocks(c, L) * L.n_params * sizeof(float);
 }
 
-extern "C" int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
-                                  const float* x_d, const float* params_flat_d,
-                                  const uint16_t* const* mask_bits_d, const float* z_d,
-                                  const float* in_shift_d, const float* in_iscale_d,
-                                  const float* out_scale_d, const float* out_shift_d,
-                                  const float* sq_scale_d, const float* sq_bias_d,
-                                  const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
-                                  float* grad_x_d, float* grad_params_d) {
-  MlpLayout L;
-  int rc = mlp_backward_layout(c, L);
+// the concrete-dropout layers of a pmbrl_mlp_backward_concrete call: which hidden layers, where their logits sit in the
+// gradient, and the kernel's LDS need with one Q buffer per such layer
+struct MlpConcLayout {
+  int n_conc, q_idx[PM_MAXL];
+  size_t g_off[PM_MAXL], n_logit, lds;
+};
+static int mlp_concrete_layout(const pmbrl_mlp_call* c, const pmbrl_mlp_concrete* conc, MlpLayout& L, MlpConcLayout& Q) {
+  int rc = mlp_layout(c, L);
   if (rc) return rc;
+  if (!conc) return fail(-1, "null argument");
+  Q.n_conc = 0;
+  Q.n_logit = 0;
+  for (int l = 0; l < PM_MAXL; ++l) {
+    Q.q_idx[l] = 0;
+    Q.g_off[l] = 0;
+    if (!conc->u_d[l]) continue;
+    if (l >= L.nl - 1) return fail(-2, "mlp concrete: u_d given for a layer that is not a hidden layer");
+    if (!conc->logit_d[l]) return fail(-1, "mlp concrete: a layer with u_d needs logit_d");
+    if (!(conc->temp[l] > 0.f)) return fail(-2, "mlp concrete: temp must be > 0");
+    if (c->net.keep[l] != 1.f) return fail(-2, "mlp concrete: a concrete layer is not divided by p (keep must be 1)");
+    Q.q_idx[l] = Q.n_conc++;
+    Q.g_off[l] = Q.n_logit;
+    Q.n_logit += (size_t)L.dim[l + 1];
+  }
+  if (!Q.n_conc) return fail(-2, "mlp concrete: no concrete layer (use pmbrl_mlp_backward)");
+  Q.lds = pm_mlp_bwdp_lds_floats(L.nl, L.LD, L.act, Q.n_conc) * sizeof(float);
+  if (Q.lds > 160 * 1024)
+    return fail(-3, "mlp: network too wide / deep for the concrete backward kernel's LDS budget (160 KB)");
+  return 0;
+}
+// the logit slabs follow the parameter slabs
+static size_t mlp_logit_slab_offset(const pmbrl_mlp_call* c, const MlpLayout& L) {
+  return (mlp_slab_offset(L) + (size_t)mlp_backward_blocks(c, L) * L.n_params * sizeof(float) + 255) & ~(size_t)255;
+}
+
+extern "C" size_t pmbrl_mlp_backward_concrete_workspace_bytes(const pmbrl_mlp_call* c, const pmbrl_mlp_concrete* conc) {
+  MlpLayout L;
+  MlpConcLayout Q;
+  if (mlp_concrete_layout(c, conc, L, Q)) return 0;
+  return mlp_logit_slab_offset(c, L) + (size_t)mlp_backward_blocks(c, L) * Q.n_logit * sizeof(float);
+}
+
+// pmbrl_mlp_backward (conc == nullptr) and pmbrl_mlp_backward_concrete: one marshalling, two kernels
+static int mlp_backward_run(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
+                            const float* x_d, const float* params_flat_d,
+                            const uint16_t* const* mask_bits_d, const float* z_d,
+                            const float* in_shift_d, const float* in_iscale_d,
+                            const float* out_scale_d, const float* out_shift_d,
+                            const float* sq_scale_d, const float* sq_bias_d,
+                            const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                            float* grad_x_d, float* grad_params_d, const pmbrl_mlp_concrete* conc, float* grad_logit_d) {
+  MlpLayout L;
+  MlpConcLayout Q;
+  int rc = conc ? mlp_concrete_layout(c, conc, L, Q) : mlp_backward_layout(c, L);
+  if (rc) return rc;
+  if (conc && !grad_logit_d) return fail(-1, "null argument");
   if (!workspace_d || !x_d || !params_flat_d) return fail(-1, "null argument");
   if (!g_sample_d && !g_mean_d && !g_log_std_d) return fail(-1, "mlp backward: no upstream gradient given");
   if ((in_shift_d == nullptr) != (in_iscale_d == nullptr) || (out_scale_d == nullptr) != (out_shift_d == nullptr) ||
       (sq_scale_d == nullptr) != (sq_bias_d == nullptr))
     return fail(-1, "mlp: shift/scale pointers come in pairs");
-  if (!grad_x_d && !grad_params_d) return 0;
+  if (!grad_x_d && !grad_params_d && !conc) return 0;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace_d);
   PackArgs PK;
@@ -236,15 +281,65 @@ extern "C" int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* c, void* w
   const int n_blocks = mlp_backward_blocks(c, L);
   P.n_params = L.n_params;
   P.slab = grad_params_d ? reinterpret_cast<float*>(ws + mlp_slab_offset(L)) : nullptr;
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdp_kernel),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bwdp));
   pm_pack_all_launch(PK, s);
-  hipLaunchKernelGGL(pm_mlp_bwdp_kernel, dim3(n_blocks), dim3(PM_NT), L.lds_bwdp, s, P);
-  HIPCHK(hipGetLastError());
+  if (conc) {
+    MlpBwdCArgs Cc;
+    memset(&Cc, 0, sizeof(Cc));
+    Cc.p = P;
+    for (int l = 0; l < L.nl - 1; ++l) {
+      Cc.c.u[l] = conc->u_d[l];
+      Cc.c.logit[l] = conc->logit_d[l];
+      Cc.c.temp[l] = conc->temp[l];
+      Cc.c.q_idx[l] = Q.q_idx[l];
+      Cc.c.g_off[l] = Q.g_off[l];
+    }
+    Cc.c.slab = reinterpret_cast<float*>(ws + mlp_logit_slab_offset(c, L));
+    Cc.c.n_logit = Q.n_logit;
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdp_kernel<true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)Q.lds));
+    hipLaunchKernelGGL(pm_mlp_bwdp_kernel<true>, dim3(n_blocks), dim3(PM_NT), Q.lds, s, Cc);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(pm_mlp_bwd_reduce_kernel, dim3((unsigned)((Q.n_logit + 255) / 256)), dim3(256), 0, s, Cc.c.slab,
+                       n_blocks, Q.n_logit, grad_logit_d);
+    HIPCHK(hipGetLastError());
+  } else {
+    HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(&pm_mlp_bwdp_kernel<false>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds_bwdp));
+    hipLaunchKernelGGL(pm_mlp_bwdp_kernel<false>, dim3(n_blocks), dim3(PM_NT), L.lds_bwdp, s, P);
+    HIPCHK(hipGetLastError());
+  }
   if (grad_params_d) {
     hipLaunchKernelGGL(pm_mlp_bwd_reduce_kernel, dim3((unsigned)((L.n_params + 255) / 256)), dim3(256), 0, s, P.slab,
                        n_blocks, L.n_params, grad_params_d);
     HIPCHK(hipGetLastError());
   }
   return 0;
+}
+
+extern "C" int pmbrl_mlp_backward(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
+                                  const float* x_d, const float* params_flat_d,
+                                  const uint16_t* const* mask_bits_d, const float* z_d,
+                                  const float* in_shift_d, const float* in_iscale_d,
+                                  const float* out_scale_d, const float* out_shift_d,
+                                  const float* sq_scale_d, const float* sq_bias_d,
+                                  const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                                  float* grad_x_d, float* grad_params_d) {
+  return mlp_backward_run(stream, c, workspace_d, x_d, params_flat_d, mask_bits_d, z_d, in_shift_d, in_iscale_d, out_scale_d,
+                          out_shift_d, sq_scale_d, sq_bias_d, g_sample_d, g_mean_d, g_log_std_d, grad_x_d, grad_params_d,
+                          nullptr, nullptr);
+}
+
+extern "C" int pmbrl_mlp_backward_concrete(void* stream, const pmbrl_mlp_call* c, void* workspace_d,
+                                           const float* x_d, const float* params_flat_d,
+                                           const uint16_t* const* mask_bits_d, const float* z_d,
+                                           const float* in_shift_d, const float* in_iscale_d,
+                                           const float* out_scale_d, const float* out_shift_d,
+                                           const float* sq_scale_d, const float* sq_bias_d,
+                                           const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                                           float* grad_x_d, float* grad_params_d, const pmbrl_mlp_concrete* conc,
+                                           float* grad_logit_d) {
+  if (!conc) return fail(-1, "null argument");
+  return mlp_backward_run(stream, c, workspace_d, x_d, params_flat_d, mask_bits_d, z_d, in_shift_d, in_iscale_d, out_scale_d,
+                          out_shift_d, sq_scale_d, sq_bias_d, g_sample_d, g_mean_d, g_log_std_d, grad_x_d, grad_params_d,
+                          conc, grad_logit_d);
 }

@@ -166,13 +166,34 @@ class _MlpCall:
         return gx
 
 
-    def backward(self, g_sample=None, g_mean=None, g_log_std=None, want_x=True, want_params=True, out=None):
+    def backward(self, g_sample=None, g_mean=None, g_log_std=None, want_x=True, want_params=True, out=None,
+                 concrete=None):
         """(grad_x [B, n_in], grad_params flat in the order of params_flat) of pmbrl_mlp_backward; an output that is
-        not wanted is None and is not computed.  out = (grad_x, grad_params): write into these tensors."""
-        nbytes = self.lib.pmbrl_mlp_backward_workspace_bytes(C.byref(self.call))
+        not wanted is None and is not computed.  out = (grad_x, grad_params): write into these tensors.
+        concrete: per hidden layer None or (u [B, h_l], logit_p [h_l], temp) of a train-mode concrete-dropout layer
+        whose hard sample the call's mask bits hold; the call is then pmbrl_mlp_backward_concrete and a third result
+        follows, the list of d / d logit_p [h_l] per such layer (None for the others)."""
+        conc = None
+        if concrete is not None and any(c is not None for c in concrete):
+            conc, keep, dev = _lib.MlpConcrete(), [], self.x.device
+            for l, c in enumerate(concrete):
+                if c is None:
+                    continue
+                u, lg = _f32c(c[0].detach(), dev), _f32c(c[1].detach().reshape(-1), dev)
+                h = self.dims[l + 1]
+                if lg.numel() == 1 and h > 1:
+                    lg = lg.expand(h).contiguous()
+                assert u.shape == (self.B, h) and lg.numel() == h
+                keep += [u, lg]
+                conc.u_d[l], conc.logit_d[l], conc.temp[l] = u.data_ptr(), lg.data_ptr(), float(c[2])
+            nbytes = self.lib.pmbrl_mlp_backward_concrete_workspace_bytes(C.byref(self.call), C.byref(conc))
+            name = 'pmbrl_mlp_backward_concrete'
+        else:
+            nbytes = self.lib.pmbrl_mlp_backward_workspace_bytes(C.byref(self.call))
+            name = 'pmbrl_mlp_backward'
         if nbytes == 0:
             msg = self.lib.pmbrl_last_error()
-            raise ValueError('pmbrl_mlp_backward_workspace_bytes: %s' % (msg.decode() if msg else 'bad shape'))
+            raise ValueError('%s_workspace_bytes: %s' % (name, msg.decode() if msg else 'bad shape'))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.x.device)
         gx, gp = out if out is not None else (None, None)
         gx = (torch.empty_like(self.x) if gx is None else gx) if want_x else None
@@ -181,9 +202,20 @@ class _MlpCall:
             assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == like.shape)
         p = self._p
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_sample, g_mean, g_log_std)]
-        _lib.check(self.lib.pmbrl_mlp_backward(_stream(), C.byref(self.call), p(ws), *self._common(),
-                                               p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp)), 'pmbrl_mlp_backward')
-        return gx, gp
+        if conc is None:
+            _lib.check(self.lib.pmbrl_mlp_backward(_stream(), C.byref(self.call), p(ws), *self._common(),
+                                                   p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp)), name)
+            return gx, gp
+        widths = [self.dims[l + 1] if c is not None else 0 for l, c in enumerate(concrete)]
+        gl = torch.empty(sum(widths), dtype=torch.float32, device=self.x.device)
+        _lib.check(self.lib.pmbrl_mlp_backward_concrete(_stream(), C.byref(self.call), p(ws), *self._common(),
+                                                        p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp), C.byref(conc),
+                                                        p(gl)), name)
+        parts, off = [], 0
+        for w, c in zip(widths, concrete):
+            parts.append(gl[off:off + w] if c is not None else None)
+            off += w
+        return gx, gp, parts
 
 
 class _MlpFunction(torch.autograd.Function):
@@ -204,12 +236,21 @@ class _MlpFunction(torch.autograd.Function):
 
 class _MlpParamFunction(torch.autograd.Function):
     """Differentiable with respect to the input rows and the parameter tensors W0, b0, W1, b1, ... (the pieces of the
-    call's params_flat), first order: one pmbrl_mlp_backward per backward pass."""
+    call's params_flat), first order: one pmbrl_mlp_backward per backward pass.  concrete: per hidden layer None or
+    (u, temp) of a train-mode concrete-dropout layer; the logit_p tensors of those layers follow the parameters as
+    further differentiable inputs (pmbrl_mlp_backward_concrete; a scalar or singleton logit_p gets the sum over the
+    units)."""
 
     @staticmethod
-    def forward(ctx, call, want, x, *params):
+    def forward(ctx, call, want, concrete, x, *params):
         ctx.call, ctx.want = call, want
+        n_conc = sum(c is not None for c in concrete) if concrete is not None else 0
+        ctx.n_lin = len(params) - n_conc
         ctx.shapes = [p.shape for p in params]
+        ctx.concrete = None
+        if n_conc:
+            logits = iter(params[ctx.n_lin:])
+            ctx.concrete = [None if c is None else (c[0], next(logits).detach(), c[1]) for c in concrete]
         ctx.set_materialize_grads(False)
         out = call.forward(want)
         return tuple(out[k] for k in want)
@@ -218,20 +259,29 @@ class _MlpParamFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
         g = dict(zip(ctx.want, grads))
-        need_x, need_p = ctx.needs_input_grad[2], ctx.needs_input_grad[3:]
-        gx, gp = ctx.call.backward(g.get('sample'), g.get('mean'), g.get('log_std'), want_x=need_x,
-                                   want_params=any(need_p))
+        need_x, need_p = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
+        need_lin, need_lg = need_p[:ctx.n_lin], need_p[ctx.n_lin:]
+        res = ctx.call.backward(g.get('sample'), g.get('mean'), g.get('log_std'), want_x=need_x,
+                                want_params=any(need_lin), concrete=ctx.concrete if any(need_lg) else None)
+        gx, gp = res[0], res[1]
         out, off = [], 0
-        for shape, need in zip(ctx.shapes, need_p):
+        for shape, need in zip(ctx.shapes[:ctx.n_lin], need_lin):
             n = shape.numel()
             out.append(gp[off:off + n].view(shape) if need else None)
             off += n
-        return (None, None, gx) + tuple(out)
+        if ctx.concrete is not None:
+            gls = [t for t in res[2] if t is not None] if any(need_lg) else [None] * len(need_lg)
+            for shape, need, gl in zip(ctx.shapes[ctx.n_lin:], need_lg, gls):
+                if not need:
+                    out.append(None)
+                else:
+                    out.append(gl.view(shape) if shape.numel() == gl.numel() else gl.sum().expand(shape).clone())
+        return (None, None, None, gx) + tuple(out)
 
 
 def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=None, in_iscale=None,
                 out_scale=None, out_shift=None, sq_scale=None, sq_bias=None, max_log_std=math.log(5.0),
-                want=('sample',), act=0, params=None):
+                want=('sample',), act=0, params=None, concrete=None):
     """Stand-alone evaluation of one Bayesian MLP with a diagonal-Gaussian head on the rows of x
     (pmbrl_mlp_forward; models/core.py:169-187, 221-248).  dims = [n_in, h..., 2*n_out];
     mask_bits: per hidden layer an int16 bit-row tensor (pack_mask) or None.
@@ -239,15 +289,20 @@ def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=Non
     Returns a dict with the requested outputs among 'sample', 'mean', 'log_std' ([B, n_out]).
     If x requires grad the outputs are differentiable with respect to x (pmbrl_mlp_grad_input).
     params: the tensors [W0, b0, W1, b1, ...] whose values params_flat holds; where one of them requires grad the
-    outputs are connected to them (and to x where it requires grad) through pmbrl_mlp_backward."""
+    outputs are connected to them (and to x where it requires grad) through pmbrl_mlp_backward.
+    concrete (with params): per hidden layer None or (u [B, h_l], logit_p, temp) of a concrete-dropout layer in train
+    mode, mask_bits[l] being the hard sample drawn from u: the outputs are connected to those logit_p tensors too
+    (pmbrl_mlp_backward_concrete)."""
     want = tuple(want)
     xc = x.contiguous()
     call = _MlpCall(xc.detach(), params_flat, dims, keep, mask_bits, z, in_shift, in_iscale, out_scale,
                     out_shift, sq_scale, sq_bias, max_log_std, act=act)
-    if params is not None and torch.is_grad_enabled() and any(p.requires_grad for p in params):
+    logits = [c[1] for c in concrete if c is not None] if (concrete is not None and params is not None) else []
+    if params is not None and torch.is_grad_enabled() and any(p.requires_grad for p in list(params) + logits):
         assert [tuple(p.shape) for p in params] == [s for i in range(len(dims) - 1)
                                                     for s in ((dims[i + 1], dims[i]), (dims[i + 1],))]
-        outs = _MlpParamFunction.apply(call, want, xc, *params)
+        noise = [None if c is None else (c[0], c[2]) for c in concrete] if logits else None
+        outs = _MlpParamFunction.apply(call, want, noise, xc, *params, *logits)
         return dict(zip(want, outs))
     if x.requires_grad and torch.is_grad_enabled():
         outs = _MlpFunction.apply(xc, call, want)

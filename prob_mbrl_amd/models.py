@@ -37,9 +37,12 @@ def param_grad_enabled():
 def param_grad(enabled=True):
     """Inside this context a stand-alone Policy / Regressor / DynamicsModel / critic call returns outputs connected
     to the Linear parameters of the network (and to x where it requires grad), as the reference's torch modules
-    always are: `loss.backward()` fills `fc*.weight.grad` / `.bias.grad` (pmbrl_mlp_backward, first order; the dropout
-    masks are constants).  The forward is the same kernel with the same values.  Outside the context -- the default
-    -- the network is a constant of such a call.  Thread-local; nests, and restores the previous state on exit."""
+    always are: `loss.backward()` fills `fc*.weight.grad` / `.bias.grad` (pmbrl_mlp_backward, first order; eval-mode
+    and Bernoulli dropout masks are constants) and, for every CDropout layer in train() mode, `drop*.logit_p.grad`: the
+    forward applies a hard Bernoulli sample of the relaxed probabilities and the backward goes through those
+    probabilities (pmbrl_mlp_backward_concrete; models/modules.py:102-118,151-153).  The forward is the same kernel with
+    the same values.  Outside the context -- the default -- the network is a constant of such a call.  Thread-local;
+    nests, and restores the previous state on exit."""
     prev = param_grad_enabled()
     _param_grad_state.on = bool(enabled)
     try:
@@ -192,6 +195,9 @@ class CDropout(BDropout):
         concrete_p = self.logit_p + ((noise + 1e-7) / (1 - (noise - 1e-7))).log()
         probs = (concrete_p / self.temp).sigmoid()
         forced = getattr(self, '_forced_sample', None)      # tests: replay recorded draws
+        seq = getattr(self, '_forced_samples', None)        # ... one per call, consumed in order (train mode draws at
+        if seq is not None:                                 # every forward)
+            forced = seq.pop(0)
         hard = torch.bernoulli(probs) if forced is None else forced.to(probs)
         self.concrete_noise = (hard - probs).detach() + probs
         self._mask_gen = getattr(self, '_mask_gen', 0) + 1
@@ -200,12 +206,12 @@ class CDropout(BDropout):
     def keep_prob(self):
         return 1.0   # x * concrete_noise, no division (models/modules.py:158-160)
 
-    def forward_mask(self, B, width, resample=False, seed=None):
+    def forward_mask(self, B, width, resample=False, seed=None, return_noise=False):
         """Mask of a stand-alone forward (models/modules.py:120-160).  Eval mode: the stored hard
         sample (redrawn only when the noise is).  Training mode: a fresh Bernoulli sample of the
-        relaxed probabilities at every call, like the reference -- its VALUE only: a stand-alone
-        forward is not differentiable with respect to the network here (the training step is
-        pmbrl_bnn_loss_grad)."""
+        relaxed probabilities at every call, like the reference.  return_noise: (mask, u) with u the
+        uniform noise [B, width] this call's probabilities were formed from -- what the gradient with
+        respect to logit_p needs (BSequential.device_forward under param_grad())."""
         resampled = False
         noise = self.noise
         c = self.concrete_noise
@@ -213,6 +219,9 @@ class CDropout(BDropout):
             if seed is not None:
                 torch.manual_seed(int(seed))
             noise = torch.rand(B, width, device=self.noise.device, dtype=self.noise.dtype)
+            nseq = getattr(self, '_forced_noises', None)    # tests: replay the recorded uniforms, one per call
+            if nseq is not None:
+                noise = nseq.pop(0).to(noise).reshape(-1, width)
             resampled = True
         elif (noise.dim() != 2 or c.dim() != 2 or noise.shape[1] != width or c.shape[1] != width
               or B > c.shape[0]):
@@ -221,7 +230,8 @@ class CDropout(BDropout):
             resampled = True
         if self.training or resampled:
             self.update_concrete_noise(noise)
-        return self.concrete_noise.detach()[:B]
+        mask = self.concrete_noise.detach()[:B]
+        return (mask, noise[:B]) if return_noise else mask
 
     def step_mask_bits(self, H, B, width):
         """H fresh eval-mode masks as bit rows, one device launch (see BDropout.step_mask_bits): new uniform noise and
@@ -431,9 +441,10 @@ class BSequential(nn.Sequential):
                        out_shift=None, squash=None, gmm_draws=None, **kwargs):
         """Evaluate the network + Gaussian head on the rows of x with pmbrl_mlp_forward
         (models/modules.py:215-232 + models/densities.py:87-121).  Returns samples [B, n_out]
-        (squashed if `squash=(scale, bias)`) or (mean, log_std)."""
+        (squashed if `squash=(scale, bias)`) or (mean, log_std).  Under param_grad() the outputs are connected to the
+        Linear parameters and to the logit_p of every CDropout layer in train() mode."""
         from . import engine as E
-        from .rollout import flat_parameters
+        from .rollout import flat_parameters, _scalar_of
         linears, drops, inner, acts = self._parse()
         from . import activations as ACT
         act = ACT.pack(acts)
@@ -475,24 +486,35 @@ class BSequential(nn.Sequential):
             if params is not None:      # (the zero rows are constants: their gradient is sliced away by autograd)
                 params[-2:] = [torch.cat([params[-2], params[-2].new_zeros(O, K)]),
                                torch.cat([params[-1], params[-1].new_zeros(O)])]
-        keep, bits = [], []
+        keep, bits, conc = [], [], []
         for lin, dr in zip(linears[:-1], drops):
             if dr is None:
                 keep.append(1.0)
                 bits.append(None)
+                conc.append(None)
+            elif params is not None and isinstance(dr, CDropout) and dr.training:
+                # train-mode concrete dropout under param_grad(): logit_p is a differentiable input of the call
+                m, u = dr.forward_mask(B, lin.out_features, resample=resample, seed=seed, return_noise=True)
+                if dr.logit_p.numel() not in (1, lin.out_features):
+                    raise ValueError('logit_p has %d entries for a layer of width %d' % (dr.logit_p.numel(), lin.out_features))
+                keep.append(dr.keep_prob())
+                bits.append(E.pack_mask(m.to(device=x.device, dtype=torch.float32)))
+                conc.append((u.to(device=x.device, dtype=torch.float32), dr.logit_p, _scalar_of(dr, 'temp')))
             else:
                 m = dr.forward_mask(B, lin.out_features, resample=resample, seed=seed)
                 keep.append(dr.keep_prob())
                 bits.append(E.pack_mask(m.to(device=x.device, dtype=torch.float32)))
+                conc.append(None)
+        conc = conc if any(c is not None for c in conc) else None
         if mixture:
             # the network on the device (raw head rows), the few head formulas of the mixture with torch ops on
             # those rows (stand-alone evaluation is not the hot path; rollouts and training are fused kernels)
-            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act, params=params)['mean']
+            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act, params=params, concrete=conc)['mean']
             return density.from_head(o, out_shift, out_scale, return_samples=return_samples,
                                      resample_noise=resample_noise, draws=gmm_draws)
         if plain:
             return E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, out_scale,
-                                 out_shift, want=('mean',), act=act, params=params)['mean']
+                                 out_shift, want=('mean',), act=act, params=params, concrete=conc)['mean']
         z = None
         if return_samples:
             z = density.frozen_noise(B, resample_noise, seed).to(device=x.device, dtype=torch.float32)
@@ -500,7 +522,7 @@ class BSequential(nn.Sequential):
                             squash[0] if (squash and return_samples) else None,
                             squash[1] if (squash and return_samples) else None,
                             max_log_std=float(density.max_log_std),
-                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act, params=params)
+                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act, params=params, concrete=conc)
         if return_samples:
             return out['sample']
         return out['mean'], out['log_std']

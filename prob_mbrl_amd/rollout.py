@@ -428,8 +428,9 @@ def _rollout_stepwise(states, dynamics, policy, steps, resample_model, resample_
                       resample_action_noise, mm_states, mm_rewards, infer_ns, z_mm, z_rr, mm_groups,
                       breaking_condition, on_step, on_pol_eval):
     """The reference's loop (utils/rollout.py:93-163) over the modules' own stand-alone forwards, differentiable in the
-    parameters (models.param_grad: pmbrl_mlp_forward / pmbrl_mlp_backward per network and step), with
-    `states, actions = on_pol_eval(i, states, actions)` between the two halves of a step.  The acting path, not a
+    parameters (models.param_grad: pmbrl_mlp_forward / pmbrl_mlp_backward per network and step) and in the logit_p of a
+    train-mode concrete-dropout policy (pmbrl_mlp_backward_concrete), with
+    `states, actions = on_pol_eval(i, states, actions)`, where given, between the two halves of a step.  The acting path, not a
     throughput path: some tens of launches per step where the fused rollout has one per horizon."""
     if not isinstance(policy, M.Policy) or not isinstance(dynamics, M.DynamicsModel):
         raise TypeError('rollout() needs prob_mbrl_amd.models.Policy / DynamicsModel')
@@ -454,7 +455,8 @@ def _rollout_stepwise(states, dynamics, policy, steps, resample_model, resample_
                 z2 = get_z_rnd(z_rr, i, (B, 1), dev) if mm_rewards else None
                 actions = policy(states, resample=resample_policy, return_samples=True,
                                  resample_noise=resample_action_noise)
-                states, actions = on_pol_eval(i, states, actions)
+                if callable(on_pol_eval):
+                    states, actions = on_pol_eval(i, states, actions)
                 kw = {}
                 if draws is not None:
                     zt = draws[0][i]
@@ -490,6 +492,12 @@ def _rollout_stepwise(states, dynamics, policy, steps, resample_model, resample_
     return trajectory
 
 
+def concrete_train_policy(policy):
+    """True for a Policy with a CDropout layer in train() mode: its rollouts are differentiable in logit_p and run on
+    the stepwise path."""
+    return isinstance(policy, M.Policy) and any(isinstance(m, M.CDropout) and m.training for m in policy.modules())
+
+
 def rollout(states, dynamics, policy, steps, resample_model=False, resample_policy=False,
             resample_state_noise=True, resample_action_noise=True, mm_states=False,
             mm_rewards=False, infer_noise_variables=False, z_mm=None, z_rr=None, mm_groups=None,
@@ -499,15 +507,27 @@ def rollout(states, dynamics, policy, steps, resample_model=False, resample_poli
     rewards (steps x [B,1])], connected to policy.parameters() (and to `states`) for autograd.
     Same arguments as the reference (utils/rollout.py:62-79).  on_pol_eval: `states, actions = hook(i, states,
     actions)` between the policy and the dynamics half of every step; such a rollout runs step by step
-    (_rollout_stepwise) instead of as one fused call."""
+    (_rollout_stepwise) instead of as one fused call, and so does one whose policy is in train() mode with a CDropout
+    layer: the trajectory is then connected to those layers' logit_p as well (a dynamics model in train() mode stays
+    refused)."""
+    why = None
     if callable(on_pol_eval):
+        why = 'on_pol_eval'
+    elif concrete_train_policy(policy):
+        # the logit gradient needs the activations and their gradients at DROPPED units, which the fused sweeps do not
+        # keep (their stashes hold masked values): the reference's loop over stand-alone calls serves it
+        why = 'a concrete-dropout policy in train() mode'
+        if any(isinstance(m, M.CDropout) and m.training for m in dynamics.modules()):
+            raise NotImplementedError('training-mode (relaxed) concrete dropout of the DYNAMICS model is not on the '
+                                      'rollout path; call dynamics.eval() like mc_pilco does')
+    if why is not None:
         sharded = [k for k in ('B_global', 'mm_span', 'agree_group') if kwargs.get(k) is not None]
         if sharded:
-            raise NotImplementedError('on_pol_eval together with rows sharded over ranks (%s) is not offered: the '
-                                      'stepwise rollout is single-process' % ', '.join(sharded))
+            raise NotImplementedError('%s together with rows sharded over ranks (%s) is not offered: the '
+                                      'stepwise rollout is single-process' % (why, ', '.join(sharded)))
         if kwargs.get('action_grad_norms_out') is not None:
-            raise NotImplementedError('on_pol_eval together with prioritized replay (the per-step action gradient '
-                                      'norms are an output of the fused adjoint sweep) is not offered')
+            raise NotImplementedError('%s together with prioritized replay (the per-step action gradient '
+                                      'norms are an output of the fused adjoint sweep) is not offered' % why)
         return _rollout_stepwise(states, dynamics, policy, int(steps), resample_model, resample_policy,
                                  resample_state_noise, resample_action_noise, mm_states, mm_rewards,
                                  bool(infer_noise_variables), z_mm, z_rr, mm_groups, breaking_condition, on_step,

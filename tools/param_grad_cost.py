@@ -2,7 +2,8 @@
 """What the parameter gradient of a stand-alone network call and a hooked rollout cost on the device.
 
   mlp      pmbrl_mlp_backward (input + parameter gradient) against pmbrl_mlp_grad_input (input gradient only) at
-           2 500 rows of a [4, 200, 200, 2] network, all three upstream gradients
+           2 500 rows of a [4, 200, 200, 2] network, all three upstream gradients; and pmbrl_mlp_backward_concrete
+           (both hidden layers train-mode concrete dropout: the logit gradient on top) on the same call
   rollout  rollout(..., on_pol_eval=identity) + loss.backward() at the C2 shape (2 500 rows, H = 40, 2 x 200 networks,
            cart-pole widths, no moment matching): the stepwise path, beside the fused rollout + backward of the same
            modules through the same autograd surface
@@ -10,7 +11,7 @@
 Blocks timed from a device synchronise to a device synchronise; prints median, min and max milliseconds per call as one
 JSON line.
 
-    python tools/param_grad_cost.py [--blocks 20] [--iters 10] [--warmup 3]
+    python tools/param_grad_cost.py [--blocks 20] [--iters 10] [--warmup 3] [--only mlp]
 """
 import argparse
 import json
@@ -51,7 +52,12 @@ def mlp_case(dev, B=2500, dims=(4, 200, 200, 2)):
                       torch.randn(B, n_out, generator=g).to(dev), None, None, None, None, torch.ones(n_out), torch.zeros(n_out),
                       E.LOG_MAX_STD)
     ups = [torch.randn(B, n_out, generator=g).to(dev) for _ in range(3)]
-    return (lambda: call.backward(*ups)), (lambda: call.grad_input(*ups))
+    # the same network with concrete layers (keep = 1; the hard samples are the masks above)
+    conc_call = E._MlpCall(call.x, call.pf, list(dims), [1.0] * (nl - 1), bits, call.z, None, None, None, None,
+                           torch.ones(n_out), torch.zeros(n_out), E.LOG_MAX_STD)
+    conc = [(torch.rand(B, dims[i + 1], generator=g).to(dev), torch.full((dims[i + 1],), 2.2, device=dev), 0.1)
+            for i in range(nl - 1)]
+    return (lambda: call.backward(*ups)), (lambda: call.grad_input(*ups)), (lambda: conc_call.backward(*ups, concrete=conc))
 
 
 def rollout_case(dev, B=2500, H=40, D=4, U=1, hidden=(200, 200)):
@@ -80,15 +86,19 @@ def main():
     ap.add_argument('--blocks', type=int, default=20)
     ap.add_argument('--iters', type=int, default=10)
     ap.add_argument('--warmup', type=int, default=3)
+    ap.add_argument('--only', default=None, choices=['mlp'], help='mlp: the stand-alone calls only')
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit('needs a HIP device')
     dev = torch.device('cuda:0')
-    bwd, gin = mlp_case(dev)
-    hooked, fused = rollout_case(dev)
+    bwd, gin, bwd_conc = mlp_case(dev)
     out = dict(blocks=a.blocks,
                mlp_backward=timed(bwd, a.blocks, a.iters, a.warmup), mlp_grad_input=timed(gin, a.blocks, a.iters, a.warmup),
-               rollout_hooked=timed(hooked, a.blocks, 1, 1), rollout_fused_autograd=timed(fused, a.blocks, a.iters, a.warmup))
+               mlp_backward_concrete=timed(bwd_conc, a.blocks, a.iters, a.warmup))
+    if a.only != 'mlp':
+        hooked, fused = rollout_case(dev)
+        out.update(rollout_hooked=timed(hooked, a.blocks, 1, 1),
+                   rollout_fused_autograd=timed(fused, a.blocks, a.iters, a.warmup))
     print(json.dumps(out))
 
 
