@@ -74,6 +74,9 @@ def parse(argv=None):
                     help='dropout of the policy: fixed-rate Bernoulli (BDropout at --pol_drop_rate) or concrete (CDropout, '
                          'rates learned by the policy search from --pol_drop_rate; such a search runs at the stepwise '
                          "rollout's cost and does not combine with --prioritized_replay)")
+    ap.add_argument('--pol_layer_norm', action='store_true',
+                    help='a LayerNorm between every hidden Linear of the policy and its activation (mlp(layer_norm=True)); '
+                         "such a search runs at the stepwise rollout's cost and does not combine with --prioritized_replay")
     ap.add_argument('--pol_opt_iters', type=int, default=1000)
     ap.add_argument('--pol_batch_size', type=int, default=100)
     ap.add_argument('--ps_iters', type=int, default=100)
@@ -150,7 +153,7 @@ def main(argv=None):
                    dropout_layers=[None if args.pol_drop_rate <= 0 else
                                    (models.BDropout(args.pol_drop_rate) if args.pol_dropout == 'bernoulli' else
                                     models.CDropout(args.pol_drop_rate * np.ones(h))) for h in args.pol_shape], nonlin=nonlin,
-                   output_nonlin=partial(models.DiagGaussianDensity, U)), maxU, minU).float()
+                   output_nonlin=partial(models.DiagGaussianDensity, U), layer_norm=args.pol_layer_norm), maxU, minU).float()
     exp = utils.ExperienceDataset()
     if args.load_from is not None:
         utils.load_checkpoint(args.load_from, dyn, pol, exp)

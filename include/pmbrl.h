@@ -749,6 +749,68 @@ int pmbrl_mlp_backward_concrete(void* stream, const pmbrl_mlp_call* call, void* 
                                 const pmbrl_mlp_concrete* conc,
                                 float* grad_logit_d /* the concrete layers' [h_l] in layer order */);
 
+/* Layer-normalised hidden layers (models/core.py:56-58: torch.nn.LayerNorm(h_l) between fc_l and nonlin_l).  A hidden
+ * layer l with gamma_d[l] != NULL computes, over its h_l true units (padding never enters the statistics),
+ *   v = h_{l-1} W_l^T + b_l ;  mu_r = mean_j v[r][j] ;  var_r = mean_j (v[r][j] - mu_r)^2     (biased, two passes)
+ *   zhat = (v - mu_r) / sqrt(var_r + eps_l) ;  y = gamma_l zhat + beta_l ;  h_l = act(y) * mask / keep
+ * (a row of constant v gives 1 / sqrt(eps_l): finite), and the backward
+ *   g_y = g_h act'(y) mask / keep ;  d beta = sum_r g_y ;  d gamma = sum_r g_y zhat ;  g_zhat = g_y gamma
+ *   g_v = (g_zhat - mean_j g_zhat - zhat mean_j (g_zhat zhat)) / sqrt(var_r + eps_l)
+ * A train-mode concrete layer's probabilities multiply a = act(y).  params_flat keeps its W, b layout; gamma and beta are
+ * separate [h_l] vectors and their gradient comes back in grad_ln_d: per layer-norm layer [d gamma | d beta], in layer
+ * order, OVERWRITTEN, formed like the bias gradient (per-workgroup slabs summed in slab order; no atomics: the same bits
+ * call after call).  ln == NULL: no layer is normalised, and each call is the call it extends, bit for bit
+ * (pmbrl_mlp_forward, pmbrl_mlp_grad_input, pmbrl_mlp_backward, or pmbrl_mlp_backward_concrete where conc != NULL).
+ * Refused: a struct with no gamma_d at all (-2), gamma_d at an index that is no hidden layer (-2), beta_d missing (-1),
+ * eps <= 0 (-2).
+ * LDS: the forward needs no more than pmbrl_mlp_forward; the input gradient and the backward keep zhat, one more 16-row
+ * buffer per layer-norm layer (1 / sqrt(var + eps) sits in its rows' spare columns).  Beyond 160 KB the workspace query
+ * gives 0 and the call -3, both with "LDS" in the message.  With two hidden layers of 200 units (buffers of 16 x 216
+ * floats, + 24 KB), the backward holds 5 buffers, + 2 with Tanh / SiLU / ..., + 1 per concrete layer, + 1 per layer-norm
+ * layer:
+ *   ReLU, 2 LN               7  121 344 B  fits        Tanh, 2 LN               9  148 992 B  fits
+ *   ReLU, 2 LN + 1 concrete  8  135 168 B  fits        Tanh, 2 LN + 1 concrete 10  162 816 B  fits
+ *   ReLU, 2 LN + 2 concrete  9  148 992 B  fits        Tanh, 2 LN + 2 concrete 11  176 640 B  refused
+ *   Tanh, 1 LN + 2 concrete 10  162 816 B  fits        (160 KB = 163 840 B)
+ * conc (pmbrl_mlp_backward_ln only) may be NULL; given, it is pmbrl_mlp_backward_concrete's and grad_logit_d is
+ * required.  grad_ln_d may be NULL (not wanted). */
+typedef struct {
+  const float* gamma_d[PMBRL_MAX_LAYERS];  /* [h_l], NULL: hidden layer l has no layer norm */
+  const float* beta_d[PMBRL_MAX_LAYERS];   /* [h_l] */
+  float eps[PMBRL_MAX_LAYERS];             /* > 0 (torch's default: 1e-5) */
+} pmbrl_mlp_layer_norm;
+size_t pmbrl_mlp_ln_workspace_bytes(const pmbrl_mlp_call* call, const pmbrl_mlp_layer_norm* ln);
+int pmbrl_mlp_forward_ln(void* stream, const pmbrl_mlp_call* call, void* workspace_d,
+                         const float* x_d, const float* params_flat_d,
+                         const uint16_t* const* mask_bits_d, const float* z_d,
+                         const float* in_shift_d, const float* in_iscale_d,
+                         const float* out_scale_d, const float* out_shift_d,
+                         const float* sq_scale_d, const float* sq_bias_d,
+                         float* sample_d, float* mean_d, float* log_std_d, const pmbrl_mlp_layer_norm* ln);
+int pmbrl_mlp_grad_input_ln(void* stream, const pmbrl_mlp_call* call, void* workspace_d,
+                            const float* x_d, const float* params_flat_d,
+                            const uint16_t* const* mask_bits_d, const float* z_d,
+                            const float* in_shift_d, const float* in_iscale_d,
+                            const float* out_scale_d, const float* out_shift_d,
+                            const float* sq_scale_d, const float* sq_bias_d,
+                            const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                            float* grad_x_d, const pmbrl_mlp_layer_norm* ln);
+size_t pmbrl_mlp_backward_ln_workspace_bytes(const pmbrl_mlp_call* call, const pmbrl_mlp_concrete* conc,
+                                             const pmbrl_mlp_layer_norm* ln);
+int pmbrl_mlp_backward_ln(void* stream, const pmbrl_mlp_call* call, void* workspace_d,
+                          const float* x_d, const float* params_flat_d,
+                          const uint16_t* const* mask_bits_d, const float* z_d,
+                          const float* in_shift_d, const float* in_iscale_d,
+                          const float* out_scale_d, const float* out_shift_d,
+                          const float* sq_scale_d, const float* sq_bias_d,
+                          const float* g_sample_d, const float* g_mean_d, const float* g_log_std_d,
+                          float* grad_x_d /* [B][n_in] or NULL */,
+                          float* grad_params_d /* flat, the layout of params_flat, or NULL */,
+                          const pmbrl_mlp_concrete* conc /* or NULL */,
+                          float* grad_logit_d /* the concrete layers' [h_l] in layer order (conc given) */,
+                          const pmbrl_mlp_layer_norm* ln /* or NULL */,
+                          float* grad_ln_d /* per layer-norm layer [d gamma | d beta] in layer order, or NULL */);
+
 /* ---- BNN maximum-likelihood training of the dynamics model ---------------- */
 /* Loss and gradient of one minibatch: the iteration body of the reference's
  * utils.train_regressor (utils/train_regressor.py:113-131) with the model in train() mode --

@@ -51,6 +51,11 @@ class MlpConcrete(C.Structure):
     _fields_ = [('u_d', C.c_void_p * MAX_LAYERS), ('logit_d', C.c_void_p * MAX_LAYERS), ('temp', C.c_float * MAX_LAYERS)]
 
 
+class MlpLayerNorm(C.Structure):
+    """pmbrl_mlp_layer_norm (include/pmbrl.h): the layer-normalised hidden layers of the pmbrl_mlp_*_ln calls."""
+    _fields_ = [('gamma_d', C.c_void_p * MAX_LAYERS), ('beta_d', C.c_void_p * MAX_LAYERS), ('eps', C.c_float * MAX_LAYERS)]
+
+
 class BnnConfig(C.Structure):
     _fields_ = [('M', C.c_int32), ('N', C.c_int32), ('net', MLP), ('max_log_std', C.c_float),
                 ('temperature', C.c_float * MAX_LAYERS), ('reg_scale', C.c_float * MAX_LAYERS),
@@ -112,6 +117,8 @@ EXPORTS = [
     'pmbrl_mlp_workspace_bytes', 'pmbrl_mlp_forward', 'pmbrl_mlp_grad_input',
     'pmbrl_mlp_backward_workspace_bytes', 'pmbrl_mlp_backward',
     'pmbrl_mlp_backward_concrete_workspace_bytes', 'pmbrl_mlp_backward_concrete',
+    'pmbrl_mlp_ln_workspace_bytes', 'pmbrl_mlp_forward_ln', 'pmbrl_mlp_grad_input_ln',
+    'pmbrl_mlp_backward_ln_workspace_bytes', 'pmbrl_mlp_backward_ln',
     'pmbrl_bnn_plan_create', 'pmbrl_bnn_plan_destroy', 'pmbrl_bnn_plan_workspace_bytes',
     'pmbrl_bnn_plan_n_params', 'pmbrl_bnn_plan_set_unit_keep', 'pmbrl_bnn_loss_grad', 'pmbrl_bnn_loss_grad_ex', 'pmbrl_bnn_train_steps',
     'pmbrl_comm_unique_id', 'pmbrl_comm_init', 'pmbrl_allreduce_sum', 'pmbrl_comm_count', 'pmbrl_comm_destroy',
@@ -225,6 +232,19 @@ def load():
     lib.pmbrl_mlp_backward_concrete.restype = C.c_int
     lib.pmbrl_mlp_backward_concrete.argtypes = ([vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 12 +
                                                 [C.POINTER(MlpConcrete), vp])
+    if hasattr(lib, 'pmbrl_mlp_backward_ln'):      # (PMBRL_LIB_PATH may name an older build: no layer-norm calls there)
+        ln = C.POINTER(MlpLayerNorm)
+        lib.pmbrl_mlp_ln_workspace_bytes.restype = C.c_size_t
+        lib.pmbrl_mlp_ln_workspace_bytes.argtypes = [C.POINTER(MlpCall), ln]
+        lib.pmbrl_mlp_forward_ln.restype = C.c_int
+        lib.pmbrl_mlp_forward_ln.argtypes = [vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 10 + [ln]
+        lib.pmbrl_mlp_grad_input_ln.restype = C.c_int
+        lib.pmbrl_mlp_grad_input_ln.argtypes = [vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 11 + [ln]
+        lib.pmbrl_mlp_backward_ln_workspace_bytes.restype = C.c_size_t
+        lib.pmbrl_mlp_backward_ln_workspace_bytes.argtypes = [C.POINTER(MlpCall), C.POINTER(MlpConcrete), ln]
+        lib.pmbrl_mlp_backward_ln.restype = C.c_int
+        lib.pmbrl_mlp_backward_ln.argtypes = ([vp, C.POINTER(MlpCall), vp, vp, vp, C.POINTER(vp)] + [vp] * 12 +
+                                              [C.POINTER(MlpConcrete), vp, ln, vp])
     lib.pmbrl_bnn_plan_create.restype = C.c_int
     lib.pmbrl_bnn_plan_create.argtypes = [C.POINTER(BnnConfig), C.c_int, C.POINTER(vp)]
     lib.pmbrl_bnn_plan_destroy.restype = None

@@ -8,7 +8,8 @@ Two execution paths, same semantics:
    parameters (any groups, weight decay, amsgrad, maximize: optim.py) and no option needs autograd (CVaR, regulariser, value_func,
    prioritized_replay).
  * autograd: `rollout()`'s single autograd node (the stepwise rollout for a train-mode concrete-dropout policy, whose
-   logit_p the optimiser then updates too) + torch's loss / clip / optimiser
+   logit_p the optimiser then updates too, and for a policy or dynamics model with layer norm) + torch's loss / clip /
+   optimiser
    for everything else the reference signature allows.  value_func is evaluated by
    pmbrl_mlp_forward and differentiated by pmbrl_mlp_grad_input; the priorities of
    prioritized_replay come from pmbrl_rollout_bwd's action_grad_norms output.
@@ -178,9 +179,10 @@ def mc_pilco(init_states, dynamics, policy, steps, opt=None, exp=None, opt_iters
         if not (isinstance(init_state_noise, float) and init_state_noise == 0.0):
             x0_ = x0_ + torch.as_tensor(init_state_noise, device=run.dev) * torch.randn_like(x0_)
         try:
-            if RO.concrete_train_policy(policy):
-                # learned policy dropout rates: the stepwise rollout, torch's clip and step over policy.parameters()
-                # (logit_p among them); the fused and pipelined paths never see such a policy
+            if RO.stepwise_networks(dynamics, policy) is not None:
+                # learned policy dropout rates, layer norm in either network: the stepwise rollout, torch's clip and step
+                # over policy.parameters() (logit_p, ln*.weight and ln*.bias among them); the fused and pipelined paths
+                # never see such networks
                 path = 'autograd'
             else:
                 bundle = _make_bundle(run, x0_, run.precision)

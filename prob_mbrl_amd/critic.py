@@ -30,6 +30,7 @@ def update_value_function(V, opt, H, i, states, actions, rewards, discount, V_ta
     straight-through samples; BDropout layers: the masks), in the order the reference makes them (V0's layers, then
     V_tgt's), instead of fresh ones."""
     V_tgt = V if V_target is None else V_target
+    V.model.refuse_layer_norm('the fused critic fit (critic.update_value_function)')
     V.train()
     dev = V.mx.device
     if dev.type != 'cuda':

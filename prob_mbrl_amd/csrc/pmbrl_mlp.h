@@ -79,9 +79,161 @@ struct EpiMlpHidden {
   }
 };
 
-__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_fwd_kernel(const MlpArgs A) {
+// ---------------------------------------------------------------------------
+// layer norm (pmbrl_mlp_layer_norm; models/core.py:56-58): hidden layer l with gamma[l] != nullptr normalises the row of
+// v = h W^T + b over the layer's true width before the activation.  The GEMM's epilogue stores v (EpiMlpLnPre), and
+// behind the barrier a row pass (pm_mlp_ln_rows) does the rest in place: a wave owns rows wid, wid + PM_NW of the tile,
+// a lane the units lane, lane + 64, ..., and the row sums meet by a butterfly over the wave's lanes -- a fixed order.
+// The LN instances of the three kernels are compile-time (template <bool LN>); the <false> instances are the kernels as
+// they were.
+// ---------------------------------------------------------------------------
+struct MlpLnArgs {
+  const float* gamma[PM_MAXL];     // [dim[l + 1]] of hidden layer l, or null: no layer norm
+  const float* beta[PM_MAXL];
+  float eps[PM_MAXL];
+  int z_idx[PM_MAXL];              // which zhat buffer (the backward kernels)
+  size_t g_off[PM_MAXL];           // offset of the layer's [d gamma | d beta] in grad_ln
+  float* slab;                     // [gridDim.x][n_ln] or null (pm_mlp_bwdp_kernel)
+  size_t n_ln;
+};
+
+// v = acc + b, exact zeros in rows >= nvalid and columns >= width
+struct EpiMlpLnPre {
+  const float* bias;
+  float* lds_out;
+  int ld, nvalid, lane, width;
+  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
+    const int g = lane >> 4;
+    const int lrow = rt * 16 + (lane & 15);
+    const int f0 = ot * 16 + 4 * g;
+    const f32x4 b = ldg4(bias + f0);
+    f32x4 v;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) v[r] = (lrow < nvalid && f0 + r < width) ? acc[r] + b[r] : 0.f;
+    *reinterpret_cast<f32x4*>(lds_out + lrow * ld + f0) = v;
+  }
+};
+
+__device__ __forceinline__ float pm_wave_sum(float s) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) s += __shfl_xor(s, o);
+  return s;
+}
+
+// where 1 / sqrt(var + eps) of a row sits: the first of the 8 spare columns of its zhat row (LD = widest layer + 8)
+#define PM_LN_RSTD(ld) ((ld) - 8)
+
+// The row pass of a layer-norm layer.  V [16][ld]: v in, h = act(y) * mask / keep out.  Next to it, each where its
+// buffer is given: D = act'(y) * mask / keep, Z = zhat (and the row's rstd), Q = a probs (1 - probs) / temp of a
+// train-mode concrete layer (a = act(y) before the mask; EpiMlpConcFwd).  Rows >= nvalid and columns >= width: exact
+// zeros in all of them.
+struct MlpLnRows {
+  const float *gamma, *beta;
+  float eps;
+  const uint16_t* mask;
+  float keep;
+  int act, width, nt;
+  float *V, *D, *Z;
+  const float *u, *logit;          // (Q given)
+  float temp;
+  float* Q;
+};
+__device__ __forceinline__ void pm_mlp_ln_rows(const MlpLnRows& p, int ld, int row0, int nvalid, int wid, int lane) {
+  const int W16 = p.nt * 16;
+  for (int r = wid; r < 16; r += PM_NW) {
+    float* v = p.V + r * ld;
+    float* d = p.D ? p.D + r * ld : nullptr;
+    float* z = p.Z ? p.Z + r * ld : nullptr;
+    float* q = p.Q ? p.Q + r * ld : nullptr;
+    float mu = 0.f, rstd = 0.f;
+    if (r < nvalid) {
+      float s = 0.f;
+      for (int j = lane; j < p.width; j += 64) s += v[j];
+      mu = pm_wave_sum(s) / (float)p.width;
+      float ss = 0.f;
+      for (int j = lane; j < p.width; j += 64) {
+        const float c = v[j] - mu;
+        ss += c * c;
+      }
+      rstd = 1.f / sqrtf(pm_wave_sum(ss) / (float)p.width + p.eps);
+    }
+    for (int j = lane; j < W16; j += 64) {
+      float hv = 0.f, dv = 0.f, zv = 0.f, qv = 0.f;
+      if (r < nvalid && j < p.width) {
+        zv = (v[j] - mu) * rstd;
+        float a, da;
+        pm_act(p.act, p.gamma[j] * zv + p.beta[j], j, p.width, a, da);
+        bool m = true;
+        if (p.mask) m = ((unsigned)p.mask[(size_t)(row0 + r) * p.nt + (j >> 4)] >> (j & 15)) & 1u;
+        if (m) {
+          hv = p.keep == 1.f ? a : a / p.keep;
+          dv = p.keep == 1.f ? da : da / p.keep;
+        }
+        if (q) {
+          const float uu = p.u[(size_t)(row0 + r) * p.width + j];
+          const float c = p.logit[j] + logf((uu + 1e-7f) / (1.f - (uu - 1e-7f)));
+          const float e = expf(-fabsf(c / p.temp));
+          qv = a * (e / ((1.f + e) * (1.f + e))) / p.temp;
+        }
+      }
+      v[j] = hv;
+      if (d) d[j] = dv;
+      if (z) z[j] = zv;
+      if (q) q[j] = qv;
+    }
+    if (z && lane == 0) z[PM_LN_RSTD(ld)] = rstd;
+  }
+}
+
+// The backward's row pass: G [16][ld] holds g_y (what the dX epilogue left), and becomes
+//   g_v = rstd (g_zhat - mean_j g_zhat - zhat mean_j (g_zhat zhat)),   g_zhat = g_y gamma
+// in place.  Rows >= nvalid hold zeros in G and Z (rstd 0) and stay zeros; columns >= width are not touched.
+__device__ __forceinline__ void pm_mlp_ln_bwd_rows(float* G, const float* Z, const float* gamma, int width, int ld,
+                                                   int wid, int lane) {
+  for (int r = wid; r < 16; r += PM_NW) {
+    float* g = G + r * ld;
+    const float* z = Z + r * ld;
+    const float rstd = z[PM_LN_RSTD(ld)];
+    float s1 = 0.f, s2 = 0.f;
+    for (int j = lane; j < width; j += 64) {
+      const float gz = g[j] * gamma[j];
+      s1 += gz;
+      s2 += gz * z[j];
+    }
+    s1 = pm_wave_sum(s1) / (float)width;
+    s2 = pm_wave_sum(s2) / (float)width;
+    for (int j = lane; j < width; j += 64) g[j] = rstd * (g[j] * gamma[j] - s1 - z[j] * s2);
+  }
+}
+
+// slab[d gamma | d beta] (+)= column sums over the tile's valid rows of g_y zhat | g_y, as pm_mlp_accum_dw sums db
+__device__ __forceinline__ void pm_mlp_ln_accum(const float* G, const float* Z, int ld, int width, float* dgb, bool first,
+                                                int nvalid, int tid) {
+  for (int o = tid; o < width; o += PM_NT) {
+    float sg = first ? 0.f : dgb[o], sb = first ? 0.f : dgb[width + o];
+    for (int r = 0; r < nvalid; ++r) {
+      const float gy = G[r * ld + o];
+      sg += gy * Z[r * ld + o];
+      sb += gy;
+    }
+    dgb[o] = sg;
+    dgb[width + o] = sb;
+  }
+}
+
+struct MlpLnFwdArgs : MlpArgs {
+  MlpLnArgs ln;
+};
+template <bool LN> struct MlpFwdSel { typedef MlpArgs type; };
+template <> struct MlpFwdSel<true> { typedef MlpLnFwdArgs type; };
+
+// LN: some hidden layers are layer-normalised (MlpLnFwdArgs); <false> is pmbrl_mlp_forward's kernel as it always was
+template <bool LN>
+__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_fwd_kernel(const typename MlpFwdSel<LN>::type A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 16;
+  const MlpLnArgs* Ln = nullptr;
+  if constexpr (LN) Ln = &A.ln;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int row0 = blockIdx.x * R;
@@ -102,6 +254,19 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_fwd_kernel(const MlpArgs A) {
   }
   __syncthreads();
   for (int l = 0; l < A.nl - 1; ++l) {
+    if constexpr (LN) {
+      if (Ln->gamma[l]) {
+        EpiMlpLnPre e{A.bias[l], Y, LD, nvalid, lane, A.dim[l + 1]};
+        gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], X, LD, wid, lane, e);
+        __syncthreads();
+        const MlpLnRows p{Ln->gamma[l], Ln->beta[l], Ln->eps[l], A.mask[l], A.keep[l], pm_act_code(A.act, l), A.dim[l + 1],
+                          A.nt[l + 1], Y, nullptr, nullptr, nullptr, nullptr, 1.f, nullptr};
+        pm_mlp_ln_rows(p, LD, row0, nvalid, wid, lane);
+        __syncthreads();
+        float* t = X; X = Y; Y = t;
+        continue;
+      }
+    }
     if (A.act != PMBRL_ACT_RELU) {
       EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], Y, nullptr, LD, row0, nvalid, A.nt[l + 1], lane, pm_act_code(A.act, l), A.dim[l + 1]};
       gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], X, LD, wid, lane, e);
@@ -229,14 +394,31 @@ __device__ __forceinline__ void pm_mlp_head_grad(const MlpBwdArgs& B, const floa
   }
 }
 
-__host__ __device__ inline size_t pm_mlp_bwd_lds_floats(int nl, int LD, int act = 0) {
-  // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: the first hidden layer's derivatives
-  return ((size_t)nl + 2 + (act ? 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
+__host__ __device__ inline size_t pm_mlp_bwd_lds_floats(int nl, int LD, int act = 0, int n_ln = 0) {
+  // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: the first hidden layer's derivatives; one zhat
+  // buffer per layer-norm layer (pmbrl_mlp_grad_input_ln)
+  return ((size_t)nl + 2 + (act ? 1 : 0) + n_ln) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
 }
 
-__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs B) {
+struct MlpLnBwdArgs {
+  MlpBwdArgs b;
+  MlpLnArgs ln;
+};
+template <bool LN> struct MlpBwdSel { typedef MlpBwdArgs type; };
+template <> struct MlpBwdSel<true> { typedef MlpLnBwdArgs type; };
+__device__ __forceinline__ const MlpBwdArgs& pm_bwd_of(const MlpBwdArgs& a) { return a; }
+__device__ __forceinline__ const MlpBwdArgs& pm_bwd_of(const MlpLnBwdArgs& a) { return a.b; }
+__device__ __forceinline__ const MlpLnArgs* pm_ln_of(const MlpBwdArgs&) { return nullptr; }
+__device__ __forceinline__ const MlpLnArgs* pm_ln_of(const MlpLnBwdArgs& a) { return &a.ln; }
+
+// LN: as pm_mlp_fwd_kernel's; the recomputed forward also leaves zhat and rstd of every layer-norm layer in a buffer of
+// its own, and the dX chain turns g_y into g_v behind each dX GEMM (pm_mlp_ln_bwd_rows)
+template <bool LN>
+__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const typename MlpBwdSel<LN>::type BB) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 16;
+  const MlpBwdArgs& B = pm_bwd_of(BB);
+  const MlpLnArgs* Ln = pm_ln_of(BB);
   const MlpArgs& A = B.f;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -252,9 +434,24 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
   // derivatives of hidden layer l (the output of Linear l): D0 for l = 0, else the dead input buffer of Linear l - 1
   auto dbuf = [&](int l) { return l == 0 ? D0 : H + (size_t)(l - 1) * R * LD; };
   const int K0 = A.dim[0];
+  float* Z = D0 + (smooth ? (size_t)R * LD : 0);      // (LN only) [layer-norm layers][16][LD]
   pm_mlp_load_rows(A, H, row0, nvalid, tid);
   __syncthreads();
   for (int l = 0; l < nl - 1; ++l) {
+    if constexpr (LN) {
+      if (Ln->gamma[l]) {
+        float* Hn = H + (size_t)(l + 1) * R * LD;
+        EpiMlpLnPre e{A.bias[l], Hn, LD, nvalid, lane, A.dim[l + 1]};
+        gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+        __syncthreads();
+        const MlpLnRows p{Ln->gamma[l], Ln->beta[l], Ln->eps[l], A.mask[l], A.keep[l], pm_act_code(A.act, l), A.dim[l + 1],
+                          A.nt[l + 1], Hn, smooth ? dbuf(l) : nullptr, Z + (size_t)Ln->z_idx[l] * R * LD, nullptr, nullptr,
+                          1.f, nullptr};
+        pm_mlp_ln_rows(p, LD, row0, nvalid, wid, lane);
+        __syncthreads();
+        continue;
+      }
+    }
     if (smooth) {
       EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, dbuf(l), LD, row0, nvalid, A.nt[l + 1],
                   lane, pm_act_code(A.act, l), A.dim[l + 1]};
@@ -280,6 +477,12 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdx_kernel(const MlpBwdArgs 
       gemm_tiles<1>(B.wb[l], A.nt[l], A.nt[l + 1], Gin, LD, wid, lane, e);
     }
     __syncthreads();
+    if constexpr (LN) {
+      if (Ln->gamma[l - 1]) {                          // Gout = g_y of hidden layer l - 1 -> g_v
+        pm_mlp_ln_bwd_rows(Gout, Z + (size_t)Ln->z_idx[l - 1] * R * LD, Ln->gamma[l - 1], A.dim[l], LD, wid, lane);
+        __syncthreads();
+      }
+    }
     float* t = Gin; Gin = Gout; Gout = t;
   }
   // first layer: d / d x_in, then the input normalisation
@@ -314,10 +517,13 @@ struct MlpBwdPArgs {
   size_t w_off[PM_MAXL], b_off[PM_MAXL];   // offsets of W_l [out][in] and b_l in the flat parameter order
 };
 
-__host__ __device__ inline size_t pm_mlp_bwdp_lds_floats(int nl, int LD, int act, int n_conc = 0) {
+__host__ __device__ inline size_t pm_mlp_bwdp_lds_floats(int nl, int LD, int act, int n_conc = 0, int n_ln = 0) {
   // H[0..nl-1], two gradient buffers, K-split scratch; act != ReLU: one derivative buffer per hidden layer; one Q buffer
-  // per train-mode concrete-dropout layer (pmbrl_mlp_backward_concrete)
-  return ((size_t)nl + 2 + (act ? nl - 1 : 0) + n_conc) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
+  // per train-mode concrete-dropout layer (pmbrl_mlp_backward_concrete); one zhat buffer per layer-norm layer
+  // (pmbrl_mlp_backward_ln).  Two hidden layers of 200 (LD = 216, 13 824 B a buffer, 24 KB scratch) against 160 KB:
+  // ReLU + 2 LN + 2 concrete is 9 buffers = 148 992 B and fits, Tanh / SiLU + 2 LN + 2 concrete is 11 = 176 640 B and does
+  // not; Tanh + 2 LN + 1 concrete (10 = 162 816 B) still fits (the table in include/pmbrl.h).
+  return ((size_t)nl + 2 + (act ? nl - 1 : 0) + n_conc + n_ln) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256;
 }
 
 // ---------------------------------------------------------------------------
@@ -444,21 +650,34 @@ struct MlpBwdCArgs {
   MlpBwdPArgs p;
   MlpConcArgs c;
 };
-template <bool CONC> struct MlpBwdPSel { typedef MlpBwdPArgs type; };
-template <> struct MlpBwdPSel<true> { typedef MlpBwdCArgs type; };
+struct MlpBwdLArgs {               // a layer-norm call: c is all zeros where no layer is concrete
+  MlpBwdPArgs p;
+  MlpConcArgs c;
+  MlpLnArgs ln;
+};
+template <bool CONC, bool LN> struct MlpBwdPSel { typedef MlpBwdPArgs type; };
+template <> struct MlpBwdPSel<true, false> { typedef MlpBwdCArgs type; };
+template <bool CONC> struct MlpBwdPSel<CONC, true> { typedef MlpBwdLArgs type; };
 __device__ __forceinline__ const MlpBwdPArgs& pm_bwdp_of(const MlpBwdPArgs& a) { return a; }
 __device__ __forceinline__ const MlpBwdPArgs& pm_bwdp_of(const MlpBwdCArgs& a) { return a.p; }
+__device__ __forceinline__ const MlpBwdPArgs& pm_bwdp_of(const MlpBwdLArgs& a) { return a.p; }
 __device__ __forceinline__ const MlpConcArgs* pm_conc_of(const MlpBwdPArgs&) { return nullptr; }
 __device__ __forceinline__ const MlpConcArgs* pm_conc_of(const MlpBwdCArgs& a) { return &a.c; }
+__device__ __forceinline__ const MlpConcArgs* pm_conc_of(const MlpBwdLArgs& a) { return &a.c; }
+__device__ __forceinline__ const MlpLnArgs* pm_ln_of(const MlpBwdPArgs&) { return nullptr; }
+__device__ __forceinline__ const MlpLnArgs* pm_ln_of(const MlpBwdCArgs&) { return nullptr; }
+__device__ __forceinline__ const MlpLnArgs* pm_ln_of(const MlpBwdLArgs& a) { return &a.ln; }
 
-// CONC: some hidden layers are train-mode concrete dropout (MlpBwdCArgs); <false> is pmbrl_mlp_backward's kernel as it
-// always was
-template <bool CONC>
-__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename MlpBwdPSel<CONC>::type PP) {
+// CONC: some hidden layers are train-mode concrete dropout (MlpBwdCArgs); LN: some are layer-normalised (MlpBwdLArgs;
+// z_idx counts on from the Q buffers).  <false, false> is pmbrl_mlp_backward's kernel as it always was, <true, false>
+// pmbrl_mlp_backward_concrete's.
+template <bool CONC, bool LN>
+__global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename MlpBwdPSel<CONC, LN>::type PP) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   constexpr int R = 16;
   const MlpBwdPArgs& P = pm_bwdp_of(PP);
   const MlpConcArgs* Cc = pm_conc_of(PP);
+  const MlpLnArgs* Ln = pm_ln_of(PP);
   const MlpBwdArgs& B = P.b;
   const MlpArgs& A = B.f;
   const int tid = threadIdx.x, lane = tid & 63;
@@ -477,6 +696,12 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename Ml
     Q = D + (smooth ? (size_t)(nl - 1) * R * LD : 0);
     lslab = Cc->slab + (size_t)blockIdx.x * Cc->n_logit;
   }
+  float* Z = nullptr;                                // (LN) [Q buffers, then layer-norm layers][16][LD]
+  float* nslab = nullptr;
+  if constexpr (LN) {
+    Z = D + (smooth ? (size_t)(nl - 1) * R * LD : 0);
+    if (Ln->slab) nslab = Ln->slab + (size_t)blockIdx.x * Ln->n_ln;
+  }
   const int K0 = A.dim[0];
   const int n_tiles = (A.B + R - 1) / R;
   for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
@@ -488,6 +713,28 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename Ml
     for (int l = 0; l < nl - 1; ++l) {
       bool conc = false;
       if constexpr (CONC) conc = Cc->u[l] != nullptr;
+      if constexpr (LN) {
+        if (Ln->gamma[l]) {
+          float* Hn = H + (size_t)(l + 1) * R * LD;
+          EpiMlpLnPre e{A.bias[l], Hn, LD, nvalid, lane, A.dim[l + 1]};
+          gemm_tiles<1>(A.wf[l], A.nt[l + 1], A.nt[l], H + (size_t)l * R * LD, LD, wid, lane, e);
+          __syncthreads();
+          MlpLnRows p{Ln->gamma[l], Ln->beta[l], Ln->eps[l], A.mask[l], A.keep[l], pm_act_code(A.act, l), A.dim[l + 1],
+                      A.nt[l + 1], Hn, smooth ? D + (size_t)l * R * LD : nullptr, Z + (size_t)Ln->z_idx[l] * R * LD, nullptr,
+                      nullptr, 1.f, nullptr};
+          if constexpr (CONC) {
+            if (conc) {
+              p.u = Cc->u[l];
+              p.logit = Cc->logit[l];
+              p.temp = Cc->temp[l];
+              p.Q = Q + (size_t)Cc->q_idx[l] * R * LD;
+            }
+          }
+          pm_mlp_ln_rows(p, LD, row0, nvalid, wid, lane);
+          __syncthreads();
+          continue;
+        }
+      }
       if (smooth) {
         EpiMlpAct e{A.bias[l], A.mask[l], A.keep[l], H + (size_t)(l + 1) * R * LD, D + (size_t)l * R * LD, LD, row0,
                     nvalid, A.nt[l + 1], lane, pm_act_code(A.act, l), A.dim[l + 1]};
@@ -545,6 +792,17 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename Ml
         }
       }
       __syncthreads();
+      if constexpr (LN) {
+        if (Ln->gamma[l - 1]) {                        // Gout = g_y of hidden layer l - 1: d gamma, d beta, then -> g_v
+          const float* Zl = Z + (size_t)Ln->z_idx[l - 1] * R * LD;
+          if (nslab) {
+            pm_mlp_ln_accum(Gout, Zl, LD, A.dim[l], nslab + Ln->g_off[l - 1], first, nvalid, tid);
+            __syncthreads();
+          }
+          pm_mlp_ln_bwd_rows(Gout, Zl, Ln->gamma[l - 1], A.dim[l], LD, wid, lane);
+          __syncthreads();
+        }
+      }
       float* t = Gin; Gin = Gout; Gout = t;
     }
     if (B.grad_x) {
@@ -563,12 +821,8 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_mlp_bwdp_kernel(const typename Ml
   }
 }
 
-// grad_params[i] = sum over the slabs, in slab order
-__global__ void pm_mlp_bwd_reduce_kernel(const float* __restrict__ slab, int n_slab, size_t n_params,
-                                         float* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_params) return;
-  float s = 0.f;
-  for (int b = 0; b < n_slab; ++b) s += slab[(size_t)b * n_params + i];
-  out[i] = s;
-}
+
+// the launches of the layer-norm instances (pmbrl_mlp_ln.hip, the one object that compiles them); 0 or a pmbrl error code
+int pm_mlp_ln_launch_fwd(hipStream_t s, int n_blocks, size_t lds, const MlpLnFwdArgs& a);
+int pm_mlp_ln_launch_bwdx(hipStream_t s, int n_blocks, size_t lds, const MlpLnBwdArgs& a);
+int pm_mlp_ln_launch_bwdp(hipStream_t s, int n_blocks, size_t lds, const MlpBwdLArgs& a, bool conc);

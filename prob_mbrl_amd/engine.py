@@ -90,7 +90,7 @@ class _MlpCall:
     """Marshalled arguments of one stand-alone network evaluation (kept alive for the backward)."""
 
     def __init__(self, x, params_flat, dims, keep, mask_bits, z, in_shift, in_iscale, out_scale,
-                 out_shift, sq_scale, sq_bias, max_log_std, act=0):
+                 out_shift, sq_scale, sq_bias, max_log_std, act=0, layer_norm=None):
         self.lib = _lib.load()
         assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.is_contiguous()
         B = x.shape[0]
@@ -139,10 +139,27 @@ class _MlpCall:
             z = z.contiguous()
         self.z = z
         self.pf = params_flat.detach().contiguous()
+        # layer_norm: per hidden layer None or (gamma [h_l], beta [h_l], eps); with one the calls are the *_ln entry points
+        # ln_entry: take the *_ln entry points even without such a layer (ln = NULL: they are then the calls they extend)
+        self.ln, self.ln_widths, self.ln_entry = None, [], False
+        if layer_norm is not None and any(t is not None for t in layer_norm):
+            assert len(layer_norm) == nl - 1
+            self.ln = _lib.MlpLayerNorm()
+            for l, t in enumerate(layer_norm):
+                if t is None:
+                    continue
+                g, b = (_f32c(v.detach().reshape(-1), x.device) for v in t[:2])
+                assert g.numel() == dims[l + 1] and b.numel() == dims[l + 1]
+                self.keepalive += [g, b]
+                self.ln.gamma_d[l], self.ln.beta_d[l], self.ln.eps[l] = g.data_ptr(), b.data_ptr(), float(t[2])
+                self.ln_widths.append(dims[l + 1])
 
     @staticmethod
     def _p(t):
         return C.c_void_p(t.data_ptr()) if t is not None else None
+
+    def _ln_ref(self):
+        return C.byref(self.ln) if self.ln is not None else None
 
     def _common(self):
         p = self._p
@@ -152,6 +169,11 @@ class _MlpCall:
     def forward(self, want):
         out = {k: torch.empty((self.B, self.n_out), dtype=torch.float32, device=self.x.device) for k in want}
         p = self._p
+        if self.ln is not None or self.ln_entry:
+            _lib.check(self.lib.pmbrl_mlp_forward_ln(_stream(), C.byref(self.call), p(self.ws), *self._common(),
+                                                     p(out.get('sample')), p(out.get('mean')), p(out.get('log_std')),
+                                                     self._ln_ref()), 'pmbrl_mlp_forward_ln')
+            return out
         _lib.check(self.lib.pmbrl_mlp_forward(_stream(), C.byref(self.call), p(self.ws), *self._common(),
                                               p(out.get('sample')), p(out.get('mean')), p(out.get('log_std'))),
                    'pmbrl_mlp_forward')
@@ -161,18 +183,25 @@ class _MlpCall:
         gx = torch.empty_like(self.x)
         p = self._p
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_sample, g_mean, g_log_std)]
+        if self.ln is not None or self.ln_entry:
+            _lib.check(self.lib.pmbrl_mlp_grad_input_ln(_stream(), C.byref(self.call), p(self.ws), *self._common(),
+                                                        p(gs[0]), p(gs[1]), p(gs[2]), p(gx), self._ln_ref()),
+                       'pmbrl_mlp_grad_input_ln')
+            return gx
         _lib.check(self.lib.pmbrl_mlp_grad_input(_stream(), C.byref(self.call), p(self.ws), *self._common(),
                                                  p(gs[0]), p(gs[1]), p(gs[2]), p(gx)), 'pmbrl_mlp_grad_input')
         return gx
 
 
     def backward(self, g_sample=None, g_mean=None, g_log_std=None, want_x=True, want_params=True, out=None,
-                 concrete=None):
+                 concrete=None, want_ln=True):
         """(grad_x [B, n_in], grad_params flat in the order of params_flat) of pmbrl_mlp_backward; an output that is
         not wanted is None and is not computed.  out = (grad_x, grad_params): write into these tensors.
         concrete: per hidden layer None or (u [B, h_l], logit_p [h_l], temp) of a train-mode concrete-dropout layer
         whose hard sample the call's mask bits hold; the call is then pmbrl_mlp_backward_concrete and a third result
-        follows, the list of d / d logit_p [h_l] per such layer (None for the others)."""
+        follows, the list of d / d logit_p [h_l] per such layer (None for the others).
+        A call with layer-norm layers is pmbrl_mlp_backward_ln; its result is always (grad_x, grad_params, logit parts or
+        None, [(d gamma, d beta) per layer-norm layer] or None where want_ln is False)."""
         conc = None
         if concrete is not None and any(c is not None for c in concrete):
             conc, keep, dev = _lib.MlpConcrete(), [], self.x.device
@@ -186,6 +215,11 @@ class _MlpCall:
                 assert u.shape == (self.B, h) and lg.numel() == h
                 keep += [u, lg]
                 conc.u_d[l], conc.logit_d[l], conc.temp[l] = u.data_ptr(), lg.data_ptr(), float(c[2])
+        if self.ln is not None or self.ln_entry:
+            nbytes = self.lib.pmbrl_mlp_backward_ln_workspace_bytes(C.byref(self.call), C.byref(conc) if conc else None,
+                                                                    self._ln_ref())
+            name = 'pmbrl_mlp_backward_ln'
+        elif conc is not None:
             nbytes = self.lib.pmbrl_mlp_backward_concrete_workspace_bytes(C.byref(self.call), C.byref(conc))
             name = 'pmbrl_mlp_backward_concrete'
         else:
@@ -202,6 +236,29 @@ class _MlpCall:
             assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape == like.shape)
         p = self._p
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_sample, g_mean, g_log_std)]
+        if self.ln is not None or self.ln_entry:
+            dev = self.x.device
+            gl = parts = None
+            if conc is not None:
+                widths = [self.dims[l + 1] if c is not None else 0 for l, c in enumerate(concrete)]
+                gl = torch.empty(sum(widths), dtype=torch.float32, device=dev)
+            want_ln = want_ln and self.ln is not None
+            gn = torch.empty(2 * sum(self.ln_widths), dtype=torch.float32, device=dev) if want_ln else None
+            _lib.check(self.lib.pmbrl_mlp_backward_ln(_stream(), C.byref(self.call), p(ws), *self._common(),
+                                                      p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp),
+                                                      C.byref(conc) if conc else None, p(gl), self._ln_ref(), p(gn)), name)
+            if conc is not None:
+                parts, off = [], 0
+                for w, c in zip(widths, concrete):
+                    parts.append(gl[off:off + w] if c is not None else None)
+                    off += w
+            lns, off = None, 0
+            if want_ln:
+                lns = []
+                for w in self.ln_widths:
+                    lns.append((gn[off:off + w], gn[off + w:off + 2 * w]))
+                    off += 2 * w
+            return gx, gp, parts, lns
         if conc is None:
             _lib.check(self.lib.pmbrl_mlp_backward(_stream(), C.byref(self.call), p(ws), *self._common(),
                                                    p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp)), name)
@@ -239,17 +296,18 @@ class _MlpParamFunction(torch.autograd.Function):
     call's params_flat), first order: one pmbrl_mlp_backward per backward pass.  concrete: per hidden layer None or
     (u, temp) of a train-mode concrete-dropout layer; the logit_p tensors of those layers follow the parameters as
     further differentiable inputs (pmbrl_mlp_backward_concrete; a scalar or singleton logit_p gets the sum over the
-    units)."""
+    units).  n_ln: the call has that many layer-norm layers, and their (weight, bias) pairs follow the logits
+    (pmbrl_mlp_backward_ln)."""
 
     @staticmethod
-    def forward(ctx, call, want, concrete, x, *params):
-        ctx.call, ctx.want = call, want
+    def forward(ctx, call, want, concrete, n_ln, x, *params):
+        ctx.call, ctx.want, ctx.n_ln = call, want, n_ln
         n_conc = sum(c is not None for c in concrete) if concrete is not None else 0
-        ctx.n_lin = len(params) - n_conc
+        ctx.n_lin = len(params) - n_conc - 2 * n_ln
         ctx.shapes = [p.shape for p in params]
         ctx.concrete = None
         if n_conc:
-            logits = iter(params[ctx.n_lin:])
+            logits = iter(params[ctx.n_lin:ctx.n_lin + n_conc])
             ctx.concrete = [None if c is None else (c[0], next(logits).detach(), c[1]) for c in concrete]
         ctx.set_materialize_grads(False)
         out = call.forward(want)
@@ -259,29 +317,35 @@ class _MlpParamFunction(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, *grads):
         g = dict(zip(ctx.want, grads))
-        need_x, need_p = ctx.needs_input_grad[3], ctx.needs_input_grad[4:]
-        need_lin, need_lg = need_p[:ctx.n_lin], need_p[ctx.n_lin:]
+        need_x, need_p = ctx.needs_input_grad[4], ctx.needs_input_grad[5:]
+        n_p = len(need_p) - 2 * ctx.n_ln
+        need_lin, need_lg, need_ln = need_p[:ctx.n_lin], need_p[ctx.n_lin:n_p], need_p[n_p:]
         res = ctx.call.backward(g.get('sample'), g.get('mean'), g.get('log_std'), want_x=need_x,
-                                want_params=any(need_lin), concrete=ctx.concrete if any(need_lg) else None)
+                                want_params=any(need_lin), concrete=ctx.concrete if any(need_lg) else None,
+                                want_ln=any(need_ln))
         gx, gp = res[0], res[1]
         out, off = [], 0
+        shapes_lg, shapes_ln = ctx.shapes[ctx.n_lin:n_p], ctx.shapes[n_p:]
         for shape, need in zip(ctx.shapes[:ctx.n_lin], need_lin):
             n = shape.numel()
             out.append(gp[off:off + n].view(shape) if need else None)
             off += n
         if ctx.concrete is not None:
             gls = [t for t in res[2] if t is not None] if any(need_lg) else [None] * len(need_lg)
-            for shape, need, gl in zip(ctx.shapes[ctx.n_lin:], need_lg, gls):
+            for shape, need, gl in zip(shapes_lg, need_lg, gls):
                 if not need:
                     out.append(None)
                 else:
                     out.append(gl.view(shape) if shape.numel() == gl.numel() else gl.sum().expand(shape).clone())
-        return (None, None, None, gx) + tuple(out)
+        if ctx.n_ln:
+            flat = [t for pair in res[3] for t in pair] if any(need_ln) else [None] * len(need_ln)
+            out += [t.view(shape) if need else None for shape, need, t in zip(shapes_ln, need_ln, flat)]
+        return (None, None, None, None, gx) + tuple(out)
 
 
 def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=None, in_iscale=None,
                 out_scale=None, out_shift=None, sq_scale=None, sq_bias=None, max_log_std=math.log(5.0),
-                want=('sample',), act=0, params=None, concrete=None):
+                want=('sample',), act=0, params=None, concrete=None, layer_norm=None):
     """Stand-alone evaluation of one Bayesian MLP with a diagonal-Gaussian head on the rows of x
     (pmbrl_mlp_forward; models/core.py:169-187, 221-248).  dims = [n_in, h..., 2*n_out];
     mask_bits: per hidden layer an int16 bit-row tensor (pack_mask) or None.
@@ -292,17 +356,21 @@ def mlp_forward(x, params_flat, dims, keep, mask_bits=None, z=None, in_shift=Non
     outputs are connected to them (and to x where it requires grad) through pmbrl_mlp_backward.
     concrete (with params): per hidden layer None or (u [B, h_l], logit_p, temp) of a concrete-dropout layer in train
     mode, mask_bits[l] being the hard sample drawn from u: the outputs are connected to those logit_p tensors too
-    (pmbrl_mlp_backward_concrete)."""
+    (pmbrl_mlp_backward_concrete).
+    layer_norm: per hidden layer None or (weight [h_l], bias [h_l], eps) of a torch.nn.LayerNorm between that layer's
+    Linear and its activation (pmbrl_mlp_forward_ln, pmbrl_mlp_grad_input_ln); with params, the outputs are connected to
+    those weights and biases too (pmbrl_mlp_backward_ln)."""
     want = tuple(want)
     xc = x.contiguous()
     call = _MlpCall(xc.detach(), params_flat, dims, keep, mask_bits, z, in_shift, in_iscale, out_scale,
-                    out_shift, sq_scale, sq_bias, max_log_std, act=act)
+                    out_shift, sq_scale, sq_bias, max_log_std, act=act, layer_norm=layer_norm)
+    lns = [t for pair in (layer_norm or []) if pair is not None for t in pair[:2]] if params is not None else []
     logits = [c[1] for c in concrete if c is not None] if (concrete is not None and params is not None) else []
-    if params is not None and torch.is_grad_enabled() and any(p.requires_grad for p in list(params) + logits):
+    if params is not None and torch.is_grad_enabled() and any(p.requires_grad for p in list(params) + logits + lns):
         assert [tuple(p.shape) for p in params] == [s for i in range(len(dims) - 1)
                                                     for s in ((dims[i + 1], dims[i]), (dims[i + 1],))]
         noise = [None if c is None else (c[0], c[2]) for c in concrete] if logits else None
-        outs = _MlpParamFunction.apply(call, want, noise, xc, *params, *logits)
+        outs = _MlpParamFunction.apply(call, want, noise, len(lns) // 2, xc, *params, *logits, *lns)
         return dict(zip(want, outs))
     if x.requires_grad and torch.is_grad_enabled():
         outs = _MlpFunction.apply(xc, call, want)

@@ -442,10 +442,12 @@ class BSequential(nn.Sequential):
         """Evaluate the network + Gaussian head on the rows of x with pmbrl_mlp_forward
         (models/modules.py:215-232 + models/densities.py:87-121).  Returns samples [B, n_out]
         (squashed if `squash=(scale, bias)`) or (mean, log_std).  Under param_grad() the outputs are connected to the
-        Linear parameters and to the logit_p of every CDropout layer in train() mode."""
+        Linear parameters, to the logit_p of every CDropout layer in train() mode and to the weight and bias of every
+        LayerNorm (pmbrl_mlp_forward_ln / pmbrl_mlp_backward_ln serve a network with one)."""
         from . import engine as E
         from .rollout import flat_parameters, _scalar_of
-        linears, drops, inner, acts = self._parse()
+        linears, drops, inner, acts, norms = self._parse_full()
+        ln = [None if n is None else (n.weight, n.bias, float(n.eps)) for n in norms] if any(norms) else None
         from . import activations as ACT
         act = ACT.pack(acts)
         density = inner if inner is not None else density
@@ -509,12 +511,12 @@ class BSequential(nn.Sequential):
         if mixture:
             # the network on the device (raw head rows), the few head formulas of the mixture with torch ops on
             # those rows (stand-alone evaluation is not the hot path; rollouts and training are fused kernels)
-            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act, params=params, concrete=conc)['mean']
+            o = E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, None, None, want=('mean',), act=act, params=params, concrete=conc, layer_norm=ln)['mean']
             return density.from_head(o, out_shift, out_scale, return_samples=return_samples,
                                      resample_noise=resample_noise, draws=gmm_draws)
         if plain:
             return E.mlp_forward(x, flat, dims, keep, bits, None, in_shift, in_iscale, out_scale,
-                                 out_shift, want=('mean',), act=act, params=params, concrete=conc)['mean']
+                                 out_shift, want=('mean',), act=act, params=params, concrete=conc, layer_norm=ln)['mean']
         z = None
         if return_samples:
             z = density.frozen_noise(B, resample_noise, seed).to(device=x.device, dtype=torch.float32)
@@ -522,7 +524,7 @@ class BSequential(nn.Sequential):
                             squash[0] if (squash and return_samples) else None,
                             squash[1] if (squash and return_samples) else None,
                             max_log_std=float(density.max_log_std),
-                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act, params=params, concrete=conc)
+                            want=('sample',) if return_samples else ('mean', 'log_std'), act=act, params=params, concrete=conc, layer_norm=ln)
         if return_samples:
             return out['sample']
         return out['mean'], out['log_std']
@@ -557,18 +559,44 @@ class BSequential(nn.Sequential):
         from . import activations as ACT
         return ACT.pack(self._parse()[3])
 
+    def layer_norms(self):
+        """The torch.nn.LayerNorm between hidden layer l's Linear and its activation, or None, per hidden layer
+        (mlp(layer_norm=True): models/core.py:56-58).  Served by the stand-alone calls and the stepwise rollout; the fused
+        rollout and the fused fits refuse such a network (refuse_layer_norm)."""
+        return list(self._parse_full()[4])
+
+    def refuse_layer_norm(self, what):
+        """For the fused consumers, which read layers_spec() and would not see a LayerNorm."""
+        if any(n is not None for n in self._parse_full()[4]):
+            raise NotImplementedError('%s does not serve a network with layer norm (mlp(layer_norm=True)): the fused '
+                                      'kernels hold no row statistics.  Evaluate and fit it with the stand-alone calls under '
+                                      'models.param_grad(), which are differentiable in every parameter, ln*.weight and '
+                                      'ln*.bias included; rollout() and mc_pilco() take it on their stepwise path' % what)
+
     def _parse(self):
+        return self._parse_full()[:4]
+
+    def _parse_full(self):
         from . import activations as ACT
         linears, drops, density = [], [], None
         pending = None
-        acts = []
+        acts, norms = [], []
         for name, m in self._modules.items():
             if isinstance(m, nn.Linear):
                 if pending is not None:
                     drops.append(pending['drop'])
                     acts.append(ACT.NONE if pending['act'] is None else pending['act'])
-                pending = dict(drop=None, act=None)
+                    norms.append(pending['norm'])
+                pending = dict(drop=None, act=None, norm=None)
                 linears.append(m)
+            elif isinstance(m, nn.LayerNorm):
+                # right behind a Linear, over that layer's units, affine: what mlp(layer_norm=True) builds
+                if pending is None or pending['act'] is not None or pending['drop'] is not None or pending['norm'] is not None:
+                    raise NotImplementedError('module %s: a LayerNorm is offered right behind a hidden Linear only' % name)
+                if tuple(m.normalized_shape) != (linears[-1].out_features,) or m.weight is None or m.bias is None:
+                    raise NotImplementedError('module %s: a LayerNorm must normalise over the %d units of the Linear in '
+                                              'front of it and be affine (with a bias)' % (name, linears[-1].out_features))
+                pending['norm'] = m
             elif pending is not None and pending['act'] is None and pending['drop'] is None and \
                     ACT.code_of(m) is not None:
                 pending['act'] = ACT.code_of(m)
@@ -581,7 +609,8 @@ class BSequential(nn.Sequential):
             else:
                 raise NotImplementedError('module %s (%s) is not offered on the device path; hidden activations '
                                           'offered: %s' % (name, type(m).__name__, ACT.OFFERED))
-        if pending is not None and (pending['drop'] is not None or pending['act'] is not None):
+        if pending is not None and (pending['drop'] is not None or pending['act'] is not None or
+                                    pending['norm'] is not None):
             raise NotImplementedError('the output layer must be a plain Linear')
         if len(acts) > ACT.MAX_HIDDEN:
             raise NotImplementedError('at most %d hidden layers on the device path' % ACT.MAX_HIDDEN)
@@ -589,7 +618,11 @@ class BSequential(nn.Sequential):
             raise NotImplementedError('per-unit BDropout rates fold 1 / p_j into the layer in front, which is only valid '
                                       'for ReLU (positively homogeneous) on every hidden layer; with any other '
                                       'activation use a scalar rate (hidden activations offered: %s)' % ACT.OFFERED)
-        return linears, drops, density, acts
+        if any(n is not None for n in norms) and any(d is not None and d.unit_inv_keep() is not None for d in drops):
+            raise NotImplementedError('per-unit BDropout rates fold 1 / p_j into the Linear in front of the activation, '
+                                      'which a LayerNorm behind that Linear would normalise away; with layer_norm use a '
+                                      'scalar rate')
+        return linears, drops, density, acts, norms
 
 
 def mlp(input_dims, output_dims, hidden_dims=[200, 200], nonlin=nn.ReLU, output_nonlin=None,
@@ -598,10 +631,11 @@ def mlp(input_dims, output_dims, hidden_dims=[200, 200], nonlin=nn.ReLU, output_
         output_biases=True, dropout_layers=BDropout, input_dropout=None, spectral_norm=False,
         spectral_norm_output=False, layer_norm=False):
     """Same factory signature and module names as models/core.py:15-99
-    (fc%d / nonlin%d / drop%d / fc_out / fc_nonlin)."""
-    if spectral_norm or spectral_norm_output or layer_norm or input_dropout is not None:
-        raise NotImplementedError('spectral_norm / layer_norm / input_dropout are outside the '
-                                  'accelerated MC-PILCO path')
+    (fc%d / ln%d / nonlin%d / drop%d / fc_out / fc_nonlin).  layer_norm=True puts a torch.nn.LayerNorm(dout) between
+    every hidden Linear and its activation (core.py:56-58); its weight stays at ones, its bias is drawn by
+    biases_initializer (core.py:83-92)."""
+    if spectral_norm or spectral_norm_output or input_dropout is not None:
+        raise NotImplementedError('spectral_norm / input_dropout are outside the accelerated MC-PILCO path')
     if not (hidden_biases and output_biases):
         raise NotImplementedError('bias-free layers are not offered on the device path')
     hidden_dims = list(hidden_dims)
@@ -616,6 +650,8 @@ def mlp(input_dims, output_dims, hidden_dims=[200, 200], nonlin=nn.ReLU, output_
         if inspect.isclass(drop_i):
             drop_i = drop_i(name='drop%d' % i)
         mods['fc%d' % i] = nn.Linear(din, dout, bias=True)
+        if layer_norm:
+            mods['ln%d' % i] = nn.LayerNorm(dout)
         if callable(nonlin[i]):
             mods['nonlin%d' % i] = nonlin[i]()
         if drop_i is not None:
@@ -630,6 +666,8 @@ def mlp(input_dims, output_dims, hidden_dims=[200, 200], nonlin=nn.ReLU, output_
                 weights_initializer(m.weight)
             if callable(biases_initializer):
                 biases_initializer(m.bias)
+        elif isinstance(m, nn.LayerNorm) and callable(biases_initializer):
+            biases_initializer(m.bias)
     net.float()
     return net
 

@@ -119,6 +119,7 @@ def train_regressor(model, iters=2000, batchsize=100, resample=True, optimizer=N
     elif not _is_diag_gaussian_ll(log_likelihood):
         raise NotImplementedError('the diagonal-Gaussian and the Gaussian-mixture log-likelihoods are offered on '
                                   'the device path')
+    model.model.refuse_layer_norm('the fused BNN fit (train_regressor)')
     model.train()
     dev = model.mx.device
     if dev.type != 'cuda':

@@ -1,0 +1,268 @@
+"""Layer-normalised networks restated in plain torch, at any dtype, and the loader of tests/golden/layer_norm
+(tools/make_golden_layer_norm.py).
+
+A hidden layer l with a LayerNorm between its Linear and its activation (models/core.py:56-58, mlp(layer_norm=True)):
+
+    v    = h_{l-1} W_l^T + b_l
+    mu   = mean_j v ;  var = mean_j (v - mu)^2          biased, over the layer's units
+    y    = gamma_l (v - mu) / sqrt(var + eps_l) + beta_l
+    h_l  = act(y) * mask / keep                         mask: a constant, or a train-mode concrete mask of a = act(y)
+
+The normalisation is written out (not torch.nn.functional.layer_norm), so that the restatement is a second statement of
+the formula, held to the reference by the fixtures.  Everything behind the networks (the reward, moment matching, the
+loss) is oracle.ref_torch's; the heads follow oracle.ref_torch.policy_forward / dynamics_forward line by line."""
+import math
+import os
+
+import numpy as np
+import torch
+
+from oracle import ref_torch as R
+from tests import common
+from tests import concrete_policy_ref as CP
+
+DIR = os.path.join(common.GOLDEN, 'layer_norm')
+ITER = ['ln_iter_tanh', 'ln_iter_relu_mmg', 'ln_iter_dyn']
+MCP = ['ln_mcp']
+RELU, TANH, SILU, HHSINLU = 0, 1, 2, 6
+EPS = 1e-5
+
+
+def load(name):
+    return R.load_fixture(os.path.join(DIR, name + '.npz'))
+
+
+def hhsinlu(x):
+    """models/activations.py:28-39 (prob_mbrl_amd.activations.hhSinLU)."""
+    n = x.shape[-1]
+    j = torch.arange(n)
+    sx = x * (2 * (j % 2) - 1).to(x.dtype)
+    return torch.where(j < (n + 1) // 2, torch.sin(sx), torch.relu(sx))
+
+
+ACT = {RELU: torch.relu, TANH: torch.tanh, SILU: lambda x: x * torch.sigmoid(x), HHSINLU: hhsinlu}
+
+
+def layer_norm(v, gamma, beta, eps):
+    mu = v.mean(-1, keepdim=True)
+    c = v - mu
+    var = (c * c).mean(-1, keepdim=True)
+    return gamma * (c / (var + eps).sqrt()) + beta
+
+
+def mlp(x, weights, act, norms, logits, us, temps, hards, margin=None, pre=None):
+    """Linear -> [LayerNorm] -> act -> dropout ... -> Linear.  norms: per hidden layer None or (gamma, beta, eps).  logits /
+    us / temps / hards as concrete_policy_ref.mlp's (hards[l]: the hard sample of a concrete layer, else a constant mask that
+    carries its 1 / keep, or None).  margin: receives the smallest |y| among the kept units of every hidden layer; pre:
+    receives every hidden layer's v."""
+    h, n = x, len(weights)
+    for l, (W, b) in enumerate(weights):
+        v = h @ W.t() + b
+        if l == n - 1:
+            return v
+        if pre is not None:
+            pre.append(v.detach())
+        y = layer_norm(v, *norms[l]) if norms[l] is not None else v
+        a = ACT[int(act[l] if isinstance(act, (list, tuple)) else act)](y)
+        m = CP.concrete_mask(logits[l], us[l], temps[l], hards[l]) if logits[l] is not None else hards[l]
+        if margin is not None:
+            kept = y.detach().abs()[hards[l] > 0] if hards[l] is not None else y.detach().abs()
+            margin.append(float(kept.min()))
+        h = a * m if m is not None else a
+
+
+# ---------------------------------------------------------------------------
+# the fixtures: a rollout, its loss and gradient; mc_pilco iterations
+# ---------------------------------------------------------------------------
+def _norms(d, pre, n_hidden, dtype, grad):
+    out = []
+    for l in range(n_hidden):
+        if '%s_ln_g%d' % (pre, l) not in d:
+            out.append(None)
+            continue
+        g = torch.tensor(np.asarray(d['%s_ln_g%d' % (pre, l)]), dtype=dtype).requires_grad_(grad)
+        b = torch.tensor(np.asarray(d['%s_ln_b%d' % (pre, l)]), dtype=dtype).requires_grad_(grad)
+        out.append((g, b, float(d['%s_ln_eps%d' % (pre, l)])))
+    return out
+
+
+class Problem:
+    """A fixture as tensors of `dtype`.  The policy's parameters are leaves that require grad, in the order of
+    policy.parameters(): fc0.weight, fc0.bias, [ln0.weight, ln0.bias,] fc1.weight, ..."""
+
+    def __init__(self, d, dtype=torch.float64):
+        self.d, self.dtype = d, dtype
+        self.x0, self.pol, self.dyn, self.spec, self.meta, self.z_mm, self.z_rr, self.gamma = R.problem_from_npz(d, dtype)
+        self.pol_norms = _norms(d, 'pol', len(self.pol['weights']) - 1, dtype, True)
+        self.dyn_norms = _norms(d, 'dyn', len(self.dyn['weights']) - 1, dtype, False)
+        for p in R.policy_params(self.pol):
+            p.requires_grad_(True)
+        self.margin = []
+
+    def leaves(self):
+        out = []
+        for l, (W, b) in enumerate(self.pol['weights']):
+            out += [W, b]
+            if l < len(self.pol_norms) and self.pol_norms[l] is not None:
+                out += list(self.pol_norms[l][:2])
+        return out
+
+    def names(self):
+        out, nl = [], len(self.pol['weights'])
+        for l in range(nl):
+            fc = 'fc%d' % l if l < nl - 1 else 'fc_out'
+            out += [fc + '.weight', fc + '.bias']
+            if l < len(self.pol_norms) and self.pol_norms[l] is not None:
+                out += ['ln%d.weight' % l, 'ln%d.bias' % l]
+        return out
+
+    @staticmethod
+    def _hards(net):
+        # a constant mask carries its 1 / keep (oracle.ref_torch.mlp_forward: h * m / keep)
+        return [None if m is None else (m if k == 1.0 else m / k) for m, k in zip(net['masks'], net['keep'])]
+
+    def _net(self, x, net, norms, margin=None):
+        n = len(net['weights']) - 1
+        hards = [h[:x.shape[0]] if h is not None else None for h in self._hards(net)]
+        return mlp(x, net['weights'], net.get('act', 0), norms, [None] * n, [None] * n, [None] * n, hards, margin)
+
+    def policy(self, x):
+        """oracle.ref_torch.policy_forward over the layer-normalised network."""
+        if len(self.pol.get('angle_dims', [])) > 0:
+            x = R.to_complex(x, self.pol['angle_dims'])
+        o = self._net(x, self.pol, self.pol_norms, self.margin)
+        mean, log_std = o.split(o.shape[-1] // 2, -1)
+        s = mean + self.pol['z'][:x.shape[0]] * R.clamp_log_std(log_std).exp()
+        return self.pol['scale'] * s.tanh() + self.pol['bias']
+
+    def dynamics(self, x, a):
+        """oracle.ref_torch.dynamics_forward (diagonal-Gaussian head, analytic reward) over the layer-normalised network."""
+        dyn = self.dyn
+        xa = torch.cat([x, a], -1)
+        if len(dyn.get('angle_dims', [])) > 0:
+            xa = R.to_complex(xa, dyn['angle_dims'])
+        o = self._net((xa - dyn['mx']) * dyn['iSx'], dyn, self.dyn_norms, self.margin)
+        mean, log_std = o.split(o.shape[-1] // 2, -1)
+        log_std = R.clamp_log_std(log_std) + dyn['Sy'].log()
+        mean = mean * dyn['Sy'] + dyn['my']
+        nxt = x + mean + dyn['z'][:x.shape[0]] * log_std.exp()
+        return nxt, R.reward_forward(nxt, a, self.spec)
+
+    def iteration(self):
+        """One rollout, loss and backward: (states [H + 1, B, D], loss); the gradients are on the leaves."""
+        m, D = self.meta, self.x0.shape[1]
+        B, G = self.x0.shape[0], self.meta['mm_groups']
+        j1, j2 = 1e-12 * torch.eye(D, dtype=self.dtype), 1e-12 * torch.eye(1, dtype=self.dtype)
+
+        def mm(t, z, j):
+            w = t.shape[-1]
+            if G is not None:
+                return R.mm_resample(t.view(G, -1, w), z.view(G, -1, w), j, m['infer_ns']).view(-1, w)
+            return R.mm_resample(t, z, j, m['infer_ns'])
+
+        for p in self.leaves():
+            p.grad = None
+        states, S, Rw = self.x0, [], []
+        for t in range(m['H']):
+            actions = self.policy(states)
+            nxt, rew = self.dynamics(states, actions)
+            if m['mm_states']:
+                nxt = mm(nxt, R.get_z_rnd(self.z_mm, t, B), j1)
+            if m['mm_rewards']:
+                rew = mm(rew, R.get_z_rnd(self.z_rr, t, B), j2)
+            S.append(states)
+            Rw.append(rew)
+            states = nxt
+        S.append(states)
+        loss = R.mc_loss(Rw, self.gamma, m['maximize'])
+        loss.backward()
+        return torch.stack(S).detach(), loss.detach()
+
+    def flat_grad(self):
+        return torch.cat([p.grad.reshape(-1) for p in self.leaves()])
+
+    def flat_params(self):
+        return torch.cat([p.detach().reshape(-1) for p in self.leaves()])
+
+    def split(self, flat):
+        """{parameter name: its slice} of a vector in the order of leaves()."""
+        out, off = {}, 0
+        for name, p in zip(self.names(), self.leaves()):
+            out[name] = np.asarray(flat[off:off + p.numel()]).reshape(tuple(p.shape))
+            off += p.numel()
+        return out
+
+    def mc_pilco(self):
+        """The fixture's iterations of algorithms/mc_pilco.py:86-216: loss, clip over all policy parameters, Adam.  Returns
+        the losses and the optimiser; the leaves hold the final parameters."""
+        d = self.d
+        opt = torch.optim.Adam(self.leaves(), float(d['mcp_lr']))
+        losses = []
+        for _ in range(int(d['mcp_n_iters'])):
+            _, loss = self.iteration()
+            torch.nn.utils.clip_grad_norm_(self.leaves(), float(d['mcp_clip']))
+            opt.step()
+            losses.append(float(loss))
+        return losses, opt
+
+    def kink_margin(self):
+        return min(self.margin) if self.margin else math.inf
+
+
+# ---------------------------------------------------------------------------
+# stand-alone network calls
+# ---------------------------------------------------------------------------
+def standalone(dims, act, B, seed, layers, temp=0.1, bias_shift=0.0, zero_var_row=None, zero_gamma=None):
+    """Inputs of a stand-alone network call (CPU tensors, fp32 values), drawn once per argument set.  layers: per hidden
+    layer a string of 'L' (layer norm) and at most one of 'c' (train-mode concrete dropout), 'b' (Bernoulli, keep 0.8).
+    bias_shift: added to layer 0's bias (the cancellation case).  zero_var_row: that row of layer 0's v is constant, to the
+    bit -- its input equals the input shift, so the normalised input is 0, and layer 0's bias is the same in every unit.
+    zero_gamma = (layer, unit): that gamma is 0."""
+    kinds = [next((k for k in s if k in 'cb'), None) for s in layers]
+    c = CP.standalone(dims, act, B, seed, temp, kinds)
+    g = torch.Generator().manual_seed(seed + 7919)
+    c['layers'] = list(layers)
+    c['gamma'], c['beta'], c['eps'] = [], [], []
+    for l, s in enumerate(layers):
+        h = dims[l + 1]
+        if 'L' in s:
+            c['gamma'].append(1.0 + 0.3 * torch.randn(h, generator=g))
+            c['beta'].append(0.1 * torch.randn(h, generator=g))
+            c['eps'].append(EPS)
+        else:
+            c['gamma'].append(None), c['beta'].append(None), c['eps'].append(None)
+    if bias_shift:
+        c['bs'][0] = c['bs'][0] + bias_shift
+    if zero_var_row is not None:
+        c['x'][zero_var_row] = c['shift']
+        c['bs'][0] = torch.full_like(c['bs'][0], 0.25)
+    if zero_gamma is not None:
+        c['gamma'][zero_gamma[0]][zero_gamma[1]] = 0.0
+    return c
+
+
+def standalone_reference(c, dtype=torch.float64, mls=float(np.log(5.0))):
+    """Of sum(sample * up0 + mean * up1 + log_std * up2) by torch autograd in `dtype`: a dict with the outputs (sample,
+    mean, log_std), grad_x, params [grad W0, grad b0, ...], gamma / beta / logit [per hidden layer or None], margin (the
+    smallest kept |y|) and pre (every hidden layer's v)."""
+    d = lambda t: t.to(dtype)  # noqa: E731
+    leaf = lambda t: d(t).requires_grad_(True) if t is not None else None  # noqa: E731
+    x = leaf(c['x'])
+    weights = [(leaf(W), leaf(b)) for W, b in zip(c['Ws'], c['bs'])]
+    gammas, betas = [leaf(t) for t in c['gamma']], [leaf(t) for t in c['beta']]
+    norms = [None if g is None else (g, b, e) for g, b, e in zip(gammas, betas, c['eps'])]
+    logits = [leaf(t) for t in c['logit']]
+    us = [d(t) if t is not None else None for t in c['u']]
+    hards = [None if h is None else (d(h) if k == 'c' else d(h) / keep) for h, k, keep in zip(c['hard'], c['kinds'], c['keep'])]
+    margin, pre = [], []
+    o = mlp((x - d(c['shift'])) * d(c['iscale']), weights, c['act'], norms, logits, us, c['temp'], hards, margin, pre)
+    n = c['n_out']
+    mu, ls = o[:, :n], o[:, n:]
+    ls = -torch.nn.functional.softplus(-ls + mls) + mls + d(c['osc']).log()
+    mu = mu * d(c['osc']) + d(c['osh'])
+    smp = d(c['sqs']) * torch.tanh(mu + d(c['z']) * ls.exp()) + d(c['sqb'])
+    sum((t * d(up)).sum() for t, up in zip((smp, mu, ls), c['up'])).backward()
+    g = lambda t: t.grad if t is not None else None  # noqa: E731
+    return dict(sample=smp.detach(), mean=mu.detach(), log_std=ls.detach(), grad_x=x.grad,
+                params=[t.grad for pair in weights for t in pair], gamma=[g(t) for t in gammas], beta=[g(t) for t in betas],
+                logit=[g(t) for t in logits], margin=min(margin), pre=pre)
