@@ -124,6 +124,8 @@ extern "C" {
 
 /* One MLP as built by models/core.py:15-99 (mlp): Linear -> activation -> dropout ...
  * -> Linear.  dims[0] = input width, dims[n_layers] = output width.
+ * n_layers = 1 .. PMBRL_MAX_LAYERS.  A rollout plan takes a network of ONE Linear layer -- no hidden layer, no mask:
+ * the linear policy, a linear dynamics model -- on the general kernel family (tests/test_gpu_general_envelope.py: l0-*).
  * keep[i] is the keep-probability the masked activation of hidden layer i is
  * DIVIDED by (BDropout, models/modules.py:61) or 1.0 (eval-mode CDropout,
  * models/modules.py:158-160, and layers without dropout). */

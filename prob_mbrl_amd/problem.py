@@ -262,8 +262,9 @@ def engine_from_problem(d, device='cuda:0', rows_per_wg_hint=0, shard=None, B_gl
     Bl = hi - lo
     Gl = (G * Bl // B) if G > 0 else None
     # [H, B, h] masks: a fresh dropout mask at every step (resample_policy / resample_model=True)
-    pol_ps = np.asarray(d['pol_mask0']).ndim == 3
-    dyn_ps = np.asarray(d['dyn_mask0']).ndim == 3
+    # (a network without hidden layers -- the linear policy -- has no mask at all)
+    pol_ps = 'pol_mask0' in d and np.asarray(d['pol_mask0']).ndim == 3
+    dyn_ps = 'dyn_mask0' in d and np.asarray(d['dyn_mask0']).ndim == 3
     eng = E.Engine(Bl, D, U, H, layer_dims(d, 'pol'), list(np.asarray(d['pol_keep'])),
                    layer_dims(d, 'dyn'), list(np.asarray(d['dyn_keep'])),
                    reward_spec or reward_spec_from_problem(d), mm_states=bool(d['mm_states']),

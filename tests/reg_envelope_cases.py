@@ -199,13 +199,16 @@ def oracle(d, dtype, n_steps=None):
                rewards=torch.stack(Rw).detach().numpy()[..., 0], loss=float(loss), grad=g.numpy())
     with torch.no_grad():
         us, lp, ld = [], [], []
+        # (angle features and activations as policy_forward / dynamics_forward apply them: tests/general_envelope_cases.py
+        #  has cases with both; none of this module's has either)
         for t in range(len(A)):
-            o = R.mlp_forward(S[t], pol['weights'], pol['masks'], pol['keep'], t)
+            o = R.mlp_forward(R.to_complex(S[t], pol.get('angle_dims', [])), pol['weights'], pol['masks'], pol['keep'], t,
+                              pol.get('act', 0))
             U = o.shape[-1] // 2
             us.append(o[:, :U] + pol['z'][:o.shape[0]] * R.clamp_log_std(o[:, U:]).exp())
             lp.append(o[:, U:] - R.LOG_MAX_STD)
-            xin = (torch.cat([S[t], A[t]], -1) - dyn['mx']) * dyn['iSx']
-            o = R.mlp_forward(xin, dyn['weights'], dyn['masks'], dyn['keep'], t)
+            xin = (R.to_complex(torch.cat([S[t], A[t]], -1), dyn.get('angle_dims', [])) - dyn['mx']) * dyn['iSx']
+            o = R.mlp_forward(xin, dyn['weights'], dyn['masks'], dyn['keep'], t, dyn.get('act', 0))
             ld.append(o[:, o.shape[-1] // 2:] - R.LOG_MAX_STD)
         out.update(u=torch.stack(us).numpy(), ls_pol=torch.stack(lp).numpy(), ls_dyn=torch.stack(ld).numpy())
     return out
