@@ -47,6 +47,9 @@ def parse(argv=None):
     ap.add_argument('--no_mm', action='store_true', help='particles only (deep_pilco_no_mm.py)')
     ap.add_argument('--learn_reward', action='store_true',
                     help='a learned reward head: the dynamics model predicts the reward (examples/deep_pilco_mm.py:94-99)')
+    ap.add_argument('--reward', type=str, default='analytic', choices=['analytic', 'callable'],
+                    help="callable: hand the environment's reward over as a plain torch function of (states, actions) -- how "
+                         'a reward of your own reaches the fused rollout (DynamicsModel states the contract)')
     ap.add_argument('--nonlin', type=nonlin_names, default='relu',
                     help='activation of the hidden layers of the dynamics model and the policy: relu | tanh | silu | sin | '
                          'exp | sinlu | hhsinlu | none, or a comma list with one name per hidden layer (relu,sin)')
@@ -132,6 +135,11 @@ def main(argv=None):
         reward_func, args.learn_reward = None, True
     else:
         reward_func = env.reward_func
+        if args.reward == 'callable':
+            # the same reward as a plain function: nothing tells the library its closed form, so the fused rollout calls it
+            # in torch on all row-steps at once.  (A copy on the device: the environment keeps evaluating its own on the host.)
+            rew = copy.deepcopy(env.reward_func).to(dev)
+            reward_func = lambda states, actions: rew(states, actions)  # noqa: E731
     # (learned reward: the density has one more dimension, examples/deep_pilco_mm.py:94-99,117-121)
     Dy = D + 1 if args.learn_reward else D
     if args.dyn_components > 1:     # mixture-of-Gaussians head: (2 Dy + 1) n + 1 outputs

@@ -89,6 +89,19 @@ extern "C" {
  * (z_dyn_step_stride = B Dh); the noise term's derivative is taken with the last step's rows, or each step's own under
  * PMBRL_FLAG_GMM_EXACT_NOISE_GRAD, in all Dh dimensions. */
 #define PMBRL_REWARD_LEARNED 2
+/* The reward is evaluated by the CALLER, between the library's calls (models/core.py:290-293: any reward_func(states,
+ * actions) the host language can express).  The other fields of pmbrl_reward are ignored.  Kernel family, pmbrl_plan_info
+ * and pmbrl_plan_sweep_kernel are those of the same configuration with an analytic reward; groups spread over ranks
+ * (mm_span_rows) are served.  The sequence of one rollout on such a plan:
+ *   pmbrl_rollout_fwd       packs and sweeps only: states and actions are final, rewards_d is left alone, no loss is formed
+ *   (caller)                r [H][B] and, for a rollout that will be differentiated, Jx = d r / d x~ [H][B][D] and
+ *                           Ja = d r / d a [H][B][U] for unit upstream gradient, on the same stream, from the array
+ *                           pmbrl_plan_reward_input names and from actions_d
+ *   pmbrl_rollout_rewards   takes them in, moment-matches the rewards where the plan does, forms the loss of
+ *                           pmbrl_plan_set_loss
+ *   pmbrl_rollout_bwd(_adam) as for any plan; -3 unless a pmbrl_rollout_rewards call WITH Jacobians followed the latest
+ *                           forward call */
+#define PMBRL_REWARD_EXTERNAL 3
 
 /* Activation of a network's hidden layers (models/core.py:15-99, nonlin=; models/activations.py), chosen per network and,
  * within a network, per hidden layer -- pmbrl_config::pol_act / dyn_act, pmbrl_mlp_call::act, pmbrl_bnn_config::act, each
@@ -412,6 +425,26 @@ int pmbrl_rollout_bwd(pmbrl_plan* plan, void* stream, void* workspace_d,
                       const float* grad_rewards_d, const float* grad_states_d,
                       const float* grad_actions_d, float* grad_pol_flat_d,
                       float* grad_x0_d, float* action_grad_norms_d, int32_t* status_d);
+
+/* ---- a reward evaluated by the caller (PMBRL_REWARD_EXTERNAL) -------------------------------------------------------
+ * pmbrl_plan_reward_input: where the [H][B][D] array the reward is a function of lives -- the sampled next states BEFORE
+ * their moment matching, row (t, b) being the state r[t][b] is the reward of (models/core.py:292: prev_states + dstates).
+ * *ws_offset_out: its byte offset into workspace_d (a multiple of 256) when the plan moment-matches its states
+ * (PMBRL_FLAG_MM_STATES), else -1: the array is then states_d + B D, the states of steps 1 .. H.  No launch; any plan kind.
+ * pmbrl_rollout_rewards: the rest of a forward call on an external plan.  r_d [H][B]; jx_d [H][B][D] and ja_d [H][B][U]
+ * together, or both NULL for a forward-only rollout; the arrays are read by the call's first launch and may be reused
+ * once the stream has passed it.  One launch copies r to where the plan's reward moment matching (or rewards_d) expects
+ * it and the Jacobians to where the adjoint sweeps read them, reports the first step with a non-finite sampled state,
+ * reward or Jacobian entry by atomicMin(status_d[0], t) and clears status_d[1]; behind it the reward moment matching
+ * (PMBRL_FLAG_MM_REWARDS; groups spread over ranks: one exchange through the attached collective) and the loss of
+ * pmbrl_plan_set_loss.  Rows of steps at or beyond a failed one may hold anything; what they hold is ignored.
+ * workspace_d, stream and status_d are the forward call's; the forward call's inputs (pmbrl_inputs and what it points
+ * at) must still be alive.  Never recorded or replayed (pmbrl_plan_set_replay).
+ * Returns -1 for a NULL plan, workspace_d, r_d, rewards_d or status_d and for exactly one of jx_d / ja_d being NULL, -2 on
+ * a plan of another reward kind, -3 without a forward call on the plan before it; nothing is queued then. */
+int pmbrl_plan_reward_input(const pmbrl_plan* plan, int64_t* ws_offset_out);
+int pmbrl_rollout_rewards(pmbrl_plan* plan, void* stream, void* workspace_d, const float* r_d, const float* jx_d,
+                          const float* ja_d, float* rewards_d, int32_t* status_d);
 
 /* out[0] = sum_i a[i] * w[i]  (the discounted-return loss of
  * algorithms/mc_pilco.py:134-144,190 given w = dL/dr). Deterministic. */

@@ -20,7 +20,7 @@ FLAG_NO_SHAPED = 32
 FLAG_POL_MASKS_PER_STEP, FLAG_DYN_MASKS_PER_STEP = 64, 128
 FLAG_GMM_EXACT_NOISE_GRAD = 256
 MAX_COMP = 8
-REWARD_EXP, REWARD_NEG, REWARD_LEARNED = 0, 1, 2
+REWARD_EXP, REWARD_NEG, REWARD_LEARNED, REWARD_EXTERNAL = 0, 1, 2, 3
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
 DROP_BY_TEMPERATURE, DROP_BERNOULLI = 0, 1      # pmbrl_bnn_config.drop_kind
@@ -127,6 +127,7 @@ EXPORTS = [
     'pmbrl_plan_set_p2p', 'pmbrl_p2p_error', 'pmbrl_p2p_destroy', 'pmbrl_plan_set_grad_comm',
     'pmbrl_opt_rule_check', 'pmbrl_clip_adam_rule', 'pmbrl_clip_adam_rule_guarded', 'pmbrl_plan_set_optimizer',
     'pmbrl_bnn_plan_set_optimizer', 'pmbrl_act_check',
+    'pmbrl_plan_reward_input', 'pmbrl_rollout_rewards',
 ]
 
 class Adam(C.Structure):
@@ -323,6 +324,11 @@ def load():
     lib.pmbrl_plan_set_optimizer.argtypes = [vp, rule]
     lib.pmbrl_bnn_plan_set_optimizer.restype = C.c_int
     lib.pmbrl_bnn_plan_set_optimizer.argtypes = [vp, rule]
+    if hasattr(lib, 'pmbrl_rollout_rewards'):      # (PMBRL_LIB_PATH may name an older build: no external reward there)
+        lib.pmbrl_plan_reward_input.restype = C.c_int
+        lib.pmbrl_plan_reward_input.argtypes = [vp, C.POINTER(i64)]
+        lib.pmbrl_rollout_rewards.restype = C.c_int
+        lib.pmbrl_rollout_rewards.argtypes = [vp] * 8
     _lib = lib
     return lib
 

@@ -452,9 +452,11 @@ static int plan_nets(pmbrl_plan* p) {
   if (c.dyn_components < 0 || c.dyn_components > PMBRL_MAX_COMP)
     return fail(-2, "dyn_components out of range (<= PMBRL_MAX_COMP)");
   const bool gmm = c.dyn_components > 1;
-  if (c.reward.kind != PMBRL_REWARD_EXP && c.reward.kind != PMBRL_REWARD_NEG && c.reward.kind != PMBRL_REWARD_LEARNED)
+  if (c.reward.kind != PMBRL_REWARD_EXP && c.reward.kind != PMBRL_REWARD_NEG && c.reward.kind != PMBRL_REWARD_LEARNED &&
+      c.reward.kind != PMBRL_REWARD_EXTERNAL)
     return fail(-2, "unknown reward kind");
   p->learned = c.reward.kind == PMBRL_REWARD_LEARNED;
+  p->ext = c.reward.kind == PMBRL_REWARD_EXTERNAL;      // (nothing of the layout depends on it: the plan of an analytic reward)
   if (p->learned && c.mm_span_rows > 0)
     return fail(-2, "learned reward head: not offered with moment-matching groups spread over ranks (mm_span_rows > 0)");
   if (p->learned && c.D + 1 > PMBRL_MAX_DIM) return fail(-2, "learned reward head: D + 1 exceeds PMBRL_MAX_DIM");
@@ -824,6 +826,15 @@ static int plan_reward(pmbrl_plan* p) {
     HIPCHK(hipMemset(p->wflag_d, 0, sizeof(int)));
     return 0;
   }
+  if (p->ext) {      // (no constants either, but rew_d stays NON-null -- an all-zero record nothing reads: a null one is how the
+                     //  sweeps tell a learned head, fill_args and RolloutArgs::Jx)
+    p->rew_k = 0;
+    HIPCHK(hipMalloc(&p->rew_d, sizeof(RewardDev)));
+    HIPCHK(hipMemcpy(p->rew_d, &r, sizeof(RewardDev), hipMemcpyHostToDevice));
+    HIPCHK(hipMalloc(&p->wflag_d, sizeof(int)));
+    HIPCHK(hipMemset(p->wflag_d, 0, sizeof(int)));
+    return 0;
+  }
   r.expand = s.expand;
   r.k = s.k;
   r.n_angle = s.expand ? s.n_angle : 0;
@@ -1089,7 +1100,8 @@ extern "C" int pmbrl_plan_create(const pmbrl_config* cfg, int device, pmbrl_plan
   const pmbrl_config& c = *cfg;
   if (c.B < 1 || c.D < 1 || c.U < 1 || c.H < 1) return fail(-2, "B, D, U, H must be >= 1");
   if (c.D > 32 || c.U > 16) return fail(-2, "supported widths: D <= 32, U <= 16");
-  if (c.reward.kind != PMBRL_REWARD_LEARNED && (c.reward.k < 1 || c.reward.k > PMBRL_MAX_TIP))
+  if (c.reward.kind != PMBRL_REWARD_LEARNED && c.reward.kind != PMBRL_REWARD_EXTERNAL &&
+      (c.reward.k < 1 || c.reward.k > PMBRL_MAX_TIP))
     return fail(-2, "reward.k out of range");
   // (every failure below frees the plan and whatever it already owns)
   std::unique_ptr<pmbrl_plan, void (*)(pmbrl_plan*)> p(new pmbrl_plan(), pmbrl_plan_destroy);
@@ -1778,7 +1790,8 @@ static int rollout_fwd_impl(pmbrl_plan* p, const FwdCall& C) {
     }
     if (rc) return rc;
   }
-  {
+  // (a reward evaluated by the caller: stage 3 and the loss are pmbrl_rollout_rewards' -- rewards_d is left alone)
+  if (!p->ext) {
     ScopedTimer tm(p, PMBRL_TIMER_REWARD, s);
     if (int rc = fwd_rewards(p, C, A)) return rc;
     // the loss (pmbrl_plan_set_loss).  (Folding this sum into the reward launch -- per-block partials, last block finishes --
@@ -1799,11 +1812,66 @@ extern "C" int pmbrl_rollout_fwd(pmbrl_plan* p, void* stream, void* workspace, c
   ReplayKey K;
   K.val(C.stream); K.val(C.workspace); K.add(C.in, sizeof(*C.in));
   K.val(C.states); K.val(C.actions); K.val(C.rewards); K.val(C.status); K.val(p->loss_w); K.val(p->loss_out);
-  return replay_call(p, 0, K, C.stream, [&](hipStream_t on) {
+  const int rc = replay_call(p, 0, K, C.stream, [&](hipStream_t on) {
     FwdCall Con = C;
     Con.stream = on;
     return rollout_fwd_impl(p, Con);
   });
+  if (p->ext) {      // (host-side notes, taken here and not in the body: a replayed call leaves them too)
+    p->ext_state = rc == 0 ? 1 : 0;
+    p->ext_in = *C.in;
+    p->ext_states = C.states;
+    p->ext_actions = C.actions;
+  }
+  return rc;
+}
+
+// ---------------------------------------------------------------------------
+// a reward evaluated by the caller (PMBRL_REWARD_EXTERNAL): where its argument lives, and the rest of the forward call
+// ---------------------------------------------------------------------------
+extern "C" int pmbrl_plan_reward_input(const pmbrl_plan* p, int64_t* ws_offset_out) {
+  if (!p || !ws_offset_out) return fail(-1, "null argument");
+  *ws_offset_out = (p->cfg.flags & PMBRL_FLAG_MM_STATES) ? (int64_t)p->off_xt : -1;
+  return 0;
+}
+
+extern "C" int pmbrl_rollout_rewards(pmbrl_plan* p, void* stream, void* workspace, const float* r_d, const float* jx_d,
+                                     const float* ja_d, float* rewards_d, int32_t* status_d) {
+  if (!p) return fail(-1, "null plan");
+  if (!p->ext) return fail(-2, "pmbrl_rollout_rewards: the plan's reward kind is not PMBRL_REWARD_EXTERNAL");
+  if (!workspace || !r_d || !rewards_d || !status_d) return fail(-1, "null argument");
+  if ((jx_d == nullptr) != (ja_d == nullptr))
+    return fail(-1, "pmbrl_rollout_rewards: jx_d and ja_d go together (both NULL: a forward-only rollout)");
+  if (p->ext_state == 0) return fail(-3, "pmbrl_rollout_rewards: no pmbrl_rollout_fwd call on this plan before it");
+  if (int rc = check_collective(p)) return rc;
+  HIPCHK(hipSetDevice(p->device));
+  hipStream_t s = (hipStream_t)stream;
+  RolloutArgs A;
+  if (int rc = fill_args(p, workspace, &p->ext_in, A)) return rc;
+  A.states = p->ext_states; A.actions = p->ext_actions; A.rewards = rewards_d; A.status = status_d;
+  const pmbrl_config& c = p->cfg;
+  const bool mmr = (c.flags & PMBRL_FLAG_MM_REWARDS) != 0;
+  ScopedTimer tm(p, PMBRL_TIMER_REWARD, s);
+  RewardExtArgs R;
+  R.r = r_d; R.jx = jx_d; R.ja = ja_d;
+  R.x = (c.flags & PMBRL_FLAG_MM_STATES) ? A.xt : A.states + (size_t)c.B * c.D;
+  R.dst_r = mmr ? A.rt : A.rewards;
+  R.Jx = A.Jx; R.Ja = A.Ja;
+  R.status = status_d;
+  R.H = c.H; R.B = c.B; R.D = c.D; R.U = c.U;
+  pm_reward_ext_launch(R, s);
+  p->ext_state = jx_d ? 3 : 2;
+  // behind it, what fwd_rewards queues behind the analytic launch: the rewards' moment matching, then the loss
+  if (mmr) {
+    if (p->span) {
+      if (int rc = mmx_fwd(p, static_cast<char*>(workspace), A, true, 0, s)) return rc;
+    } else {
+      hipLaunchKernelGGL(pm_mm_rewards_fwd_kernel, dim3(c.H * p->G), dim3(64), pm_mmr_lds_bytes(p->M, 2), s, A);
+    }
+  }
+  if (p->loss_w) launch_weighted_sum(s, rewards_d, p->loss_w, (long long)c.H * c.B, p->loss_out, status_d, c.B);
+  HIPCHK(hipGetLastError());
+  return 0;
 }
 
 extern "C" int pmbrl_plan_set_loss(pmbrl_plan* p, const float* loss_weights_d, float* loss_out_d) {
@@ -2163,6 +2231,13 @@ static ReplayKey bwd_key(const pmbrl_plan* p, const BwdCall& C, bool reg_bwd) {
 static int rollout_bwd_replay(pmbrl_plan* p, const BwdCall& C) {
   if (!p || !C.workspace || !C.in || !C.states || !C.actions || !C.rewards || !C.grad_rewards || !C.grad_pol_flat)
     return fail(-1, "null argument");
+  // a reward evaluated by the caller: the sweeps read its Jacobians from the workspace, where only a pmbrl_rollout_rewards
+  // call that was given them, behind the latest forward call, has left them
+  if (p->ext && p->ext_state == 2)
+    return fail(-3, "external reward: the latest pmbrl_rollout_rewards call was given no Jacobians (a forward-only rollout); "
+                    "the adjoint needs a rewards call with jx_d and ja_d behind the forward call");
+  if (p->ext && p->ext_state != 3)
+    return fail(-3, "external reward: no pmbrl_rollout_rewards call since the latest pmbrl_rollout_fwd on this plan");
   HIPCHK(hipSetDevice(p->device));
   RolloutArgs A;      // (no stream in it: the same for the eager call, the recording and the key)
   if (int rc = bwd_args(p, C, A)) return rc;

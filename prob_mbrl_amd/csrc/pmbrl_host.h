@@ -4,7 +4,8 @@
 // (pmbrl_instances.h).  The objects:
 //   pmbrl.hip                error string, version, build id, graph capture, the rollout plan, argument assembly and the two
 //                            rollout calls, with the kernels only they launch (the general family in exact fp32, external
-//                            moment matching, the reward kernels, pm_pack_all), and the GEMM test hook
+//                            moment matching, the reward kernels, pm_pack_all), the host side of pmbrl_rollout_rewards,
+//                            and the GEMM test hook
 //                            (it also resolves a plan's sweep kernels from the tables and launches them)
 //   pmbrl_general_split.hip  the general family on split operands: instances and table, nothing else
 //   pmbrl_general_act.hip    the general family for networks that are not ReLU: the same
@@ -15,6 +16,7 @@
 //   pmbrl_reg.hip            register-resident family: instances, resolution, packer and launch
 //   pmbrl_dw.hip             the policy-gradient dW GEMMs: kernels, the plan's dW record made and released
 //                            (pmbrl_dw_plan.h: the host-only planner), a call's argument record, the launches
+//   pmbrl_reward_ext.hip     the ingest launch of a reward evaluated by the caller (pmbrl_rollout_rewards)
 //   pmbrl_tail.hip           mask packing / drawing, weighted sum, dW reduction, gradient norm, clip + Adam, sharded tail
 //   pmbrl_bnn.hip            BNN training step
 //   pmbrl_mlp.hip            stand-alone network evaluation
@@ -78,6 +80,13 @@ struct pmbrl_plan {
   int act;             // some hidden layer of some network is not ReLU: the general family's ACT instances, per-unit act' stashes in place of the activity bits
   int learned;         // PMBRL_REWARD_LEARNED: the dynamics head predicts the reward (general family only)
   int rew_k = PMBRL_MAX_TIP;   // tip residuals of the reward (which instance of the reward launch: pm_reward_kernel_for)
+  // PMBRL_REWARD_EXTERNAL: the caller evaluates the reward between pmbrl_rollout_fwd and pmbrl_rollout_rewards (rew_d is
+  // then an all-zero record, never read: the sweeps take a null one for a learned head).  ext_state: 0 no forward call yet,
+  // 1 a forward call with no rewards call behind it, 2 rewards taken in without Jacobians, 3 with them (what an adjoint
+  // call needs); ext_in / ext_states / ext_actions: the latest forward call's arguments, which the rewards call goes on from
+  int ext = 0, ext_state = 0;
+  pmbrl_inputs ext_in;
+  float *ext_states = nullptr, *ext_actions = nullptr;
   int* wflag_d;        // weight-range flag of the fp16 packer (see RolloutArgs::wflag)
   int wgen;            // generation of the last forward call
   AngleDev* ang_d;
@@ -284,6 +293,15 @@ void pm_tail_hmin_launch(hipStream_t s, const float* hvec, int world, int* statu
 void pm_tail_pack_launch(hipStream_t s, float* xb, int n, int n_loss_part, int loss_here, const int* status, const int* err);
 void pm_tail_finish_launch(hipStream_t s, const float* xb, float* g, long long n, int* status, int expect, long long* step,
                            const int* err);
+// a reward evaluated by the caller (pmbrl_reward_ext.hip): r -> dst_r, jx -> Jx, ja -> Ja (both or neither), the first
+// step with a non-finite entry of x, r, jx or ja -> atomicMin(status[0]), status[1] cleared; one launch
+struct RewardExtArgs {
+  const float *r, *jx, *ja, *x;     // [H][B], [H][B][D], [H][B][U] (or both nullptr), [H][B][D]
+  float *dst_r, *Jx, *Ja;
+  int* status;
+  int H, B, D, U;
+};
+void pm_reward_ext_launch(const RewardExtArgs& R, hipStream_t s);
 // peer-to-peer transport (pmbrl_p2p.hip): what the fused iteration tail needs to know of one
 void pm_p2p_describe(const pmbrl_p2p* p, int* rank, int* nranks, size_t* cap_bytes, int** err_d);
 // register-resident family (pmbrl_reg.hip)

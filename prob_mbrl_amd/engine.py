@@ -494,14 +494,20 @@ class BnnStep:
 
 # the reward spec of a learned reward head (PMBRL_REWARD_LEARNED): the dynamics head predicts the reward
 LEARNED_REWARD = dict(kind='learned')
+# the reward spec of a torch callable the host evaluates between the two halves of the forward call
+# (PMBRL_REWARD_EXTERNAL); the callable itself is an argument of Engine.forward, not part of the plan
+EXTERNAL_REWARD = dict(kind='external')
 
 
 def make_reward_struct(spec, D, U):
     """spec: dict(kind, expand, angle_dims, C [k,De], tip_target [k], norm, w,
-    Q [k,k], R [U,U]) with numpy / float entries, or LEARNED_REWARD."""
+    Q [k,k], R [U,U]) with numpy / float entries, LEARNED_REWARD or EXTERNAL_REWARD."""
     r = _lib.Reward()
     if spec['kind'] == 'learned':
         r.kind = _lib.REWARD_LEARNED
+        return r
+    if spec['kind'] == 'external':
+        r.kind = _lib.REWARD_EXTERNAL
         return r
     r.kind = _lib.REWARD_EXP if spec['kind'] == 'exp' else _lib.REWARD_NEG
     r.expand = 1 if spec['expand'] else 0
@@ -585,6 +591,8 @@ class Engine:
         self.n_dyn_in = D + U + len(dyn_angle_dims)
         # learned reward head: my / Sy and the rows of z_dyn carry the reward column after the states
         self.learned = reward_spec['kind'] == 'learned'
+        # a torch callable as the reward: forward() evaluates it between pmbrl_rollout_fwd and pmbrl_rollout_rewards
+        self.external = reward_spec['kind'] == 'external'
         self.Dy = D + 1 if self.learned else D
         # GaussianMixtureDensity dynamics head (models/densities.py:151-259): components (0 / 1: diagonal Gaussian)
         self.n_comp = int(dyn_components) if dyn_components and int(dyn_components) > 1 else 0
@@ -625,6 +633,15 @@ class Engine:
         off = (-self.workspace.data_ptr()) % 256
         self._ws_ptr = C.c_void_p(self.workspace.data_ptr() + off)
         dev = self.device
+        # external reward: the [H * B, D] array the callable is a function of -- a view of the workspace (the sampled states
+        # before their moment matching), or None: steps 1 .. H of the call's states tensor (pmbrl_plan_reward_input)
+        self._reward_x = None
+        if self.external:
+            xo = C.c_int64(-1)
+            _lib.check(self.lib.pmbrl_plan_reward_input(plan, C.byref(xo)), 'pmbrl_plan_reward_input')
+            if xo.value >= 0:
+                lo = off + xo.value
+                self._reward_x = self.workspace[lo:lo + 4 * H * B * D].view(torch.float32).view(H * B, D)
         self.states = torch.empty((H + 1, B, D), dtype=torch.float32, device=dev)
         self.actions = torch.empty((H, B, U), dtype=torch.float32, device=dev)
         self.rewards = torch.empty((H, B, 1), dtype=torch.float32, device=dev)
@@ -747,9 +764,15 @@ class Engine:
 
     # ------------------------------------------------------------------
     def forward(self, x0, pol_flat, dyn_flat, mx, iSx, my, Sy, pol_scale, pol_bias,
-                pol_mask_bits, dyn_mask_bits, z_pol, z_dyn, z_mm=None, z_rr=None, out=None, z_pi=None, u_cat=None):
+                pol_mask_bits, dyn_mask_bits, z_pol, z_dyn, z_mm=None, z_rr=None, out=None, z_pi=None, u_cat=None,
+                reward_fn=None, want_jac=True):
         """z_pol / z_dyn: [B,.] (frozen, the same at every step) or [H,B,.] (a fresh
-        draw per step).  out: optional (states, actions, rewards) tensors to fill."""
+        draw per step).  out: optional (states, actions, rewards) tensors to fill.
+        reward_fn (a plan with EXTERNAL_REWARD): the torch callable ([N, D], [N, U]) -> [N, 1] or [N], evaluated once on
+        the N = H * B sampled row-steps between the sweep and the rewards' moment matching (_external_rewards);
+        want_jac=False: a forward-only rollout -- no Jacobians are formed and backward() is refused."""
+        if self.external != (reward_fn is not None):
+            raise ValueError('reward_fn goes with a plan made for EXTERNAL_REWARD, and only with one')
         dev = self.device
         t = [_f32c(v, dev) for v in (x0, pol_flat, dyn_flat, mx, iSx, my, Sy, pol_scale,
                                      pol_bias, z_pol, z_dyn)]
@@ -817,7 +840,42 @@ class Engine:
         _lib.check(self.lib.pmbrl_rollout_fwd(self.plan, _stream(), self._ws_ptr, C.byref(inp),
                                               _ptr(S), _ptr(A), _ptr(R), _ptr(self.status)),
                    'pmbrl_rollout_fwd')
+        if self.external:
+            self._external_rewards(reward_fn, S, A, R, want_jac)
         return S, A, R
+
+    def _external_rewards(self, fn, S, A, R, want_jac):
+        """The reward half of a forward call on an external plan: r = fn(x, u) on all H * B row-steps at once, its
+        Jacobians by one torch.autograd.grad of r.sum() (fn is row-wise: row i of that gradient is d r_i / d (x_i, u_i)),
+        then pmbrl_rollout_rewards -- all on the current stream, nothing read back.  Rows of steps behind a failed one
+        may hold non-finite states; the library ignores what fn returns there."""
+        N = self.H * self.B
+        xs = self._reward_x if self._reward_x is not None else S[1:].view(N, self.D)
+        us = A.view(N, self.U)
+        jx = ja = None
+        with torch.enable_grad() if want_jac else torch.no_grad():
+            x, u = xs.detach(), us.detach()
+            if want_jac:
+                x.requires_grad_(True)
+                u.requires_grad_(True)
+            r = fn(x, u)
+            if not torch.is_tensor(r) or r.dtype != torch.float32 or r.device != x.device or \
+                    tuple(r.shape) not in ((N, 1), (N,)):
+                what = 'a %s' % type(r).__name__ if not torch.is_tensor(r) else \
+                    '%s %s on %s' % (tuple(r.shape), r.dtype, r.device)
+                raise ValueError('reward_func(states [%d, %d], actions [%d, %d]) must return a float32 tensor [%d, 1] or '
+                                 '[%d] on %s, got %s' % (N, self.D, N, self.U, N, N, x.device, what))
+            r = r.reshape(N)
+            if want_jac:
+                if r.requires_grad:
+                    jx, ja = torch.autograd.grad(r.sum(), (x, u), allow_unused=True)
+                # (an input the reward does not depend on: a zero Jacobian)
+                jx = torch.zeros_like(x) if jx is None else _f32c(jx, self.device)
+                ja = torch.zeros_like(u) if ja is None else _f32c(ja, self.device)
+        r = _f32c(r.detach(), self.device)
+        _lib.check(self.lib.pmbrl_rollout_rewards(self.plan, _stream(), self._ws_ptr, _ptr(r), _ptr(jx), _ptr(ja),
+                                                  _ptr(R), _ptr(self.status)), 'pmbrl_rollout_rewards')
+        # (the call's first launch has read r / jx / ja; torch's allocator hands their memory out again on this stream only)
 
     def valid_steps(self):
         """Host sync: number of steps completed before a numerical failure (H if none)."""

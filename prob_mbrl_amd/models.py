@@ -743,7 +743,23 @@ class DynamicsModel(Regressor):
     and predicts the transition's reward in the last dimension of its density's sample
     (examples/deep_pilco_mm.py:94-99,117-121; trained on get_dynmodel_dataset(return_costs=True)).  The reference's own
     learned-reward branch takes D from the concatenated-input path only (an UnboundLocalError with tuple inputs,
-    SURVEY.md 8c); here D is the width of prev_states for tuple inputs and outs.shape[-1] - 1 otherwise."""
+    SURVEY.md 8c); here D is the width of prev_states for tuple inputs and outs.shape[-1] - 1 otherwise.
+
+    Any other callable is a reward of the caller's, as in the reference (models/core.py:290-293:
+    `reward_func(prev_states + dstates, actions)`): the fused rollout and mc_pilco's fused routes evaluate it in torch
+    between the forward sweep and the rewards' moment matching and hand the adjoint sweep its Jacobians
+    (pmbrl_rollout_rewards).  Its contract there:
+      - `reward_func(states [N, D], actions [N, U]) -> [N, 1]` or `[N]`, float32 tensors on the modules' device; any
+        other shape, dtype or device of the result is a ValueError;
+      - row-wise: row i of the result depends on row i of the two inputs only (the Jacobians are one
+        torch.autograd.grad of the result's sum);
+      - made of differentiable torch ops, with no random draws of its own;
+      - called ONCE per rollout with the N = H * B row-steps of the whole horizon, not H times with B rows; which
+        row-step is which row is not part of the contract;
+      - its own parameters are constants: no gradient is formed for them;
+      - after a numerical failure the rows of later steps may hold non-finite states; what it returns there is ignored.
+    The stepwise rollout (on_pol_eval, train-mode concrete policies, layer norm) calls it once per step, as forward()
+    below does."""
 
     def __init__(self, model, reward_func=None, predict_done=False, **kwargs):
         super().__init__(model, **kwargs)

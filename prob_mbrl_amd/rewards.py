@@ -230,7 +230,8 @@ def from_module(obj):
     the constants of its closed form as parameters (envs/cartpole/env.py:27-40: Q, R, target, pole_length; likewise
     pendulum, double_cartpole, cart_acrobot, rendezvous).  The constants are read from the module (not assumed), so
     non-default lengths / weights / targets carry over.  Returns `obj` itself if it already is one of ours, None if
-    it is not a module this build recognises (the caller then treats it as a learned / unknown reward)."""
+    it is not a module this build recognises: DynamicsModel then keeps the object as it is, and where it is callable the
+    fused rollout evaluates it as a torch reward of the caller's (engine.EXTERNAL_REWARD) instead of refusing it."""
     if obj is None or isinstance(obj, AnalyticReward):
         return obj
     hit = _BY_NAME.get(type(obj).__name__)

@@ -96,8 +96,8 @@ def _masked(key, dr, B, w):
 
 
 def _reward_key(spec):
-    if spec['kind'] == 'learned':
-        return ('learned',)
+    if spec['kind'] in ('learned', 'external'):      # (an external reward's callable is an argument of the call, not of the plan)
+        return (spec['kind'],)
     return (spec['kind'], spec['expand'], tuple(spec['angle_dims']),
             np.asarray(spec['C'], dtype=np.float64).tobytes(),
             np.asarray(spec['tip_target'], dtype=np.float64).tobytes(), float(spec['norm']),
@@ -142,9 +142,17 @@ class Bundle:
             raise TypeError('rollout() needs prob_mbrl_amd.models.Policy / DynamicsModel')
         # reward_func=None: the dynamics head predicts the reward (a learned reward head, checked below)
         self.learned = dynamics.reward_func is None
+        # a callable without a spec: any torch reward_func(states, actions) (models/core.py:290-293), evaluated by the
+        # host between the sweep and the rewards' moment matching (engine.EXTERNAL_REWARD; the contract: DynamicsModel)
+        self.reward_fn = None
         if not self.learned and not hasattr(dynamics.reward_func, 'spec'):
-            raise NotImplementedError('DynamicsModel.reward_func must be a prob_mbrl_amd.rewards module, or None '
-                                      'with a learned reward head')
+            if not callable(dynamics.reward_func):
+                raise NotImplementedError('DynamicsModel.reward_func must be a prob_mbrl_amd.rewards module, or None '
+                                          'with a learned reward head')
+            self.reward_fn = dynamics.reward_func
+        # can a gradient be asked of this rollout later?  (rollout() says no under torch.no_grad() with no input that
+        # requires one; mc_pilco's fused routes always differentiate)
+        self.want_jac = True
         policy.model.refuse_layer_norm('the fused rollout (rollout.Bundle)')
         dynamics.model.refuse_layer_norm('the fused rollout (rollout.Bundle)')
         plin, pdrop, pdens, _ = policy.model.layers_spec()
@@ -194,7 +202,8 @@ class Bundle:
         self.B, self.H = B, H
         if getattr(dynamics.reward_func, 'bind_action_dim', None):
             dynamics.reward_func.bind_action_dim(self.U)
-        self.spec = E.LEARNED_REWARD if self.learned else dynamics.reward_func.spec(self.D)
+        self.spec = E.LEARNED_REWARD if self.learned else E.EXTERNAL_REWARD if self.reward_fn is not None \
+            else dynamics.reward_func.spec(self.D)
         self.pol_keep = [dr.keep_prob() if dr is not None else 1.0 for dr in pdrop]
         self.dyn_keep = [dr.keep_prob() if dr is not None else 1.0 for dr in ddrop]
         # per-unit Bernoulli rates: 1 / p_j folded into row j of the Linear in front of the dropout (models.BDropout.
@@ -326,7 +335,7 @@ class Bundle:
         return self.engine.forward(x0, pol_flat, dyn_flat, self.mx, self.iSx, self.my,
                                    self.Sy, self.scale, self.bias, self.pol_bits, self.dyn_bits,
                                    self.z_pol, self.z_dyn, self.z_mm, self.z_rr, out=out, z_pi=self.z_pi,
-                                   u_cat=self.u_cat)
+                                   u_cat=self.u_cat, reward_fn=self.reward_fn, want_jac=self.want_jac)
 
 
 class RolloutFunction(torch.autograd.Function):
@@ -585,6 +594,8 @@ def rollout(states, dynamics, policy, steps, resample_model=False, resample_poli
         # a list that backward() appends the [H, B] matrix of ||dL/da_t|| to (prioritised replay)
         bundle.agn_out = agn_out
         x0 = states.to(device=bundle.device, dtype=torch.float32)
+        # (an external reward's Jacobians are formed only where this rollout can be differentiated)
+        bundle.want_jac = torch.is_grad_enabled() and (x0.requires_grad or any(p.requires_grad for p in bundle.pol_params))
         S, A, R = RolloutFunction.apply(bundle, x0, *bundle.pol_params)
         n = bundle.engine.valid_steps()
         failed = n < steps
