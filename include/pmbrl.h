@@ -689,7 +689,10 @@ int pmbrl_plan_set_prof(pmbrl_plan* plan, long long* fwd_d, long long* bwd_d);
  *   out_scale/out_shift given:  mu <- mu*out_scale + out_shift ;  l <- l + log(out_scale)
  *   sample = mu + z * exp(l)                              (z NULL: sample = mu)
  *   sq_scale/sq_bias given:    sample <- sq_scale * tanh(sample) + sq_bias
- * Outputs may be NULL.  mask_bits are bit rows as produced by pmbrl_pack_mask. */
+ * Outputs may be NULL.  mask_bits are bit rows as produced by pmbrl_pack_mask.
+ * Accepted: 2 .. 8 Linear layers, every width (input and head included) 1 .. 1024, an even head; else -2.  The forward
+ * keeps two 16-row buffers of (widest layer rounded up to 16, + 8) floats + 24 KB in LDS: 156 672 B at 1024, so its own
+ * LDS refusal (-3, "too wide for LDS") cannot be reached with widths the range check lets through. */
 typedef struct {
   int32_t B;                  /* rows */
   pmbrl_mlp net;              /* dims[0] = input width, dims[n_layers] = 2 * output width */
@@ -711,7 +714,13 @@ int pmbrl_mlp_forward(void* stream, const pmbrl_mlp_call* call, void* workspace_
  * grad_x = (d sample / d x)^T g_sample + (d mean / d x)^T g_mean + (d log_std / d x)^T g_log_std,
  * same arguments as the forward; any of the three upstream gradients may be NULL.  Used when a
  * stand-alone network sits inside a differentiable computation (the terminal value V(x_H) of
- * algorithms/mc_pilco.py:136-140). */
+ * algorithms/mc_pilco.py:136-140).
+ * LDS: the kernel keeps every Linear's input and two gradient buffers -- and, where a hidden layer is not ReLU, the
+ * first hidden layer's derivatives (the others live in dead input buffers) -- resident:
+ *   (n_layers + 2 [+ 1]) * 16 * (widest layer rounded up to 16, + 8) floats + 24 KB,
+ * the widest taken over ALL widths, input and head included.  Beyond 160 KB the call is refused with -3 and "LDS" in
+ * the message (there is no workspace query of its own: pmbrl_mlp_workspace_bytes serves the forward too and does not
+ * refuse).  One hidden layer of 528 units (4 buffers) is the widest it takes, 416 with two (5), 208 with seven (10). */
 int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* call, void* workspace_d,
                          const float* x_d, const float* params_flat_d,
                          const uint16_t* const* mask_bits_d, const float* z_d,
@@ -733,7 +742,9 @@ int pmbrl_mlp_grad_input(void* stream, const pmbrl_mlp_call* call, void* workspa
  *    run; each walks its 16-row tiles in order and sums its share of the gradient in a slab [n_params] of its own in
  *    the workspace, and a second launch adds the slabs in slab order.  The workspace therefore stops growing at
  *    B = 16 * PMBRL_MLP_BWD_MAX_BLOCKS rows.  A network so large that this many slabs would exceed
- *    PMBRL_MLP_BWD_SLAB_BYTES gets fewer workgroups (PMBRL_MLP_BWD_SLAB_BYTES / (4 n_params), at least one).
+ *    PMBRL_MLP_BWD_SLAB_BYTES gets fewer workgroups (PMBRL_MLP_BWD_SLAB_BYTES / (4 n_params), at least one; "at least
+ *    one" needs more than 16 M parameters, which no network within the LDS limit below has: the largest, one hidden
+ *    layer of 528 between 528 inputs and a head of 528, has 0.56 M and gets 30).
  *  - The kernel keeps every Linear's input -- and with Tanh / SiLU every hidden layer's derivatives -- in LDS:
  *    (n_layers + 2 [+ n_layers - 1]) * 16 * (widest layer rounded up to 16, + 8) floats + 24 KB.  Beyond 160 KB the
  *    workspace query gives 0 and the call -3, both with a message (pmbrl_mlp_grad_input, which needs less, is a

@@ -166,8 +166,14 @@ class _MlpCall:
         return [p(self.x), p(self.pf), self.masks, p(self.z), p(self.in_shift), p(self.in_iscale),
                 p(self.out_scale), p(self.out_shift), p(self.sq_scale), p(self.sq_bias)]
 
-    def forward(self, want):
-        out = {k: torch.empty((self.B, self.n_out), dtype=torch.float32, device=self.x.device) for k in want}
+    def _given(self, t, shape):
+        assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+        return t
+
+    def forward(self, want, out=None):
+        """{name: [B, n_out]} of the outputs in `want`; out: {name: tensor} to write into instead of fresh ones."""
+        out = {k: self._given(out[k], (self.B, self.n_out)) if out is not None and k in out else
+               torch.empty((self.B, self.n_out), dtype=torch.float32, device=self.x.device) for k in want}
         p = self._p
         if self.ln is not None or self.ln_entry:
             _lib.check(self.lib.pmbrl_mlp_forward_ln(_stream(), C.byref(self.call), p(self.ws), *self._common(),
@@ -179,8 +185,8 @@ class _MlpCall:
                    'pmbrl_mlp_forward')
         return out
 
-    def grad_input(self, g_sample=None, g_mean=None, g_log_std=None):
-        gx = torch.empty_like(self.x)
+    def grad_input(self, g_sample=None, g_mean=None, g_log_std=None, out=None):
+        gx = torch.empty_like(self.x) if out is None else self._given(out, self.x.shape)
         p = self._p
         gs = [None if g is None else g.to(torch.float32).contiguous() for g in (g_sample, g_mean, g_log_std)]
         if self.ln is not None or self.ln_entry:
@@ -196,7 +202,8 @@ class _MlpCall:
     def backward(self, g_sample=None, g_mean=None, g_log_std=None, want_x=True, want_params=True, out=None,
                  concrete=None, want_ln=True):
         """(grad_x [B, n_in], grad_params flat in the order of params_flat) of pmbrl_mlp_backward; an output that is
-        not wanted is None and is not computed.  out = (grad_x, grad_params): write into these tensors.
+        not wanted is None and is not computed.  out = (grad_x, grad_params[, grad_logit, grad_ln]): write into these
+        tensors (grad_logit: the concrete layers' [h_l] concatenated, grad_ln: [d gamma | d beta] per layer-norm layer).
         concrete: per hidden layer None or (u [B, h_l], logit_p [h_l], temp) of a train-mode concrete-dropout layer
         whose hard sample the call's mask bits hold; the call is then pmbrl_mlp_backward_concrete and a third result
         follows, the list of d / d logit_p [h_l] per such layer (None for the others).
@@ -229,7 +236,7 @@ class _MlpCall:
             msg = self.lib.pmbrl_last_error()
             raise ValueError('%s_workspace_bytes: %s' % (name, msg.decode() if msg else 'bad shape'))
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.x.device)
-        gx, gp = out if out is not None else (None, None)
+        gx, gp, gl_out, gn_out = (tuple(out) + (None, None))[:4] if out is not None else (None,) * 4
         gx = (torch.empty_like(self.x) if gx is None else gx) if want_x else None
         gp = (torch.empty_like(self.pf) if gp is None else gp) if want_params else None
         for t, like in ((gx, self.x), (gp, self.pf)):
@@ -241,9 +248,13 @@ class _MlpCall:
             gl = parts = None
             if conc is not None:
                 widths = [self.dims[l + 1] if c is not None else 0 for l, c in enumerate(concrete)]
-                gl = torch.empty(sum(widths), dtype=torch.float32, device=dev)
+                gl = torch.empty(sum(widths), dtype=torch.float32, device=dev) if gl_out is None else \
+                    self._given(gl_out, (sum(widths),))
             want_ln = want_ln and self.ln is not None
-            gn = torch.empty(2 * sum(self.ln_widths), dtype=torch.float32, device=dev) if want_ln else None
+            gn = None
+            if want_ln:
+                gn = torch.empty(2 * sum(self.ln_widths), dtype=torch.float32, device=dev) if gn_out is None else \
+                    self._given(gn_out, (2 * sum(self.ln_widths),))
             _lib.check(self.lib.pmbrl_mlp_backward_ln(_stream(), C.byref(self.call), p(ws), *self._common(),
                                                       p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp),
                                                       C.byref(conc) if conc else None, p(gl), self._ln_ref(), p(gn)), name)
@@ -264,7 +275,8 @@ class _MlpCall:
                                                    p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp)), name)
             return gx, gp
         widths = [self.dims[l + 1] if c is not None else 0 for l, c in enumerate(concrete)]
-        gl = torch.empty(sum(widths), dtype=torch.float32, device=self.x.device)
+        gl = torch.empty(sum(widths), dtype=torch.float32, device=self.x.device) if gl_out is None else \
+            self._given(gl_out, (sum(widths),))
         _lib.check(self.lib.pmbrl_mlp_backward_concrete(_stream(), C.byref(self.call), p(ws), *self._common(),
                                                         p(gs[0]), p(gs[1]), p(gs[2]), p(gx), p(gp), C.byref(conc),
                                                         p(gl)), name)

@@ -24,7 +24,7 @@ from tests import concrete_policy_ref as CP
 DIR = os.path.join(common.GOLDEN, 'layer_norm')
 ITER = ['ln_iter_tanh', 'ln_iter_relu_mmg', 'ln_iter_dyn']
 MCP = ['ln_mcp']
-RELU, TANH, SILU, HHSINLU = 0, 1, 2, 6
+RELU, TANH, SILU, SIN, EXP, SINLU, HHSINLU, NONE = range(8)      # PMBRL_ACT_*
 EPS = 1e-5
 
 
@@ -40,7 +40,10 @@ def hhsinlu(x):
     return torch.where(j < (n + 1) // 2, torch.sin(sx), torch.relu(sx))
 
 
-ACT = {RELU: torch.relu, TANH: torch.tanh, SILU: lambda x: x * torch.sigmoid(x), HHSINLU: hhsinlu}
+# the formulas of include/pmbrl.h (PMBRL_ACT_*)
+ACT = {RELU: torch.relu, TANH: torch.tanh, SILU: lambda x: x * torch.sigmoid(x), SIN: torch.sin,
+       EXP: lambda x: torch.exp(-0.5 * x * x), SINLU: lambda x: torch.where(x > 0, x, torch.sin(x)), HHSINLU: hhsinlu,
+       NONE: lambda x: x}
 
 
 def layer_norm(v, gamma, beta, eps):
@@ -241,10 +244,26 @@ def standalone(dims, act, B, seed, layers, temp=0.1, bias_shift=0.0, zero_var_ro
     return c
 
 
+def head(o, c, mls, d=lambda t: t, use_z=True):
+    """(sample, mean, log_std) of the raw head outputs o = [mu | l] (include/pmbrl.h: the clamp, the output scaling, the
+    noise, the squashing).  c['osc'] / c['osh'], c['z'], c['sqs'] / c['sqb'] that are None are null pointers of the call:
+    that step is left out.  d: the cast of the inputs to o's dtype."""
+    n = o.shape[-1] // 2
+    mu, ls = o[:, :n], o[:, n:]
+    ls = -torch.nn.functional.softplus(-ls + mls) + mls
+    if c['osc'] is not None:
+        ls = ls + d(c['osc']).log()
+        mu = mu * d(c['osc']) + d(c['osh'])
+    s = mu + d(c['z']) * ls.exp() if use_z and c['z'] is not None else mu
+    smp = d(c['sqs']) * torch.tanh(s) + d(c['sqb']) if c['sqs'] is not None else s
+    return smp, mu, ls
+
+
 def standalone_reference(c, dtype=torch.float64, mls=float(np.log(5.0))):
     """Of sum(sample * up0 + mean * up1 + log_std * up2) by torch autograd in `dtype`: a dict with the outputs (sample,
     mean, log_std), grad_x, params [grad W0, grad b0, ...], gamma / beta / logit [per hidden layer or None], margin (the
-    smallest kept |y|) and pre (every hidden layer's v)."""
+    smallest kept |y|), margins (that of every hidden layer) and pre (every hidden layer's v).  c['shift'] / c['iscale'] and
+    the head's optional inputs may be None (head)."""
     d = lambda t: t.to(dtype)  # noqa: E731
     leaf = lambda t: d(t).requires_grad_(True) if t is not None else None  # noqa: E731
     x = leaf(c['x'])
@@ -255,14 +274,10 @@ def standalone_reference(c, dtype=torch.float64, mls=float(np.log(5.0))):
     us = [d(t) if t is not None else None for t in c['u']]
     hards = [None if h is None else (d(h) if k == 'c' else d(h) / keep) for h, k, keep in zip(c['hard'], c['kinds'], c['keep'])]
     margin, pre = [], []
-    o = mlp((x - d(c['shift'])) * d(c['iscale']), weights, c['act'], norms, logits, us, c['temp'], hards, margin, pre)
-    n = c['n_out']
-    mu, ls = o[:, :n], o[:, n:]
-    ls = -torch.nn.functional.softplus(-ls + mls) + mls + d(c['osc']).log()
-    mu = mu * d(c['osc']) + d(c['osh'])
-    smp = d(c['sqs']) * torch.tanh(mu + d(c['z']) * ls.exp()) + d(c['sqb'])
+    xin = (x - d(c['shift'])) * d(c['iscale']) if c['shift'] is not None else x
+    smp, mu, ls = head(mlp(xin, weights, c['act'], norms, logits, us, c['temp'], hards, margin, pre), c, mls, d)
     sum((t * d(up)).sum() for t, up in zip((smp, mu, ls), c['up'])).backward()
     g = lambda t: t.grad if t is not None else None  # noqa: E731
     return dict(sample=smp.detach(), mean=mu.detach(), log_std=ls.detach(), grad_x=x.grad,
                 params=[t.grad for pair in weights for t in pair], gamma=[g(t) for t in gammas], beta=[g(t) for t in betas],
-                logit=[g(t) for t in logits], margin=min(margin), pre=pre)
+                logit=[g(t) for t in logits], margin=min(margin), margins=margin, pre=pre)

@@ -19,6 +19,7 @@ import pytest
 import torch
 
 from tests import common, grad_bars  # noqa: F401
+from tests import layer_norm_ref as LN
 
 MLS = float(np.log(5.0))
 RELU, TANH, SILU = 0, 1, 2
@@ -105,15 +106,7 @@ def reference(name, up=ALL, use_z=True, dtype=torch.float64):
             h = h * d(c['masks'][i]) / c['keep'][i]
         else:
             margin = min(margin, float(v.detach().abs().min()))
-    o = h @ params[-2].t() + params[-1]
-    n = c['n_out']
-    mu, ls = o[:, :n], o[:, n:]
-    ls = -torch.nn.functional.softplus(-ls + MLS) + MLS
-    if c['osc'] is not None:
-        ls = ls + d(c['osc']).log()
-        mu = mu * d(c['osc']) + d(c['osh'])
-    s = mu + d(c['z']) * ls.exp() if use_z and c['z'] is not None else mu
-    smp = d(c['sqs']) * torch.tanh(s) + d(c['sqb']) if c['sqs'] is not None else s
+    smp, mu, ls = LN.head(h @ params[-2].t() + params[-1], c, MLS, d, use_z)
     outs = dict(sample=smp, mean=mu, log_std=ls)
     sum((outs[k] * d(c['up'][k])).sum() for k in up).backward()
     return x.grad, [p.grad for p in params], margin, {k: v.detach() for k, v in outs.items()}
