@@ -904,6 +904,17 @@ typedef struct {
 typedef struct pmbrl_bnn_plan pmbrl_bnn_plan;
 
 int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pmbrl_bnn_plan** out);
+/* The kernel form of the step's forward + backward launch.  RESIDENT keeps every layer's values in LDS between the two
+ * passes: pmbrl_bnn_plan_create, which returns -3 ("... LDS budget") beyond two hidden layers of 256 with ReLU.  SPILL keeps
+ * one layer's working set in LDS and what the backward pass needs of the others in the workspace: any depth, activation
+ * and mix of dropout kinds up to 688 units a layer (inputs and head included; -3 "... LDS ..." beyond), e.g. 3 x 512.
+ * AUTO: RESIDENT where it fits, else SPILL.  Where both fit they return the same bits.  Any other value: -2.  Every call
+ * that takes a pmbrl_bnn_plan serves both forms; a SPILL plan's workspace includes its stashes. */
+#define PMBRL_BNN_FORM_RESIDENT 0
+#define PMBRL_BNN_FORM_SPILL 1
+#define PMBRL_BNN_FORM_AUTO 2
+int pmbrl_bnn_plan_create_form(const pmbrl_bnn_config* cfg, int device, int32_t form, pmbrl_bnn_plan** out);
+int32_t pmbrl_bnn_plan_form(const pmbrl_bnn_plan* plan);      /* the form the plan took (RESIDENT or SPILL) */
 void pmbrl_bnn_plan_destroy(pmbrl_bnn_plan* plan);
 /* Per-unit keep probabilities of Bernoulli layer `layer` (BDropout with a tensor rate): keep_h, n host values in
  * (0, 1], copied into memory the plan owns (the call waits for the device).  n must be the layer's width; a layer

@@ -24,6 +24,7 @@ REWARD_EXP, REWARD_NEG, REWARD_LEARNED, REWARD_EXTERNAL = 0, 1, 2, 3
 PREC_F32, PREC_SPLIT, PREC_SPLIT_F16 = 0, 1, 2
 ACT_RELU, ACT_TANH, ACT_SILU = 0, 1, 2
 DROP_BY_TEMPERATURE, DROP_BERNOULLI = 0, 1      # pmbrl_bnn_config.drop_kind
+BNN_FORM_RESIDENT, BNN_FORM_SPILL, BNN_FORM_AUTO = 0, 1, 2      # pmbrl_bnn_plan_create_form
 MLP_BWD_MAX_BLOCKS = 256                        # PMBRL_MLP_BWD_MAX_BLOCKS: workgroups (gradient slabs) of pmbrl_mlp_backward
 MLP_BWD_SLAB_BYTES = 64 << 20                   # PMBRL_MLP_BWD_SLAB_BYTES: ... fewer where that many slabs would exceed this
 # pmbrl_plan_info indices (PMBRL_INFO_* of include/pmbrl.h)
@@ -128,6 +129,7 @@ EXPORTS = [
     'pmbrl_opt_rule_check', 'pmbrl_clip_adam_rule', 'pmbrl_clip_adam_rule_guarded', 'pmbrl_plan_set_optimizer',
     'pmbrl_bnn_plan_set_optimizer', 'pmbrl_act_check',
     'pmbrl_plan_reward_input', 'pmbrl_rollout_rewards',
+    'pmbrl_bnn_plan_create_form', 'pmbrl_bnn_plan_form',
 ]
 
 class Adam(C.Structure):
@@ -248,6 +250,11 @@ def load():
                                               [C.POINTER(MlpConcrete), vp, ln, vp])
     lib.pmbrl_bnn_plan_create.restype = C.c_int
     lib.pmbrl_bnn_plan_create.argtypes = [C.POINTER(BnnConfig), C.c_int, C.POINTER(vp)]
+    if hasattr(lib, 'pmbrl_bnn_plan_create_form'):      # (PMBRL_LIB_PATH may name an older build: the resident form only)
+        lib.pmbrl_bnn_plan_create_form.restype = C.c_int
+        lib.pmbrl_bnn_plan_create_form.argtypes = [C.POINTER(BnnConfig), C.c_int, i32, C.POINTER(vp)]
+        lib.pmbrl_bnn_plan_form.restype = i32
+        lib.pmbrl_bnn_plan_form.argtypes = [vp]
     lib.pmbrl_bnn_plan_destroy.restype = None
     lib.pmbrl_bnn_plan_destroy.argtypes = [vp]
     lib.pmbrl_bnn_plan_workspace_bytes.restype = C.c_size_t

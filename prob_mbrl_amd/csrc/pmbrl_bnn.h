@@ -14,173 +14,12 @@
 // pre-activation gradients and layer inputs are stashed feature-major, exactly the layout the
 // policy-gradient dW GEMM (pmbrl_dw_kernels.h) consumes, so dW / db come from the same kernel.
 // pm_bnn_finish adds the regulariser, reduces the dropout-logit gradients and the loss.
+// (The argument record, the two epilogues and the LDS maps are pmbrl_bnn_parts.h's, the loss sections pmbrl_bnn_loss.h's:
+//  the spill form of the step, pmbrl_bnn_spill.h, is made of the same parts.)
 #pragma once
 #include <type_traits>
 
-#include "pmbrl_dev.h"
-
-struct BnnArgs {
-  int M, nl, LD, n_out, nwg, n_in, sum_h;
-  int dim[PM_MAXL + 1], nt[PM_MAXL + 1];
-  const float* wf[PM_MAXL];
-  const float* wb[PM_MAXL];
-  const float* bias[PM_MAXL];
-  const float* logit_p[PM_MAXL];   // hidden layer l: [dim[l+1]] or nullptr (no dropout)
-  const float* u[PM_MAXL];         // [M][dim[l+1]] uniform noise of the concrete relaxation
-  const float* bvar[PM_MAXL];      // [M][dim[l+1]] uniform variate of the Bernoulli draw (hard = bvar < probs)
-  float inv_temp[PM_MAXL];
-  int lp_off[PM_MAXL];             // offset of layer l's logits in the concatenated logit vector
-  const float *X, *Y;              // normalised dataset [N][n_in], [N][n_out]
-  const int* idx;                  // [M] minibatch rows
-  float mls, inv_M;
-  int mse;                         // loss: mean squared error of the mean head instead of the Gaussian NLL
-  int gmm_n;                       // > 1: mixture-of-Gaussians NLL, head = [n D means | n D log-stds | n logits | log-T]
-  const float* row_w;              // [M] per-row weight of the log-likelihood (importance sampling) or nullptr
-  float* row_lp;                   // [M] out: per-row log-likelihood (unweighted) or nullptr
-  float* actT[PM_MAXL];            // stash: input of layer l   [wg][nt[l]*16][16]
-  float* gT[PM_MAXL];              // stash: grad wrt pre-activation of layer l [wg][nt[l+1]*16][16]
-  float* part_lp;                  // [nwg][sum_h]
-  float* part_loss;                // [nwg]
-  // u / bvar drawn inside the kernel (pmbrl_bnn_train_steps without recorded draws): Philox keyed by the caller's seed,
-  // counter = (minibatch row, feature quad, hidden layer | stream << 8, step)
-  int rng;
-  unsigned rng_k0, rng_k1, rng_step;
-  long long* prof;                 // debugging: cycle stamps of workgroup 0 (nullptr: none)
-  int act;                         // PMBRL_ACT_* per hidden layer, pm_act_code (pm_bnn_fwd_bwd<true> when not 0 = all ReLU)
-  // fixed-rate Bernoulli dropout behind hidden layer l (pm_bnn_fwd_bwd<., true>): the units' keep probabilities
-  // [nt[l+1] * 16] (a scalar rate is stored once per unit), nullptr for a layer of another kind.  m = bvar < p_j.
-  const float* keep[PM_MAXL];
-};
-
-// 1 / x to an ulp or two: v_rcp_f32 and one Newton step
-__device__ __forceinline__ float pm_fast_rcp(float d) {
-  const float r = __builtin_amdgcn_rcpf(d);
-  return __builtin_fmaf(__builtin_fmaf(-d, r, 1.f), r, r);
-}
-
-// hidden layer forward: out = relu(acc + b) * hard ;  q = relu(.) * d mask / d logit_p
-// ACT: out = act(acc + b) * hard, q = act(.) * d mask / d logit_p, and d_out = act'(acc + b) * hard for the backward pass
-// (pm_act; act = this layer's PMBRL_ACT_* code).  The ReLU instance is what it was.  Padded units and rows past nvalid
-// are forced to 0 in out, q and d_out after the activation, whatever act(0) is (PMBRL_ACT_EXP: 1).
-// BERN (plans with a Bernoulli layer; keep != nullptr marks one): m = bvar < p_j, out = act(acc + b) * m / p_j -- divided as
-// BDropout.forward divides, per unit -- q = 0 (there is no logit), d_out = act'(acc + b) * m / p_j.
-template <bool ACT = false, bool BERN = false>
-struct EpiBnnFwd {
-  int act;
-  float* d_out;
-  const float* bias;
-  const float* logit_p;
-  const float* keep;
-  const float *u, *bvar;
-  float inv_temp;
-  float *h_out, *q_out, *stash;
-  int ld, row0, nvalid, width, lane;
-  int rng;                       // 1: u / bvar from the generator (rk0, rk1, rstep; rlayer = this hidden layer)
-  unsigned rk0, rk1, rstep, rlayer;
-  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
-    const int g = lane >> 4, lrow = lane & 15;
-    const int f0 = ot * 16 + 4 * g;
-    const f32x4 b = ldg4(bias + f0);
-    f32x4 h, q, dd;
-    unsigned ru[4] = {0u, 0u, 0u, 0u}, rv[4] = {0u, 0u, 0u, 0u};
-    if (rng && logit_p) {      // 24-bit uniforms in [0, 1), what torch.rand gives a float tensor
-      pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer, rstep, rk0, rk1, ru);
-      pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer | 0x100u, rstep, rk0, rk1, rv);
-    }
-    f32x4 kp = {1.f, 1.f, 1.f, 1.f};
-    if constexpr (BERN) {
-      if (keep) {
-        kp = ldg4(keep + f0);
-        if (rng) pm_philox((unsigned)(row0 + lrow), (unsigned)(f0 >> 2), rlayer | 0x100u, rstep, rk0, rk1, rv);
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int f = f0 + r;
-      float v, dv = 0.f;
-      if constexpr (ACT) pm_act(act, acc[r] + b[r], f, width, v, dv);
-      else v = fmaxf(acc[r] + b[r], 0.f);
-      float hv = v, qv = 0.f;
-      if (logit_p && f < width && lrow < nvalid) {
-        const size_t o = (size_t)(row0 + lrow) * width + f;
-        const float uu = rng ? (float)(ru[r] >> 8) * (1.0f / 16777216.0f) : u[o];
-        // the logistic noise and the keep probability on the hardware's log2 / exp2 / reciprocal (1 ulp each, what the
-        // library routines wrap in range handling this argument range does not need: u in [0, 1), the exponent clamped
-        // so that the reciprocal never sees an infinity): 12.2 k -> 9.3 k cycles for the 5 -> 200 layer's 13 tile
-        // epilogues, 19.6 k -> 17.9 k for the 200 -> 200 layer's -- the epilogues are instruction issue, four tiles a SIMD.
-        // (Staging bias and logits in LDS at the head of the kernel, so that the epilogues load nothing from memory, was
-        //  measured with it: the staging cost what the epilogues gained; not kept.)
-        const float cp = logit_p[f] + 0.6931471805599453f * (__builtin_amdgcn_logf(uu + 1e-7f) - __builtin_amdgcn_logf(1.f - (uu - 1e-7f)));
-        const float pr = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(fminf(-1.4426950408889634f * (cp * inv_temp), 80.f)));
-        const bool hard = (rng ? (float)(rv[r] >> 8) * (1.0f / 16777216.0f) : bvar[o]) < pr;
-        hv = hard ? v : 0.f;
-        qv = v * pr * (1.f - pr) * inv_temp;
-        if (!hard) dv = 0.f;
-      }
-      if constexpr (BERN) {
-        if (keep && f < width && lrow < nvalid) {
-          const size_t o = (size_t)(row0 + lrow) * width + f;
-          const bool hard = (rng ? (float)(rv[r] >> 8) * (1.0f / 16777216.0f) : bvar[o]) < kp[r];
-          hv = hard ? v / kp[r] : 0.f;
-          dv = hard ? dv / kp[r] : 0.f;
-        }
-      }
-      if (f >= width || lrow >= nvalid) { hv = 0.f; qv = 0.f; dv = 0.f; }
-      h[r] = hv;
-      q[r] = qv;
-      dd[r] = dv;
-    }
-    *reinterpret_cast<f32x4*>(h_out + lrow * ld + f0) = h;
-    *reinterpret_cast<f32x4*>(q_out + lrow * ld + f0) = q;
-    if constexpr (ACT) *reinterpret_cast<f32x4*>(d_out + lrow * ld + f0) = dd;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) stash[(size_t)(f0 + r) * 16 + lrow] = h[r];
-  }
-};
-
-// backward through hidden layer l-1's output: acc = dL/d out ; gq = acc * q (dropout-logit term),
-// g_pre = out > 0 ? acc : 0
-// (ACT: g_pre = acc * d, h_in = the d_out of EpiBnnFwd<true>)
-// BERN, behind a Bernoulli layer (keep != nullptr): out = relu(.) m / p_j, so g_pre = out > 0 ? acc / p_j : 0 (the ACT
-// instances carry m / p_j in d already)
-template <bool ACT = false, bool BERN = false>
-struct EpiBnnBwd {
-  const float *h_in, *q_in;   // out and q of that layer
-  const float* keep;
-  float *g_out, *gq_out, *stash;
-  int ld, lane;
-  __device__ __forceinline__ void operator()(int ot, int rt, f32x4 acc) {
-    const int g = lane >> 4, lrow = lane & 15;
-    const int f0 = ot * 16 + 4 * g;
-    const f32x4 h = *reinterpret_cast<const f32x4*>(h_in + lrow * ld + f0);
-    const f32x4 q = *reinterpret_cast<const f32x4*>(q_in + lrow * ld + f0);
-    f32x4 gp, gq;
-    f32x4 kp = {1.f, 1.f, 1.f, 1.f};
-    if constexpr (BERN && !ACT) {
-      if (keep) kp = ldg4(keep + f0);
-    }
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      if constexpr (ACT) gp[r] = h[r] != 0.f ? acc[r] * h[r] : 0.f;
-      else if constexpr (BERN) gp[r] = h[r] > 0.f ? (keep ? acc[r] / kp[r] : acc[r]) : 0.f;
-      else gp[r] = h[r] > 0.f ? acc[r] : 0.f;
-      gq[r] = acc[r] * q[r];
-    }
-    *reinterpret_cast<f32x4*>(g_out + lrow * ld + f0) = gp;
-    *reinterpret_cast<f32x4*>(gq_out + lrow * ld + f0) = gq;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) stash[(size_t)(f0 + r) * 16 + lrow] = gp[r];
-  }
-};
-
-// (A GEMM variant that requests ALL of a wave's weight fragments of a layer at once was measured: pm_bnn_fwd_bwd 27.7 ->
-//  34.3 us -- the first MFMA then waits for 32 loads where gemm_tiles starts on four; the layer chain is not what bounds it.)
-__host__ __device__ inline size_t pm_bnn_lds_floats(int nl, int LD, int act = 0) {
-  // H[0..nl-1], Q[0..nl-2], two gradient buffers, one gq buffer, K-split scratch, loss scratch; an activation other than
-  // ReLU: one more buffer, the first hidden layer's derivatives (those of hidden layer l >= 1 go where the input of
-  // Linear l - 1 was: the dW stash has it, and the backward pass of these instances does not read H)
-  return ((size_t)nl + (nl - 1) + 3 + (act ? 1 : 0)) * 16 * LD + (size_t)PM_NW * PM_KS_NT * 256 + PM_NT;
-}
+#include "pmbrl_bnn_parts.h"
 
 template <bool ACT = false, bool BERN = false>
 __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
@@ -231,132 +70,8 @@ __global__ __launch_bounds__(PM_NT, 1) void pm_bnn_fwd_bwd(const BnnArgs A) {
   gemm_narrow<1>(A.wf[nl - 1], A.nt[nl], A.nt[nl - 1], A.bias[nl - 1], H + (size_t)(nl - 1) * R * LD, G1, LD, part,
                  wid, lane, tid);
   BNN_STAMP(10);
-  // ---- mixture negative log-likelihood (losses.py:40-64; head parametrisation models/densities.py:173-207):
-  //      ll = logsumexp_c [log_softmax(logit / T)_c - sum_d lsc_dc - D/2 log 2 pi - 1/2 sum_d t_dc^2]
-  if (A.gmm_n > 1) {
-    const int n = A.gmm_n, D = A.n_out, nD = n * D, W16 = A.nt[nl] * 16;
-    float* gst = A.gT[nl - 1] + (size_t)wg * W16 * 16;
-    __shared__ float s_resp[16][PMBRL_MAX_COMP], s_sm[16][PMBRL_MAX_COMP], s_temp[16], s_ll[16];
-    // responsibilities: one thread per row (n <= 8, D <= 64: a few hundred flops)
-    if (tid < R) {
-      const int r = tid;
-      float ll = 0.f;
-      if (r < nvalid) {
-        const float* o = G1 + r * LD;
-        const float* y = A.Y + (size_t)A.idx[row0 + r] * D;
-        const float temp = 0.1f + softplusf(o[2 * nD + n]);
-        float lg[PMBRL_MAX_COMP], lp[PMBRL_MAX_COMP], mx = -3.0e38f;
-        for (int c = 0; c < n; ++c) { lg[c] = o[2 * nD + c] / temp; mx = fmaxf(mx, lg[c]); }
-        float se = 0.f;
-        for (int c = 0; c < n; ++c) se += expf(lg[c] - mx);
-        const float lse = mx + logf(se);
-        float mxp = -3.0e38f;
-        for (int c = 0; c < n; ++c) {
-          float sls = 0.f, sq = 0.f;
-          for (int d = 0; d < D; ++d) {
-            const float lsc = -softplusf(-o[nD + d * n + c] + A.mls) + A.mls;
-            const float t = (o[d * n + c] - y[d]) * expf(-lsc);
-            sls += lsc;
-            sq = fmaf(t, t, sq);
-          }
-          lp[c] = (lg[c] - lse) + (-(float)D * 0.9189385332046727f - sls) - 0.5f * sq;
-          s_sm[r][c] = expf(lg[c] - lse);
-          mxp = fmaxf(mxp, lp[c]);
-        }
-        float sp = 0.f;
-        for (int c = 0; c < n; ++c) sp += expf(lp[c] - mxp);
-        ll = mxp + logf(sp);
-        for (int c = 0; c < n; ++c) s_resp[r][c] = expf(lp[c] - ll);
-        s_temp[r] = temp;
-      }
-      s_ll[r] = ll;
-    }
-    __syncthreads();
-    float lsum = 0.f;
-    for (int i = tid; i < R * W16; i += PM_NT) {
-      const int r = i / W16, j = i - r * W16;
-      float gval = 0.f;
-      if (r < nvalid && j <= 2 * nD + n) {
-        const float* o = G1 + r * LD;
-        const float rw = (A.row_w ? A.row_w[row0 + r] : 1.f) * A.inv_M;
-        if (j < 2 * nD) {
-          const int jj = j < nD ? j : j - nD, d = jj / n, c = jj - d * n;
-          const float ls = o[nD + jj];
-          const float lsc = -softplusf(-ls + A.mls) + A.mls;
-          const float sd = expf(-lsc);
-          const float t = (o[jj] - A.Y[(size_t)A.idx[row0 + r] * D + d]) * sd;
-          gval = j < nD ? rw * s_resp[r][c] * t * sd : rw * s_resp[r][c] * (1.f - t * t) * sigmoidf(A.mls - ls);
-        } else if (j < 2 * nD + n) {
-          const int c = j - 2 * nD;
-          gval = -rw * (s_resp[r][c] - s_sm[r][c]) / s_temp[r];
-        } else {
-          float a = 0.f;
-          for (int c = 0; c < n; ++c) a += (s_resp[r][c] - s_sm[r][c]) * o[2 * nD + c];
-          gval = rw * a * sigmoidf(o[2 * nD + n]) / (s_temp[r] * s_temp[r]);
-        }
-        if (j == 0) lsum -= (A.row_w ? A.row_w[row0 + r] : 1.f) * s_ll[r];
-      }
-      G0[r * LD + j] = gval;
-      gst[(size_t)j * 16 + r] = gval;
-    }
-    red[tid] = lsum;
-    __syncthreads();
-    for (int o = PM_NT / 2; o > 0; o >>= 1) {
-      if (tid < o) red[tid] += red[tid + o];
-      __syncthreads();
-    }
-    if (tid == 0) A.part_loss[wg] = red[0];
-    if (A.row_lp && tid < nvalid) A.row_lp[row0 + tid] = s_ll[tid];
-  } else
-  // ---- Gaussian negative log-likelihood and its gradient wrt the head outputs
-  {
-    const int n = A.n_out;
-    float* gst = A.gT[nl - 1] + (size_t)wg * A.nt[nl] * 16 * 16;
-    float lsum = 0.f;
-    __shared__ float rowlp[16];
-    if (tid < 16) rowlp[tid] = 0.f;
-    __syncthreads();
-    for (int i = tid; i < R * A.nt[nl] * 16; i += PM_NT) {
-      const int r = i / (A.nt[nl] * 16), j = i - r * (A.nt[nl] * 16);
-      float gval = 0.f;
-      if (r < nvalid && j < 2 * n) {
-        const int d = j < n ? j : j - n;
-        const float mu = G1[r * LD + d];
-        const float ls = G1[r * LD + n + d];
-        if (A.mse) {
-          // torch.nn.functional.mse_loss: mean over the M x n entries
-          const float dl = mu - A.Y[(size_t)A.idx[row0 + r] * n + d];
-          if (j < n) {
-            gval = 2.f * dl * A.inv_M / (float)n;
-            lsum += dl * dl / (float)n;
-          }
-        } else {
-        const float lsc = -softplusf(-ls + A.mls) + A.mls;
-        const float s = expf(-lsc);
-        const float t = (mu - A.Y[(size_t)A.idx[row0 + r] * n + d]) * s;
-        const float rw = A.row_w ? A.row_w[row0 + r] : 1.f;
-        if (j < n) {
-          gval = rw * t * s * A.inv_M;
-          const float nl_d = 0.5f * t * t + lsc + 0.9189385332046727f;   // + 1/2 log(2 pi)
-          lsum += rw * nl_d;
-          if (A.row_lp) atomicAdd(&rowlp[r], -nl_d);
-        } else {
-          gval = rw * (1.f - t * t) * sigmoidf(A.mls - ls) * A.inv_M;
-        }
-        }
-      }
-      G0[r * LD + j] = gval;
-      gst[(size_t)j * 16 + r] = gval;
-    }
-    red[tid] = lsum;
-    __syncthreads();
-    for (int o = PM_NT / 2; o > 0; o >>= 1) {
-      if (tid < o) red[tid] += red[tid + o];
-      __syncthreads();
-    }
-    if (tid == 0) A.part_loss[wg] = red[0];
-    if (A.row_lp && tid < nvalid) A.row_lp[row0 + tid] = rowlp[tid];
-  }
+  // ---- the likelihood (mixture, Gaussian or squared error) and its gradient wrt the head outputs: G1 -> G0
+#include "pmbrl_bnn_loss.h"
   __syncthreads();
   BNN_STAMP(11);
   // ---- backward: dX chain, dropout-logit terms, G stash

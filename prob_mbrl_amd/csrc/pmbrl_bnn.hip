@@ -53,6 +53,10 @@ struct pmbrl_bnn_plan {
   BnnTailArgs tail;
   DwArgs dw;
   int n_finish;   // workgroups of pm_bnn_finish
+  // PMBRL_BNN_FORM_RESIDENT or _SPILL: which kernel the forward + backward launch is (bnn_fwd_bwd_launch); a spill plan's
+  // lds is pm_bnn_spill_lds_floats', its workspace holds the stashes of BnnSpillArgs::hq (off_spill)
+  int form;
+  size_t off_spill;
   int units;      // workgroups of pm_bnn_tail (more than 512: pmbrl_bnn_train_steps refuses)
   // optimiser rule (pmbrl_bnn_plan_set_optimizer): the groups of the layers' tensors, resolved when it was attached
   int has_rule;
@@ -137,8 +141,22 @@ static PackArgs bnn_bind(const pmbrl_bnn_plan* p, char* ws, const float* params_
   return PK;
 }
 
-extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pmbrl_bnn_plan** out) {
+// the forward + backward launch of a call, in the plan's form
+static void bnn_fwd_bwd_launch(const pmbrl_bnn_plan* p, const BnnArgs& A, char* ws, hipStream_t s) {
+  if (p->form == PMBRL_BNN_FORM_SPILL) {
+    BnnSpillArgs S;
+    static_cast<BnnArgs&>(S) = A;
+    S.hq = reinterpret_cast<float*>(ws + p->off_spill);
+    pm_bnn_spill_launch(S, p->acts != 0, p->any_bern, p->lds, s);
+  } else {
+    hipLaunchKernelGGL(p->kern.fwd_bwd, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+  }
+}
+
+extern "C" int pmbrl_bnn_plan_create_form(const pmbrl_bnn_config* cfg, int device, int32_t form, pmbrl_bnn_plan** out) {
   if (!cfg || !out) return fail(-1, "null argument");
+  if (form != PMBRL_BNN_FORM_RESIDENT && form != PMBRL_BNN_FORM_SPILL && form != PMBRL_BNN_FORM_AUTO)
+    return fail(-2, "bnn: unknown kernel form (PMBRL_BNN_FORM_RESIDENT, _SPILL and _AUTO are offered)");
   const pmbrl_mlp& m = cfg->net;
   if (m.n_layers < 2 || m.n_layers > PM_MAXL) return fail(-2, "bnn: 2..8 layers");
   if (cfg->M < 1 || cfg->N < 1) return fail(-2, "bnn: M, N must be >= 1");
@@ -196,7 +214,15 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   }
   p->acts = pm_act_layers(cfg->act, p->nl - 1);
   p->lds = pm_bnn_lds_floats(p->nl, p->LD, p->acts) * sizeof(float);
-  if (p->lds > 160 * 1024) { delete p; return fail(-3, "bnn: network too wide / deep for the fused training step's LDS budget"); }
+  p->form = PMBRL_BNN_FORM_RESIDENT;
+  if (form == PMBRL_BNN_FORM_SPILL || (form == PMBRL_BNN_FORM_AUTO && p->lds > 160 * 1024)) {
+    p->form = PMBRL_BNN_FORM_SPILL;
+    p->lds = pm_bnn_spill_lds_floats(p->LD) * sizeof(float);
+    if (p->lds + PM_BNN_LDS_STATIC > 160 * 1024) {
+      delete p;
+      return fail(-3, "bnn: network too wide for the spill form's LDS budget (three [16][LD] buffers: at most 688 units a layer)");
+    }
+  } else if (p->lds > 160 * 1024) { delete p; return fail(-3, "bnn: network too wide / deep for the fused training step's LDS budget"); }
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; };
   for (int l = 0; l < p->nl; ++l) {
@@ -210,6 +236,8 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
   p->off_part_lp = take((size_t)p->nwg * std::max(p->sum_h, 1) * sizeof(float));
   p->off_part_loss = take((size_t)p->nwg * sizeof(float));
   p->off_part = take((size_t)p->nwg * p->part_stride * sizeof(float));
+  // (a spill plan's stashes in front of the scratch, which stays the workspace's last 4 KB)
+  if (p->form == PMBRL_BNN_FORM_SPILL) p->off_spill = take(pm_bnn_spill_stash_floats(p->nwg, p->nl, p->LD) * sizeof(float));
   p->off_reg_part = take(1024 * sizeof(float));
   p->ws_bytes = off;
   HIPCHK(hipSetDevice(device));
@@ -232,12 +260,18 @@ extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pm
       if (p->has_drop[l] == 2) p->keep_d[l] = p->keep_all_d + koff[l];
   }
   p->kern = bnn_kernels(p->acts, p->any_bern);
-  HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(p->kern.fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)p->lds));
+  if (p->form == PMBRL_BNN_FORM_SPILL) HIPCHK(pm_bnn_spill_prepare(p->acts != 0, p->any_bern));
+  else HIPCHK(hipFuncSetAttribute(reinterpret_cast<const void*>(p->kern.fwd_bwd), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)p->lds));
   bnn_plan_records(p);
   *out = p;
   return 0;
 }
+
+extern "C" int pmbrl_bnn_plan_create(const pmbrl_bnn_config* cfg, int device, pmbrl_bnn_plan** out) {
+  return pmbrl_bnn_plan_create_form(cfg, device, PMBRL_BNN_FORM_RESIDENT, out);
+}
+extern "C" int32_t pmbrl_bnn_plan_form(const pmbrl_bnn_plan* p) { return p ? p->form : -1; }
 
 extern "C" void pmbrl_bnn_plan_destroy(pmbrl_bnn_plan* p) {
   if (!p) return;
@@ -321,7 +355,7 @@ extern "C" int pmbrl_bnn_loss_grad_ex(pmbrl_bnn_plan* p, void* stream, void* wor
     HIPCHK(hipMemsetAsync(grad_flat_d, 0, (size_t)p->n_params * sizeof(float), s));
   } else {
     pm_pack_all_launch(PK, s);
-    hipLaunchKernelGGL(p->kern.fwd_bwd, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+    bnn_fwd_bwd_launch(p, A, ws, s);
     DwArgs W = p->dw;
     for (int l = 0; l < p->nl; ++l) { W.actT[l] = A.actT[l]; W.gT[l] = A.gT[l]; }
     W.part = reinterpret_cast<float*>(ws + p->off_part);
@@ -410,7 +444,7 @@ extern "C" int pmbrl_bnn_train_steps(pmbrl_bnn_plan* p, void* stream, void* work
         A.bvar[l] = bvar_d + (size_t)i * noise + (size_t)p->cfg.M * p->noise_off[l];
       }
     T.loss_out = loss_hist_d ? loss_hist_d + (size_t)3 * i : loss_out_d;
-    hipLaunchKernelGGL(p->kern.fwd_bwd, dim3(p->nwg), dim3(PM_NT), p->lds, s, A);
+    bnn_fwd_bwd_launch(p, A, ws, s);
     if (p->has_rule) {
       static_cast<BnnTailArgs&>(TR) = T;
       hipLaunchKernelGGL(p->kern.tail_rule, dim3(p->units), dim3(PM_BNT_NT), 0, s, TR);

@@ -19,6 +19,7 @@
 //   pmbrl_reward_ext.hip     the ingest launch of a reward evaluated by the caller (pmbrl_rollout_rewards)
 //   pmbrl_tail.hip           mask packing / drawing, weighted sum, dW reduction, gradient norm, clip + Adam, sharded tail
 //   pmbrl_bnn.hip            BNN training step
+//   pmbrl_bnn_spill.hip      its spill form (networks wider than the LDS-resident kernel takes): instances and launcher
 //   pmbrl_mlp.hip            stand-alone network evaluation
 //   pmbrl_comm.hip           RCCL through dlopen, the plan's transports (host code only)
 //   pmbrl_p2p.hip            peer-to-peer transport

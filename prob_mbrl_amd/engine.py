@@ -397,10 +397,15 @@ class BnnStep:
     bernoulli_keep: one entry per hidden layer -- None (the layer is what temperature[l] says), a float or a tensor of
     the layer's width: fixed-rate Bernoulli dropout with these keep probabilities (BDropout, models/modules.py:14-61;
     reg_scale[l] is then its regularizer_scale buffer).  u / bvar hold one [M, h_l] block per dropout layer of either
-    kind; a Bernoulli layer's mask is bvar < p, its u block is not read."""
+    kind; a Bernoulli layer's mask is bvar < p, its u block is not read.
+    form: the kernel form of the forward + backward launch (pmbrl_bnn_plan_create_form) -- 'resident' (every layer in LDS:
+    up to two hidden layers of 256 with ReLU), 'spill' (one layer's working set in LDS, the rest in the workspace: up to
+    688 units a layer at any depth) or 'auto' (resident where it fits, else spill); self.form: what the plan took.  The
+    two give the same bits where both fit."""
 
     def __init__(self, dims, temperature, reg_scale, drop_reg, M, N, reg_weight=1.0,
-                 max_log_std=LOG_MAX_STD, device=None, loss_kind='nll', n_components=0, act=0, bernoulli_keep=None):
+                 max_log_std=LOG_MAX_STD, device=None, loss_kind='nll', n_components=0, act=0, bernoulli_keep=None,
+                 form='auto'):
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else 'cuda:0')
         cfg = _lib.BnnConfig()
@@ -437,8 +442,19 @@ class BnnStep:
                             if cfg.temperature[l] > 0 or cfg.drop_kind[l] == _lib.DROP_BERNOULLI]
         self.sum_h = sum(self.drop_widths)
         self.plan = C.c_void_p()
-        _lib.check(self.lib.pmbrl_bnn_plan_create(C.byref(cfg), self.device.index or 0, C.byref(self.plan)),
-                   'pmbrl_bnn_plan_create')
+        forms = {'resident': _lib.BNN_FORM_RESIDENT, 'spill': _lib.BNN_FORM_SPILL, 'auto': _lib.BNN_FORM_AUTO}
+        if form not in forms:
+            raise ValueError("BnnStep: form must be 'resident', 'spill' or 'auto', not %r" % (form,))
+        if hasattr(self.lib, 'pmbrl_bnn_plan_create_form'):
+            _lib.check(self.lib.pmbrl_bnn_plan_create_form(C.byref(cfg), self.device.index or 0, forms[form],
+                                                           C.byref(self.plan)), 'pmbrl_bnn_plan_create_form')
+            self.form = {v: k for k, v in forms.items()}[int(self.lib.pmbrl_bnn_plan_form(self.plan))]
+        else:      # (an older build named by PMBRL_LIB_PATH: the resident form is all it has)
+            if form == 'spill':
+                raise _lib.PmbrlError("this build of the library has no spill form of the training step (pmbrl_bnn_plan_create_form)")
+            _lib.check(self.lib.pmbrl_bnn_plan_create(C.byref(cfg), self.device.index or 0, C.byref(self.plan)),
+                       'pmbrl_bnn_plan_create')
+            self.form = 'resident'
         for l, k in unit_keep.items():
             _lib.check(self.lib.pmbrl_bnn_plan_set_unit_keep(self.plan, l, k.ctypes.data_as(C.POINTER(C.c_float)),
                                                              int(k.size)), 'pmbrl_bnn_plan_set_unit_keep')
